@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- edges/s (and nodes/s) per message-passing layer on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 may be started either way: under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...
 bench.py --gpus N ...` (what the driver does; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment), or
@@ -14,8 +14,16 @@ plan cache is cleared each step).
 
 Primary workload: the batch BASELINE.json quotes its metric on -- the Graph2Class-style batch of configs[2] (48 graphs,
 ~116k nodes, 8 raw -> 17 edge types, Typilus GGNN stack: 8 GGNN layers, hidden 128, max aggregation, fp32, forward).
-`value` = E / t_layer (edges per second per message-passing layer, E counted after reverse + self augmentation).  At N=1
-the same run also reports, each with its own full-size parity against the CPU oracle (benchmarks/*.py):
+`value` = E / t_layer (edges per second per message-passing layer, E counted after reverse + self augmentation) and
+`ms_per_step` = the wall time of the K timed steps / K.
+
+A plain run does only that: build the inputs, W warm-up steps, the K timed steps, the outputs of the last timed step
+(`--dump-outputs DIR`: one DIR/<name>.npy per array the step returns, float32 / float64, a fixed seeded row sample of the
+node tables when they exceed 64 MB together; rank 0's at N > 1), the JSON line.
+
+`--full` adds everything else, after the timed steps: the per-kernel HIP-event pass (`kernels`, `roofline`), the
+single-minibatch replay, `repeats`, the >= 10 s sustained block, and at N=1 the other configs, each with its own
+full-size parity against the CPU oracle (benchmarks/*.py):
   config1            configs[0] as the reference batches it (3 000-node cap): GGNN-64 layer and the shipped PPI stack
   config2            configs[1]: synthetic 200k / 1.1M graph, one MLP-MP layer
   config3_sum        configs[2] with sum aggregation
@@ -25,12 +33,12 @@ the same run also reports, each with its own full-size parity against the CPU or
   graph2class_train, readme_default_arch    training steps (the README's own quantity)
   cpu_baseline       the CPU restatement timed on this box's host cores
 `parity` (top level) rolls every config up: `strict_1e-5` and `configs_on_relaxed_bar`.  A parity miss fails the run (exit
-code 3).
+code 3).  The `--no-*` options drop single parts of a `--full` run.
 
 N>1: the path partitions over whole graphs (a minibatch is a disjoint union; the reference's own multi-GPU mode hands
 whole graphs to ranks), so every rank runs the single-GPU step on ITS OWN Graph2Class batch: no data-path collective,
-weak scaling.  After it, by default, the dst-range-sharded cut-edge workloads run (ptgnn_amd.sharded: halo all-to-all over
-RCCL): `sharded_cfg5` (top level) and `cut_edges_variant`.
+weak scaling.  With `--full` the dst-range-sharded cut-edge workloads run after it (ptgnn_amd.sharded: halo all-to-all
+over RCCL): `sharded_cfg5` (top level) and `cut_edges_variant`.
 
 Prints ONE JSON line on rank 0.
 """
@@ -57,6 +65,11 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--workload", default="cfg3", choices=["cfg3", "cfg2"])
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the kernel pass, roofline, repeats, sustained block, secondary "
+                        "configs, sharded variants, CPU baseline and oracle parity (a plain run does none of them)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--gemm", default=None, choices=["tile", "stream"],
                    help="kernel family / arithmetic of the dense blocks for the PRIMARY line (default: stream = exact fp32)")
@@ -77,9 +90,11 @@ def parse():
                    help="N>1: the per-rank graphs as ONE disjoint-union batch with global node ids, split by "
                         "ptgnn_amd.sharded (no-cut detection = one all-reduce per minibatch)")
     p.add_argument("--no-sharded-variants", action="store_true",
-                   help="skip the dst-range-sharded cut-edge workloads (cfg5 shard; at N>1 also the cfg4 stack) that run "
-                        "after the primary measurement by default")
+                   help="skip the dst-range-sharded cut-edge workloads (cfg5 shard; at N>1 also the cfg4 stack) that a "
+                        "--full run times after the primary measurement")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be >= 1")
     a.force_sharded = a.force_sharded or a.global_ids or a.cut_edges   # all three need the process group
     return a
 
@@ -117,8 +132,10 @@ def main():
         raise SystemExit("bench.py needs an MI355X (no CPU path)")
     C.hold_stdout()
     rank, world, dev = C.dist_setup(args)
-    # N = 1: the cfg5 shard also runs through the dst-range code path (world-1 process group, nothing cut) unless skipped
-    sharded_leg = (not args.no_sharded_variants and not args.no_secondary) or args.sharded_variants or args.force_sharded
+    # N = 1, --full: the cfg5 shard also runs through the dst-range code path (world-1 process group, nothing cut) unless
+    # skipped
+    sharded_leg = ((args.full and not args.no_sharded_variants and not args.no_secondary) or args.sharded_variants
+                   or args.force_sharded)
     from benchmarks import cpu_baseline as CPU, graph2class as G2C, synthetic as SYN
     # CPU legs before the final thread sweep (the cfg4 / cfg5 oracle parity) run on a bounded pool: a 256-thread
     # OpenMP pool on a quota-limited container oversubscribes, and its spinning workers then slow every later
@@ -148,9 +165,16 @@ def main():
             return G2C.step_cfg3(cur)
 
     _log(f"workload {args.workload} built; timing the primary region")
-    seconds, summary = C.timed_region(step, args.steps, args.warmup, world, dev)
+    launched = ops.launch_counts()        # host-side counters of the library: no device work, nothing timed
+    seconds, last_out = C.timed_steps(step, args.steps, args.warmup, world, dev)
+    launched = ops.launches_since(launched)
     ms_per_step = seconds / args.steps * 1e3
     _log(f"primary: {ms_per_step:.3f} ms/step")
+    if args.dump_outputs and rank == 0:
+        shapes = C.dump_outputs(args.dump_outputs, C.output_arrays(last_out))
+        _log(f"outputs of the last timed step -> {args.dump_outputs}: {shapes}")
+    del last_out
+    summary = C.kernel_pass(step, args.steps, world) if args.full else None
     layers = st["layers_per_step"]
     if rotation is not None:   # mean over the K timed steps (step i of the run uses minibatch i mod 4; W warm-ups came first)
         timed = [rotation[(args.warmup + i) % len(rotation)] for i in range(args.steps)]
@@ -160,12 +184,6 @@ def main():
     edges_all_ranks = C.sum_over_ranks(e_mine, world, dev)       # per-rank batches differ in size
     nodes_all_ranks = C.sum_over_ranks(n_mine, world, dev)
     value = edges_all_ranks / (seconds / args.steps / layers)
-    ktab = C.kernel_table(summary)
-    dominant = max(ktab, key=lambda k: ktab[k]["total_ms"])
-    roof = {k: ktab[dominant][k] for k in ("bound", "achieved", "peak", "unit", "frac",
-                                           "algorithmic_bytes_per_launch")}
-    roof.update(kernel=dominant, avg_ms=ktab[dominant]["avg_ms"])
-    roof.update(C.pmc_traffic(args.workload, dominant))
 
     result = {
         "metric": "edges/sec per MP layer", "value": round(value, 1), "unit": "edges/s",
@@ -178,7 +196,7 @@ def main():
                    "plan_build_in_step": True,
                    # GGNN edge form: one GEMM row per distinct (edge type, source) pair of the batch, read per edge by
                    # the aggregation -- the unit of `value` stays the edge (ptgnn_amd.ops.GraphPlan.unique_messages)
-                   "message_rows": ("shared per (edge type, source) pair" if "edge_linear_shared" in summary
+                   "message_rows": ("shared per (edge type, source) pair" if launched.get("k_stream_edge_shared")
                                     else "one per edge"),
                    "parallelism": ("single GPU" if world == 1 else
                                    f"{world} GPUs x whole graphs (one batch per GPU), no data-path collective")
@@ -187,8 +205,15 @@ def main():
                        f"dst-range shard x{world} on graph boundaries (no cut edges => no data-path collective)")},
         "nodes_per_sec_per_layer": round(nodes_all_ranks / (seconds / args.steps / layers), 1),
         "edges_per_sec_readme_convention": round(edges_all_ranks / (seconds / args.steps), 1),
-        "roofline": roof, "kernels": ktab,
     }
+    if summary is not None:
+        ktab = C.kernel_table(summary)
+        dominant = max(ktab, key=lambda k: ktab[k]["total_ms"])
+        roof = {k: ktab[dominant][k] for k in ("bound", "achieved", "peak", "unit", "frac",
+                                               "algorithmic_bytes_per_launch")}
+        roof.update(kernel=dominant, avg_ms=ktab[dominant]["avg_ms"])
+        roof.update(C.pmc_traffic(args.workload, dominant))
+        result.update(roofline=roof, kernels=ktab)
     exit_code = 0
     parities = {}
     if rotation is not None and len(rotation) > 1:
@@ -198,6 +223,7 @@ def main():
         result["config"]["nodes_per_gpu"] = round(n_mine, 1)
         result["config"]["nodes_per_minibatch"] = [t["N"] for t in rotation]
         result["config"]["edges_per_minibatch"] = [t["E"] for t in rotation]
+    if args.full and rotation is not None and len(rotation) > 1:
         try:      # the round-1..4 form of the headline (one minibatch replayed), beside the rotating one
             sec1, _ = C.timed_region(lambda: G2C.step_cfg3(st), args.steps, 2, world, dev)
             result["single_minibatch_replay"] = {
@@ -235,18 +261,19 @@ def main():
             # loop for the host: a launch-bound secondary measured 7 % slower with the group alive (round 6)
             C.drop_group()
 
-    if (world > 1 and not args.no_sharded_variants) or (world > 1 and args.sharded_variants):
+    if world > 1 and ((args.full and not args.no_sharded_variants) or args.sharded_variants):
         sharded_variants()
     if rank == 0 and world == 1 and not (args.force_sharded and args.workload == "cfg2"):
-        result["repeats"] = C.repeat_stats(step, args.steps)
-        if args.workload == "cfg3" and not args.no_sustained:
+        if args.full:
+            result["repeats"] = C.repeat_stats(step, args.steps)
+        if args.full and args.workload == "cfg3" and not args.no_sustained:
             _log("sustained: >= 10 s of the primary step over 4 rotating minibatches")
             try:
                 result["sustained"] = G2C.sustained_stats(dev, seconds=args.sustained_seconds)
             except Exception as exc:  # noqa: BLE001  (never costs the primary line)
                 result["sustained"] = {"error": f"{type(exc).__name__}: {exc}"}
             torch.cuda.empty_cache()
-        if not args.no_secondary:
+        if args.full and not args.no_secondary:
             check = not args.no_cpu_baseline
 
             def leg(key, fn, parity_of=lambda r: r.get("parity")):
@@ -287,7 +314,7 @@ def main():
             # N = 1: the cfg5 shard through the dst-range code path (world-1 process group over RCCL, nothing cut), after
             # every launch-bound measurement of the run
             sharded_variants()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             _log("cpu baseline (thread sweep) + full-size parity")
             first = (lambda: G2C.step_cfg3(st)) if rotation is not None else step     # parity: the FIRST minibatch of the rotation
             with torch.no_grad():

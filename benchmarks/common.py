@@ -119,21 +119,29 @@ def max_over_ranks(seconds, world, dev):
 
 
 # ------------------------------------------------------------------------------------------------
-def timed_region(step_fn, steps, warmup, world, dev):
+def timed_steps(step_fn, steps, warmup, world, dev):
     """The contract's timed region: W untimed warm-up steps, then EXACTLY K steps bracketed by
     barrier + synchronize on both sides, max over ranks.  No per-kernel instrumentation runs here:
     a HIP event pair around every launch costs ~0.1 ms of queue serialisation per kernel on this
-    stack and would be charged to `value`.  The per-kernel HIP-event pass runs right after, over the
-    same K steps of the same inputs (`kernel_pass`)."""
+    stack and would be charged to `value`.  Returns (seconds, what the last timed step returned); only
+    that last result is kept, so the steps before it free their outputs exactly as an untimed loop does."""
+    assert steps >= 1, steps
     for _ in range(warmup):
         step_fn()
     barrier_sync(world)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step_fn()
+    last = step_fn()
     barrier_sync(world)
     dt = time.perf_counter() - t0
-    return max_over_ranks(dt, world, dev), kernel_pass(step_fn, steps, world)
+    return max_over_ranks(dt, world, dev), last
+
+
+def timed_region(step_fn, steps, warmup, world, dev):
+    """`timed_steps`, then the per-kernel HIP-event pass over the same K steps of the same inputs (`kernel_pass`)."""
+    seconds = timed_steps(step_fn, steps, warmup, world, dev)[0]
+    return seconds, kernel_pass(step_fn, steps, world)
 
 
 def kernel_pass(step_fn, steps, world):
@@ -195,6 +203,62 @@ def pmc_traffic(workload, kernel):
                         "traffic_source": f"profiles/{rnd}_{workload}_traffic.json ({prof['source']})"}
     return {"traffic": None}
 
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20     # `--dump-outputs` writes at most 64 MB in all; headroom for the .npy headers
+
+
+def output_arrays(out):
+    """The arrays a caller of the timed step receives, by name: every tensor of a GnnOutput (the cfg3 forward), or the
+    node table one layer returns (cfg2)."""
+    if isinstance(out, torch.Tensor):
+        return {"output_node_representations": out}
+    if not hasattr(out, "output_node_representations"):
+        raise TypeError(f"no output arrays known for a step result of type {type(out).__name__}")
+    arrays = {"input_node_representations": out.input_node_representations,
+              "output_node_representations": out.output_node_representations,
+              "node_to_graph_idx": out.node_to_graph_idx,
+              "num_graphs": torch.tensor(out.num_graphs)}
+    for k, v in out.node_idx_references.items():
+        arrays[f"node_idx_references_{k}"] = v
+    for k, v in out.node_graph_idx_reference.items():
+        arrays[f"node_graph_idx_reference_{k}"] = v
+    return arrays
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every array as `out_dir/<name>.npy`: floating point as float32 (float64 stays float64), integers as float64
+    (exact below 2**53).  When together they exceed `budget` bytes, the node tables (the 2-D arrays, one row per node)
+    are cut to one fixed sample of rows drawn with `seed` -- the same rows for every table and for every run of the same
+    arguments -- and the row indices are written as `sampled_rows.npy`; every other array stays whole.
+    Returns {name: shape} of what was written."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+    nbytes = lambda t: t.numel() * t.element_size()      # noqa: E731
+    total = sum(nbytes(t) for t in host.values())
+    tables = [name for name, t in host.items() if t.dim() == 2]
+    if total > budget and tables:
+        rows = {host[name].shape[0] for name in tables}
+        if len(rows) != 1:
+            raise ValueError(f"node tables of different lengths {sorted(rows)}: no common row sample")
+        n_rows = rows.pop()
+        fixed = total - sum(nbytes(host[name]) for name in tables)
+        per_row = sum(nbytes(host[name][:1]) for name in tables) + 8        # + the float64 row index
+        keep = (budget - fixed) // per_row
+        if keep < 1:
+            raise ValueError(f"outputs do not fit in {budget} bytes even with one row per table")
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randperm(n_rows, generator=g)[:keep].sort().values
+        for name in tables:
+            host[name] = host[name][idx]
+        host["sampled_rows"] = idx.double()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+    return {name: list(t.shape) for name, t in host.items()}
 
 
 def repeat_stats(step_fn, steps, blocks=5):

@@ -12,5 +12,5 @@ if [ -z "$skip" ]; then
   timeout 1800 python -m pytest tests -q -m gpu > $out/pytest.log 2>&1
   echo "pytest rc=$?" >> $out/pytest.log; tail -15 $out/pytest.log
 fi
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench rc=$?"; tail -5 $out/bench.err

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$OUT/pmc_l2" -o l2 -- \
-  python $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary $* > "$OUT/pmc_l2.log" 2>&1
+  python $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary $* > "$OUT/pmc_l2.log" 2>&1
 python - "$OUT" <<'PY'
 import csv, glob, os, sys
 from collections import defaultdict

@@ -404,3 +404,33 @@ def test_bench_stdout_carries_only_the_json_line():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout == '{"ok": 1}\n', (r.stdout, r.stderr[-500:])
     assert "banner through C stdio" in r.stderr and "python noise" in r.stderr
+
+
+def test_bench_dump_outputs_keeps_within_budget_with_one_seeded_row_sample(tmp_path):
+    """benchmarks.common.dump_outputs (`bench.py --dump-outputs`): float32 / float64 files only, whole arrays while they
+    fit, else the node tables cut to one seeded row sample (the same rows in every table and in every run) with its
+    indices beside them."""
+    import numpy as np
+    from benchmarks.common import dump_outputs
+    g = torch.Generator().manual_seed(3)
+    out = torch.randn(1000, 16, generator=g)
+    arrays = {"output_node_representations": out, "input_node_representations": out * 2,
+              "node_to_graph_idx": torch.arange(1000) // 10, "num_graphs": torch.tensor(100)}
+    shapes = dump_outputs(str(tmp_path / "whole"), arrays)
+    assert "sampled_rows" not in shapes and shapes["output_node_representations"] == [1000, 16]
+    got = {p.stem: np.load(p) for p in (tmp_path / "whole").iterdir()}
+    assert got["output_node_representations"].dtype == np.float32 and got["node_to_graph_idx"].dtype == np.float64
+    assert np.array_equal(got["output_node_representations"], out.numpy()) and float(got["num_graphs"]) == 100.0
+    budget = 40_000
+    runs = []
+    for tag in ("a", "b"):
+        dump_outputs(str(tmp_path / tag), arrays, budget=budget)
+        runs.append({p.stem: np.load(p) for p in (tmp_path / tag).iterdir()})
+        assert sum(p.stat().st_size for p in (tmp_path / tag).iterdir()) <= budget + 128 * len(runs[-1])
+    a, b = runs
+    rows = a["sampled_rows"].astype(np.int64)
+    assert a["sampled_rows"].dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["output_node_representations"], out.numpy()[rows])
+    assert np.array_equal(a["input_node_representations"], 2 * out.numpy()[rows])
+    assert a["node_to_graph_idx"].shape == (1000,)                       # 1-D arrays stay whole
+    assert all(np.array_equal(a[k], b[k]) for k in a) and set(a) == set(b)
