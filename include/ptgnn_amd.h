@@ -120,6 +120,16 @@ enum {
   PTGNN_AMD_KERNEL_GATHER_UPDATE,
   PTGNN_AMD_KERNEL_COUNT_
 };
+/* A second id range for the aggregation kernels (not reached by walking ids 0, 1, ... up to the first NULL name, so
+ * the GEMM family list above stays as it is); ptgnn_amd_launch_count / _name take these ids too. */
+enum {
+  PTGNN_AMD_KERNEL_AGG_FIRST_ = 64,
+  PTGNN_AMD_KERNEL_GATHER_REDUCE = PTGNN_AMD_KERNEL_AGG_FIRST_, /* ptgnn_amd_gather_reduce_f32 / _rows_f32 */
+  PTGNN_AMD_KERNEL_EGC_GATHER_COMBINE,
+  PTGNN_AMD_KERNEL_EGC_COMBINE,
+  PTGNN_AMD_KERNEL_EGC_COMBINE_BACKWARD,
+  PTGNN_AMD_KERNEL_AGG_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -607,6 +617,37 @@ int ptgnn_amd_weighted_pool_backward_f32(const float *x, int64_t ld_x, const flo
                                          const float *grad_out, int64_t ld_go, int64_t num_elements, int32_t dim,
                                          float *grad_x, int64_t ld_gx, float *grad_w, void *workspace,
                                          size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * EGC-S layer (egcmessagepassing.py:63-91; aggregation abstractmessagepassing.py:38-50), K heads, B bases,
+ * Dh = D / K, message rows [K, B, Dh] (msg_dim = K*B*Dh):
+ *   out[v, k*Dh + d] = sum_b coef[v, k*B + b] * agg[v, k*B*Dh + b*Dh + d],   agg = reduce over the in-edges of v.
+ *
+ * ptgnn_amd_egc_gather_combine_f32: the aggregation of ptgnn_amd_gather_reduce_f32 (same plan, `msg`/`col`/`type_bits`
+ *   table or edge forms, hub rows and workspaces; no destination term, no epilogue) with the combine as its row finish:
+ *   the [N, msg_dim] aggregate is not written unless `agg_out` (nullable, [N, msg_dim] contiguous) is given; `argout`
+ *   (nullable, max/min only, needs agg_out) as in ptgnn_amd_gather_reduce_f32.  coef [N, K*B] (ld_coef), out [N, K*Dh]
+ *   (ld_out).  PTGNN_AMD_EUNSUPPORTED when msg_dim exceeds one lane group's row (512 on 16-byte aligned float rows,
+ *   256 otherwise): the caller then aggregates with ptgnn_amd_gather_reduce_f32 and combines separately.
+ * ptgnn_amd_egc_combine_f32: the combine alone, agg [rows, K*B*Dh] (ld_agg) -> out [rows, K*Dh]; any K, B, Dh.
+ * ptgnn_amd_egc_combine_backward_f32: from grad = dL/dout [rows, K*Dh], in one pass (both outputs OVERWRITTEN)
+ *   grad_agg[v, k,b,d] = coef[v, k*B + b] * grad[v, k*Dh + d]     grad_coef[v, k*B + b] = sum_d agg[v, k,b,d] * grad[v, k*Dh + d].
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_egc_gather_combine_f32(const float *msg, int64_t ld_msg, const int32_t *rowptr, const int32_t *col,
+                                     int32_t type_bits, int64_t num_nodes, int32_t num_heads, int32_t num_bases,
+                                     int32_t head_dim, int reduce, const float *coef, int64_t ld_coef, float *out,
+                                     int64_t ld_out, float *agg_out /* nullable */, int32_t *argout /* nullable */,
+                                     int64_t num_edges, int32_t hub_threshold,
+                                     const int32_t *hub_entries /* nullable */, const int32_t *hub_count /* nullable */,
+                                     void *hub_ws /* nullable */, size_t hub_ws_bytes,
+                                     int32_t *hub_tickets /* nullable */, void *stream);
+int ptgnn_amd_egc_combine_f32(const float *agg, int64_t ld_agg, const float *coef, int64_t ld_coef, int64_t num_rows,
+                              int32_t num_heads, int32_t num_bases, int32_t head_dim, float *out, int64_t ld_out,
+                              void *stream);
+int ptgnn_amd_egc_combine_backward_f32(const float *agg, int64_t ld_agg, const float *coef, int64_t ld_coef,
+                                       const float *grad, int64_t ld_grad, int64_t num_rows, int32_t num_heads,
+                                       int32_t num_bases, int32_t head_dim, float *grad_agg, int64_t ld_grad_agg,
+                                       float *grad_coef, int64_t ld_grad_coef, void *stream);
 
 /* Row gather out[i, :] = x[idx[i], :] (F.embedding at gatedmessagepassing.py:54-56,
  * mlpmessagepassing.py:88,91) for the general per-edge path (edge features / training dropout /

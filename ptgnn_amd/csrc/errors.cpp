@@ -19,14 +19,21 @@ void set_error(const char *fmt, ...) {
 // shape / size / mode decision the tests assert on (a parity test that silently ran the tile kernel pins nothing about
 // the streaming one).  Relaxed atomics on the host side of a launch; never read by the library itself.
 static std::atomic<int64_t> g_launches[PTGNN_AMD_KERNEL_COUNT_];
+static std::atomic<int64_t> g_agg_launches[PTGNN_AMD_KERNEL_AGG_END_ - PTGNN_AMD_KERNEL_AGG_FIRST_];
+static std::atomic<int64_t> *counter(int kernel_id) {
+  if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
+  if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
+    return &g_agg_launches[kernel_id - PTGNN_AMD_KERNEL_AGG_FIRST_];
+  return nullptr;
+}
 void count_launch(int kernel_id) {
-  if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) g_launches[kernel_id].fetch_add(1, std::memory_order_relaxed);
+  if (std::atomic<int64_t> *c = counter(kernel_id)) c->fetch_add(1, std::memory_order_relaxed);
 }
 }  // namespace ptgnn_amd
 
 extern "C" int64_t ptgnn_amd_launch_count(int kernel_id) {
-  if (kernel_id < 0 || kernel_id >= PTGNN_AMD_KERNEL_COUNT_) return -1;
-  return ptgnn_amd::g_launches[kernel_id].load(std::memory_order_relaxed);
+  std::atomic<int64_t> *c = ptgnn_amd::counter(kernel_id);
+  return c ? c->load(std::memory_order_relaxed) : -1;
 }
 
 extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
@@ -34,6 +41,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "k_stream_linear", "k_stream_linear_ring", "k_stream_gru", "k_stream_gru_ring", "k_stream_edge",
       "k_stream_edge_shared", "k_stream_edge_v2", "k_wgrad_stream", "k_linear_tlp", "k_gru", "k_edge_linear",
       "k_edge_wgrad", "k_gather_update"};
+  static const char *const agg_names[PTGNN_AMD_KERNEL_AGG_END_ - PTGNN_AMD_KERNEL_AGG_FIRST_] = {
+      "k_gather_reduce", "egc_gather_combine", "egc_combine", "egc_combine_backward"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
+    return agg_names[kernel_id - PTGNN_AMD_KERNEL_AGG_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

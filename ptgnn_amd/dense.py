@@ -218,3 +218,25 @@ def row_epilogue(x: torch.Tensor, gelu: bool, ln: Optional[torch.nn.LayerNorm]) 
     if ln is not None:
         return _RowEpilogue.apply(x, ln.weight, ln.bias, float(ln.eps), flags)
     return _RowEpilogue.apply(x, None, None, 1e-5, flags)
+
+
+class _BasisCombine(torch.autograd.Function):
+    """EGC head / basis combination (egcmessagepassing.py:89-91) as one autograd node: forward
+    ops.basis_combine, backward the one-pass HIP kernel for both inputs (ops.basis_combine_backward)."""
+
+    @staticmethod
+    def forward(ctx, agg, coef, num_heads, num_bases, head_dim):
+        ctx.save_for_backward(agg, coef)
+        ctx.dims = (num_heads, num_bases, head_dim)
+        return ops.basis_combine(agg, coef, num_heads, num_bases, head_dim)
+
+    @staticmethod
+    def backward(ctx, g):
+        agg, coef = ctx.saved_tensors
+        g_agg, g_coef = ops.basis_combine_backward(agg, coef, g.contiguous(), *ctx.dims)
+        return g_agg, g_coef, None, None, None
+
+
+def basis_combine(agg: torch.Tensor, coef: torch.Tensor, num_heads: int, num_bases: int, head_dim: int) -> torch.Tensor:
+    """Differentiable out[v, k*Dh + d] = sum_b coef[v, k*B + b] * agg[v, k*B*Dh + b*Dh + d] on the HIP kernels."""
+    return _BasisCombine.apply(agg, coef, int(num_heads), int(num_bases), int(head_dim))

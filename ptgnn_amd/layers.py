@@ -513,6 +513,103 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
 
 
 # ------------------------------------------------------------------------------------------------
+# EGC-S layer
+# ------------------------------------------------------------------------------------------------
+class EGCMessagePassingLayer(AbstractMessagePassingLayer):
+    """EGC-S layer; constructor, parameters and semantics of egcmessagepassing.py:8-99:
+        w      = X Wc^T + bc                                      [N, K*B]
+        msg_e  = W_{t(e)} Dropout(x[src_e])                       [E, K*B*Dh]   (bias-free per-type bases)
+        out[v] = sum_b w[v, k, b] * (reduce_{e -> v} msg_e)[k, b, :]   per head k, Dh = D / K
+    Edge features are accepted and ignored, as in the reference.
+
+    Inference (fp32, no gradient, torch_scatter reduce set): the bases run as the per-node table X [W_0; ...]^T or, with
+    many sparse edge types, as the grouped per-edge GEMM (`_prefer_edge_path`), and ONE launch aggregates and combines
+    (ops.gather_combine): the [N, K*B*Dh] aggregate never reaches memory.  Training: the same GEMMs as autograd nodes
+    (per-edge input dropout folded into the edge form), the HIP segment reduce, and the combine as `dense.basis_combine`
+    with its one-pass HIP backward."""
+
+    def __init__(self, input_state_dimension: int, output_state_dimension: int, num_edge_types: int,
+                 message_aggregation_function: str, num_bases: int = 4, num_heads: int = 8,
+                 dropout_rate: float = 0.0):
+        super().__init__()
+        self.__input_state_dim = input_state_dimension
+        assert output_state_dimension % num_heads == 0
+        self.__aggregation_fn = message_aggregation_function
+        self.__num_bases = num_bases
+        self.__num_heads = num_heads
+        self.__output_state_dim = output_state_dimension
+        # construction order of the reference (Dropout, bases, coefficients): the same seed gives the same parameters
+        self.__dropout = nn.Dropout(p=dropout_rate)
+        self.__bases = nn.ModuleList(
+            [nn.Linear(input_state_dimension, num_bases * output_state_dimension, bias=False)
+             for _ in range(num_edge_types)])
+        self.__weight_coeffs = nn.Linear(input_state_dimension, num_heads * num_bases)
+
+    def forward(self, node_states: torch.Tensor, adjacency_lists: Adj, node_to_graph_idx,
+                reference_node_ids: Dict[str, torch.Tensor],
+                reference_node_graph_idx: Dict[str, torch.Tensor],
+                edge_features: List[torch.Tensor]) -> torch.Tensor:
+        assert len(adjacency_lists) == len(self.__bases)
+        K, B, D = self.__num_heads, self.__num_bases, self.__output_state_dim
+        if _on_host(node_states):
+            return torch_route.egc_layer(node_states, adjacency_lists, edge_features, list(self.__bases),
+                                         self.__weight_coeffs, self.__dropout, K, B, D, self.__aggregation_fn)
+        if node_states.dtype in _AMP_DTYPES:
+            # AMP: the whole layer runs in fp32 on the HIP kernels, the result goes back to the caller's dtype
+            return self.forward(node_states.float(), adjacency_lists, node_to_graph_idx, reference_node_ids,
+                                reference_node_graph_idx, edge_features).to(node_states.dtype)
+        if node_states.dtype != torch.float32:
+            raise _lib.PtgnnAmdError(f"EGCMessagePassingLayer: node states must be float32 / float16 / bfloat16 on the "
+                                     f"GPU (got {node_states.dtype})")
+        N, H, T = node_states.shape[0], self.__input_state_dim, len(adjacency_lists)
+        Dh, M = D // K, B * D
+        agg_fn = self.__aggregation_fn
+        plan = ops.plan_for(adjacency_lists, N)
+        wc = self.__weight_coeffs
+        weights = [l.weight for l in self.__bases]
+        p = self.__dropout.p if self.training else 0.0
+        reduce_ok = agg_fn in ops.REDUCE_IDS
+        edge_form = _prefer_edge_path(plan.num_edges, N, T, H, M)
+
+        if reduce_ok and p == 0.0 and _no_grad_needed(node_states, *self.parameters()):
+            coef = ops.linear(node_states, wc.weight, wc.bias)                                      # [N, K*B]
+            if edge_form:
+                msgs = ops.edge_linear(node_states, adjacency_lists, weights, False)              # [E, M]
+                return ops.gather_combine(msgs, plan, K, B, Dh, agg_fn, coef, type_bits=0, col=plan.perm)
+            w = weights[0].detach() if T == 1 else torch.cat([x.detach() for x in weights], dim=0)
+            return ops.gather_combine(ops.linear(node_states, w), plan, K, B, Dh, agg_fn, coef)     # table [N, T*M]
+
+        coef = dense.linear(node_states, wc.weight, wc.bias)
+        if reduce_ok and _edge_training_ok(H, M) and (p > 0 or edge_form):
+            # training, edge form: grouped per-edge GEMM with the reference's per-edge input dropout folded in
+            w_stack = _scoped(self, "edge_w", lambda: torch.stack(weights))
+            msgs = edge_linear_autograd(node_states, plan, w_stack, False, p, _dropout_seed() if p > 0 else 0)
+            agg = segment_reduce(msgs, plan, agg_fn)
+        elif reduce_ok and p == 0.0:
+            # training without dropout, few edge types: the message table and the differentiable HIP aggregation
+            y = dense.linear(node_states, weights[0] if T == 1 else torch.cat(weights, dim=0))
+            agg = gather_reduce_autograd(y, None, plan, M, agg_fn)
+        else:
+            # general per-edge path (odd widths, "mul"): message order = type-major, as the reference concatenates
+            msgs = [dense.linear(self.__dropout(node_states.index_select(0, src)), lin.weight)
+                    for (src, _), lin in zip(adjacency_lists, self.__bases)]
+            agg = segment_reduce(torch.cat(msgs, dim=0), plan, agg_fn)
+        return dense.basis_combine(agg, coef, K, B, Dh)
+
+    def forward_sharded(self, node_states: torch.Tensor, shard) -> torch.Tensor:
+        raise _lib.PtgnnAmdError("EGCMessagePassingLayer is not supported under dst-range sharding "
+                                 "(ptgnn_amd.sharded); run it unsharded")
+
+    @property
+    def input_state_dimension(self) -> int:
+        return self.__input_state_dim
+
+    @property
+    def output_state_dimension(self) -> int:
+        return self.__output_state_dim
+
+
+# ------------------------------------------------------------------------------------------------
 # MLP message passing layer
 # ------------------------------------------------------------------------------------------------
 class MlpMessagePassingLayer(AbstractMessagePassingLayer):

@@ -37,23 +37,30 @@ def get_gemm_mode() -> int:
     return _lib.load().ptgnn_amd_get_gemm_mode()
 
 
-def launch_counts() -> dict:
+_AGG_FAMILY_FIRST = 64   # PTGNN_AMD_KERNEL_AGG_FIRST_: the aggregation families' id range (include/ptgnn_amd.h)
+
+
+def launch_counts(aggregation: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
-    to assert which kernel a shape / size / mode was dispatched to."""
+    to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
+    (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward)."""
     lib = _lib.load()
-    out, i = {}, 0
-    while True:
-        name = lib.ptgnn_amd_launch_name(i)
-        if name is None:
-            return out
-        out[name.decode()] = int(lib.ptgnn_amd_launch_count(i))
-        i += 1
+    out = {}
+    for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
+        i = first
+        while True:
+            name = lib.ptgnn_amd_launch_name(i)
+            if name is None:
+                break
+            out[name.decode()] = int(lib.ptgnn_amd_launch_count(i))
+            i += 1
+    return out
 
 
 def launches_since(before: dict) -> dict:
-    """Kernel families launched since `before = launch_counts()` -> {name: count}, zero entries dropped."""
-    now = launch_counts()
-    return {k: v - before.get(k, 0) for k, v in now.items() if v != before.get(k, 0)}
+    """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
+    now = launch_counts(aggregation=True)
+    return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -936,6 +943,109 @@ def segment_mul(messages: torch.Tensor, plan: GraphPlan) -> torch.Tensor:
                                            _stream(out))
     _lib.check(rc, "ptgnn_amd_segment_mul_f32")
     return out
+
+
+def _egc_dims(coef: torch.Tensor, num_heads: int, num_bases: int, head_dim: int):
+    K, B, Dh = int(num_heads), int(num_bases), int(head_dim)
+    if K <= 0 or B <= 0 or Dh <= 0:
+        raise _lib.PtgnnAmdError(f"EGC combine: bad heads / bases / head_dim ({K}, {B}, {Dh})")
+    if coef.shape[1] != K * B:
+        raise _lib.PtgnnAmdError(f"EGC combine: coefficients have {coef.shape[1]} columns, need heads*bases = {K * B}")
+    return K, B, Dh
+
+
+def gather_combine(ysrc: torch.Tensor, plan: GraphPlan, num_heads: int, num_bases: int, head_dim: int, reduce: str,
+                   coef: torch.Tensor, type_bits: Optional[int] = None, col: Optional[torch.Tensor] = None,
+                   return_agg: bool = False, return_arg: bool = False):
+    """EGC aggregation with the head / basis combination as its row finish (ptgnn_amd_egc_gather_combine_f32):
+        out[v, k*Dh + d] = sum_b coef[v, k*B + b] * (reduce_{slots of v} ysrc[src, t*M:(t+1)*M])[k*B*Dh + b*Dh + d]
+    with M = heads * bases * head_dim; `ysrc` / `type_bits` / `col` as in `gather_reduce`.  Returns out, or
+    (out, agg, arg) when `return_agg` (training: the aggregate and, for max / min with `return_arg`, its arg).  Message
+    widths beyond one lane group's row aggregate with `gather_reduce` and combine with `basis_combine` (both HIP)."""
+    lib = _lib.load()
+    _require_cuda_f32("ysrc", ysrc)
+    _require_cuda_f32("coef", coef)
+    if reduce not in REDUCE_IDS:
+        raise ValueError(f"unknown aggregation function {reduce!r}")
+    K, B, Dh = _egc_dims(coef, num_heads, num_bases, head_dim)
+    M, D, N = K * B * Dh, K * Dh, plan.num_nodes
+    if return_arg and (not return_agg or REDUCE_IDS[reduce] < REDUCE_IDS["max"]):
+        raise _lib.PtgnnAmdError("gather_combine: return_arg needs return_agg and max / min")
+    ysrc, coef = _rowmajor(ysrc), _rowmajor(coef)
+    if coef.shape[0] != N:
+        raise _lib.PtgnnAmdError(f"gather_combine: coef has {coef.shape[0]} rows, the plan {N} nodes")
+    out = torch.empty(N, D, dtype=torch.float32, device=ysrc.device)
+    agg = torch.empty(N, M, dtype=torch.float32, device=ysrc.device) if return_agg else None
+    arg = torch.empty(N, M, dtype=torch.int32, device=ysrc.device) if return_arg else None
+    plan.wait()
+    tb = plan.type_bits if type_bits is None else type_bits
+    colt = plan.col if col is None else col
+    # algorithmic bytes: per edge one message row + its col entry; per node the coefficients, the output row, the rowptr
+    # entry (and the aggregate / arg when asked for)
+    nbytes = (plan.num_edges * (4.0 * M + 4) + N * (4.0 * (K * B + D) + 4)
+              + (N * 4.0 * M if agg is not None else 0.0) + (N * 4.0 * M if arg is not None else 0.0))
+    hub_ws, hub_bytes = _hub_workspace(plan, M, arg is not None, ysrc.device)
+    with _timed("egc_gather_combine", bytes=nbytes):
+        rc = lib.ptgnn_amd_egc_gather_combine_f32(
+            _ptr_or(ysrc, plan.rowptr), _ld(ysrc), plan.rowptr.data_ptr(), colt.data_ptr(), tb, N, K, B, Dh,
+            REDUCE_IDS[reduce], coef.data_ptr(), _ld(coef), out.data_ptr(), D,
+            agg.data_ptr() if agg is not None else None, arg.data_ptr() if arg is not None else None,
+            plan.num_edges, HUB_THRESHOLD if hub_ws is not None else 0,
+            plan.hub_entries.data_ptr() if hub_ws is not None else None,
+            plan.hub_count.data_ptr() if hub_ws is not None else None,
+            hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes,
+            plan.hub_tickets(M).data_ptr() if hub_ws is not None else None, _stream(out))
+    if rc == _lib.EUNSUPPORTED:
+        res = gather_reduce(ysrc, plan, M, reduce, return_arg=return_arg, type_bits=tb, col=colt)
+        agg, arg = res if return_arg else (res, None)
+        out = basis_combine(agg, coef, K, B, Dh)
+    else:
+        _lib.check(rc, "ptgnn_amd_egc_gather_combine_f32")
+    return (out, agg, arg) if return_agg else out
+
+
+def basis_combine(agg: torch.Tensor, coef: torch.Tensor, num_heads: int, num_bases: int, head_dim: int) -> torch.Tensor:
+    """out[v, k*Dh + d] = sum_b coef[v, k*B + b] * agg[v, k*B*Dh + b*Dh + d]  (ptgnn_amd_egc_combine_f32, any shape)."""
+    lib = _lib.load()
+    _require_cuda_f32("agg", agg)
+    _require_cuda_f32("coef", coef)
+    K, B, Dh = _egc_dims(coef, num_heads, num_bases, head_dim)
+    agg, coef = _rowmajor(agg), _rowmajor(coef)
+    n = agg.shape[0]
+    if agg.shape[1] != K * B * Dh or coef.shape[0] != n:
+        raise _lib.PtgnnAmdError(f"basis_combine: agg {tuple(agg.shape)} / coef {tuple(coef.shape)} do not match "
+                                 f"({K}, {B}, {Dh})")
+    out = torch.empty(n, K * Dh, dtype=torch.float32, device=agg.device)
+    with _timed("egc_combine", bytes=4.0 * n * (K * B * Dh + K * B + K * Dh)):
+        rc = lib.ptgnn_amd_egc_combine_f32(agg.data_ptr() if n else None, _ld(agg), coef.data_ptr() if n else None,
+                                           _ld(coef), n, K, B, Dh, out.data_ptr() if n else None, K * Dh, _stream(out))
+    _lib.check(rc, "ptgnn_amd_egc_combine_f32")
+    return out
+
+
+def basis_combine_backward(agg: torch.Tensor, coef: torch.Tensor, grad: torch.Tensor, num_heads: int, num_bases: int,
+                           head_dim: int):
+    """(grad_agg, grad_coef) of `basis_combine` in one pass (ptgnn_amd_egc_combine_backward_f32):
+    grad_agg[v, k,b,d] = coef[v, k*B + b] * grad[v, k*Dh + d],  grad_coef[v, k*B + b] = sum_d agg[v, k,b,d] grad[v, k*Dh + d]."""
+    lib = _lib.load()
+    _require_cuda_f32("agg", agg)
+    _require_cuda_f32("coef", coef)
+    _require_cuda_f32("grad", grad)
+    K, B, Dh = _egc_dims(coef, num_heads, num_bases, head_dim)
+    agg, coef, grad = _rowmajor(agg), _rowmajor(coef), _rowmajor(grad)
+    n = agg.shape[0]
+    if agg.shape[1] != K * B * Dh or tuple(grad.shape) != (n, K * Dh) or coef.shape[0] != n:
+        raise _lib.PtgnnAmdError(f"basis_combine_backward: agg {tuple(agg.shape)} / coef {tuple(coef.shape)} / grad "
+                                 f"{tuple(grad.shape)} do not match ({K}, {B}, {Dh})")
+    g_agg = torch.empty(n, K * B * Dh, dtype=torch.float32, device=agg.device)
+    g_coef = torch.empty(n, K * B, dtype=torch.float32, device=agg.device)
+    with _timed("egc_combine_backward", bytes=4.0 * n * (2 * K * B * Dh + K * Dh + 2 * K * B)):
+        rc = lib.ptgnn_amd_egc_combine_backward_f32(
+            agg.data_ptr() if n else None, _ld(agg), coef.data_ptr() if n else None, _ld(coef),
+            grad.data_ptr() if n else None, _ld(grad), n, K, B, Dh, g_agg.data_ptr() if n else None, K * B * Dh,
+            g_coef.data_ptr() if n else None, K * B, _stream(g_agg))
+    _lib.check(rc, "ptgnn_amd_egc_combine_backward_f32")
+    return g_agg, g_coef
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,

@@ -265,3 +265,21 @@ def mlp_layer(node_states, adjacency_lists, edge_features, edge_mlps: Sequence[n
     if activation is not None:
         agg = activation(agg)
     return state_update(agg)
+
+
+def egc_layer(node_states, adjacency_lists, edge_features, bases: Sequence[nn.Linear], weight_coeffs: nn.Linear,
+              dropout: nn.Module, num_heads: int, num_bases: int, output_dim: int, reduce: str) -> torch.Tensor:
+    """egcmessagepassing.py:63-91 on host tensors, in the reference's operator order: node coefficients, then per type
+    bases(Dropout(x_src)) as [E_t, K, B, Dh] (edge features are zipped over and ignored, as there), fp32 segment reduce
+    onto the targets, (agg * w).sum over the bases."""
+    _host_only(node_states)
+    node_weights = weight_coeffs(node_states).reshape(-1, num_heads, num_bases, 1)
+    targets, messages = [], []
+    for (src, dst), _features, lin in zip(adjacency_lists, edge_features, bases):
+        targets.append(dst)
+        inp = dropout(nn.functional.embedding(src, node_states))
+        messages.append(lin(inp).reshape(-1, num_heads, num_bases, output_dim // num_heads))
+    msgs = torch.cat(messages, dim=0)
+    agg = aggregate(msgs.reshape(msgs.shape[0], -1), torch.cat(targets, dim=0), node_states.shape[0], reduce)
+    agg = agg.reshape(-1, num_heads, num_bases, output_dim // num_heads)
+    return (agg * node_weights).sum(axis=-2).reshape(-1, output_dim)
