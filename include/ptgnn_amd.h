@@ -128,6 +128,8 @@ enum {
   PTGNN_AMD_KERNEL_EGC_GATHER_COMBINE,
   PTGNN_AMD_KERNEL_EGC_COMBINE,
   PTGNN_AMD_KERNEL_EGC_COMBINE_BACKWARD,
+  PTGNN_AMD_KERNEL_PNA_AGGREGATE,          /* ptgnn_amd_pna_aggregate_f32 */
+  PTGNN_AMD_KERNEL_PNA_AGGREGATE_BACKWARD, /* ptgnn_amd_pna_aggregate_backward_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -648,6 +650,52 @@ int ptgnn_amd_egc_combine_backward_f32(const float *agg, int64_t ld_agg, const f
                                        const float *grad, int64_t ld_grad, int64_t num_rows, int32_t num_heads,
                                        int32_t num_bases, int32_t head_dim, float *grad_agg, int64_t ld_grad_agg,
                                        float *grad_coef, int64_t ld_grad_coef, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * PNA aggregation (pna_aggregation.py:27-56, PnaMessageAggregation(delta)) over a plan of ptgnn_amd_csr_build.  Per
+ * destination row v with in-degree d (its CSR slots) and message rows m_e:
+ *   A   = [sum, mean, max, min, std]   (5 blocks of msg_dim columns, fp32)
+ *         sum = sum_e m_e (slot order)      mean = sum / (float(d) + 1e-5)
+ *         max / min as ptgnn_amd_gather_reduce_f32 (0 for empty rows, ties -> the earliest slot)
+ *         std = sqrt(sum_e (relu(m_e*m_e - mean*mean) + 1e-10)), m*m and mean*mean each rounded (no contraction)
+ *   s   = log(float(d) + 1) / delta,  s' = 1 / (s + 1e-3)
+ *   out = [A | A*s | A*s']             ([N, 15*msg_dim], ld_out)
+ * then, with `epilogue` (PTGNN_AMD_EPI_*), GELU (erf form) and / or an affine LayerNorm over the 15*msg_dim columns
+ * (ln_gamma / ln_beta [15*msg_dim], ln_eps) -- msg_dim <= 256 only (else EUNSUPPORTED).
+ * Messages: `ysrc` / `ydst` / `col` / `type_bits` as in ptgnn_amd_gather_reduce_f32 (table form with an optional
+ *   destination term; edge form: [E, msg_dim] messages with col = the plan's perm and type_bits = 0).
+ * round_mode: 0, or 1 / 2 to round A to fp16 / bf16 before the scalers (the reference's `.to(msg_dtype)` for half /
+ *   bfloat16 messages; the scaled blocks are products of the rounded values).
+ * argmax / argmin: nullable together, [N, msg_dim] int32 contiguous: the winning CSR slot (-1 for empty rows); not with
+ *   a destination term.
+ * agg_out: nullable, [N, 5*msg_dim] contiguous: A before the rounding of round_mode (what the backward needs); not with
+ *   an epilogue.
+ * Rows of more than 256 in-edges are reduced by a whole workgroup (slots interleaved over its lane groups, partials
+ *   combined in a fixed order): deterministic, sums in a different rounding order than the serial fold.
+ *
+ * ptgnn_amd_pna_aggregate_backward_f32 (edge form): from grad = dL/dout [N, 15*msg_dim] and the forward's UNROUNDED A
+ *   (`agg`, ld_agg >= 5*msg_dim: only blocks 0 (sum) and 1 (mean) are read; std is recomputed) and args, for every
+ *   slot i of row v
+ *   writes row col[i] of grad_msg ([E, msg_dim], ld_grad_msg; every row referenced by `col` is OVERWRITTEN):
+ *     g_k = grad[v, k] + s*grad[v, 5+k] + s'*grad[v, 10+k]   (block k of A),  gS = g_4 / (2*std),
+ *     P   = #{slots of v with m*m - mean*mean > 0}  (per column),
+ *     g_m = g_0 + (g_1 - gS*2*mean*P) / (d + 1e-5) + [pos]*gS*2*m + g_2*[argmax == i] + g_3*[argmin == i]
+ *   with pos = (m*m - mean*mean > 0) in the forward's fp32 arithmetic; mean, std and the std terms are formed in float64
+ *   from A's sum block (they cancel to ~1e-2 of their size on degree-1 rows).  round_mode as in the forward: with 1 / 2
+ *   g_k is rounded to fp16 / bf16 as the reference's autograd accumulates it, h(h(h(grad[k]) + h(s'*grad[10+k])) +
+ *   h(s*grad[5+k])).
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_pna_aggregate_f32(const float *ysrc, int64_t ld_y, const float *ydst /* nullable */, int64_t ld_yd,
+                                const int32_t *rowptr, const int32_t *col, int32_t type_bits, int64_t num_nodes,
+                                int32_t msg_dim, float delta, int epilogue, const float *ln_gamma /* nullable */,
+                                const float *ln_beta /* nullable */, float ln_eps, int32_t round_mode, float *out,
+                                int64_t ld_out, int32_t *argmax /* nullable */, int32_t *argmin /* nullable */,
+                                float *agg_out /* nullable */, int64_t num_edges, void *stream);
+int ptgnn_amd_pna_aggregate_backward_f32(const float *msg, int64_t ld_msg, const int32_t *rowptr, const int32_t *col,
+                                         int64_t num_nodes, int32_t msg_dim, float delta, const float *agg,
+                                         int64_t ld_agg, const int32_t *argmax, const int32_t *argmin,
+                                         const float *grad, int64_t ld_grad, float *grad_msg, int64_t ld_grad_msg,
+                                         int32_t round_mode, int64_t num_edges, void *stream);
 
 /* Row gather out[i, :] = x[idx[i], :] (F.embedding at gatedmessagepassing.py:54-56,
  * mlpmessagepassing.py:88,91) for the general per-edge path (edge features / training dropout /

@@ -96,6 +96,10 @@ SIGNATURES = {
     "ptgnn_amd_egc_combine_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
     "ptgnn_amd_egc_combine_backward_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp,
                                                       _i64, _vp, _i64, _vp]),
+    "ptgnn_amd_pna_aggregate_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _f32, _c.c_int, _vp,
+                                               _vp, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "ptgnn_amd_pna_aggregate_backward_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _i64, _vp, _vp, _vp,
+                                                        _i64, _vp, _i64, _i32, _i64, _vp]),
     "ptgnn_amd_gather_rows_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "ptgnn_amd_weighted_pool_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32]),
     "ptgnn_amd_weighted_pool_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _c.c_size_t,

@@ -42,7 +42,8 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "k_stream_edge_shared", "k_stream_edge_v2", "k_wgrad_stream", "k_linear_tlp", "k_gru", "k_edge_linear",
       "k_edge_wgrad", "k_gather_update"};
   static const char *const agg_names[PTGNN_AMD_KERNEL_AGG_END_ - PTGNN_AMD_KERNEL_AGG_FIRST_] = {
-      "k_gather_reduce", "egc_gather_combine", "egc_combine", "egc_combine_backward"};
+      "k_gather_reduce", "egc_gather_combine", "egc_combine", "egc_combine_backward", "pna_aggregate",
+      "pna_aggregate_backward"};
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
     return agg_names[kernel_id - PTGNN_AMD_KERNEL_AGG_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;

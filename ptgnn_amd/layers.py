@@ -47,7 +47,8 @@ from torch import nn
 
 from ptgnn_amd import _lib, dense, ops, torch_route
 from ptgnn_amd.scatter import (edge_linear as edge_linear_autograd, edge_linear_feat as edge_linear_feat_autograd,
-                               gather_reduce as gather_reduce_autograd, segment_reduce)
+                               gather_reduce as gather_reduce_autograd, pna_aggregate as pna_aggregate_autograd,
+                               segment_reduce)
 
 try:  # inside a ptgnn install the layers ARE ptgnn layers
     from ptgnn.neuralmodels.gnn.messagepassing.abstractmessagepassing import (  # type: ignore
@@ -610,6 +611,41 @@ class EGCMessagePassingLayer(AbstractMessagePassingLayer):
 
 
 # ------------------------------------------------------------------------------------------------
+# PNA aggregation module
+# ------------------------------------------------------------------------------------------------
+class PnaMessageAggregation(AbstractMessageAggregation):
+    """Principal Neighbourhood Aggregation; constructor and semantics of pna_aggregation.py:13-59 (no parameters, no
+    buffers).  forward(messages [E, M], message_targets [E] int64, num_nodes) -> [N, 15M]:
+        A = [sum, mean, max, min, std] per target (fp32, cast to the message dtype),  out = [A | A*s | A*s']
+    with s = log(in-degree + 1) / delta, s' = 1 / (s + 1e-3).
+
+    GPU tensors: one fused HIP launch over a plan of the targets (ops.pna_aggregate; with gradients the `_PnaAggregate`
+    autograd node and its one-pass HIP backward).  CPU tensors: torch_route.pna_aggregate.  Inside an
+    `MlpMessagePassingLayer` the aggregation runs over the layer's own plan instead (MlpMessagePassingLayer._forward_pna),
+    with GELU + LayerNorm fused into the launch for inference."""
+
+    def __init__(self, delta: float = 1):
+        super().__init__()
+        self._delta = delta  # Eq. 5 of the paper
+
+    def forward(self, messages: torch.Tensor, message_targets: torch.Tensor, num_nodes):
+        if not messages.is_cuda:
+            return torch_route.pna_aggregate(messages, message_targets, num_nodes, self._delta)
+        if messages.dim() != 2 or message_targets.dim() != 1 or message_targets.shape[0] != messages.shape[0]:
+            raise _lib.PtgnnAmdError(f"PnaMessageAggregation: messages [E, M] and 1-D targets of length E expected (got "
+                                     f"{tuple(messages.shape)}, {tuple(message_targets.shape)})")
+        if messages.dtype not in ops.PNA_ROUND:
+            raise _lib.PtgnnAmdError(f"PnaMessageAggregation: messages must be float32 / float16 / bfloat16 on the GPU "
+                                     f"(got {messages.dtype})")
+        # torch_scatter semantics: a plan whose "source" column is unused; (targets, targets) gives dst = targets
+        plan = ops.build_plan([(message_targets, message_targets)], int(num_nodes))
+        return pna_aggregate_autograd(messages.to(torch.float32), plan, float(self._delta), round_to=messages.dtype)
+
+    def output_state_size(self, message_input_size: int) -> int:
+        return message_input_size * 5 * 3
+
+
+# ------------------------------------------------------------------------------------------------
 # MLP message passing layer
 # ------------------------------------------------------------------------------------------------
 class MlpMessagePassingLayer(AbstractMessagePassingLayer):
@@ -799,6 +835,48 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         ydst = ops.linear(node_states, w[T * M:]) if use_dst else None
         return self._aggregate_and_update(ysrc, ydst, shard.plan)
 
+    def _forward_pna(self, node_states: torch.Tensor, adjacency_lists: Adj, edge_features) -> Optional[torch.Tensor]:
+        """The layer with exactly `PnaMessageAggregation` (not a subclass) over its own plan; None where this route does
+        not apply (edge features, deeper or biased edge MLPs, non-fp32 states: the general per-edge path, which calls
+        the aggregation module).  Inference: the message table (or the grouped per-edge GEMM), ONE launch that
+        aggregates, scales and applies GELU + LayerNorm(15M) -- the [N, 15M] pre-LayerNorm tensor never exists -- and the
+        dense block.  Training: the differentiable message GEMMs, `_PnaAggregate`, `_update`."""
+        if (self._features_dimension != 0 or any(f is not None and f.shape[-1] != 0 for f in edge_features)
+                or not all(m.is_single_linear for m in self.__edge_message_transformation_layers)
+                or node_states.dtype != torch.float32):
+            return None
+        N, T, M, H = node_states.shape[0], len(adjacency_lists), self._message_dimension, self.__input_state_dim
+        delta = float(self.__aggregation_fn._delta)
+        use_dst = self.__use_target_state_as_message_input
+        ws = [m.linears[0].weight for m in self.__edge_message_transformation_layers]
+        plan = ops.plan_for(adjacency_lists, N)
+        edge_form = _prefer_edge_path(plan.num_edges, N, T, H, M)
+        if _no_grad_needed(node_states, *self.parameters()):
+            act = self.__message_activation
+            gelu_ok = act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
+            ln_ok = self._ln is None or (self._ln.elementwise_affine and self._ln.bias is not None)
+            fused = gelu_ok and ln_ok and M <= 256
+            epi = {}
+            if fused:
+                epi = dict(epilogue=(ops.EPI_GELU if act is not None else 0) | (ops.EPI_LAYERNORM if self._ln is not None else 0),
+                           ln_weight=self._ln.weight if self._ln is not None else None,
+                           ln_bias=self._ln.bias if self._ln is not None else None,
+                           ln_eps=self._ln.eps if self._ln is not None else 1e-5)
+            if edge_form:
+                msgs = ops.edge_linear(node_states, adjacency_lists, ws, use_dst)
+                agg = ops.pna_aggregate(msgs, plan, M, delta, type_bits=0, col=plan.perm, **epi)
+            else:
+                y = ops.linear(node_states, self._stacked_edge_weights())
+                agg = ops.pna_aggregate(y[:, :T * M], plan, M, delta, ydst=y[:, T * M:] if use_dst else None, **epi)
+            return self._update(agg, fused)
+        if not _edge_training_ok(H, M):
+            return None
+        # training: the grouped per-edge GEMM as one autograd node (messages in the plan's type-major order), the fused
+        # aggregation with its HIP backward, then the state update
+        w_stack = _scoped(self, "edge_w", lambda: torch.stack(ws))
+        msgs = edge_linear_autograd(node_states, plan, w_stack, use_dst)
+        return self._update(pna_aggregate_autograd(msgs, plan, delta), False)
+
     def _update(self, agg: torch.Tensor, fused_epilogue_done: bool) -> torch.Tensor:
         x = agg
         if not fused_epilogue_done:
@@ -857,6 +935,11 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
                                 reference_node_graph_idx, feats).to(node_states.dtype)
         num_nodes = node_states.shape[0]
         T, M = len(adjacency_lists), self._message_dimension
+
+        if type(self.__aggregation_fn) is PnaMessageAggregation:
+            out = self._forward_pna(node_states, adjacency_lists, edge_features)
+            if out is not None:
+                return out
 
         if self._fused_ok(node_states, edge_features):
             plan = ops.plan_for(adjacency_lists, num_nodes)

@@ -43,7 +43,7 @@ _AGG_FAMILY_FIRST = 64   # PTGNN_AMD_KERNEL_AGG_FIRST_: the aggregation families
 def launch_counts(aggregation: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
-    (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward)."""
+    (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward)."""
     lib = _lib.load()
     out = {}
     for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
@@ -1046,6 +1046,95 @@ def basis_combine_backward(agg: torch.Tensor, coef: torch.Tensor, grad: torch.Te
             g_coef.data_ptr() if n else None, K * B, _stream(g_agg))
     _lib.check(rc, "ptgnn_amd_egc_combine_backward_f32")
     return g_agg, g_coef
+
+
+PNA_ROUND = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def pna_aggregate(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, delta: float = 1.0,
+                  ydst: Optional[torch.Tensor] = None, type_bits: Optional[int] = None, col: Optional[torch.Tensor] = None,
+                  epilogue: int = EPI_NONE, ln_weight: Optional[torch.Tensor] = None,
+                  ln_bias: Optional[torch.Tensor] = None, ln_eps: float = 1e-5, return_arg: bool = False,
+                  round_to: torch.dtype = torch.float32, agg_out: Optional[torch.Tensor] = None):
+    """PNA aggregation (pna_aggregation.py:27-56) in one launch (ptgnn_amd_pna_aggregate_f32): per destination v
+        A = [sum, mean, max, min, std] of the messages of v,  out = EPI([A | A*s | A*s'])   [N, 15 * msg_dim]
+    with s = log(d + 1) / delta, s' = 1 / (s + 1e-3).  Messages as in `gather_reduce` (table form `ysrc` [+ `ydst`] or
+    the edge form with col = plan.perm, type_bits = 0).  `epilogue` = EPI_GELU | EPI_LAYERNORM (msg_dim <= 256) fuses
+    the MLP layer's activation and LayerNorm(15 * msg_dim).  `round_to` (float16 / bfloat16) rounds A to the message
+    dtype before the scalers; `agg_out` (contiguous fp32 [N, 5 * msg_dim], no epilogue) then receives A unrounded, as
+    the backward needs it.  Returns out, or (out, argmax, argmin) with `return_arg` (int32 [N, msg_dim] slots)."""
+    lib = _lib.load()
+    _require_cuda_f32("ysrc", ysrc)
+    ysrc = _rowmajor(ysrc)
+    ld_yd = _ld(ysrc)
+    if ydst is not None:
+        _require_cuda_f32("ydst", ydst)
+        ydst = _rowmajor(ydst)
+        ld_yd = _ld(ydst)
+    if float(delta) == 0.0:
+        raise _lib.PtgnnAmdError("pna_aggregate: delta must be non-zero")
+    if round_to not in PNA_ROUND:
+        raise _lib.PtgnnAmdError(f"pna_aggregate: messages of dtype {round_to} are not supported")
+    M, N = int(msg_dim), plan.num_nodes
+    out = torch.empty(N, 15 * M, dtype=torch.float32, device=ysrc.device)
+    amax = torch.empty(N, M, dtype=torch.int32, device=ysrc.device) if return_arg else None
+    amin = torch.empty(N, M, dtype=torch.int32, device=ysrc.device) if return_arg else None
+    if epilogue & EPI_LAYERNORM:
+        if ln_weight is None or ln_bias is None:
+            raise _lib.PtgnnAmdError("pna_aggregate: the LayerNorm epilogue needs ln_weight and ln_bias")
+        ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
+    if agg_out is not None and (tuple(agg_out.shape) != (N, 5 * M) or agg_out.dtype != torch.float32
+                                or not agg_out.is_contiguous() or agg_out.device != ysrc.device):
+        raise _lib.PtgnnAmdError(f"pna_aggregate: `agg_out` must be a contiguous float32 [{N}, {5 * M}] tensor")
+    plan.wait()
+    tb = plan.type_bits if type_bits is None else type_bits
+    colt = plan.col if col is None else col
+    # algorithmic bytes: per edge one message row + its col entry; per node the rowptr entry, the 15M-wide output row
+    # (and the destination-term row, the two arg rows)
+    nbytes = (plan.num_edges * (4.0 * M + 4) + N * (60.0 * M + 4) + (N * 4.0 * M if ydst is not None else 0.0)
+              + (N * 8.0 * M if return_arg else 0.0))
+    with _timed("pna_aggregate", bytes=nbytes):
+        rc = lib.ptgnn_amd_pna_aggregate_f32(
+            _ptr_or(ysrc, plan.rowptr), _ld(ysrc), ydst.data_ptr() if ydst is not None else None, ld_yd,
+            plan.rowptr.data_ptr(), colt.data_ptr(), tb, N, M, float(delta), int(epilogue),
+            ln_weight.data_ptr() if ln_weight is not None else None,
+            ln_bias.data_ptr() if ln_bias is not None else None, float(ln_eps), PNA_ROUND[round_to],
+            out.data_ptr() if N else None, 15 * M, amax.data_ptr() if amax is not None and N else None,
+            amin.data_ptr() if amin is not None and N else None,
+            agg_out.data_ptr() if agg_out is not None and N else None, plan.num_edges, _stream(out))
+    _lib.check(rc, "ptgnn_amd_pna_aggregate_f32")
+    return (out, amax, amin) if return_arg else out
+
+
+def pna_aggregate_backward(messages: torch.Tensor, plan: GraphPlan, agg: torch.Tensor, argmax: torch.Tensor,
+                           argmin: torch.Tensor, grad: torch.Tensor, delta: float = 1.0,
+                           round_to: torch.dtype = torch.float32) -> torch.Tensor:
+    """Gradient of `pna_aggregate` (edge form) w.r.t. the [E, M] messages in message order, in one pass per row
+    (ptgnn_amd_pna_aggregate_backward_f32).  `agg` holds the forward's UNROUNDED A in its first 5M columns: the
+    forward's [N, 15M] output when it ran without rounding, else its `agg_out` [N, 5M].  `grad` = dL/dout [N, 15M];
+    `round_to` as in the forward (the block gradients are then rounded as the reference's autograd rounds them)."""
+    lib = _lib.load()
+    for name, t in (("messages", messages), ("agg", agg), ("grad", grad)):
+        _require_cuda_f32(name, t)
+    messages, agg, grad = _rowmajor(messages), _rowmajor(agg), _rowmajor(grad)
+    E, M, N = plan.num_edges, messages.shape[1], plan.num_nodes
+    if round_to not in PNA_ROUND:
+        raise _lib.PtgnnAmdError(f"pna_aggregate_backward: messages of dtype {round_to} are not supported")
+    if messages.shape[0] != E or tuple(agg.shape) not in ((N, 5 * M), (N, 15 * M)) or tuple(grad.shape) != (N, 15 * M):
+        raise _lib.PtgnnAmdError(f"pna_aggregate_backward: messages {tuple(messages.shape)} / agg {tuple(agg.shape)} / "
+                                 f"grad {tuple(grad.shape)} do not match the plan ({N} nodes, {E} edges)")
+    out = torch.empty(E, M, dtype=torch.float32, device=messages.device)
+    if E == 0:
+        return out
+    plan.wait()
+    nbytes = E * (3 * 4.0 * M + 8) + N * (4.0 * (15 * M + 2 * M) + 8.0 * M + 4)
+    with _timed("pna_aggregate_backward", bytes=nbytes):
+        rc = lib.ptgnn_amd_pna_aggregate_backward_f32(
+            messages.data_ptr(), _ld(messages), plan.rowptr.data_ptr(), plan.perm.data_ptr(), N, M, float(delta),
+            agg.data_ptr(), _ld(agg), argmax.contiguous().data_ptr(), argmin.contiguous().data_ptr(),
+            grad.data_ptr(), _ld(grad), out.data_ptr(), M, PNA_ROUND[round_to], E, _stream(out))
+    _lib.check(rc, "ptgnn_amd_pna_aggregate_backward_f32")
+    return out
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,

@@ -86,6 +86,39 @@ def segment_reduce(messages: torch.Tensor, plan: "ops.GraphPlan", reduce: str) -
     return _SegmentReduce.apply(messages, plan, reduce)
 
 
+class _PnaAggregate(torch.autograd.Function):
+    """PNA aggregation (pna_aggregation.py:27-56) of [E, M] messages (message order) over a plan -> [N, 15M]: forward
+    the fused HIP launch with its argmax / argmin, backward the one-pass HIP kernel (ops.pna_aggregate_backward)."""
+
+    @staticmethod
+    def forward(ctx, messages, plan, delta, round_to):
+        M = messages.shape[1]
+        # half / bfloat16 messages: the output carries A rounded to that dtype, the backward needs A unrounded
+        raw = None if round_to == torch.float32 else \
+            torch.empty(plan.num_nodes, 5 * M, dtype=torch.float32, device=messages.device)
+        out, amax, amin = ops.pna_aggregate(messages, plan, M, delta, type_bits=0, col=plan.perm, return_arg=True,
+                                            round_to=round_to, agg_out=raw)
+        ctx.plan, ctx.delta, ctx.round_to = plan, delta, round_to
+        ctx.save_for_backward(messages, out if raw is None else raw, amax, amin)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        messages, agg, amax, amin = ctx.saved_tensors
+        g = ops.pna_aggregate_backward(messages, ctx.plan, agg, amax, amin, grad_out.contiguous(), ctx.delta,
+                                       round_to=ctx.round_to)
+        return g, None, None, None
+
+
+def pna_aggregate(messages: torch.Tensor, plan: "ops.GraphPlan", delta: float = 1.0,
+                  round_to: torch.dtype = torch.float32) -> torch.Tensor:
+    """Differentiable PNA aggregation of fp32 [E, M] messages in the plan's message order (type-major)."""
+    msg = messages if messages.shape[0] > 0 else messages.new_zeros(1, messages.shape[1])
+    if not messages.requires_grad or not torch.is_grad_enabled():
+        return ops.pna_aggregate(msg, plan, messages.shape[1], delta, type_bits=0, col=plan.perm, round_to=round_to)
+    return _PnaAggregate.apply(messages, plan, float(delta), round_to)
+
+
 def _prepare(src: torch.Tensor, index: torch.Tensor, dim: int, out, dim_size):
     """Common argument handling of the torch_scatter-shaped entry points: 2-D (or 1-D) `src`, 1-D int64
     `index` along dim 0.  Anything else raises (no silent fallback)."""

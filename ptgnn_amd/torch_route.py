@@ -228,6 +228,27 @@ def aggregate(messages: torch.Tensor, targets: torch.Tensor, num_nodes: int, red
     return segment(messages.to(torch.float32), targets, int(num_nodes), reduce).to(messages.dtype)
 
 
+def pna_aggregate(messages: torch.Tensor, targets: torch.Tensor, num_nodes: int, delta: float = 1) -> torch.Tensor:
+    """pna_aggregation.py:27-56 on host tensors, in the reference's operator order: fp32 sum / mean / max / min / "std"
+    of the messages per target, cast to the message dtype, then the degree scalers (the result promotes to float32
+    for half / bfloat16 messages, as there)."""
+    _host_only(messages, targets)
+    n = int(num_nodes)
+    degree = segment(torch.ones_like(targets).unsqueeze(1), targets, n, "sum").squeeze(1)
+    msg_dtype = messages.dtype
+    m = messages.to(torch.float32)
+    sum_agg = segment(m, targets, n, "sum")
+    mean_agg = sum_agg / (degree.unsqueeze(-1) + 1e-5)
+    max_agg = segment(m, targets, n, "max")
+    min_agg = segment(m, targets, n, "min")
+    std_components = torch.relu(m.pow(2) - mean_agg[targets].pow(2)) + 1e-10
+    std = torch.sqrt(segment(std_components, targets, n, "sum"))
+    all_aggregations = torch.cat([sum_agg, mean_agg, max_agg, min_agg, std], dim=-1).to(msg_dtype)
+    scaler_p1 = torch.log(degree.float() + 1).unsqueeze(-1) / delta
+    scaler_m1 = 1 / (scaler_p1 + 1e-3)
+    return torch.cat([all_aggregations, all_aggregations * scaler_p1, all_aggregations * scaler_m1], dim=-1)
+
+
 def _message_inputs(node_states, adjacency_lists, edge_features, with_target: bool):
     for (src, dst), feats in zip(adjacency_lists, edge_features):
         parts = [node_states.index_select(0, src)]
