@@ -525,10 +525,17 @@ __device__ __forceinline__ void hub_chunks_body(const Args &a, int first, int st
     // partial slot of this (chunk, row): 0 if the hub owns the chunk's first slot, else 1
     const int which = rbeg <= cbeg ? 0 : 1;
     Op op(a, g, cbase);
-    // the chunk's slots are interleaved over the lane groups (stride G); same prefetched groups of 8 as the main kernel
+    // the chunk's slots are interleaved over the lane groups (stride G); same prefetched groups of 8 as the main kernel.
+    // max / min without an arg have nothing to break a tie of -0.0 and +0.0 with when the partials combine: there each
+    // lane group folds a contiguous run of the chunk instead, so the fixed combine order below is slot order and the
+    // earliest slot's zero stays, as in the serial fold (torch_scatter)
     constexpr int UP = (VEC == 4 && !MASKED && !HAS_DST && CH == 1) ? (FUSED ? 4 : 8) : 0;
-    if constexpr (UP == 0) op.reduce(row, sbeg + grp, send, G);
-    else op.template reduce_pf<UP>(row, sbeg + grp, send, G);
+    constexpr bool kRuns = (REDUCE == PTGNN_AMD_MAX || REDUCE == PTGNN_AMD_MIN) && !HAS_ARG;
+    const int per = kRuns ? (send - sbeg + G - 1) / G : 0;
+    const int rb = kRuns ? sbeg + grp * per : sbeg + grp;
+    const int re = kRuns ? (rb + per < send ? rb + per : send) : send;
+    if constexpr (UP == 0) op.reduce(row, rb, re, kRuns ? 1 : G);
+    else op.template reduce_pf<UP>(row, rb, re, kRuns ? 1 : G);
     __syncthreads();  // the previous entry's readers are done with the staging arrays
 #pragma unroll
     for (int c = 0; c < CH; ++c)

@@ -14,12 +14,12 @@ import pytest
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
+from agg_paths import TOL, attributed_ok, pna_ref
 from helpers import to_cuda_adj
 from oracle.fixtures import unpack_adj
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-5
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 LAYER_FIXTURES = sorted(f for f in glob.glob(os.path.join(GOLDEN, "pna_*.npz"))
                         if not f.endswith(("pna_stack.npz", "pna_module.npz")))
@@ -32,43 +32,6 @@ def load(path):
 
 def prefixed(fx, prefix):
     return {k[len(prefix):]: torch.from_numpy(v) for k, v in fx.items() if k.startswith(prefix)}
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# float64 restatement of pna_aggregation.py:27-56 (torch_scatter semantics: one winner per max / min, the first in
-# message order; any dtype, any device)
-# ---------------------------------------------------------------------------------------------------------------------
-def _winner(m, t, n, best):
-    E, M = m.shape
-    pos = torch.arange(E, device=m.device).unsqueeze(1).expand(E, M)
-    cand = torch.where(m.detach() == best.index_select(0, t), pos, torch.full_like(pos, E))
-    arg = torch.full((n, M), E, dtype=torch.int64, device=m.device)
-    return arg.scatter_reduce_(0, t.unsqueeze(1).expand(E, M), cand, "amin", include_self=True)
-
-
-def _extreme(m, t, n, red):
-    E, M = m.shape
-    with torch.no_grad():
-        best = torch.zeros(n, M, dtype=m.dtype, device=m.device).scatter_reduce_(
-            0, t.unsqueeze(1).expand(E, M), m.detach(), red, include_self=False)
-        arg = _winner(m, t, n, best)
-    if E == 0:
-        return torch.zeros(n, M, dtype=m.dtype, device=m.device)
-    return torch.where(arg < E, m.gather(0, arg.clamp(max=E - 1)), torch.zeros((), dtype=m.dtype, device=m.device))
-
-
-def pna_ref(m, t, n, delta):
-    """The reference's operator sequence in the dtype of `m`."""
-    M = m.shape[1]
-    deg = torch.zeros(n, dtype=m.dtype, device=m.device).index_add_(0, t, torch.ones(t.shape[0], dtype=m.dtype,
-                                                                                       device=m.device))
-    s = torch.zeros(n, M, dtype=m.dtype, device=m.device).index_add(0, t, m)
-    mean = s / (deg.unsqueeze(-1) + 1e-5)
-    comp = torch.relu(m.pow(2) - mean[t].pow(2)) + 1e-10
-    std = torch.sqrt(torch.zeros(n, M, dtype=m.dtype, device=m.device).index_add(0, t, comp))
-    A = torch.cat([s, mean, _extreme(m, t, n, "amax"), _extreme(m, t, n, "amin"), std], dim=-1)
-    s1 = torch.log(deg + 1).unsqueeze(-1) / delta
-    return torch.cat([A, A * s1, A * (1 / (s1 + 1e-3))], dim=-1)
 
 
 class Pna64(torch.nn.Module):
@@ -88,16 +51,6 @@ def restated(layer, dtype):
     assert isinstance(agg, PnaMessageAggregation)
     ref._MlpMessagePassingLayer__aggregation_fn = Pna64(agg._delta)
     return ref
-
-
-def attributed_ok(got, want32, exact, tol=TOL, scale=1.0):
-    """|got - fp32 reference| <= tol, or |got - float64| <= max(tol, 2 |fp32 reference - float64|) (all scaled)."""
-    got, want32, exact = (torch.as_tensor(v).detach().double().cpu() for v in (got, want32, exact))
-    if float((got - want32).abs().max()) <= tol * scale:
-        return True
-    ref_err = float((want32 - exact).abs().max())
-    err = float((got - exact).abs().max())
-    return err <= max(tol * scale, 2.0 * ref_err)
 
 
 def call(layer, x, adj):
