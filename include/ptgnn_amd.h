@@ -130,6 +130,9 @@ enum {
   PTGNN_AMD_KERNEL_EGC_COMBINE_BACKWARD,
   PTGNN_AMD_KERNEL_PNA_AGGREGATE,          /* ptgnn_amd_pna_aggregate_f32 */
   PTGNN_AMD_KERNEL_PNA_AGGREGATE_BACKWARD, /* ptgnn_amd_pna_aggregate_backward_f32 */
+  PTGNN_AMD_KERNEL_ATTENTION_POOL,          /* ptgnn_amd_attention_pool_f32 */
+  PTGNN_AMD_KERNEL_ATTENTION_POOL_BACKWARD, /* ptgnn_amd_attention_pool_backward_f32 */
+  PTGNN_AMD_KERNEL_HEAD_PROJECTION,         /* ptgnn_amd_head_projection_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -619,6 +622,52 @@ int ptgnn_amd_weighted_pool_backward_f32(const float *x, int64_t ld_x, const flo
                                          const float *grad_out, int64_t ld_go, int64_t num_elements, int32_t dim,
                                          float *grad_x, int64_t ld_gx, float *grad_w, void *workspace,
                                          size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Attention pooling of elements into samples, `heads` softmax heads over the same element rows:
+ *   s[i,h] = u[g,h,:] . x[i,:]  (g = map[i]),   p[i,h] = exp(s[i,h] - lse[g,h]),   out[g,h,:] = sum_{i : map[i] == g} p[i,h] x[i,:]
+ * Replaces: SelfAttentionVarSizedElementReduce.forward and MultiheadSelfAttentionVarSizedElementReduce.forward,
+ *   ptgnn/neuralmodels/reduceops/varsizedsummary.py:99-113 and :140-178 -- `queries[map]`, the key `nn.Linear` over all
+ *   elements, the einsum, `exp(scatter_log_softmax(eps=0))`, the broadcast multiply that materialises [N, heads * D] and
+ *   `scatter_sum` -- as used by the Graph2Seq summariser (graph2seq/graph2seq.py:56-66,116-122).  The key Linear moves
+ *   onto the samples: u = c * blockdiag(q) W_k (ptgnn_amd_head_projection_f32, mode 0), c = 1 / sqrt(hidden / heads)
+ *   for the multi-head class and 1 for the single-head one.  One pass over x: online softmax per 128-row chunk counted
+ *   from the sample's own start, chunks merged in chunk order (no float atomics; deterministic).
+ *   x [num_elements, dim] (ld_x), u [num_segments, heads, dim] contiguous, rowptr / perm: the stable plan of the map
+ *   (as ptgnn_amd_weighted_pool_f32), out [num_segments, heads, dim] contiguous, stats [num_segments, 2 * heads]: per
+ *   (g, h) the max score and the log-sum-exp (0 for a sample without elements, whose out rows are 0).
+ *   1 <= heads <= 8 and dim <= 1024 (ptgnn_amd_attention_pool_supported), else EUNSUPPORTED.
+ *   workspace: ptgnn_amd_attention_pool_workspace_bytes.
+ * Backward (one pass over x): from grad_out = dL/dout [num_segments, heads, dim] and the forward's out and stats,
+ *   grad_x [num_elements, dim] (ld_gx; every element of the plan OVERWRITTEN) and grad_u [num_segments, heads, dim]
+ *   (deterministic: chunk partials folded in chunk order).  workspace: ptgnn_amd_attention_pool_backward_workspace_bytes.
+ * ptgnn_amd_head_projection_f32: the per-head block products around the pool, on [rows, ...] tensors (dk = head_dim,
+ *   hidden = heads * dk, w [hidden, dim], all contiguous):
+ *   mode 0  out[g,h,:] = scale * w[h*dk:(h+1)*dk, :]^T a[g, h*dk:(h+1)*dk]   a [rows, hidden] -> out [rows, heads, dim]
+ *           (the key projection of the queries; the input gradient of mode 1)
+ *   mode 1  out[g, j]  = scale * w[j, :] . b[g, j / dk, :]                    b [rows, heads, dim] -> out [rows, hidden]
+ *           (the value Linear on the pools, varsizedsummary.py:161-166; the input gradient of mode 0)
+ *   mode 2  out[j, :]  = scale * sum_g a[g, j] b[g, j / dk, :]                 -> out [hidden, dim], a fixed order
+ *           (the weight gradient of modes 0 and 1)
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_attention_pool_supported(int32_t dim, int32_t num_heads);
+size_t ptgnn_amd_attention_pool_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim,
+                                                int32_t num_heads);
+int ptgnn_amd_attention_pool_f32(const float *x, int64_t ld_x, const float *u, const int32_t *rowptr,
+                                 const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                 int32_t num_heads, float *out, float *stats, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t ptgnn_amd_attention_pool_backward_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim,
+                                                         int32_t num_heads);
+int ptgnn_amd_attention_pool_backward_f32(const float *x, int64_t ld_x, const float *u, const int32_t *rowptr,
+                                          const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                          int32_t num_heads, const float *out, const float *stats,
+                                          const float *grad_out, float *grad_x, int64_t ld_gx, float *grad_u,
+                                          void *workspace, size_t workspace_bytes, void *stream);
+int ptgnn_amd_head_projection_f32(int mode, const float *a /* nullable in mode 1 */,
+                                  const float *b /* nullable in mode 0 */, const float *w /* nullable in mode 2 */,
+                                  int64_t num_rows, int32_t num_heads, int32_t head_dim, int32_t dim, float scale,
+                                  float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * EGC-S layer (egcmessagepassing.py:63-91; aggregation abstractmessagepassing.py:38-50), K heads, B bases,

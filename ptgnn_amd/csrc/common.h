@@ -58,4 +58,15 @@ inline int64_t xcd_padded_blocks(int64_t nblocks) {
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Segment pools cut every segment of a plan into chunks of kPoolChunkRows rows counted from the segment's own start and
+// add the chunk partials in chunk order (weighted_pool.hip; attention_pool.hip uses the same chunk table and fold).
+constexpr int kPoolChunkRows = 128;
+int64_t pool_chunk_count_bound(int64_t segments, int64_t elements);   // upper bound of the chunks of a plan
+size_t pool_chunk_table_bytes(int64_t segments);                     // int32 chunk_start[segments + 1], padded
+// chunk_start[g] = chunks of the segments in front of g, chunk_start[G] = all chunks (one workgroup)
+void launch_pool_chunk_starts(const int32_t *rowptr, int num_segments, int32_t *chunk_start, hipStream_t st);
+// out[g, :dim] = partial rows chunk_start[g] .. chunk_start[g + 1] - 1 added in chunk order (0 for an empty segment)
+void launch_fold_segments(const float *partial, const int32_t *chunk_start, int dim, int64_t segments, float *out,
+                          int64_t ld_out, hipStream_t st);
+
 }  // namespace ptgnn_amd

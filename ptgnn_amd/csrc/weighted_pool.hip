@@ -42,7 +42,7 @@ __device__ __forceinline__ float group_sum(float v, int lanes) {
 constexpr int kPoolThreads = 256;
 // COLS = chunks (float4 or float) of one row a lane holds: 1 for dim <= lanes * VEC (hidden 64 ... 256), up to 16
 
-constexpr int kPoolChunk = 128;       // rows of one chunk, counted from the start of its segment
+constexpr int kPoolChunk = kPoolChunkRows;   // rows of one chunk, counted from the start of its segment
 
 // chunk_start[g] = chunks of the segments in front of g (chunk_start[G] = all chunks); one workgroup
 __global__ __launch_bounds__(1024) void k_pool_chunk_starts(const int32_t *__restrict__ rowptr, int num_segments,
@@ -291,6 +291,22 @@ int64_t pool_chunk_bound(int64_t segments, int64_t elements) { return elements /
 size_t pool_starts_bytes(int64_t segments) { return (size_t)((segments + 1 + 3) / 4 * 4) * sizeof(int32_t); }
 
 }  // namespace
+
+int64_t pool_chunk_count_bound(int64_t segments, int64_t elements) { return pool_chunk_bound(segments, elements); }
+
+size_t pool_chunk_table_bytes(int64_t segments) { return pool_starts_bytes(segments); }
+
+void launch_pool_chunk_starts(const int32_t *rowptr, int num_segments, int32_t *chunk_start, hipStream_t st) {
+  k_pool_chunk_starts<<<1, 1024, 0, st>>>(rowptr, num_segments, chunk_start);
+}
+
+void launch_fold_segments(const float *partial, const int32_t *chunk_start, int dim, int64_t segments, float *out,
+                          int64_t ld_out, hipStream_t st) {
+  const int64_t total = segments * dim;
+  if (total > 0)
+    k_fold_segments<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(partial, chunk_start, dim, segments, out, ld_out);
+}
+
 }  // namespace ptgnn_amd
 
 using namespace ptgnn_amd;

@@ -1675,3 +1675,132 @@ def weighted_pool_backward(x: torch.Tensor, w: torch.Tensor, index: torch.Tensor
                                                       ws_bytes, _stream(gx))
     _lib.check(rc, "ptgnn_amd_weighted_pool_backward_f32")
     return gx, gw
+
+
+def attention_pool_supported(dim: int, num_heads: int) -> bool:
+    """Whether the fused attention pool takes (dim, heads) (ptgnn_amd_attention_pool_supported: heads <= 8, dim <= 1024)."""
+    return bool(_lib.load().ptgnn_amd_attention_pool_supported(int(dim), int(num_heads)))
+
+
+def _attention_pool_args(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, what: str):
+    _require_cuda_f32("x", x)
+    _require_cuda_f32("u", u, dims=3)
+    x = _rowmajor(x)
+    n, d = x.shape
+    G, H = plan.num_nodes, u.shape[1]
+    if n != plan.num_edges or tuple(u.shape) != (G, H, d) or plan.perm is None:
+        raise _lib.PtgnnAmdError(f"{what}: x {tuple(x.shape)}, u {tuple(u.shape)} do not fit a plan of "
+                                 f"{plan.num_edges} elements in {G} samples")
+    return x, u.contiguous(), n, d, G, H
+
+
+def attention_pool(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan):
+    """Multi-head segment-softmax pool over the plan of an element -> sample map (ptgnn_amd_attention_pool_f32):
+        s[i,h] = u[g(i),h] . x_i,   p = softmax of s[., h] within each sample,   P[g,h] = sum_{i in g} p[i,h] x_i
+    in one pass over x.  Returns (P [G, heads, D], stats [G, 2 * heads] = per-(g, h) max score | log-sum-exp)."""
+    lib = _lib.load()
+    x, u, n, d, G, H = _attention_pool_args(x, u, plan, "attention_pool")
+    out = torch.empty(G, H, d, dtype=torch.float32, device=x.device)
+    stats = torch.empty(G, 2 * H, dtype=torch.float32, device=x.device)
+    if G == 0:
+        return out, stats
+    ws_bytes = int(lib.ptgnn_amd_attention_pool_workspace_bytes(G, n, d, H))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    plan.wait()
+    with _timed("attention_pool", bytes=4.0 * (n * d + 2 * G * H * d) + 4.0 * n):
+        rc = lib.ptgnn_amd_attention_pool_f32(x.data_ptr() if n else None, _ld(x) if n else d, u.data_ptr(),
+                                              plan.rowptr.data_ptr(), plan.perm.data_ptr() if n else None, G, n, d, H,
+                                              out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws_bytes, _stream(out))
+    _lib.check(rc, "ptgnn_amd_attention_pool_f32")
+    return out, stats
+
+
+def attention_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, pooled: torch.Tensor,
+                            stats: torch.Tensor, grad_out: torch.Tensor):
+    """(grad_x [n, D], grad_u [G, heads, D]) of `attention_pool` from grad_out = dL/dP [G, heads, D] and the forward's P
+    and stats (ptgnn_amd_attention_pool_backward_f32: one pass over x, grad_u folded in a fixed order)."""
+    lib = _lib.load()
+    x, u, n, d, G, H = _attention_pool_args(x, u, plan, "attention_pool_backward")
+    _require_cuda_f32("grad_out", grad_out, dims=3)
+    pooled, stats, grad_out = pooled.contiguous(), stats.contiguous(), grad_out.contiguous()
+    if tuple(grad_out.shape) != (G, H, d) or tuple(pooled.shape) != (G, H, d) or tuple(stats.shape) != (G, 2 * H):
+        raise _lib.PtgnnAmdError(f"attention_pool_backward: grad_out {tuple(grad_out.shape)} / pooled "
+                                 f"{tuple(pooled.shape)} / stats {tuple(stats.shape)} do not match ({G}, {H}, {d})")
+    gx = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    gu = torch.empty(G, H, d, dtype=torch.float32, device=x.device)
+    if G == 0:
+        return gx, gu
+    ws_bytes = int(lib.ptgnn_amd_attention_pool_backward_workspace_bytes(G, n, d, H))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    plan.wait()
+    with _timed("attention_pool_backward", bytes=4.0 * (2 * n * d + 4 * G * H * d) + 4.0 * n):
+        rc = lib.ptgnn_amd_attention_pool_backward_f32(
+            x.data_ptr() if n else None, _ld(x) if n else d, u.data_ptr(), plan.rowptr.data_ptr(),
+            plan.perm.data_ptr() if n else None, G, n, d, H, pooled.data_ptr(), stats.data_ptr(), grad_out.data_ptr(),
+            gx.data_ptr() if n else None, d, gu.data_ptr(), ws.data_ptr(), ws_bytes, _stream(gu))
+    _lib.check(rc, "ptgnn_amd_attention_pool_backward_f32")
+    return gx, gu
+
+
+HEAD_EXPAND, HEAD_CONTRACT, HEAD_WEIGHT_GRAD = 0, 1, 2    # modes of ptgnn_amd_head_projection_f32
+
+
+def _head_projection(mode: int, a, b, w, rows: int, heads: int, head_dim: int, dim: int, scale: float,
+                     out: torch.Tensor) -> torch.Tensor:
+    lib = _lib.load()
+    with _timed("head_projection", flops=2.0 * rows * heads * head_dim * dim):
+        rc = lib.ptgnn_amd_head_projection_f32(mode, a.data_ptr() if a is not None and a.numel() else None,
+                                               b.data_ptr() if b is not None and b.numel() else None,
+                                               w.data_ptr() if w is not None else None, rows, heads, head_dim, dim,
+                                               float(scale), out.data_ptr() if out.numel() else None, _stream(out))
+    _lib.check(rc, "ptgnn_amd_head_projection_f32")
+    return out
+
+
+def _head_dims(hidden: int, num_heads: int, what: str) -> Tuple[int, int]:
+    H = int(num_heads)
+    if H <= 0 or hidden % H:
+        raise _lib.PtgnnAmdError(f"{what}: {hidden} columns do not split into {H} heads")
+    return H, hidden // H
+
+
+def head_expand(a: torch.Tensor, w: torch.Tensor, num_heads: int, scale: float = 1.0) -> torch.Tensor:
+    """out[g, h, :] = scale * W[h*dk:(h+1)*dk, :]^T a[g, h*dk:(h+1)*dk]: a [G, hidden], W [hidden, D] -> [G, heads, D]
+    (the key projection of the queries, varsizedsummary.py:151-158 moved onto the samples)."""
+    _require_cuda_f32("a", a)
+    _require_cuda_f32("w", w)
+    a, w = a.contiguous(), w.contiguous()
+    G, hidden = a.shape
+    H, dk = _head_dims(hidden, num_heads, "head_expand")
+    if w.shape[0] != hidden:
+        raise _lib.PtgnnAmdError(f"head_expand: a {tuple(a.shape)} and W {tuple(w.shape)} do not match")
+    out = torch.empty(G, H, w.shape[1], dtype=torch.float32, device=a.device)
+    return _head_projection(HEAD_EXPAND, a, None, w, G, H, dk, w.shape[1], scale, out)
+
+
+def head_contract(b: torch.Tensor, w: torch.Tensor, num_heads: int, scale: float = 1.0) -> torch.Tensor:
+    """out[g, h*dk + k] = scale * W[h*dk + k, :] . b[g, h, :]: b [G, heads, D], W [hidden, D] -> [G, hidden]
+    (the value Linear of the multi-head reducer applied to the pools, varsizedsummary.py:161-166)."""
+    _require_cuda_f32("b", b, dims=3)
+    _require_cuda_f32("w", w)
+    b, w = b.contiguous(), w.contiguous()
+    G, H, D = b.shape
+    _, dk = _head_dims(w.shape[0], H, "head_contract")
+    if w.shape[1] != D:
+        raise _lib.PtgnnAmdError(f"head_contract: b {tuple(b.shape)} and W {tuple(w.shape)} do not match")
+    out = torch.empty(G, w.shape[0], dtype=torch.float32, device=b.device)
+    return _head_projection(HEAD_CONTRACT, None, b, w, G, H, dk, D, scale, out)
+
+
+def head_weight_grad(a: torch.Tensor, b: torch.Tensor, num_heads: int, scale: float = 1.0) -> torch.Tensor:
+    """grad_W[h*dk + k, :] = scale * sum_g a[g, h*dk + k] b[g, h, :]: a [G, hidden], b [G, heads, D] -> [hidden, D], the
+    samples added in a fixed order (the weight gradient of `head_expand` and `head_contract`)."""
+    _require_cuda_f32("a", a)
+    _require_cuda_f32("b", b, dims=3)
+    a, b = a.contiguous(), b.contiguous()
+    G, hidden = a.shape
+    H, dk = _head_dims(hidden, num_heads, "head_weight_grad")
+    if b.shape[0] != G or b.shape[1] != H:
+        raise _lib.PtgnnAmdError(f"head_weight_grad: a {tuple(a.shape)} and b {tuple(b.shape)} do not match")
+    out = torch.empty(hidden, b.shape[2], dtype=torch.float32, device=a.device)
+    return _head_projection(HEAD_WEIGHT_GRAD, a, b, None, G, H, dk, b.shape[2], scale, out)

@@ -1,5 +1,5 @@
 """Node -> graph pooling ("var-sized element reduce") and the global-exchange layer that uses it:
-mirrors of ptgnn/neuralmodels/reduceops/varsizedsummary.py:11-81 and
+mirrors of ptgnn/neuralmodels/reduceops/varsizedsummary.py:11-41,67-178 and
 ptgnn/neuralmodels/gnn/messagepassing/globalgraphexchange.py (same class names, constructor keywords
 and name-mangled parameter names), used by the VarMisuse GGNN stack (varmisuse/train.py:76-107).
 
@@ -7,13 +7,14 @@ The pooling is the same segment reduce as message aggregation with `node_to_grap
 A disjoint-union batch lists the nodes of graph 0, then graph 1, ... (graphneuralnetwork.py:418-423),
 so the index is SORTED and the plan needs no sort at all: rowptr = searchsorted, col = identity.
 """
+import math
 import weakref
-from typing import NamedTuple, Union
+from typing import NamedTuple, Optional, Union
 
 import torch
 from torch import nn
 
-from ptgnn_amd import _lib, dense, ops, torch_route
+from ptgnn_amd import _lib, dense, ops, scatter as scatter_facade, torch_route
 from ptgnn_amd.layers import AbstractMessagePassingLayer, _check_device, _no_grad_needed
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_reduce
 
@@ -117,6 +118,154 @@ class WeightedSumVarSizedElementReduce(AbstractVarSizedElementReduce):
         if _no_grad_needed(xf, wf):
             return ops.weighted_pool(xf, wf, plan).to(dt)
         return _WeightedPool.apply(xf, wf, index, plan).to(dt)
+
+
+class _AttentionPool(torch.autograd.Function):
+    """P[g,h] = sum_{i in g} softmax_g(u[g,h] . x_i) x_i over the plan of the element -> sample map as ONE node: forward
+    and backward are the two passes of csrc/attention_pool.hip (no [N, heads * D] tensor, deterministic grad_u)."""
+
+    @staticmethod
+    def forward(ctx, x, u, plan):
+        pooled, stats = ops.attention_pool(x, u, plan)
+        ctx.plan = plan
+        ctx.save_for_backward(x, u, pooled, stats)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, u, pooled, stats = ctx.saved_tensors
+        gx, gu = ops.attention_pool_backward(x, u, ctx.plan, pooled, stats, grad.contiguous())
+        return gx, gu, None
+
+
+class _HeadExpand(torch.autograd.Function):
+    """u[g,h] = scale * W[h-block]^T q[g, h-block] (ops.head_expand); backward: dq = head_contract(du, W),
+    dW = head_weight_grad(q, du)."""
+
+    @staticmethod
+    def forward(ctx, a, w, num_heads, scale):
+        ctx.save_for_backward(a, w)
+        ctx.num_heads, ctx.scale = num_heads, scale
+        return ops.head_expand(a, w, num_heads, scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, w = ctx.saved_tensors
+        g = g.contiguous()
+        da = ops.head_contract(g, w, ctx.num_heads, ctx.scale) if ctx.needs_input_grad[0] else None
+        dw = ops.head_weight_grad(a, g, ctx.num_heads, ctx.scale) if ctx.needs_input_grad[1] else None
+        return da, dw, None, None
+
+
+class _HeadContract(torch.autograd.Function):
+    """v[g, h-block] = W[h-block] P[g,h] (ops.head_contract: the value Linear on the pools); backward:
+    dP = head_expand(dv, W), dW = head_weight_grad(dv, P)."""
+
+    @staticmethod
+    def forward(ctx, b, w, num_heads):
+        ctx.save_for_backward(b, w)
+        ctx.num_heads = num_heads
+        return ops.head_contract(b, w, num_heads)
+
+    @staticmethod
+    def backward(ctx, g):
+        b, w = ctx.saved_tensors
+        g = g.contiguous()
+        db = ops.head_expand(g, w, ctx.num_heads) if ctx.needs_input_grad[0] else None
+        dw = ops.head_weight_grad(g, b, ctx.num_heads) if ctx.needs_input_grad[1] else None
+        return db, dw, None
+
+
+def _composed_attention_summary(x, index, plan, num_samples: int, queries, key_weight, value_weight, output_weight,
+                                num_heads: int, single_head: bool) -> torch.Tensor:
+    """Shapes beyond the fused pool (more than 8 heads, D > 1024): the reference's operator sequence on the package's
+    other HIP entry points -- dense.linear, the row gather, the facade's segment log-softmax and segment sums."""
+    n, hidden = x.shape[0], key_weight.shape[0]
+    keys = dense.linear(x, key_weight)                                            # [N, hidden]
+    queries_all = gather_rows_autograd(queries.contiguous(), index, plan)          # [N, hidden]
+    if single_head:
+        scores = (queries_all * keys).sum(-1)
+    else:
+        dk = hidden // num_heads
+        scores = (queries_all * keys).reshape(n, num_heads, dk).sum(-1) / math.sqrt(dk)
+    probs = scatter_facade.scatter_log_softmax(scores, index, dim=0, eps=0.0, dim_size=num_samples).exp()
+    if single_head:
+        return scatter_facade.scatter_sum(dense.linear(x, output_weight) * probs.unsqueeze(-1), index, dim=0,
+                                          dim_size=num_samples)
+    if value_weight is not None:
+        rows = probs.unsqueeze(-1) * dense.linear(x, value_weight).reshape(n, num_heads, hidden // num_heads)
+    else:
+        rows = probs.unsqueeze(-1) * x.unsqueeze(1)
+    per_sample = scatter_facade.scatter_sum(rows.reshape(n, -1), index, dim=0, dim_size=num_samples)
+    return dense.linear(per_sample, output_weight)
+
+
+def _attention_summary(inputs, queries: torch.Tensor, key_weight: torch.Tensor, value_weight: Optional[torch.Tensor],
+                       output_weight: torch.Tensor, num_heads: int, single_head: bool) -> torch.Tensor:
+    """The attention reducers after their query summariser.  GPU: u = c * blockdiag(q) W_k on the samples, the softmax
+    pool in one HIP pass over the elements, the value / output Linears on the [G, ...] pools (csrc/attention_pool.hip
+    header); fp16 / bf16 elements are pooled in fp32 and cast back."""
+    x, index = inputs.element_embeddings, inputs.element_to_sample_map
+    G = int(inputs.num_samples)
+    if not x.is_cuda:       # device dispatch: the reference's own operator sequence
+        return torch_route.attention_summary(x, index, G, queries, key_weight, value_weight, output_weight, num_heads,
+                                             single_head)
+    dt = x.dtype
+    xf, q = x.to(torch.float32), queries.to(torch.float32)
+    wk, wo = key_weight.to(torch.float32), output_weight.to(torch.float32)
+    wv = value_weight.to(torch.float32) if value_weight is not None else None
+    plan = _index_plan(index, G)
+    hidden, D = wk.shape
+    if not ops.attention_pool_supported(D, num_heads):
+        return _composed_attention_summary(xf, index, plan, G, q, wk, wv, wo, num_heads, single_head).to(dt)
+    scale = 1.0 if single_head else 1.0 / math.sqrt(hidden // num_heads)
+    u = _HeadExpand.apply(q.contiguous(), wk, num_heads, scale)                 # [G, heads, D]
+    pooled = _AttentionPool.apply(xf, u, plan)                                  # [G, heads, D]
+    if wv is not None:
+        pooled = _HeadContract.apply(pooled, wv, num_heads)                     # [G, hidden]
+    return dense.linear(pooled.reshape(G, -1), wo).to(dt)
+
+
+class SelfAttentionVarSizedElementReduce(AbstractVarSizedElementReduce):
+    """varsizedsummary.py:84-113 (same constructor keywords, submodule order and name-mangled parameter names)."""
+
+    def __init__(self, input_representation_size: int, hidden_size: int, output_representation_size: int,
+                 query_representation_summarizer: AbstractVarSizedElementReduce):
+        super().__init__()
+        self.__query_layer = query_representation_summarizer
+        self.__key_layer = nn.Linear(input_representation_size, hidden_size, bias=False)
+        self.__output_layer = nn.Linear(input_representation_size, output_representation_size, bias=False)
+
+    def forward(self, inputs: ElementsToSummaryRepresentationInput) -> torch.Tensor:
+        queries = self.__query_layer(inputs)                                     # [num_samples, hidden]
+        return _attention_summary(inputs, queries, self.__key_layer.weight, None, self.__output_layer.weight, 1, True)
+
+
+class MultiheadSelfAttentionVarSizedElementReduce(AbstractVarSizedElementReduce):
+    """varsizedsummary.py:116-178 (same constructor keywords, submodule order and name-mangled parameter names); the
+    summariser of the Graph2Seq task (graph2seq/graph2seq.py:116-122)."""
+
+    def __init__(self, input_representation_size: int, hidden_size: int, output_representation_size: int,
+                 num_heads: int, query_representation_summarizer: AbstractVarSizedElementReduce,
+                 use_value_layer: bool = False):
+        super().__init__()
+        self.__query_layer = query_representation_summarizer
+        self.__key_layer = nn.Linear(input_representation_size, hidden_size, bias=False)
+        assert hidden_size % num_heads == 0, "Hidden size must be divisible by the number of heads."
+        self.__use_value_layer = use_value_layer
+        if use_value_layer:
+            self.__value_layer = nn.Linear(input_representation_size, hidden_size, bias=False)
+            self.__output_layer = nn.Linear(hidden_size, output_representation_size, bias=False)
+        else:
+            self.__output_layer = nn.Linear(input_representation_size * num_heads, output_representation_size,
+                                            bias=False)
+        self.__num_heads = num_heads
+
+    def forward(self, inputs: ElementsToSummaryRepresentationInput) -> torch.Tensor:
+        queries = self.__query_layer(inputs)                                     # [num_samples, hidden]
+        value_weight = self.__value_layer.weight if self.__use_value_layer else None
+        return _attention_summary(inputs, queries, self.__key_layer.weight, value_weight, self.__output_layer.weight,
+                                  self.__num_heads, False)
 
 
 class AbstractGlobalGraphExchange(AbstractMessagePassingLayer):

@@ -17,6 +17,7 @@ globalgraphexchange.py:29-45, residuallayers.py) and torch_scatter 2.0.x's publi
 from `oracle/` (the test-side restatement), and `tests/dropin_check.py` compares it with the reference's own
 layers on the reference's own container and batcher.
 """
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -304,3 +305,32 @@ def egc_layer(node_states, adjacency_lists, edge_features, bases: Sequence[nn.Li
     agg = aggregate(msgs.reshape(msgs.shape[0], -1), torch.cat(targets, dim=0), node_states.shape[0], reduce)
     agg = agg.reshape(-1, num_heads, num_bases, output_dim // num_heads)
     return (agg * node_weights).sum(axis=-2).reshape(-1, output_dim)
+
+
+def attention_summary(x: torch.Tensor, index: torch.Tensor, num_samples: int, queries: torch.Tensor,
+                      key_weight: torch.Tensor, value_weight: Optional[torch.Tensor], output_weight: torch.Tensor,
+                      num_heads: int, single_head: bool) -> torch.Tensor:
+    """SelfAttentionVarSizedElementReduce.forward (varsizedsummary.py:99-113, `single_head`) and
+    MultiheadSelfAttentionVarSizedElementReduce.forward (:140-178) after the query summariser, in the reference's
+    operator order on host tensors."""
+    _host_only(x, index, queries)
+    F = nn.functional
+    n = int(num_samples)
+    queries_all = queries[index]                                                   # [N, hidden]
+    keys = F.linear(x, key_weight)                                                 # [N, hidden]
+    if single_head:
+        scores = torch.einsum("vh,vh->v", queries_all, keys)
+        probs = torch.exp(scatter_log_softmax(scores, index, dim=0, eps=0))
+        return scatter(F.linear(x, output_weight) * probs.unsqueeze(-1), index, 0, None, n, "sum")
+    N = queries_all.shape[0]
+    queries_all = queries_all.reshape(N, num_heads, queries_all.shape[1] // num_heads)
+    keys = keys.reshape(keys.shape[0], num_heads, keys.shape[1] // num_heads)
+    scores = torch.einsum("bhk,bhk->bh", queries_all, keys) / math.sqrt(keys.shape[-1])
+    probs = torch.exp(scatter_log_softmax(scores, index, dim=0, eps=0))           # [N, heads]
+    if value_weight is not None:
+        values = F.linear(x, value_weight)
+        outputs = probs.unsqueeze(-1) * values.reshape(values.shape[0], num_heads, values.shape[1] // num_heads)
+    else:
+        outputs = probs.unsqueeze(-1) * x.unsqueeze(1)                             # [N, heads, D]
+    per_sample = scatter(outputs.reshape(outputs.shape[0], -1), index, 0, None, n, "sum")
+    return F.linear(per_sample, output_weight)
