@@ -36,6 +36,13 @@ to fp32 on entry and the result is cast back.  No GPU path runs on a vendor BLAS
 Device dispatch (round 5): tensors on the CPU take `ptgnn_amd/torch_route.py` (plain torch operators, so that the
 reference's `predict.py` -- which restores and runs on "cpu" -- and a CPU `ModelTrainer` work with these layers);
 tensors on the GPU always take the HIP library and raise when it is missing.
+
+How to read the file: every layer's `forward` is the host / AMP preamble followed by an ORDERED list of "condition ->
+route"; the order is behaviour.  Route bodies are the `_forward_*` methods of the layer (they need its name-mangled
+modules).  What the layers share is spelled once at module level: `_has_edge_features`, `_first_linear_gemm_ok` (when
+the first Linear of every edge MLP can be the grouped GEMM), `_edge_mlp_tail` (the rest of the edge MLPs),
+`_train_edge_messages` (training, edge form) and the `_shard_*` table plumbing of `forward_sharded`; the MLP layer's
+`_epilogue` decides once whether GELU + LayerNorm fold into a launch.
 """
 import contextlib
 import os
@@ -158,6 +165,22 @@ def _prefer_edge_path(num_edges: int, num_nodes: int, num_types: int, state_dim:
     return num_edges * EDGE_PATH_BIAS < num_nodes * num_types
 
 
+def _has_edge_features(feature_dim: int, edge_features) -> bool:
+    """Whether a layer call carries per-edge features: the layer was built for them, or a non-empty tensor came in."""
+    return feature_dim != 0 or any(f is not None and f.shape[-1] != 0 for f in edge_features)
+
+
+def _stack_detached(weights) -> torch.Tensor:
+    """[T*M, H] = [W_0; ...; W_{T-1}] without gradient, rebuilt per call: a cache keyed on parameter versions would go
+    stale under `p.data` updates (EMA, weight clipping), and the copy is tiny next to the GEMM."""
+    return weights[0].detach() if len(weights) == 1 else torch.cat([w.detach() for w in weights], dim=0)
+
+
+def _kernel_act(act: Optional[nn.Module]) -> Optional[str]:
+    """The kernels' name of a dense activation module; None without one and for modules the kernels do not fuse."""
+    return "tanh" if isinstance(act, nn.Tanh) else ("relu" if isinstance(act, nn.ReLU) else None)
+
+
 def _edge_messages(table: torch.Tensor, adjacency_lists, plan, weights):
     """GGNN messages of the edge form (inference) and the `col` that maps CSR slots to their rows: one row per distinct
     (edge type, source) pair of the plan where the shared-row launch applies (GraphPlan.unique_messages), else one row
@@ -197,7 +220,24 @@ def _dropout_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
+def _train_edge_messages(owner, x, plan, weights, use_dst: bool, p: float = 0.0, seed_xor: int = 0, key: str = "edge_w"):
+    """Training, edge form: the grouped per-edge GEMM as one autograd node (forward + both gradients on HIP) over the
+    per-type weights stacked once per forward scope, with the reference's per-edge input dropout folded in as a hash
+    mask (one seed draw per call with p > 0; `seed_xor` tells the ranks of a sharded graph apart)."""
+    w_stack = _scoped(owner, key, lambda: torch.stack(weights))
+    return edge_linear_autograd(x, plan, w_stack, use_dst, p, (_dropout_seed() ^ seed_xor) if p > 0 else 0)
+
+
 _AMP_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _amp_forward(layer, node_states, adjacency_lists, edge_features, cast_features: bool = True) -> torch.Tensor:
+    """AMP (trainer.py:205,221): the reference computes messages in the autocast dtype and up-casts them to fp32 at the
+    aggregation (abstractmessagepassing.py:43-50).  Here the whole layer runs in fp32 on the HIP kernels -- every
+    intermediate at least as precise as the reference's -- and only the returned states go back to the caller's dtype."""
+    if cast_features:
+        edge_features = [f.float() if f is not None and f.dtype in _AMP_DTYPES else f for f in edge_features]
+    return layer.forward(node_states.float(), adjacency_lists, None, None, None, edge_features).to(node_states.dtype)
 
 
 def _overlap_reduces():
@@ -210,6 +250,100 @@ def _run_mlp(mlp: "MLP", x: torch.Tensor) -> torch.Tensor:
     for m in mlp.modules_in_order:
         x = dense.linear(x, m.weight, m.bias) if isinstance(m, nn.Linear) else m(x)
     return x
+
+
+def _first_linear_gemm_ok(mlps, training: bool, state_dim: int, differentiable: bool) -> bool:
+    """Whether the FIRST Linear of every edge MLP can run as the grouped per-edge GEMM: bias-free, and no active Dropout
+    inside the edge MLPs (the GEMM gathers its input rows itself).  `differentiable`: the route may need the autograd
+    form (`_EdgeLinear` / `_EdgeLinearFeat`), which also wants one weight shape for all types and the widths of
+    `_edge_training_ok`; the inference-only route with edge features asks for neither."""
+    first = [m.linears[0] for m in mlps]
+    if any(l.bias is not None for l in first):
+        return False
+    if training and any(isinstance(m, nn.Dropout) and m.p > 0 for e in mlps for m in e.modules_in_order):
+        return False
+    if not differentiable:
+        return True
+    return len({tuple(l.weight.shape) for l in first}) == 1 and _edge_training_ok(state_dim, first[0].weight.shape[0])
+
+
+def _edge_mlp_tail(mlps, adjacency_lists, hid: torch.Tensor, differentiable: bool, single_block_as_is: bool = False):
+    """The modules after the first Linear of every edge MLP, run on the type's [E_t, hidden] block of rows of `hid` (the
+    first Linear's output for all edges, type-major); returns the [E, M] messages.  Differentiable form: HIP Linear
+    autograd nodes, the blocks concatenated (`single_block_as_is`: one type's block is returned without the copy).
+    Inference form: the type's last Linear writes its block of a preallocated message matrix in place, no concat."""
+    messages = None
+    if not differentiable:
+        messages = torch.empty(hid.shape[0], mlps[0].linears[-1].out_features, dtype=torch.float32, device=hid.device)
+    outs, off = [], 0
+    for (src, _), edge_mlp in zip(adjacency_lists, mlps):
+        n = int(src.shape[0])
+        mods = edge_mlp.modules_in_order
+        rest = mods[next(i for i, m in enumerate(mods) if isinstance(m, nn.Linear)) + 1:]
+        h = hid[off:off + n]
+        last = max((i for i, m in enumerate(rest) if isinstance(m, nn.Linear)), default=-1)
+        for i, m in enumerate(rest):
+            if not isinstance(m, nn.Linear):
+                h = m(h)
+            elif differentiable:
+                h = dense.linear(h, m.weight, m.bias)
+            else:
+                h = ops.linear(h, m.weight, m.bias, out=messages[off:off + n] if i == last and n > 0 else None)
+        if differentiable:
+            outs.append(h)
+        elif last < 0 and n > 0:
+            messages[off:off + n].copy_(h)
+        off += n
+    if not differentiable:
+        return messages
+    return outs[0] if single_block_as_is and len(outs) == 1 else torch.cat(outs, dim=0)
+
+
+# Table plumbing of the sharded layers (ptgnn_amd/sharded.py).  `w` is the stacked source weight [T*M, H]; what travels
+# in the table form is decided by its shape: message-table rows when T*M <= H (no wider than the state, and no
+# duplicated GEMM work), else node states, pre-transformed after arrival (the weights are replicated).
+def _shard_source_table(shard, node_states: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Single-block table form, inference: the message table of this rank's [own | halo] rows."""
+    if w.shape[0] <= w.shape[1]:
+        y = shard.new_table(w.shape[0], node_states)
+        ops.linear(node_states, w, out=y[: shard.n_local])
+        shard.exchange_into(y)
+        return y
+    return ops.linear(shard.exchange(node_states), w)
+
+
+def _shard_source_table_autograd(shard, node_states: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The differentiable twin of `_shard_source_table` (backward = transposed all-to-all + HIP segment-sum)."""
+    if w.shape[0] <= w.shape[1]:
+        return shard.exchange_autograd(dense.linear(node_states, w))
+    return dense.linear(shard.exchange_autograd(node_states), w)
+
+
+def _shard_two_blocks(shard, node_states: torch.Tensor, w: Optional[torch.Tensor], edge_messages=None):
+    """Two-block mode (the own-source block aggregates while the halo rows travel): the `(work, table_of)` pair of
+    `sharded.aggregate_two_blocks`.  Edge form: `edge_messages(table, adjacency_lists, plan) -> (messages, col)` makes a
+    block's messages from the local table [own | halo], and `w` is not read; table form: `edge_messages` is None."""
+    n, H = shard.n_local, node_states.shape[1]
+    if edge_messages is not None or w.shape[0] > H:      # node states travel
+        table = shard.new_table(H, node_states)
+        table[:n].copy_(node_states)
+        work = shard.begin_exchange(table)
+        if edge_messages is not None:
+            def table_of(block):
+                adj, plan = (shard.adj_own, shard.plan_own) if block == "own" else (shard.adj_halo, shard.plan_halo)
+                return edge_messages(table, adj, plan) + (0,)
+            return work, table_of
+        y = shard.new_table(w.shape[0], node_states)
+        ops.linear(node_states, w, out=y[:n])
+
+        def table_of(block):
+            if block == "halo":
+                ops.linear(table[n:], w, out=y[n:])
+            return y, None, None
+        return work, table_of
+    y = shard.new_table(w.shape[0], node_states)         # message-table rows travel
+    ops.linear(node_states, w, out=y[:n])
+    return shard.begin_exchange(y), lambda block: (y, None, None)
 
 
 def _check_device(node_states: torch.Tensor):
@@ -300,14 +434,12 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
 
     # -- fused path -------------------------------------------------------------------------
     def _stacked_edge_weights(self) -> torch.Tensor:
-        """[T*M, H] = [W_0; ...; W_{T-1}], rebuilt per call: a cache keyed on parameter versions would go
-        stale under `p.data` updates (EMA, weight clipping), and the copy is tiny next to the GEMM."""
-        ws = [lin.weight.detach() for lin in self.__edge_message_transformation_layers]
-        return ws[0] if len(ws) == 1 else torch.cat(ws, dim=0)
+        """[T*M, H] = [W_0; ...; W_{T-1}], detached (see `_stack_detached`)."""
+        return _stack_detached([lin.weight for lin in self.__edge_message_transformation_layers])
 
     def _table_ok(self, node_states, edge_features) -> bool:
         """Message == row of the per-node table X [W_0; ...]^T: no edge features, no per-edge dropout."""
-        if self._edge_feature_dimension != 0 or any(f is not None and f.shape[-1] != 0 for f in edge_features):
+        if _has_edge_features(self._edge_feature_dimension, edge_features):
             return False
         if self.training and self.__dropout.p > 0:
             return False
@@ -330,74 +462,67 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
                                           list(self.__edge_message_transformation_layers), self.__dropout,
                                           self.__state_update, self.__aggregation_fn)
         if node_states.dtype in _AMP_DTYPES:
-            # AMP (trainer.py:205,221): the reference computes messages in the autocast dtype and up-casts them
-            # to fp32 at the aggregation (abstractmessagepassing.py:43-50).  Here the whole layer runs in fp32 on
-            # the HIP kernels -- every intermediate at least as precise as the reference's -- and only the
-            # returned states go back to the caller's dtype.
-            feats = [f.float() if f is not None and f.dtype in _AMP_DTYPES else f for f in edge_features]
-            return self.forward(node_states.float(), adjacency_lists, node_to_graph_idx, reference_node_ids,
-                                reference_node_graph_idx, feats).to(node_states.dtype)
-        num_nodes = node_states.shape[0]
+            return _amp_forward(self, node_states, adjacency_lists, edge_features)
+        num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
         plan = ops.plan_for(adjacency_lists, num_nodes)
-        gru = self.__state_update
         if self._fused_ok(node_states, edge_features):
-            M, T = self._message_dimension, len(adjacency_lists)
-            if _prefer_edge_path(plan.num_edges, num_nodes, T, self.__state_dimension, M):
-                # many sparse edge types: one grouped per-edge GEMM.  The message W_t x[src] is the same row for
-                # every edge of type t that leaves src: the GEMM produces one row per distinct (type, source) pair
-                # of the plan (GraphPlan.unique_messages, built once per minibatch on the device) and the
-                # aggregation reads it per edge -- same bits, fewer rows.
-                weights = [l.weight for l in self.__edge_message_transformation_layers]
-                msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights)
-                tb = 0
-            else:
-                msgs, col, tb = ops.linear(node_states, self._stacked_edge_weights()), None, None      # [N, T*M]
-            # aggregation -> GRU cell, pipelined over destination-row ranges on large minibatches (ops.aggregate_gru)
-            return ops.aggregate_gru(msgs, plan, M, self.__aggregation_fn, node_states, gru.weight_ih, gru.weight_hh,
-                                     gru.bias_ih, gru.bias_hh, type_bits=tb, col=col,
-                                     out=_take_output_hint(num_nodes, self.__state_dimension, node_states))
+            return self._forward_fused(node_states, adjacency_lists, plan)
 
-        no_feats = self._edge_feature_dimension == 0 and not any(
-            f is not None and f.shape[-1] != 0 for f in edge_features)
+        agg_fn = self.__aggregation_fn
+        has_feats = _has_edge_features(self._edge_feature_dimension, edge_features)
         p = self.__dropout.p if self.training else 0.0
-        M, T = self._message_dimension, len(adjacency_lists)
-        if (no_feats and node_states.dtype == torch.float32 and _edge_training_ok(self.__state_dimension, M)
-                and (p > 0 or _prefer_edge_path(plan.num_edges, num_nodes, T, self.__state_dimension, M))):
+        ws = [l.weight for l in self.__edge_message_transformation_layers]
+        if (not has_feats and node_states.dtype == torch.float32 and _edge_training_ok(H, M)
+                and (p > 0 or _prefer_edge_path(plan.num_edges, num_nodes, len(ws), H, M))):
             # training, edge form: grouped per-edge GEMM with the reference's per-edge input dropout
             # folded in (forward + both gradients on HIP), HIP segment reduce, torch GRU cell
-            w_stack = _scoped(self, "edge_w", lambda: torch.stack(
-                [l.weight for l in self.__edge_message_transformation_layers]))
-            msgs = edge_linear_autograd(node_states, plan, w_stack, False, p, _dropout_seed() if p > 0 else 0)
-            agg = segment_reduce(msgs, plan, self.__aggregation_fn)
-            return dense.gru_cell(gru, agg, node_states)
-
-        if self._table_ok(node_states, edge_features):
+            agg = segment_reduce(_train_edge_messages(self, node_states, plan, ws, False, p), plan, agg_fn)
+        elif self._table_ok(node_states, edge_features):
             # training without per-edge dropout, few edge types: differentiable HIP GEMM nodes (ptgnn_amd/dense.py)
             # for the dense blocks, the HIP kernel (forward + backward) for the aggregation
-            w = torch.cat([l.weight for l in self.__edge_message_transformation_layers], dim=0)
-            y = dense.linear(node_states, w)
-            agg = gather_reduce_autograd(y, None, plan, self._message_dimension, self.__aggregation_fn)
-            return dense.gru_cell(gru, agg, node_states)
-
-        if (not no_feats and p == 0.0 and self.__aggregation_fn in ops.REDUCE_IDS
-                and _feat_gemm_ok(node_states, edge_features, self.__state_dimension, M, *self.parameters())):
-            # inference with edge features: fused gather of [x[src] | features] inside the grouped GEMM
-            msgs = ops.edge_linear(node_states, adjacency_lists,
-                                   [l.weight for l in self.__edge_message_transformation_layers], False,
-                                   edge_feats=edge_features)
-            agg = ops.gather_reduce(msgs, plan, M, self.__aggregation_fn, type_bits=0, col=plan.perm)
-            return ops.gru_cell(agg, node_states, gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh)
-
-        if (not no_feats and p == 0.0 and self.__aggregation_fn in ops.REDUCE_IDS and _edge_training_ok(self.__state_dimension, M)
-                and _feat_gemm_ok(node_states, edge_features, self.__state_dimension, M, shapes_only=True)):
+            agg = gather_reduce_autograd(dense.linear(node_states, torch.cat(ws, dim=0)), None, plan, M, agg_fn)
+        elif (has_feats and p == 0.0 and agg_fn in ops.REDUCE_IDS
+                and _feat_gemm_ok(node_states, edge_features, H, M, *self.parameters())):
+            return self._forward_features_inference(node_states, adjacency_lists, plan, edge_features)
+        elif (has_feats and p == 0.0 and agg_fn in ops.REDUCE_IDS and _edge_training_ok(H, M)
+                and _feat_gemm_ok(node_states, edge_features, H, M, shapes_only=True)):
             # training with edge features: the same grouped GEMM as one autograd node (scatter._EdgeLinearFeat) -- no
             # index_select, no [E, H + F] concat; weight / feature / state gradients on the HIP kernels
-            msgs = edge_linear_feat_autograd(node_states, plan, [l.weight for l in self.__edge_message_transformation_layers],
-                                             False, edge_features)
-            agg = segment_reduce(msgs, plan, self.__aggregation_fn)
-            return dense.gru_cell(gru, agg, node_states)
+            agg = segment_reduce(edge_linear_feat_autograd(node_states, plan, ws, False, edge_features), plan, agg_fn)
+        else:
+            agg = segment_reduce(self._general_messages(node_states, adjacency_lists, edge_features), plan, agg_fn)
+        return dense.gru_cell(self.__state_update, agg, node_states)
 
-        # general per-edge path (per-edge dropout with edge features, odd widths): message order = type-major
+    def _forward_fused(self, node_states, adjacency_lists, plan) -> torch.Tensor:
+        """Inference: message table (or edge form) -> aggregation -> GRU cell, pipelined over destination-row ranges on
+        large minibatches (ops.aggregate_gru)."""
+        num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
+        gru = self.__state_update
+        if _prefer_edge_path(plan.num_edges, num_nodes, len(adjacency_lists), H, M):
+            # many sparse edge types: one grouped per-edge GEMM.  The message W_t x[src] is the same row for
+            # every edge of type t that leaves src: the GEMM produces one row per distinct (type, source) pair
+            # of the plan (GraphPlan.unique_messages, built once per minibatch on the device) and the
+            # aggregation reads it per edge -- same bits, fewer rows.
+            weights = [l.weight for l in self.__edge_message_transformation_layers]
+            msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights)
+            tb = 0
+        else:
+            msgs, col, tb = ops.linear(node_states, self._stacked_edge_weights()), None, None      # [N, T*M]
+        return ops.aggregate_gru(msgs, plan, M, self.__aggregation_fn, node_states, gru.weight_ih, gru.weight_hh,
+                                 gru.bias_ih, gru.bias_hh, type_bits=tb, col=col,
+                                 out=_take_output_hint(num_nodes, H, node_states))
+
+    def _forward_features_inference(self, node_states, adjacency_lists, plan, edge_features) -> torch.Tensor:
+        """Inference with edge features: fused gather of [x[src] | features] inside the grouped GEMM."""
+        gru = self.__state_update
+        msgs = ops.edge_linear(node_states, adjacency_lists,
+                               [l.weight for l in self.__edge_message_transformation_layers], False,
+                               edge_feats=edge_features)
+        agg = ops.gather_reduce(msgs, plan, self._message_dimension, self.__aggregation_fn, type_bits=0, col=plan.perm)
+        return ops.gru_cell(agg, node_states, gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh)
+
+    def _general_messages(self, node_states, adjacency_lists, edge_features) -> torch.Tensor:
+        """General per-edge path (per-edge dropout with edge features, odd widths): message order = type-major."""
         all_messages = []
         for (src, _), feats, lin in zip(adjacency_lists, edge_features,
                                         self.__edge_message_transformation_layers):
@@ -405,9 +530,7 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             if feats is not None and feats.shape[-1] > 0:
                 inp = torch.cat([inp, feats.to(inp.dtype)], dim=-1)
             all_messages.append(dense.linear(self.__dropout(inp), lin.weight))     # HIP GEMM, K = H + F
-        messages = torch.cat(all_messages, dim=0)
-        agg = segment_reduce(messages, plan, self.__aggregation_fn)
-        return dense.gru_cell(gru, agg, node_states)
+        return torch.cat(all_messages, dim=0)
 
     def forward_sharded(self, node_states: torch.Tensor, shard) -> torch.Tensor:
         """One layer over a dst-range shard (ptgnn_amd/sharded.py): `node_states` are this rank's rows; one
@@ -423,8 +546,9 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
         if self._edge_feature_dimension != 0 or node_states.dtype != torch.float32:
             raise _lib.PtgnnAmdError("forward_sharded: edge features / non-fp32 states are not supported on a "
                                      "sharded graph")
-        if self.__aggregation_fn not in ops.REDUCE_IDS:
-            raise _lib.PtgnnAmdError(f"forward_sharded: aggregation {self.__aggregation_fn!r} is not supported on a "
+        agg_fn = self.__aggregation_fn
+        if agg_fn not in ops.REDUCE_IDS:
+            raise _lib.PtgnnAmdError(f"forward_sharded: aggregation {agg_fn!r} is not supported on a "
                                      "sharded graph (sum / mean / max / min are)")
         M, H = self._message_dimension, self.__state_dimension
         gru = self.__state_update
@@ -435,64 +559,30 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             # training.  Edge form: differentiable halo exchange (backward = transposed all-to-all + HIP
             # segment-sum) -> grouped per-edge GEMM node with the hash dropout folded in -> HIP segment reduce
             if _edge_training_ok(H, M) and (p > 0 or edge_form):
-                table = shard.exchange_autograd(node_states)
-                w_stack = _scoped(self, "edge_w", lambda: torch.stack(ws))
-                seed = (_dropout_seed() ^ (0x9E3779B97F4A7C15 * (shard.rank + 1) & (2 ** 62 - 1))) if p > 0 else 0
-                msgs = edge_linear_autograd(table, shard.plan, w_stack, False, p, seed)
-                agg = segment_reduce(msgs, shard.plan, self.__aggregation_fn)
-                return dense.gru_cell(gru, agg, node_states)
-            if p > 0:
+                msgs = _train_edge_messages(self, shard.exchange_autograd(node_states), shard.plan, ws, False, p,
+                                            seed_xor=0x9E3779B97F4A7C15 * (shard.rank + 1) & (2 ** 62 - 1))
+                agg = segment_reduce(msgs, shard.plan, agg_fn)
+            elif p > 0:
                 raise _lib.PtgnnAmdError("forward_sharded: per-edge dropout needs state and message widths that "
                                          "are multiples of 32")
-            w = torch.cat(ws, dim=0)
-            if w.shape[0] <= w.shape[1]:
-                y = shard.exchange_autograd(dense.linear(node_states, w))
             else:
-                y = dense.linear(shard.exchange_autograd(node_states), w)
-            agg = gather_reduce_autograd(y, None, shard.plan, M, self.__aggregation_fn)
+                y = _shard_source_table_autograd(shard, node_states, torch.cat(ws, dim=0))
+                agg = gather_reduce_autograd(y, None, shard.plan, M, agg_fn)
             return dense.gru_cell(gru, agg, node_states)
-        if shard.overlap and self.__aggregation_fn in _overlap_reduces():
-            # two-block mode: the own-source block aggregates while the halo rows travel (sharded.py)
+
+        def edge_messages(table, adj, plan):
+            return _edge_messages(table, adj, plan, ws)
+        if shard.overlap and agg_fn in _overlap_reduces():
             from ptgnn_amd import sharded
-            n = shard.n_local
-            if edge_form or T * M > H:      # node states travel
-                table = shard.new_table(H, node_states)
-                table[:n].copy_(node_states)
-                work = shard.begin_exchange(table)
-                if edge_form:
-                    def table_of(block):
-                        adj, plan = (shard.adj_own, shard.plan_own) if block == "own" else (shard.adj_halo, shard.plan_halo)
-                        return _edge_messages(table, adj, plan, ws) + (0,)
-                else:
-                    w = self._stacked_edge_weights()
-                    y = shard.new_table(T * M, node_states)
-                    ops.linear(node_states, w, out=y[:n])
-
-                    def table_of(block):
-                        if block == "halo":
-                            ops.linear(table[n:], w, out=y[n:])
-                        return y, None, None
-            else:                           # message-table rows travel
-                y = shard.new_table(T * M, node_states)
-                ops.linear(node_states, self._stacked_edge_weights(), out=y[:n])
-                work = shard.begin_exchange(y)
-
-                def table_of(block):
-                    return y, None, None
-            agg = sharded.aggregate_two_blocks(shard, work, table_of, M, self.__aggregation_fn)
+            work, table_of = _shard_two_blocks(shard, node_states, None if edge_form else self._stacked_edge_weights(),
+                                               edge_messages if edge_form else None)
+            agg = sharded.aggregate_two_blocks(shard, work, table_of, M, agg_fn)
         elif edge_form:
-            table = shard.exchange(node_states)
-            msgs, col = _edge_messages(table, shard.local_adj, shard.plan, ws)
-            agg = ops.gather_reduce(msgs, shard.plan, M, self.__aggregation_fn, type_bits=0, col=col)
+            msgs, col = edge_messages(shard.exchange(node_states), shard.local_adj, shard.plan)
+            agg = ops.gather_reduce(msgs, shard.plan, M, agg_fn, type_bits=0, col=col)
         else:
-            w = self._stacked_edge_weights()
-            if T * M <= H:   # ship message-table rows: no wider than the state, and no duplicated GEMM work
-                y = shard.new_table(T * M, node_states)
-                ops.linear(node_states, w, out=y[: shard.n_local])
-                shard.exchange_into(y)
-            else:            # ship node states, pre-transform own + halo rows locally
-                y = ops.linear(shard.exchange(node_states), w)
-            agg = ops.gather_reduce(y, shard.plan, M, self.__aggregation_fn)
+            y = _shard_source_table(shard, node_states, self._stacked_edge_weights())
+            agg = ops.gather_reduce(y, shard.plan, M, agg_fn)
         return ops.gru_cell(agg, node_states, gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh)
 
     @property
@@ -556,9 +646,7 @@ class EGCMessagePassingLayer(AbstractMessagePassingLayer):
             return torch_route.egc_layer(node_states, adjacency_lists, edge_features, list(self.__bases),
                                          self.__weight_coeffs, self.__dropout, K, B, D, self.__aggregation_fn)
         if node_states.dtype in _AMP_DTYPES:
-            # AMP: the whole layer runs in fp32 on the HIP kernels, the result goes back to the caller's dtype
-            return self.forward(node_states.float(), adjacency_lists, node_to_graph_idx, reference_node_ids,
-                                reference_node_graph_idx, edge_features).to(node_states.dtype)
+            return _amp_forward(self, node_states, adjacency_lists, edge_features, cast_features=False)   # (ignored)
         if node_states.dtype != torch.float32:
             raise _lib.PtgnnAmdError(f"EGCMessagePassingLayer: node states must be float32 / float16 / bfloat16 on the "
                                      f"GPU (got {node_states.dtype})")
@@ -577,15 +665,13 @@ class EGCMessagePassingLayer(AbstractMessagePassingLayer):
             if edge_form:
                 msgs = ops.edge_linear(node_states, adjacency_lists, weights, False)              # [E, M]
                 return ops.gather_combine(msgs, plan, K, B, Dh, agg_fn, coef, type_bits=0, col=plan.perm)
-            w = weights[0].detach() if T == 1 else torch.cat([x.detach() for x in weights], dim=0)
-            return ops.gather_combine(ops.linear(node_states, w), plan, K, B, Dh, agg_fn, coef)     # table [N, T*M]
+            return ops.gather_combine(ops.linear(node_states, _stack_detached(weights)), plan, K, B, Dh, agg_fn,
+                                      coef)                                                        # table [N, T*M]
 
         coef = dense.linear(node_states, wc.weight, wc.bias)
         if reduce_ok and _edge_training_ok(H, M) and (p > 0 or edge_form):
             # training, edge form: grouped per-edge GEMM with the reference's per-edge input dropout folded in
-            w_stack = _scoped(self, "edge_w", lambda: torch.stack(weights))
-            msgs = edge_linear_autograd(node_states, plan, w_stack, False, p, _dropout_seed() if p > 0 else 0)
-            agg = segment_reduce(msgs, plan, agg_fn)
+            agg = segment_reduce(_train_edge_messages(self, node_states, plan, weights, False, p), plan, agg_fn)
         elif reduce_ok and p == 0.0:
             # training without dropout, few edge types: the message table and the differentiable HIP aggregation
             y = dense.linear(node_states, weights[0] if T == 1 else torch.cat(weights, dim=0))
@@ -696,20 +782,30 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         self._features_dimension = features_dimension
 
     # -- fused path -------------------------------------------------------------------------
-    def _stacked_edge_weights(self) -> torch.Tensor:
+    def _first_weights(self) -> List[torch.Tensor]:
+        return [m.linears[0].weight for m in self.__edge_message_transformation_layers]
+
+    def _stacked_edge_weights(self, detach: bool = True, split: bool = False):
         """[(1|2)*T*M, H]: source halves of every type, then (with target state) the target halves; rebuilt
-        per call (see GatedMessagePassingLayer._stacked_edge_weights)."""
-        ws = [m.linears[0].weight.detach() for m in self.__edge_message_transformation_layers]
+        per call (see `_stack_detached`).  `detach=False`: with gradient, for the training routes; `split`: the
+        (source, target or None) stacks as two tensors."""
+        ws = [w.detach() for w in self._first_weights()] if detach else self._first_weights()
         H = self.__input_state_dim
-        parts = [w[:, :H] for w in ws]
-        if self.__use_target_state_as_message_input:
-            parts += [w[:, H:2 * H] for w in ws]
-        return torch.cat(parts, dim=0).contiguous()
+        src = [w[:, :H] for w in ws]
+        dst = [w[:, H:2 * H] for w in ws] if self.__use_target_state_as_message_input else []
+        if split:
+            return torch.cat(src, dim=0), (torch.cat(dst, dim=0) if dst else None)
+        return torch.cat(src + dst, dim=0).contiguous()
+
+    def _table_halves(self, y: torch.Tensor, num_types: int):
+        """(source term, destination term or None) of the table y = X [W^s_0; ...; W^d_0; ...]^T."""
+        TM = num_types * self._message_dimension
+        return y[:, :TM], (y[:, TM:] if self.__use_target_state_as_message_input else None)
 
     def _table_ok(self, node_states, edge_features) -> bool:
         if not isinstance(self.__aggregation_fn, str) or self.__aggregation_fn not in ops.REDUCE_IDS:
             return False                                     # aggregation modules; "mul": the seam's own kernel
-        if self._features_dimension != 0 or any(f is not None and f.shape[-1] != 0 for f in edge_features):
+        if _has_edge_features(self._features_dimension, edge_features):
             return False
         if not all(m.is_single_linear for m in self.__edge_message_transformation_layers):
             return False
@@ -720,44 +816,54 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
             return False
         return (not torch.is_grad_enabled()) or _no_grad_needed(node_states, *self.parameters())
 
+    def _epilogue(self, width: int, cap: int, cap_without_ln: bool = True) -> dict:
+        """The `epilogue / ln_weight / ln_bias / ln_eps` keywords that fold the message activation and the LayerNorm
+        into a launch over rows of `width`, or {} where they cannot be folded: only the stock ones are (erf GELU, affine
+        LayerNorm with a bias), and only up to `cap` columns (`cap_without_ln=False`: the cap is the LayerNorm's)."""
+        act, ln = self.__message_activation, self._ln
+        gelu_ok = act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
+        ln_ok = ln is None or (ln.elementwise_affine and ln.bias is not None)
+        if not (gelu_ok and ln_ok) or (width > cap and (cap_without_ln or ln is not None)):
+            return {}
+        return dict(epilogue=(ops.EPI_GELU if act is not None else 0) | (ops.EPI_LAYERNORM if ln is not None else 0),
+                    ln_weight=ln.weight if ln is not None else None, ln_bias=ln.bias if ln is not None else None,
+                    ln_eps=ln.eps if ln is not None else 1e-5)
+
     def _aggregate_and_update(self, ysrc, ydst, plan, col=None, type_bits=None, two_block=None) -> torch.Tensor:
         """Fused gather/reduce with GELU + LayerNorm folded into the kernel epilogue when the
         layer's activation/normalisation are the stock ones, then the dense update.  `two_block` =
         (shard, work, table_of): the sharded two-block aggregation instead (epilogue in its combine pass)."""
         M = self._message_dimension
-        act = self.__message_activation
-        gelu_ok = act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
-        ln_ok = self._ln is None or (M <= 512 and self._ln.elementwise_affine and self._ln.bias is not None)
-        fused = gelu_ok and ln_ok
-        epi = {}
-        if fused:
-            epi = dict(epilogue=(ops.EPI_GELU if act is not None else 0) | (ops.EPI_LAYERNORM if self._ln is not None else 0),
-                       ln_weight=self._ln.weight if self._ln is not None else None,
-                       ln_bias=self._ln.bias if self._ln is not None else None,
-                       ln_eps=self._ln.eps if self._ln is not None else 1e-5)
+        epi = self._epilogue(M, 512, cap_without_ln=False)
         if two_block is not None:
             from ptgnn_amd import sharded
             shard, work, table_of = two_block
             agg = sharded.aggregate_two_blocks(shard, work, table_of, M, self.__aggregation_fn, ydst=ydst, **epi)
-        elif (fused and ydst is None and self._dense is not None
-              and (self._dense_act is None or isinstance(self._dense_act, (nn.Tanh, nn.ReLU)))
+        elif (epi and ydst is None and self._dense is not None
+              and (self._dense_act is None or _kernel_act(self._dense_act) is not None)
               and not (self.training and getattr(self._dropout, "p", 0.0) > 0)
               and _no_grad_needed(ysrc, *self._dense.parameters())
               and ops.gather_update_supported(M, self._dense.out_features, plan)):
             # hidden 64 (the README's default architecture, BASELINE config 4), edge form: aggregation, GELU, LayerNorm,
             # Linear and Tanh in ONE launch -- the [N, M] aggregate never exists in memory (gather_reduce.hip)
-            act = "tanh" if isinstance(self._dense_act, nn.Tanh) else ("relu" if isinstance(self._dense_act, nn.ReLU) else None)
             # (the fused launch stores 16-byte vectors: a hint whose rows are not 16-byte aligned -- the right half of a
             # concat buffer whose left half is not a multiple of 4 wide -- is declined, the residual then concatenates)
             hint = _take_output_hint(plan.num_nodes, self._dense.out_features, ysrc, vector_stores=True)
             out = ops.gather_update(ysrc, plan, self.__aggregation_fn, plan.col if col is None else col,
-                                    plan.type_bits if type_bits is None else type_bits, epi.get("epilogue", 0),
-                                    epi.get("ln_weight"), epi.get("ln_bias"), epi.get("ln_eps", 1e-5),
-                                    self._dense.weight, self._dense.bias, act, out=hint)
+                                    plan.type_bits if type_bits is None else type_bits, epi["epilogue"],
+                                    epi["ln_weight"], epi["ln_bias"], epi["ln_eps"],
+                                    self._dense.weight, self._dense.bias, _kernel_act(self._dense_act), out=hint)
             return self._dropout(out)
         else:
             agg = ops.gather_reduce(ysrc, plan, M, self.__aggregation_fn, ydst=ydst, col=col, type_bits=type_bits, **epi)
-        return self._update(agg, fused)
+        return self._update(agg, bool(epi))
+
+    def _aggregate_edge_messages(self, messages, plan, inference: bool) -> torch.Tensor:
+        """Aggregation + update over [E, M] messages in type-major order: the fused launches in inference (reduce set of
+        the kernels, 16-byte rows), else the HIP segment-reduce seam with its autograd rule."""
+        if inference and self.__aggregation_fn in ops.REDUCE_IDS and messages.shape[1] % 4 == 0:
+            return self._aggregate_and_update(messages, None, plan, col=plan.perm, type_bits=0)
+        return self._update(segment_reduce(messages, plan, self.__aggregation_fn), False)
 
     def forward_sharded(self, node_states: torch.Tensor, shard) -> torch.Tensor:
         """One layer over a dst-range shard (ptgnn_amd/sharded.py).  Table form: the source term rides the halo
@@ -772,66 +878,29 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
             raise _lib.PtgnnAmdError("forward_sharded needs a string aggregation and single-Linear edge "
                                      "transforms without edge features")
         use_dst = self.__use_target_state_as_message_input
-        ws = [m.linears[0].weight for m in self.__edge_message_transformation_layers]
+        ws = self._first_weights()
         edge_form = _prefer_edge_path(*shard.form_sizes(T * M > H), T, H, M)   # one decision for the whole group
         if not self._fused_ok(node_states, feats):
             if edge_form and _edge_training_ok(H, M):
-                table = shard.exchange_autograd(node_states)
-                w_stack = _scoped(self, "edge_w", lambda: torch.stack(ws))
-                msgs = edge_linear_autograd(table, shard.plan, w_stack, use_dst)
-                return self._update(segment_reduce(msgs, shard.plan, self.__aggregation_fn), False)
-            w_src = torch.cat([w[:, :H] for w in ws], dim=0)
-            if T * M <= H:
-                ysrc = shard.exchange_autograd(dense.linear(node_states, w_src))
-            else:
-                ysrc = dense.linear(shard.exchange_autograd(node_states), w_src)
-            ydst = None
-            if use_dst:
-                ydst = dense.linear(node_states, torch.cat([w[:, H:2 * H] for w in ws], dim=0))
-            agg = gather_reduce_autograd(ysrc, ydst, shard.plan, M, self.__aggregation_fn)
-            return self._update(agg, False)
+                msgs = _train_edge_messages(self, shard.exchange_autograd(node_states), shard.plan, ws, use_dst)
+                return self._aggregate_edge_messages(msgs, shard.plan, False)
+            w_src, w_dst = self._stacked_edge_weights(detach=False, split=True)
+            ysrc = _shard_source_table_autograd(shard, node_states, w_src)
+            ydst = dense.linear(node_states, w_dst) if use_dst else None
+            return self._update(gather_reduce_autograd(ysrc, ydst, shard.plan, M, self.__aggregation_fn), False)
+
+        def edge_messages(table, adj, plan):
+            return ops.edge_linear(table, adj, ws, use_dst), plan.perm
         if shard.overlap and self.__aggregation_fn in _overlap_reduces():
-            n = shard.n_local
             w = self._stacked_edge_weights()
-            ydst = None
-            if edge_form or T * M > H:      # node states travel
-                table = shard.new_table(H, node_states)
-                table[:n].copy_(node_states)
-                work = shard.begin_exchange(table)
-                if edge_form:
-                    def table_of(block):
-                        adj, plan = (shard.adj_own, shard.plan_own) if block == "own" else (shard.adj_halo, shard.plan_halo)
-                        return ops.edge_linear(table, adj, ws, use_dst), plan.perm, 0
-                else:
-                    ysrc = shard.new_table(T * M, node_states)
-                    ops.linear(node_states, w[: T * M], out=ysrc[:n])
-
-                    def table_of(block):
-                        if block == "halo":
-                            ops.linear(table[n:], w[: T * M], out=ysrc[n:])
-                        return ysrc, None, None
-            else:                           # message-table rows travel
-                ysrc = shard.new_table(T * M, node_states)
-                ops.linear(node_states, w[: T * M], out=ysrc[:n])
-                work = shard.begin_exchange(ysrc)
-
-                def table_of(block):
-                    return ysrc, None, None
-            if use_dst and not edge_form:
-                ydst = ops.linear(node_states, w[T * M:])
-            return self._aggregate_and_update(None, ydst, None, two_block=(shard, work, table_of))
+            two_block = _shard_two_blocks(shard, node_states, w[: T * M], edge_messages if edge_form else None)
+            ydst = ops.linear(node_states, w[T * M:]) if use_dst and not edge_form else None
+            return self._aggregate_and_update(None, ydst, None, two_block=(shard,) + two_block)
         if edge_form:
-            table = shard.exchange(node_states)
-            msgs = ops.edge_linear(table, shard.local_adj, ws, use_dst)
-            return self._aggregate_and_update(msgs, None, shard.plan, col=shard.plan.perm, type_bits=0)
+            msgs, col = edge_messages(shard.exchange(node_states), shard.local_adj, shard.plan)
+            return self._aggregate_and_update(msgs, None, shard.plan, col=col, type_bits=0)
         w = self._stacked_edge_weights()
-        w_src = w[: T * M]
-        if T * M <= H:
-            ysrc = shard.new_table(T * M, node_states)
-            ops.linear(node_states, w_src, out=ysrc[: shard.n_local])
-            shard.exchange_into(ysrc)
-        else:
-            ysrc = ops.linear(shard.exchange(node_states), w_src)
+        ysrc = _shard_source_table(shard, node_states, w[: T * M])
         ydst = ops.linear(node_states, w[T * M:]) if use_dst else None
         return self._aggregate_and_update(ysrc, ydst, shard.plan)
 
@@ -841,72 +910,60 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         the aggregation module).  Inference: the message table (or the grouped per-edge GEMM), ONE launch that
         aggregates, scales and applies GELU + LayerNorm(15M) -- the [N, 15M] pre-LayerNorm tensor never exists -- and the
         dense block.  Training: the differentiable message GEMMs, `_PnaAggregate`, `_update`."""
-        if (self._features_dimension != 0 or any(f is not None and f.shape[-1] != 0 for f in edge_features)
+        if (_has_edge_features(self._features_dimension, edge_features)
                 or not all(m.is_single_linear for m in self.__edge_message_transformation_layers)
                 or node_states.dtype != torch.float32):
             return None
         N, T, M, H = node_states.shape[0], len(adjacency_lists), self._message_dimension, self.__input_state_dim
         delta = float(self.__aggregation_fn._delta)
         use_dst = self.__use_target_state_as_message_input
-        ws = [m.linears[0].weight for m in self.__edge_message_transformation_layers]
+        ws = self._first_weights()
         plan = ops.plan_for(adjacency_lists, N)
         edge_form = _prefer_edge_path(plan.num_edges, N, T, H, M)
         if _no_grad_needed(node_states, *self.parameters()):
-            act = self.__message_activation
-            gelu_ok = act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
-            ln_ok = self._ln is None or (self._ln.elementwise_affine and self._ln.bias is not None)
-            fused = gelu_ok and ln_ok and M <= 256
-            epi = {}
-            if fused:
-                epi = dict(epilogue=(ops.EPI_GELU if act is not None else 0) | (ops.EPI_LAYERNORM if self._ln is not None else 0),
-                           ln_weight=self._ln.weight if self._ln is not None else None,
-                           ln_bias=self._ln.bias if self._ln is not None else None,
-                           ln_eps=self._ln.eps if self._ln is not None else 1e-5)
+            epi = self._epilogue(M, 256)
             if edge_form:
                 msgs = ops.edge_linear(node_states, adjacency_lists, ws, use_dst)
                 agg = ops.pna_aggregate(msgs, plan, M, delta, type_bits=0, col=plan.perm, **epi)
             else:
-                y = ops.linear(node_states, self._stacked_edge_weights())
-                agg = ops.pna_aggregate(y[:, :T * M], plan, M, delta, ydst=y[:, T * M:] if use_dst else None, **epi)
-            return self._update(agg, fused)
+                ysrc, ydst = self._table_halves(ops.linear(node_states, self._stacked_edge_weights()), T)
+                agg = ops.pna_aggregate(ysrc, plan, M, delta, ydst=ydst, **epi)
+            return self._update(agg, bool(epi))
         if not _edge_training_ok(H, M):
             return None
         # training: the grouped per-edge GEMM as one autograd node (messages in the plan's type-major order), the fused
         # aggregation with its HIP backward, then the state update
-        w_stack = _scoped(self, "edge_w", lambda: torch.stack(ws))
-        msgs = edge_linear_autograd(node_states, plan, w_stack, use_dst)
+        msgs = _train_edge_messages(self, node_states, plan, ws, use_dst)
         return self._update(pna_aggregate_autograd(msgs, plan, delta), False)
 
     def _update(self, agg: torch.Tensor, fused_epilogue_done: bool) -> torch.Tensor:
         x = agg
         if not fused_epilogue_done:
-            act = self.__message_activation
-            stock_act = act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
-            stock_ln = self._ln is None or (self._ln.elementwise_affine and self._ln.bias is not None
-                                            and tuple(self._ln.normalized_shape) == (x.shape[-1],))
-            if (stock_act and stock_ln and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-                    and x.shape[1] <= 512 and (act is not None or self._ln is not None)):
+            act, ln = self.__message_activation, self._ln
+            if ((act is not None or ln is not None) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+                    and self._epilogue(x.shape[1], 512)
+                    and (ln is None or tuple(ln.normalized_shape) == (x.shape[-1],))):
                 # training: the same GELU -> LayerNorm arithmetic as the fused inference epilogue, as one HIP
                 # autograd node (forward + backward kernels of csrc/row_epilogue.hip)
-                x = dense.row_epilogue(x, act is not None, self._ln)
+                x = dense.row_epilogue(x, act is not None, ln)
             else:
                 if act is not None:
                     x = act(x)
-                if self._ln is not None:
-                    x = self._ln(x)
+                if ln is not None:
+                    x = ln(x)
         if self._dense is not None:
+            act = self._dense_act
             if _no_grad_needed(x, *self._dense.parameters()):
-                tanh = isinstance(self._dense_act, nn.Tanh)
+                tanh = _kernel_act(act) == "tanh"
                 hint = None
-                if (tanh or self._dense_act is None) and not (self.training and getattr(self._dropout, "p", 0.0) > 0):
+                if (tanh or act is None) and not (self.training and getattr(self._dropout, "p", 0.0) > 0):
                     # nothing follows the GEMM: it may write straight into the right half of a concat residual's result
                     hint = _take_output_hint(x.shape[0], self._dense.out_features, x)
                 x = ops.linear(x, self._dense.weight, self._dense.bias, act="tanh" if tanh else None, out=hint)
-                if self._dense_act is not None and not tanh:
-                    x = self._dense_act(x)
+                if act is not None and not tanh:
+                    x = act(x)
             else:
-                act = self._dense_act
-                name = "tanh" if isinstance(act, nn.Tanh) else ("relu" if isinstance(act, nn.ReLU) else None)
+                name = _kernel_act(act)
                 if (act is None or name is not None) and isinstance(self._dropout, nn.Dropout):
                     # training: Dropout(act(Linear(x))) as one autograd node (dense._LinearActDropout)
                     fused = dense.linear_act_dropout(x, self._dense.weight, self._dense.bias, name, self._dropout.p,
@@ -929,147 +986,96 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
                                          list(self.__edge_message_transformation_layers),
                                          self.__use_target_state_as_message_input, self.__aggregation_fn,
                                          self.__message_activation, self.__state_update)
-        if node_states.dtype in _AMP_DTYPES:   # see GatedMessagePassingLayer.forward
-            feats = [f.float() if f is not None and f.dtype in _AMP_DTYPES else f for f in edge_features]
-            return self.forward(node_states.float(), adjacency_lists, node_to_graph_idx, reference_node_ids,
-                                reference_node_graph_idx, feats).to(node_states.dtype)
-        num_nodes = node_states.shape[0]
-        T, M = len(adjacency_lists), self._message_dimension
+        if node_states.dtype in _AMP_DTYPES:
+            return _amp_forward(self, node_states, adjacency_lists, edge_features)
 
         if type(self.__aggregation_fn) is PnaMessageAggregation:
             out = self._forward_pna(node_states, adjacency_lists, edge_features)
             if out is not None:
                 return out
-
         if self._fused_ok(node_states, edge_features):
-            plan = ops.plan_for(adjacency_lists, num_nodes)
-            if _prefer_edge_path(plan.num_edges, num_nodes, T, self.__input_state_dim, M):
-                msgs = ops.edge_linear(node_states, adjacency_lists,
-                                       [m.linears[0].weight for m in self.__edge_message_transformation_layers],
-                                       self.__use_target_state_as_message_input)
-                return self._aggregate_and_update(msgs, None, plan, col=plan.perm, type_bits=0)
-            y = ops.linear(node_states, self._stacked_edge_weights())
-            ysrc = y[:, :T * M]
-            ydst = y[:, T * M:] if self.__use_target_state_as_message_input else None
-            return self._aggregate_and_update(ysrc, ydst, plan)
-
+            return self._forward_fused(node_states, adjacency_lists)
         if self._table_ok(node_states, edge_features):
-            plan = ops.plan_for(adjacency_lists, num_nodes)
-            H = self.__input_state_dim
-            ws = [m.linears[0].weight for m in self.__edge_message_transformation_layers]
-            if _edge_training_ok(H, M) and _prefer_edge_path(plan.num_edges, num_nodes, T, H, M):
-                # training, many sparse edge types: grouped per-edge GEMM forward + backward on HIP
-                # (the edge MLPs of this layer carry no dropout: mlpmessagepassing.py:39-47)
-                w_stack = _scoped(self, "edge_w", lambda: torch.stack(ws))
-                msgs = edge_linear_autograd(node_states, plan, w_stack, self.__use_target_state_as_message_input)
-                return self._update(segment_reduce(msgs, plan, self.__aggregation_fn), False)
-            # training: dense blocks through torch autograd, aggregation fwd + bwd on the HIP kernel
-            parts = [w[:, :H] for w in ws]
-            if self.__use_target_state_as_message_input:
-                parts += [w[:, H:2 * H] for w in ws]
-            y = dense.linear(node_states, torch.cat(parts, dim=0))
-            ysrc = y[:, :T * M]
-            ydst = y[:, T * M:] if self.__use_target_state_as_message_input else None
-            agg = gather_reduce_autograd(ysrc, ydst, plan, M, self.__aggregation_fn)
-            return self._update(agg, False)
+            return self._forward_training(node_states, adjacency_lists)
 
+        # deeper edge MLPs and / or edge features: the first Linear of every edge MLP as the grouped per-edge GEMM
         mlps = list(self.__edge_message_transformation_layers)
-        first = [m.linears[0] for m in mlps]
-        if (any(f is not None and f.shape[-1] != 0 for f in edge_features) and all(l.bias is None for l in first)
-                and isinstance(self.__aggregation_fn, str)
-                and _feat_gemm_ok(node_states, edge_features, self.__input_state_dim, first[0].weight.shape[0],
-                                  *self.parameters())
-                and not (self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for e in mlps
-                                               for m in e.modules_in_order))):
-            # inference with edge features: the FIRST Linear of every edge MLP as one grouped GEMM that gathers
-            # [x[src] | x[dst] | features] itself; the rest of the MLP (activation, further Linears) on its [E_t, .] rows
-            plan = ops.plan_for(adjacency_lists, num_nodes)
-            hid = ops.edge_linear(node_states, adjacency_lists, [l.weight for l in first],
-                                  self.__use_target_state_as_message_input, edge_feats=edge_features)
-            if all(m.is_single_linear for m in mlps):
-                messages = hid
-            else:
-                outs, off = [], 0
-                for (src, _), edge_mlp in zip(adjacency_lists, mlps):
-                    n = int(src.shape[0])
-                    mods = edge_mlp.modules_in_order
-                    rest = mods[next(i for i, m in enumerate(mods) if isinstance(m, nn.Linear)) + 1:]
-                    h = hid[off:off + n]
-                    for m in rest:
-                        h = dense.linear(h, m.weight, m.bias) if isinstance(m, nn.Linear) else m(h)
-                    outs.append(h)
-                    off += n
-                messages = torch.cat(outs, dim=0)
-            if self.__aggregation_fn in ops.REDUCE_IDS and messages.shape[1] % 4 == 0:
-                return self._aggregate_and_update(messages, None, plan, col=plan.perm, type_bits=0)
-            return self._update(segment_reduce(messages, plan, self.__aggregation_fn), False)
+        H, hidden = self.__input_state_dim, mlps[0].linears[0].weight.shape[0]
+        string_agg = isinstance(self.__aggregation_fn, str)
+        if (_has_edge_features(0, edge_features) and string_agg
+                and _first_linear_gemm_ok(mlps, self.training, H, differentiable=False)
+                and _feat_gemm_ok(node_states, edge_features, H, hidden, *self.parameters())):
+            return self._forward_features_inference(node_states, adjacency_lists, edge_features, mlps)
+        has_feats = _has_edge_features(self._features_dimension, edge_features)
+        gemm_ok = string_agg and _first_linear_gemm_ok(mlps, self.training, H, differentiable=True)
+        if gemm_ok and has_feats and _feat_gemm_ok(node_states, edge_features, H, hidden, shapes_only=True):
+            return self._forward_features_training(node_states, adjacency_lists, edge_features, mlps)
+        if gemm_ok and not has_feats and node_states.dtype == torch.float32:
+            return self._forward_deep_mlps(node_states, adjacency_lists, mlps)
+        return self._forward_general(node_states, adjacency_lists, edge_features)
 
-        no_feats = self._features_dimension == 0 and not any(f is not None and f.shape[-1] != 0 for f in edge_features)
-        H = self.__input_state_dim
-        if ((not no_feats) and isinstance(self.__aggregation_fn, str) and all(l.bias is None for l in first)
-                and len({tuple(l.weight.shape) for l in first}) == 1 and _edge_training_ok(H, first[0].weight.shape[0])
-                and _feat_gemm_ok(node_states, edge_features, H, first[0].weight.shape[0], shapes_only=True)
-                and not any(isinstance(m, nn.Dropout) and m.p > 0 and self.training for e in mlps for m in e.modules_in_order)):
-            # training with edge features: the first Linear of every edge MLP as ONE differentiable grouped GEMM that gathers
-            # [x[src] | x[dst] | features] itself (scatter._EdgeLinearFeat); the rest of each MLP on the type's rows
-            plan = ops.plan_for(adjacency_lists, num_nodes)
-            hid = edge_linear_feat_autograd(node_states, plan, [l.weight for l in first],
-                                            self.__use_target_state_as_message_input, edge_features)
-            outs, off = [], 0
-            for (src, _), edge_mlp in zip(adjacency_lists, mlps):
-                n = int(src.shape[0])
-                mods = edge_mlp.modules_in_order
-                h = hid[off:off + n]
-                for m in mods[next(i for i, m in enumerate(mods) if isinstance(m, nn.Linear)) + 1:]:
-                    h = dense.linear(h, m.weight, m.bias) if isinstance(m, nn.Linear) else m(h)
-                outs.append(h)
-                off += n
-            messages = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
-            return self._update(segment_reduce(messages, plan, self.__aggregation_fn), False)
-        if (no_feats and isinstance(self.__aggregation_fn, str) and node_states.dtype == torch.float32
-                and all(l.bias is None for l in first) and len({tuple(l.weight.shape) for l in first}) == 1
-                and _edge_training_ok(H, first[0].weight.shape[0])
-                and not any(isinstance(m, nn.Dropout) and m.p > 0 and self.training for e in mlps for m in e.modules_in_order)):
-            # deeper edge MLPs (mlp_hidden_layers > 0, mlp.py:50-77) without edge features: the FIRST Linear of every edge
-            # type is the grouped per-edge GEMM (it gathers [x[src] | x[dst]] itself: no index_select, no [E, 2H] concat --
-            # inference and training alike, `_EdgeLinear` carries the gradients); the rest of each MLP runs on the type's
-            # [E_t, hidden] rows on the HIP Linear
-            plan = ops.plan_for(adjacency_lists, num_nodes)
-            grad = not _no_grad_needed(node_states, *self.parameters())
-            use_dst = self.__use_target_state_as_message_input
-            if grad:
-                w_stack = _scoped(self, "edge_w0", lambda: torch.stack([l.weight for l in first]))
-                hid = edge_linear_autograd(node_states, plan, w_stack, use_dst)
-            else:
-                hid = ops.edge_linear(node_states, adjacency_lists, [l.weight for l in first], use_dst)
-            out_dim = mlps[0].linears[-1].out_features
-            messages = None if grad else torch.empty(hid.shape[0], out_dim, dtype=torch.float32, device=hid.device)
-            outs, off = [], 0
-            for (src, _), edge_mlp in zip(adjacency_lists, mlps):
-                n = int(src.shape[0])
-                mods = edge_mlp.modules_in_order
-                rest = mods[next(i for i, m in enumerate(mods) if isinstance(m, nn.Linear)) + 1:]
-                h = hid[off:off + n]
-                last = max((i for i, m in enumerate(rest) if isinstance(m, nn.Linear)), default=-1)
-                for i, m in enumerate(rest):
-                    if not isinstance(m, nn.Linear):
-                        h = m(h)
-                    elif grad:
-                        h = dense.linear(h, m.weight, m.bias)
-                    else:   # the type's last Linear writes its block of the message matrix in place: no concat
-                        h = ops.linear(h, m.weight, m.bias, out=messages[off:off + n] if i == last and n > 0 else None)
-                if grad:
-                    outs.append(h)
-                elif last < 0 and n > 0:
-                    messages[off:off + n].copy_(h)
-                off += n
-            if grad:
-                messages = torch.cat(outs, dim=0)
-            if (not grad) and self.__aggregation_fn in ops.REDUCE_IDS and messages.shape[1] % 4 == 0:
-                return self._aggregate_and_update(messages, None, plan, col=plan.perm, type_bits=0)
-            return self._update(segment_reduce(messages, plan, self.__aggregation_fn), False)
+    def _forward_fused(self, node_states, adjacency_lists) -> torch.Tensor:
+        """Inference, single-Linear edge transforms: grouped per-edge GEMM (many sparse edge types) or the per-node
+        table, then the fused aggregation + update."""
+        N, T = node_states.shape[0], len(adjacency_lists)
+        plan = ops.plan_for(adjacency_lists, N)
+        if _prefer_edge_path(plan.num_edges, N, T, self.__input_state_dim, self._message_dimension):
+            msgs = ops.edge_linear(node_states, adjacency_lists, self._first_weights(),
+                                   self.__use_target_state_as_message_input)
+            return self._aggregate_and_update(msgs, None, plan, col=plan.perm, type_bits=0)
+        ysrc, ydst = self._table_halves(ops.linear(node_states, self._stacked_edge_weights()), T)
+        return self._aggregate_and_update(ysrc, ydst, plan)
 
-        # general per-edge path
+    def _forward_training(self, node_states, adjacency_lists) -> torch.Tensor:
+        """Training, single-Linear edge transforms."""
+        N, T, M, H = node_states.shape[0], len(adjacency_lists), self._message_dimension, self.__input_state_dim
+        plan = ops.plan_for(adjacency_lists, N)
+        if _edge_training_ok(H, M) and _prefer_edge_path(plan.num_edges, N, T, H, M):
+            # many sparse edge types: grouped per-edge GEMM forward + backward on HIP
+            # (the edge MLPs of this layer carry no dropout: mlpmessagepassing.py:39-47)
+            msgs = _train_edge_messages(self, node_states, plan, self._first_weights(),
+                                        self.__use_target_state_as_message_input)
+            return self._aggregate_edge_messages(msgs, plan, False)
+        # dense blocks as differentiable HIP GEMM nodes, aggregation fwd + bwd on the HIP kernel
+        ysrc, ydst = self._table_halves(dense.linear(node_states, self._stacked_edge_weights(detach=False)), T)
+        return self._update(gather_reduce_autograd(ysrc, ydst, plan, M, self.__aggregation_fn), False)
+
+    def _forward_features_inference(self, node_states, adjacency_lists, edge_features, mlps) -> torch.Tensor:
+        """Inference with edge features: the FIRST Linear of every edge MLP as one grouped GEMM that gathers
+        [x[src] | x[dst] | features] itself; the rest of the MLP (activation, further Linears) on its [E_t, .] rows."""
+        plan = ops.plan_for(adjacency_lists, node_states.shape[0])
+        messages = ops.edge_linear(node_states, adjacency_lists, self._first_weights(),
+                                   self.__use_target_state_as_message_input, edge_feats=edge_features)
+        if not all(m.is_single_linear for m in mlps):
+            messages = _edge_mlp_tail(mlps, adjacency_lists, messages, differentiable=True)
+        return self._aggregate_edge_messages(messages, plan, True)
+
+    def _forward_features_training(self, node_states, adjacency_lists, edge_features, mlps) -> torch.Tensor:
+        """Training with edge features: the first Linear of every edge MLP as ONE differentiable grouped GEMM that
+        gathers [x[src] | x[dst] | features] itself (scatter._EdgeLinearFeat); the rest of each MLP on the type's rows."""
+        plan = ops.plan_for(adjacency_lists, node_states.shape[0])
+        hid = edge_linear_feat_autograd(node_states, plan, self._first_weights(),
+                                        self.__use_target_state_as_message_input, edge_features)
+        messages = _edge_mlp_tail(mlps, adjacency_lists, hid, differentiable=True, single_block_as_is=True)
+        return self._aggregate_edge_messages(messages, plan, False)
+
+    def _forward_deep_mlps(self, node_states, adjacency_lists, mlps) -> torch.Tensor:
+        """Deeper edge MLPs (mlp_hidden_layers > 0, mlp.py:50-77) without edge features: the FIRST Linear of every edge
+        type is the grouped per-edge GEMM (it gathers [x[src] | x[dst]] itself: no index_select, no [E, 2H] concat --
+        inference and training alike, `_EdgeLinear` carries the gradients); the rest of each MLP runs on the type's
+        [E_t, hidden] rows on the HIP Linear."""
+        plan = ops.plan_for(adjacency_lists, node_states.shape[0])
+        grad = not _no_grad_needed(node_states, *self.parameters())
+        use_dst = self.__use_target_state_as_message_input
+        if grad:
+            hid = _train_edge_messages(self, node_states, plan, self._first_weights(), use_dst, key="edge_w0")
+        else:
+            hid = ops.edge_linear(node_states, adjacency_lists, self._first_weights(), use_dst)
+        messages = _edge_mlp_tail(mlps, adjacency_lists, hid, differentiable=grad)
+        return self._aggregate_edge_messages(messages, plan, not grad)
+
+    def _forward_general(self, node_states, adjacency_lists, edge_features) -> torch.Tensor:
+        """General per-edge path: torch gathers / concatenates the rows, every Linear on the HIP GEMM."""
         all_targets, all_messages = [], []
         for (src, dst), feats, edge_mlp in zip(adjacency_lists, edge_features,
                                                self.__edge_message_transformation_layers):
@@ -1082,11 +1088,10 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
             all_messages.append(_run_mlp(edge_mlp, inp))                           # HIP GEMMs
         messages = torch.cat(all_messages, dim=0)
         if isinstance(self.__aggregation_fn, str):
-            plan = ops.plan_for(adjacency_lists, num_nodes)
-            agg = segment_reduce(messages, plan, self.__aggregation_fn)
-        else:
-            agg = self.__aggregation_fn(messages=messages, message_targets=torch.cat(all_targets, dim=0),
-                                        num_nodes=num_nodes)
+            plan = ops.plan_for(adjacency_lists, node_states.shape[0])
+            return self._aggregate_edge_messages(messages, plan, False)
+        agg = self.__aggregation_fn(messages=messages, message_targets=torch.cat(all_targets, dim=0),
+                                    num_nodes=node_states.shape[0])
         return self._update(agg, False)
 
     @property

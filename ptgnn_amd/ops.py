@@ -720,12 +720,21 @@ def clear_plan_cache():
 # ------------------------------------------------------------------------------------------------
 # kernels
 # ------------------------------------------------------------------------------------------------
-def _hub_workspace(plan: GraphPlan, msg_dim: int, with_arg: bool, device):
-    """Chunk-partial buffer for the hub kernels, or (None, 0) when the plan is known hub-free."""
+def _hub_args(plan: GraphPlan, msg_dim: int, with_arg: bool, device):
+    """(workspace, tail): the seven trailing hub arguments of the aggregation entry points (num_edges, hub_threshold,
+    hub_entries, hub_count, hub_ws, hub_ws_bytes, hub_tickets) and the chunk-partial buffer they point into, which the
+    caller holds until the launch is enqueued; (None, hub-free tail) when the plan is known hub-free."""
     if not plan.may_have_hubs():
-        return None, 0
+        return None, (plan.num_edges, 0, None, None, None, 0, None)
     nbytes = _lib.load().ptgnn_amd_hub_workspace_bytes(plan.num_edges, msg_dim, 1 if with_arg else 0)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws, (plan.num_edges, HUB_THRESHOLD, plan.hub_entries.data_ptr(), plan.hub_count.data_ptr(), ws.data_ptr(),
+                nbytes, plan.hub_tickets(msg_dim).data_ptr())
+
+
+def _slot_map(plan: GraphPlan, type_bits: Optional[int], col: Optional[torch.Tensor]):
+    """(type_bits, col) of a call: the plan's own table-form pair unless the caller passes the edge form's."""
+    return plan.type_bits if type_bits is None else type_bits, plan.col if col is None else col
 
 
 def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str,
@@ -760,8 +769,7 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
     if epilogue & EPI_LAYERNORM:
         ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
     plan.wait()
-    tb = plan.type_bits if type_bits is None else type_bits
-    colt = plan.col if col is None else col
+    tb, colt = _slot_map(plan, type_bits, col)
     # algorithmic bytes (SURVEY.md 8d "(L)"): per edge one message row + its col entry; per node the
     # output row, the rowptr entry and (MLP-MP) the destination-term row; gathers get no cache credit
     nbytes = (plan.num_edges * (4.0 * msg_dim + 4) + N * (4.0 * msg_dim + 4)
@@ -773,7 +781,7 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
             raise _lib.PtgnnAmdError("gather_reduce: a row range needs a caller-owned `out` (the other rows are not "
                                      "written) and returns no arg")
         nbytes *= (hi - lo) / max(N, 1)
-    hub_ws, hub_bytes = _hub_workspace(plan, msg_dim, arg is not None, ysrc.device)
+    hub_ws, hub = _hub_args(plan, msg_dim, arg is not None, ysrc.device)
     with _timed("gather_reduce", bytes=nbytes):
         rc = lib.ptgnn_amd_gather_reduce_rows_f32(
             _ptr_or(ysrc, plan.rowptr), ld_y, ydst.data_ptr() if ydst is not None else None, ld_yd,
@@ -782,11 +790,7 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
             ln_weight.data_ptr() if ln_weight is not None else None,
             ln_bias.data_ptr() if ln_bias is not None else None, float(ln_eps),
             out.data_ptr(), msg_dim, arg.data_ptr() if arg is not None else None,
-            plan.num_edges, HUB_THRESHOLD if hub_ws is not None else 0,
-            plan.hub_entries.data_ptr() if hub_ws is not None else None,
-            plan.hub_count.data_ptr() if hub_ws is not None else None,
-            hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes,
-            plan.hub_tickets(msg_dim).data_ptr() if hub_ws is not None else None, lo, hi, _stream(out))
+            *hub, lo, hi, _stream(out))
     _lib.check(rc, "ptgnn_amd_gather_reduce_rows_f32")
     return (out, arg) if return_arg else out
 
@@ -895,19 +899,12 @@ def gather_reduce_masked(grad: torch.Tensor, arg: torch.Tensor, bplan: GraphPlan
     grad = _rowmajor(grad)
     bplan.wait()
     out = torch.empty(bplan.num_nodes, msg_dim, dtype=torch.float32, device=grad.device)
-    hub_ws, hub_bytes = _hub_workspace(bplan, msg_dim, False, grad.device)
+    hub_ws, hub = _hub_args(bplan, msg_dim, False, grad.device)
     with _timed("gather_reduce_masked", bytes=bplan.num_edges * (8.0 * msg_dim + 8) + bplan.num_nodes * (4.0 * msg_dim + 4)):
         rc = lib.ptgnn_amd_gather_reduce_masked_f32(_ptr_or(grad, bplan.rowptr), _ld(grad), _ptr_or(arg, bplan.rowptr),
                                                     bplan.rowptr.data_ptr(), bplan.col.data_ptr(),
                                                     slot_of.data_ptr(), bplan.num_nodes, msg_dim,
-                                                    out.data_ptr(), msg_dim, bplan.num_edges,
-                                                    HUB_THRESHOLD if hub_ws is not None else 0,
-                                                    bplan.hub_entries.data_ptr() if hub_ws is not None else None,
-                                                    bplan.hub_count.data_ptr() if hub_ws is not None else None,
-                                                    hub_ws.data_ptr() if hub_ws is not None else None,
-                                                    hub_bytes,
-                                                    bplan.hub_tickets(msg_dim).data_ptr() if hub_ws is not None else None,
-                                                    _stream(out))
+                                                    out.data_ptr(), msg_dim, *hub, _stream(out))
     _lib.check(rc, "ptgnn_amd_gather_reduce_masked_f32")
     return out
 
@@ -978,23 +975,18 @@ def gather_combine(ysrc: torch.Tensor, plan: GraphPlan, num_heads: int, num_base
     agg = torch.empty(N, M, dtype=torch.float32, device=ysrc.device) if return_agg else None
     arg = torch.empty(N, M, dtype=torch.int32, device=ysrc.device) if return_arg else None
     plan.wait()
-    tb = plan.type_bits if type_bits is None else type_bits
-    colt = plan.col if col is None else col
+    tb, colt = _slot_map(plan, type_bits, col)
     # algorithmic bytes: per edge one message row + its col entry; per node the coefficients, the output row, the rowptr
     # entry (and the aggregate / arg when asked for)
     nbytes = (plan.num_edges * (4.0 * M + 4) + N * (4.0 * (K * B + D) + 4)
               + (N * 4.0 * M if agg is not None else 0.0) + (N * 4.0 * M if arg is not None else 0.0))
-    hub_ws, hub_bytes = _hub_workspace(plan, M, arg is not None, ysrc.device)
+    hub_ws, hub = _hub_args(plan, M, arg is not None, ysrc.device)
     with _timed("egc_gather_combine", bytes=nbytes):
         rc = lib.ptgnn_amd_egc_gather_combine_f32(
             _ptr_or(ysrc, plan.rowptr), _ld(ysrc), plan.rowptr.data_ptr(), colt.data_ptr(), tb, N, K, B, Dh,
             REDUCE_IDS[reduce], coef.data_ptr(), _ld(coef), out.data_ptr(), D,
             agg.data_ptr() if agg is not None else None, arg.data_ptr() if arg is not None else None,
-            plan.num_edges, HUB_THRESHOLD if hub_ws is not None else 0,
-            plan.hub_entries.data_ptr() if hub_ws is not None else None,
-            plan.hub_count.data_ptr() if hub_ws is not None else None,
-            hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes,
-            plan.hub_tickets(M).data_ptr() if hub_ws is not None else None, _stream(out))
+            *hub, _stream(out))
     if rc == _lib.EUNSUPPORTED:
         res = gather_reduce(ysrc, plan, M, reduce, return_arg=return_arg, type_bits=tb, col=colt)
         agg, arg = res if return_arg else (res, None)
@@ -1087,8 +1079,7 @@ def pna_aggregate(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, delta: floa
                                 or not agg_out.is_contiguous() or agg_out.device != ysrc.device):
         raise _lib.PtgnnAmdError(f"pna_aggregate: `agg_out` must be a contiguous float32 [{N}, {5 * M}] tensor")
     plan.wait()
-    tb = plan.type_bits if type_bits is None else type_bits
-    colt = plan.col if col is None else col
+    tb, colt = _slot_map(plan, type_bits, col)
     # algorithmic bytes: per edge one message row + its col entry; per node the rowptr entry, the 15M-wide output row
     # (and the destination-term row, the two arg rows)
     nbytes = (plan.num_edges * (4.0 * M + 4) + N * (60.0 * M + 4) + (N * 4.0 * M if ydst is not None else 0.0)
