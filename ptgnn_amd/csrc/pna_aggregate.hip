@@ -11,7 +11,7 @@
 // optionally followed by GELU and an affine LayerNorm over the 15M columns (the MLP layer's message activation and
 // first state-update block), so inference never writes the pre-LayerNorm row.
 //
-// Mapping (HBM-bound; the row walk of gather_reduce_core.h):
+// Mapping (HBM-bound; the lane-group row walk of RowOp in gather_reduce_core.h, restated in PnaRow below):
 //   * rows with d <= kPnaLong: one row per group of LPR lanes, each lane owning VEC-wide column chunks; pass 1 folds
 //     sum / max / min (+ arg) in slot order over prefetched groups of U slots (the next group's `col` entries ride
 //     behind the current group's rows), pass 2 re-walks the same slots for the std sum -- the rows were just read,
@@ -655,32 +655,32 @@ int pna_geometry(bool vec4, int msg_dim, F f) {
   return f(IC<1>{}, IC<64>{}, IC<4>{});
 }
 
-template <int VEC, int LPR, int CH, int DST, bool HAS_ARG, bool EPI = false>
-int pna_launch(PnaArgs a, int col_blocks, hipStream_t stream) {
-  constexpr int RPB = 256 / LPR;
-  a.num_tiles = (a.num_nodes + RPB - 1) / RPB;
+// one pass over the plan: `rows` (rpb rows per workgroup, rows up to kPnaLong in-edges), then `long_rows` (the rest).
+// The kernels arrive as host function pointers: the address of a __global__ function's host stub is its launch handle.
+int pna_launch_pair(void (*rows)(PnaArgs), void (*long_rows)(PnaArgs), int rpb, const PnaArgs &a0, int col_blocks,
+                    hipStream_t stream) {
+  PnaArgs a = a0;
+  a.num_tiles = (a.num_nodes + rpb - 1) / rpb;
   dim3 grid((unsigned)xcd_padded_blocks(a.num_tiles), (unsigned)col_blocks);
-  k_pna_rows<VEC, LPR, CH, DST, HAS_ARG, EPI><<<grid, 256, 0, stream>>>(a);
+  rows<<<grid, 256, 0, stream>>>(a);
   PTGNN_LAUNCH_CHECK();
   const int64_t lb = (a.num_nodes + 255) / 256;
   dim3 lgrid((unsigned)(lb < 1024 ? lb : 1024), (unsigned)col_blocks);
-  k_pna_long_rows<VEC, LPR, CH, DST, HAS_ARG, EPI><<<lgrid, 256, 0, stream>>>(a);
+  long_rows<<<lgrid, 256, 0, stream>>>(a);
   PTGNN_LAUNCH_CHECK();
   return PTGNN_AMD_OK;
 }
 
+template <int VEC, int LPR, int CH, int DST, bool HAS_ARG, bool EPI = false>
+int pna_launch(const PnaArgs &a, int col_blocks, hipStream_t stream) {
+  return pna_launch_pair(k_pna_rows<VEC, LPR, CH, DST, HAS_ARG, EPI>, k_pna_long_rows<VEC, LPR, CH, DST, HAS_ARG, EPI>,
+                         256 / LPR, a, col_blocks, stream);
+}
+
 template <int VEC, int LPR, int CH>
-int pna_backward_launch(PnaArgs a, int col_blocks, hipStream_t stream) {
-  constexpr int RPB = 256 / LPR;
-  a.num_tiles = (a.num_nodes + RPB - 1) / RPB;
-  dim3 grid((unsigned)xcd_padded_blocks(a.num_tiles), (unsigned)col_blocks);
-  k_pna_bwd_rows<VEC, LPR, CH><<<grid, 256, 0, stream>>>(a);
-  PTGNN_LAUNCH_CHECK();
-  const int64_t lb = (a.num_nodes + 255) / 256;
-  dim3 lgrid((unsigned)(lb < 1024 ? lb : 1024), (unsigned)col_blocks);
-  k_pna_bwd_long_rows<VEC, LPR, CH><<<lgrid, 256, 0, stream>>>(a);
-  PTGNN_LAUNCH_CHECK();
-  return PTGNN_AMD_OK;
+int pna_backward_launch(const PnaArgs &a, int col_blocks, hipStream_t stream) {
+  return pna_launch_pair(k_pna_bwd_rows<VEC, LPR, CH>, k_pna_bwd_long_rows<VEC, LPR, CH>, 256 / LPR, a, col_blocks,
+                         stream);
 }
 
 }  // namespace
