@@ -133,6 +133,8 @@ enum {
   PTGNN_AMD_KERNEL_ATTENTION_POOL,          /* ptgnn_amd_attention_pool_f32 */
   PTGNN_AMD_KERNEL_ATTENTION_POOL_BACKWARD, /* ptgnn_amd_attention_pool_backward_f32 */
   PTGNN_AMD_KERNEL_HEAD_PROJECTION,         /* ptgnn_amd_head_projection_f32 */
+  PTGNN_AMD_KERNEL_GRAPH_NORM,              /* ptgnn_amd_graph_norm_f32 */
+  PTGNN_AMD_KERNEL_GRAPH_NORM_BACKWARD,     /* ptgnn_amd_graph_norm_backward_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -668,6 +670,44 @@ int ptgnn_amd_head_projection_f32(int mode, const float *a /* nullable in mode 1
                                   const float *b /* nullable in mode 0 */, const float *w /* nullable in mode 2 */,
                                   int64_t num_rows, int32_t num_heads, int32_t head_dim, int32_t dim, float scale,
                                   float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GraphNorm: per-graph normalisation of node states, per graph g with n_g nodes, per column, fp32:
+ *   mu[g] = (1/n_g) sum_{i in g} x_i      s_i = x_i - alpha * mu[g]      sig2[g] = (1/n_g) sum_{i in g} s_i^2 + eps
+ *   y_i = gamma * s_i / sqrt(sig2[g]) + bias
+ * Replaces: GraphNorm.forward, ptgnn/neuralmodels/gnn/messagepassing/graphnorm.py:36-46 -- two torch_scatter.scatter_mean
+ *   calls, the gathers mean[idx] and sigma_2[idx] and the elementwise pow / sub / mul / sqrt / div / add, each of which
+ *   materialises [N, D].  Three reads of x and one write of y; no float atomics: a graph is cut into 128-row chunks
+ *   counted from its own start, the chunk partials are added in chunk order -- a graph's statistics and output rows are a
+ *   fixed function of its rows and their order, wherever the graph sits in the batch.  sig2 is the two-pass variance over
+ *   the rounded s_i (alpha * mu rounded, then the subtraction rounded), as the reference's.
+ *   x [num_elements, dim] (ld_x), gamma / alpha / bias [dim], rowptr int32 [num_segments + 1] / perm int32 [num_elements]:
+ *   the stable plan of the node -> graph map (any map; as ptgnn_amd_weighted_pool_f32), y [num_elements, dim] (ld_y):
+ *   every row named by perm OVERWRITTEN.  mean (nullable: inference) [num_segments, dim]: mu per graph (0 for a graph
+ *   without nodes), all the backward needs from the forward.  dim <= 1024 (ptgnn_amd_graph_norm_supported), else
+ *   EUNSUPPORTED.  workspace: ptgnn_amd_graph_norm_workspace_bytes.
+ * Backward: with r = 1/sqrt(sig2), gy = grad_y [num_elements, dim] (ld_gy), A = sum gy_i, B = sum gy_i s_i, C = sum s_i,
+ *   c = -gamma B r^3 / n_g, S = gamma r A + c C.  s_i is re-formed from the forward's `mean` (the same rounded s_i); A, B, C
+ *   and sum s_i^2 are summed with float64 accumulators and sig2 (from `eps`, the forward's), r, c, S formed in float64:
+ *   S cancels to ~0 on one- and two-node graphs, which fp32 per-graph arithmetic does not survive.
+ *   grad_x_i = gamma r gy_i + c s_i - (alpha / n_g) S    [num_elements, dim] (ld_gx), every row named by perm,
+ *   grad_gamma = sum_g B r,  grad_alpha = -sum_g mu S,  grad_bias = sum_g A   [dim] each, graphs added in graph order.
+ *   Two reads of (x, grad_y), one write of grad_x.  All outputs OVERWRITTEN and deterministic.
+ *   workspace: ptgnn_amd_graph_norm_backward_workspace_bytes.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_graph_norm_supported(int32_t dim);
+size_t ptgnn_amd_graph_norm_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim);
+int ptgnn_amd_graph_norm_f32(const float *x, int64_t ld_x, const float *gamma, const float *alpha, const float *bias,
+                             float eps, const int32_t *rowptr, const int32_t *perm, int64_t num_segments,
+                             int64_t num_elements, int32_t dim, float *y, int64_t ld_y, float *mean /* nullable */,
+                             void *workspace, size_t workspace_bytes, void *stream);
+size_t ptgnn_amd_graph_norm_backward_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim);
+int ptgnn_amd_graph_norm_backward_f32(const float *x, int64_t ld_x, const float *grad_y, int64_t ld_gy,
+                                      const float *gamma, const float *alpha, float eps, const float *mean,
+                                      const int32_t *rowptr, const int32_t *perm, int64_t num_segments,
+                                      int64_t num_elements, int32_t dim,
+                                      float *grad_x, int64_t ld_gx, float *grad_gamma, float *grad_alpha,
+                                      float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * EGC-S layer (egcmessagepassing.py:63-91; aggregation abstractmessagepassing.py:38-50), K heads, B bases,

@@ -47,6 +47,7 @@ the first Linear of every edge MLP can be the grouped GEMM), `_edge_mlp_tail` (t
 import contextlib
 import os
 import threading
+import weakref
 from typing import Dict, List, Optional, Tuple, Union
 
 import torch
@@ -54,8 +55,8 @@ from torch import nn
 
 from ptgnn_amd import _lib, dense, ops, torch_route
 from ptgnn_amd.scatter import (edge_linear as edge_linear_autograd, edge_linear_feat as edge_linear_feat_autograd,
-                               gather_reduce as gather_reduce_autograd, pna_aggregate as pna_aggregate_autograd,
-                               segment_reduce)
+                               gather_reduce as gather_reduce_autograd, graph_norm as graph_norm_autograd,
+                               pna_aggregate as pna_aggregate_autograd, scatter_mean, segment_reduce)
 
 try:  # inside a ptgnn install the layers ARE ptgnn layers
     from ptgnn.neuralmodels.gnn.messagepassing.abstractmessagepassing import (  # type: ignore
@@ -360,6 +361,31 @@ def _on_host(node_states: torch.Tensor) -> bool:
     typilus/predict.py:25-27; trainer.py:392-395 trains there without a GPU); GPU tensors ALWAYS take
     libptgnn_amd.so and raise when it is missing or fails -- there is no way from a GPU tensor into the torch route."""
     return not node_states.is_cuda
+
+
+# The node -> graph map of a minibatch, shared by GraphNorm and the global-exchange layers of ptgnn_amd/reduceops.py
+_NUM_SAMPLES = []   # (weakref(index), version, max + 1) of the most recent index tensors
+
+
+def _num_samples(index: torch.Tensor) -> int:
+    """`index.max() + 1` -- the reference's own host read-back (globalgraphexchange.py:40, once per LAYER there);
+    made once per index tensor, i.e. once per minibatch, here."""
+    for ref, ver, upper in _NUM_SAMPLES:
+        if ref() is index and ver == index._version:
+            return upper
+    upper = int(index.max()) + 1 if index.numel() else 0
+    _NUM_SAMPLES.insert(0, (weakref.ref(index), index._version, upper))
+    del _NUM_SAMPLES[4:]
+    return upper
+
+
+def _index_plan(index: torch.Tensor, num_samples: int) -> "ops.GraphPlan":
+    """Plan of an element -> sample map.  The reference's reducers are plain torch_scatter calls
+    (varsizedsummary.py:35-41,76-81) and accept ANY map, so every map takes the stable plan build -- cached per index
+    tensor (`ops.plan_for`), i.e. once per minibatch for all global-exchange layers.  Round 2 tested the map for
+    sortedness first to skip the sort for `node_to_graph_idx` (graphneuralnetwork.py:418-423,440-443); that test was
+    a host read-back per minibatch, which now costs more than the ~40 us of device time the sort takes."""
+    return ops.plan_for([(index, index)], int(num_samples))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -694,6 +720,76 @@ class EGCMessagePassingLayer(AbstractMessagePassingLayer):
     @property
     def output_state_dimension(self) -> int:
         return self.__output_state_dim
+
+
+# ------------------------------------------------------------------------------------------------
+# GraphNorm
+# ------------------------------------------------------------------------------------------------
+def _composed_graph_norm(node_states, node_to_graph_idx, num_graphs: int, gamma, alpha, bias, eps: float) -> torch.Tensor:
+    """graphnorm.py:36-46 on the HIP `scatter_mean` of the facade plus torch's elementwise operators (their autograd
+    included): widths beyond the fused kernels."""
+    per_graph_mean = scatter_mean(node_states, node_to_graph_idx, dim=0, dim_size=num_graphs)
+    shifted = node_states - alpha * per_graph_mean[node_to_graph_idx]
+    sigma_2 = scatter_mean(torch.pow(shifted, 2), node_to_graph_idx, dim=0, dim_size=num_graphs) + eps
+    return gamma * shifted / torch.sqrt(sigma_2[node_to_graph_idx]) + bias
+
+
+class GraphNorm(AbstractMessagePassingLayer):
+    """GraphNorm (arXiv:2009.03294); constructor, parameters and semantics of graphnorm.py:9-54.  Per graph g, per column:
+        mu = mean_{i in g} x_i,   s_i = x_i - alpha * mu,   sig2 = mean_{i in g} s_i^2 + eps,   y_i = gamma * s_i / sqrt(sig2) + bias
+    The number of graphs is `node_to_graph_idx.max() + 1`, as the reference's `scatter_mean` without `dim_size` reads it
+    (one cached read-back per minibatch).
+
+    GPU tensors: the fused HIP kernels of csrc/graph_norm.hip over the cached plan of the node -> graph map (any map, not
+    only a sorted one) -- three reads of x and one write of y, with gradients the `_GraphNorm` autograd node and its
+    two-read backward.  Widths beyond 1024 take the composed route.  CPU tensors: torch_route.graph_norm."""
+
+    def __init__(self, input_state_dimension: int, eps: float = 1e-10):
+        super().__init__()
+        self.__input_state_dim = input_state_dimension
+        self.__eps = eps
+
+        self.gamma = nn.Parameter(torch.ones(1, input_state_dimension))
+        self.alpha = nn.Parameter(torch.ones(1, input_state_dimension))
+        self.bias = nn.Parameter(torch.zeros(1, input_state_dimension))
+
+    def forward(self, node_states: torch.Tensor, adjacency_lists: Adj, node_to_graph_idx: torch.Tensor,
+                reference_node_ids: Dict[str, torch.Tensor],
+                reference_node_graph_idx: Dict[str, torch.Tensor],
+                edge_features: List[torch.Tensor]) -> torch.Tensor:
+        num_graphs = _num_samples(node_to_graph_idx)
+        if _on_host(node_states):
+            return torch_route.graph_norm(node_states, node_to_graph_idx, num_graphs, self.gamma, self.alpha, self.bias,
+                                          self.__eps)
+        if node_states.dtype in _AMP_DTYPES:   # AMP: fp32 inside, the caller's dtype outside
+            return self.forward(node_states.float(), adjacency_lists, node_to_graph_idx, reference_node_ids,
+                                reference_node_graph_idx, edge_features).to(node_states.dtype)
+        if node_states.dtype != torch.float32:
+            raise _lib.PtgnnAmdError(f"GraphNorm: node states must be float32 / float16 / bfloat16 on the GPU (got "
+                                     f"{node_states.dtype})")
+        if node_states.dim() != 2 or node_states.shape[1] != self.__input_state_dim:
+            raise _lib.PtgnnAmdError(f"GraphNorm: node states [N, {self.__input_state_dim}] expected (got "
+                                     f"{tuple(node_states.shape)})")
+        if not ops.graph_norm_supported(self.__input_state_dim):
+            return _composed_graph_norm(node_states, node_to_graph_idx, num_graphs, self.gamma, self.alpha, self.bias,
+                                        self.__eps)
+        plan = _index_plan(node_to_graph_idx, num_graphs)
+        if _no_grad_needed(node_states, self.gamma, self.alpha, self.bias):
+            return ops.graph_norm(node_states, self.gamma, self.alpha, self.bias, self.__eps, plan)
+        return graph_norm_autograd(node_states, self.gamma, self.alpha, self.bias, self.__eps, plan)
+
+    def forward_sharded(self, node_states: torch.Tensor, shard) -> torch.Tensor:
+        raise NotImplementedError("GraphNorm is not supported under dst-range sharding (ptgnn_amd.sharded): the nodes of a "
+                                  "graph may span ranks, and the per-graph statistics are not combined across ranks; "
+                                  "run it unsharded")
+
+    @property
+    def input_state_dimension(self) -> int:
+        return self.__input_state_dim
+
+    @property
+    def output_state_dimension(self) -> int:
+        return self.__input_state_dim
 
 
 # ------------------------------------------------------------------------------------------------

@@ -43,7 +43,8 @@ _AGG_FAMILY_FIRST = 64   # PTGNN_AMD_KERNEL_AGG_FIRST_: the aggregation families
 def launch_counts(aggregation: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
-    (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward)."""
+    (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
+    attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward)."""
     lib = _lib.load()
     out = {}
     for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
@@ -1731,6 +1732,82 @@ def attention_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, p
             gx.data_ptr() if n else None, d, gu.data_ptr(), ws.data_ptr(), ws_bytes, _stream(gu))
     _lib.check(rc, "ptgnn_amd_attention_pool_backward_f32")
     return gx, gu
+
+
+def graph_norm_supported(dim: int) -> bool:
+    """Whether the fused GraphNorm takes `dim` columns (ptgnn_amd_graph_norm_supported: dim <= 1024)."""
+    return bool(_lib.load().ptgnn_amd_graph_norm_supported(int(dim)))
+
+
+def _graph_norm_args(x: torch.Tensor, params, plan: GraphPlan, what: str):
+    _require_cuda_f32("x", x)
+    x = _rowmajor(x)
+    n, d = x.shape
+    if d % 4 == 0 and (x.data_ptr() % 16 or (n > 1 and x.stride(0) % 4)):
+        x = x.contiguous()     # float4 rows whenever the width allows: one chunk layout per width
+    if n != plan.num_edges or plan.perm is None or any(p.numel() != d for p in params):
+        raise _lib.PtgnnAmdError(f"{what}: x {tuple(x.shape)} and parameters of {[p.numel() for p in params]} entries do "
+                                 f"not fit a plan of {plan.num_edges} elements")
+    flat = []
+    for name, p in zip(("gamma", "alpha", "bias"), params):
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise _lib.PtgnnAmdError(f"{what}: {name} must be a float32 GPU tensor (got {p.dtype} on {p.device})")
+        flat.append(p.detach().reshape(-1).contiguous())
+    return x, flat, n, d, plan.num_nodes
+
+
+def graph_norm(x: torch.Tensor, gamma: torch.Tensor, alpha: torch.Tensor, bias: torch.Tensor, eps: float,
+               plan: GraphPlan, with_mean: bool = False):
+    """GraphNorm over the plan of the node -> graph map (ptgnn_amd_graph_norm_f32; graphnorm.py:36-46 in three reads of x
+    and one write of y): y [n, D], and with `with_mean` also the per-graph means [G, D], which `graph_norm_backward`
+    takes."""
+    lib = _lib.load()
+    x, (gamma, alpha, bias), n, d, G = _graph_norm_args(x, (gamma, alpha, bias), plan, "graph_norm")
+    y = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    mean = torch.empty(G, d, dtype=torch.float32, device=x.device) if with_mean else None
+    if G > 0:
+        ws_bytes = int(lib.ptgnn_amd_graph_norm_workspace_bytes(G, n, d))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        plan.wait()
+        with _timed("graph_norm", bytes=4.0 * (4 * n * d) + 3 * 4.0 * n):
+            rc = lib.ptgnn_amd_graph_norm_f32(x.data_ptr() if n else None, _ld(x) if n else d, gamma.data_ptr(),
+                                              alpha.data_ptr(), bias.data_ptr(), float(eps), plan.rowptr.data_ptr(),
+                                              plan.perm.data_ptr() if n else None, G, n, d,
+                                              y.data_ptr() if n else None, d,
+                                              mean.data_ptr() if with_mean else None, ws.data_ptr(), ws_bytes,
+                                              _stream(y))
+        _lib.check(rc, "ptgnn_amd_graph_norm_f32")
+    return (y, mean) if with_mean else y
+
+
+def graph_norm_backward(x: torch.Tensor, grad_y: torch.Tensor, gamma: torch.Tensor, alpha: torch.Tensor, eps: float,
+                        mean: torch.Tensor, plan: GraphPlan):
+    """(grad_x [n, D], grad_gamma [D], grad_alpha [D], grad_bias [D]) of `graph_norm` from grad_y = dL/dy and the
+    forward's eps and per-graph means (ptgnn_amd_graph_norm_backward_f32: two reads of (x, grad_y), one write of grad_x; per-graph
+    arithmetic in float64; deterministic)."""
+    lib = _lib.load()
+    x, (gamma, alpha), n, d, G = _graph_norm_args(x, (gamma, alpha), plan, "graph_norm_backward")
+    _require_cuda_f32("grad_y", grad_y)
+    grad_y = _rowmajor(grad_y)
+    if d % 4 == 0 and (grad_y.data_ptr() % 16 or (n > 1 and grad_y.stride(0) % 4)):
+        grad_y = grad_y.contiguous()
+    mean = mean.contiguous()
+    if tuple(grad_y.shape) != (n, d) or tuple(mean.shape) != (G, d) or mean.dtype != torch.float32:
+        raise _lib.PtgnnAmdError(f"graph_norm_backward: grad_y {tuple(grad_y.shape)} / mean {tuple(mean.shape)} do not "
+                                 f"match x {(n, d)} over {G} graphs")
+    gx = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    gp = torch.empty(3, d, dtype=torch.float32, device=x.device)
+    ws_bytes = int(lib.ptgnn_amd_graph_norm_backward_workspace_bytes(G, n, d))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    plan.wait()
+    with _timed("graph_norm_backward", bytes=4.0 * (5 * n * d) + 2 * 4.0 * n):
+        rc = lib.ptgnn_amd_graph_norm_backward_f32(
+            x.data_ptr() if n else None, _ld(x) if n else d, grad_y.data_ptr() if n else None, _ld(grad_y) if n else d,
+            gamma.data_ptr(), alpha.data_ptr(), float(eps), mean.data_ptr() if G else None, plan.rowptr.data_ptr(),
+            plan.perm.data_ptr() if n else None, G, n, d, gx.data_ptr() if n else None, d, gp[0].data_ptr(),
+            gp[1].data_ptr(), gp[2].data_ptr(), ws.data_ptr(), ws_bytes, _stream(gx))
+    _lib.check(rc, "ptgnn_amd_graph_norm_backward_f32")
+    return gx, gp[0], gp[1], gp[2]
 
 
 HEAD_EXPAND, HEAD_CONTRACT, HEAD_WEIGHT_GRAD = 0, 1, 2    # modes of ptgnn_amd_head_projection_f32

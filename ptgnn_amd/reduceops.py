@@ -8,14 +8,14 @@ A disjoint-union batch lists the nodes of graph 0, then graph 1, ... (graphneura
 so the index is SORTED and the plan needs no sort at all: rowptr = searchsorted, col = identity.
 """
 import math
-import weakref
 from typing import NamedTuple, Optional, Union
 
 import torch
 from torch import nn
 
 from ptgnn_amd import _lib, dense, ops, scatter as scatter_facade, torch_route
-from ptgnn_amd.layers import AbstractMessagePassingLayer, _check_device, _no_grad_needed
+from ptgnn_amd.layers import (AbstractMessagePassingLayer, _check_device, _index_plan, _no_grad_needed,  # noqa: F401
+                              _num_samples)
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_reduce
 
 
@@ -29,30 +29,6 @@ class ElementsToSummaryRepresentationInput(NamedTuple):
 class AbstractVarSizedElementReduce(nn.Module):
     def forward(self, inputs: ElementsToSummaryRepresentationInput) -> torch.Tensor:
         raise NotImplementedError
-
-
-_NUM_SAMPLES = []   # (weakref(index), version, max + 1) of the most recent index tensors
-
-
-def _num_samples(index: torch.Tensor) -> int:
-    """`index.max() + 1` -- the reference's own host read-back (globalgraphexchange.py:40, once per LAYER there);
-    made once per index tensor, i.e. once per minibatch, here."""
-    for ref, ver, upper in _NUM_SAMPLES:
-        if ref() is index and ver == index._version:
-            return upper
-    upper = int(index.max()) + 1 if index.numel() else 0
-    _NUM_SAMPLES.insert(0, (weakref.ref(index), index._version, upper))
-    del _NUM_SAMPLES[4:]
-    return upper
-
-
-def _index_plan(index: torch.Tensor, num_samples: int) -> "ops.GraphPlan":
-    """Plan of an element -> sample map.  The reference's reducers are plain torch_scatter calls
-    (varsizedsummary.py:35-41,76-81) and accept ANY map, so every map takes the stable plan build -- cached per index
-    tensor (`ops.plan_for`), i.e. once per minibatch for all global-exchange layers.  Round 2 tested the map for
-    sortedness first to skip the sort for `node_to_graph_idx` (graphneuralnetwork.py:418-423,440-443); that test was
-    a host read-back per minibatch, which now costs more than the ~40 us of device time the sort takes."""
-    return ops.plan_for([(index, index)], int(num_samples))
 
 
 def _pool(values: torch.Tensor, index: torch.Tensor, num_samples, reduce: str) -> torch.Tensor:

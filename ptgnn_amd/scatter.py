@@ -119,6 +119,31 @@ def pna_aggregate(messages: torch.Tensor, plan: "ops.GraphPlan", delta: float = 
     return _PnaAggregate.apply(messages, plan, float(delta), round_to)
 
 
+class _GraphNorm(torch.autograd.Function):
+    """GraphNorm (graphnorm.py:36-46) over the plan of the node -> graph map as ONE node: forward and backward are the two
+    entry points of csrc/graph_norm.hip (no [N, D] intermediate, deterministic parameter gradients).  The forward's
+    per-graph means are what the backward re-forms the forward's s_i from."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, alpha, bias, eps, plan):
+        y, mean = ops.graph_norm(x, gamma, alpha, bias, eps, plan, with_mean=True)
+        ctx.plan, ctx.eps = plan, eps
+        ctx.save_for_backward(x, gamma, alpha, mean)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, gamma, alpha, mean = ctx.saved_tensors
+        gx, gg, ga, gb = ops.graph_norm_backward(x, grad_y, gamma, alpha, ctx.eps, mean, ctx.plan)
+        return gx, gg.reshape(gamma.shape), ga.reshape(alpha.shape), gb.reshape(gamma.shape), None, None
+
+
+def graph_norm(x: torch.Tensor, gamma: torch.Tensor, alpha: torch.Tensor, bias: torch.Tensor, eps: float,
+               plan: "ops.GraphPlan") -> torch.Tensor:
+    """Differentiable fused GraphNorm of fp32 [N, D] node states over the plan of their node -> graph map."""
+    return _GraphNorm.apply(x, gamma, alpha, bias, float(eps), plan)
+
+
 def _prepare(src: torch.Tensor, index: torch.Tensor, dim: int, out, dim_size):
     """Common argument handling of the torch_scatter-shaped entry points: 2-D (or 1-D) `src`, 1-D int64
     `index` along dim 0.  Anything else raises (no silent fallback)."""

@@ -103,6 +103,16 @@ def segment(rows: torch.Tensor, index: torch.Tensor, n: int, reduce: str, return
     return out
 
 
+def graph_norm(node_states: torch.Tensor, node_to_graph_idx: torch.Tensor, num_graphs: int, gamma: torch.Tensor,
+               alpha: torch.Tensor, bias: torch.Tensor, eps: float) -> torch.Tensor:
+    """graphnorm.py:36-46, the reference's operator sequence (scatter_mean = `segment(..., "mean")`)."""
+    _host_only(node_states, node_to_graph_idx)
+    per_graph_mean = segment(node_states, node_to_graph_idx, num_graphs, "mean")          # [num_graphs, D]
+    shifted = node_states - alpha * per_graph_mean[node_to_graph_idx]                     # [num_nodes, D]
+    sigma_2 = segment(torch.pow(shifted, 2), node_to_graph_idx, num_graphs, "mean") + eps  # [num_graphs, D]
+    return gamma * shifted / torch.sqrt(sigma_2[node_to_graph_idx]) + bias
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # torch_scatter-shaped entry points (any `dim`, 1-D or broadcastable index) for host tensors
 # ------------------------------------------------------------------------------------------------------------------
