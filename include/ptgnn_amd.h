@@ -135,6 +135,8 @@ enum {
   PTGNN_AMD_KERNEL_HEAD_PROJECTION,         /* ptgnn_amd_head_projection_f32 */
   PTGNN_AMD_KERNEL_GRAPH_NORM,              /* ptgnn_amd_graph_norm_f32 */
   PTGNN_AMD_KERNEL_GRAPH_NORM_BACKWARD,     /* ptgnn_amd_graph_norm_backward_f32 */
+  PTGNN_AMD_KERNEL_BLOCK_ATTENTION,          /* ptgnn_amd_block_attention_f32 */
+  PTGNN_AMD_KERNEL_BLOCK_ATTENTION_BACKWARD, /* ptgnn_amd_block_attention_backward_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -708,6 +710,54 @@ int ptgnn_amd_graph_norm_backward_f32(const float *x, int64_t ld_x, const float 
                                       int64_t num_elements, int32_t dim,
                                       float *grad_x, int64_t ld_gx, float *grad_gamma, float *grad_alpha,
                                       float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Block self-attention among the nodes of each window of a graph, the core of MultiHeadSelfAttentionMessagePassing.
+ * Windows (ptgnn_amd_attention_windows).  Replaces: __iter_idxs_per_graph,
+ *   ptgnn/neuralmodels/gnn/messagepassing/selfattmessagepassing.py:59-75 -- scatter_sum of ones, then a Python loop that
+ *   yields torch.arange per window.  Graph g owns the rows rowptr[g] .. rowptr[g + 1] - 1 (rowptr int32
+ *   [num_graphs + 1]: the prefix sums of the per-graph node counts, i.e. the rowptr of the plan of the node -> graph map;
+ *   only the COUNTS of the map matter, as in the reference) and is cut every max_num_nodes rows; a graph without nodes
+ *   gives no window.  windows int32 [capacity], capacity >= ptgnn_amd_attention_windows_bound(...) + 1 =
+ *   ceil(num_rows / max_num_nodes) + num_graphs + 1: windows[w] = first row of window w for the W windows of the batch,
+ *   windows[W .. bound] = num_rows (window w is rows windows[w] .. windows[w + 1] - 1; the ones past W are empty).  One
+ *   launch, no host read-back.
+ * Attention (ptgnn_amd_block_attention_f32).  Replaces: selfattmessagepassing.py:104-117 -- per window the gathers
+ *   keys[graph_nodes] / queries[...] / values[...], einsum("khd,vhd->khv") / sqrt(dk), softmax over v, dropout,
+ *   einsum("khv,vhd->khd"), and the torch.cat of the windows.  Per window and head, exact fp32 (fp32 MFMA):
+ *     S[k, v] = key_k . query_v / sqrt(dk)    P = dropout(softmax_v(S))    out_k = sum_v P[k, v] value_v
+ *   (the row side is the key, the softmax runs over the queries: the reference's order).  kqv [num_rows, heads (2 dk + dv)]
+ *   (ld_kqv) is read in place, per head [keys dk | queries dk | values dv]; `windows` / num_windows: the table above and
+ *   its bound (num_windows + 1 entries are read; no window may be longer than max_num_nodes).  Flash-style: a window is
+ *   walked in 32-row tiles through LDS with a running max and sum, the [n, n] scores are never written.
+ *   out [num_rows, heads dv] (ld_out) and lse [num_rows, heads] (the log-sum-exp of every score row, which the backward
+ *   takes) are OVERWRITTEN for every row inside a window.  dropout_p in [0, 1): 0 = off; otherwise element (row r, head
+ *   h, window column j) is multiplied by the stateless hash mask of row r heads + h, column j of a [num_rows heads, W]
+ *   mask, W = max_num_nodes rounded up to even (tests/helpers.py dropout_keep_scale), after the normalisation.
+ *   1 <= dk, dv <= 128 (ptgnn_amd_block_attention_supported), else EUNSUPPORTED.
+ * Backward (ptgnn_amd_block_attention_backward_f32): autograd of lines 104-117.  P = exp(S - lse) is recomputed,
+ *   D_k = sum_d grad_out[k, d] out[k, d], dS = P o (M o dP - D), dP[k, v] = grad_out_k . value_v (M: the forward's mask):
+ *     grad key_k = sum_v dS[k, v] query_v / sqrt(dk)   grad query_v = sum_k dS[k, v] key_k / sqrt(dk)
+ *     grad value_v = sum_k (M o P)[k, v] grad_out_k
+ *   written into grad_kqv [num_rows, heads (2 dk + dv)] (ld_gkqv) in the layout of kqv, every row inside a window
+ *   OVERWRITTEN.  Every sum runs in tile order inside one wave: no float atomics, deterministic, and a window's rows do
+ *   not depend on its place in the batch.  workspace: ptgnn_amd_block_attention_backward_workspace_bytes (D).
+ * Bad arguments are refused before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_block_attention_supported(int32_t dk, int32_t dv);
+int64_t ptgnn_amd_attention_windows_bound(int64_t num_graphs, int64_t num_rows, int32_t max_num_nodes);
+int ptgnn_amd_attention_windows(const int32_t *rowptr, int64_t num_graphs, int64_t num_rows, int32_t max_num_nodes,
+                                int32_t *windows, int64_t capacity, void *stream);
+int ptgnn_amd_block_attention_f32(const float *kqv, int64_t ld_kqv, const int32_t *windows, int64_t num_windows,
+                                  int64_t num_rows, int32_t max_num_nodes, int32_t num_heads, int32_t dk, int32_t dv,
+                                  float dropout_p, uint64_t seed, float *out, int64_t ld_out, float *lse, void *stream);
+size_t ptgnn_amd_block_attention_backward_workspace_bytes(int64_t num_rows, int32_t num_heads);
+int ptgnn_amd_block_attention_backward_f32(const float *kqv, int64_t ld_kqv, const float *out, int64_t ld_out,
+                                           const float *lse, const float *grad_out, int64_t ld_go,
+                                           const int32_t *windows, int64_t num_windows, int64_t num_rows,
+                                           int32_t max_num_nodes, int32_t num_heads, int32_t dk, int32_t dv,
+                                           float dropout_p, uint64_t seed, float *grad_kqv, int64_t ld_gkqv,
+                                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * EGC-S layer (egcmessagepassing.py:63-91; aggregation abstractmessagepassing.py:38-50), K heads, B bases,

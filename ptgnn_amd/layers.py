@@ -54,7 +54,8 @@ import torch
 from torch import nn
 
 from ptgnn_amd import _lib, dense, ops, torch_route
-from ptgnn_amd.scatter import (edge_linear as edge_linear_autograd, edge_linear_feat as edge_linear_feat_autograd,
+from ptgnn_amd.scatter import (block_attention as block_attention_autograd, edge_linear as edge_linear_autograd,
+                               edge_linear_feat as edge_linear_feat_autograd,
                                gather_reduce as gather_reduce_autograd, graph_norm as graph_norm_autograd,
                                pna_aggregate as pna_aggregate_autograd, scatter_mean, segment_reduce)
 
@@ -790,6 +791,129 @@ class GraphNorm(AbstractMessagePassingLayer):
     @property
     def output_state_dimension(self) -> int:
         return self.__input_state_dim
+
+
+# ------------------------------------------------------------------------------------------------
+# MultiHeadSelfAttentionMessagePassing
+# ------------------------------------------------------------------------------------------------
+class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
+    """A transformer layer among the nodes of each graph; constructor, parameters (state_dict keys included) and
+    semantics of selfattmessagepassing.py:9-136.  With kqv = W_h x, per head [keys dk | queries dk | values dv], the nodes
+    of a graph are cut into windows of at most `max_num_nodes` consecutive rows (graph g owns the count_g rows after
+    those of the graphs in front of it: only the COUNTS of `node_to_graph_idx` are read, as in the reference), and
+        S[k, v] = key_k . query_v / sqrt(dk),  P = dropout(softmax_v(S)),  out_k = sum_v P[k, v] value_v
+        a = LN1(dropout(W_s out) + x),  y = LN2(dropout(W_o relu(W_i a + b_i) + b_o) + a)
+    (the row side is the key and the softmax runs over the queries -- the reference's order).  Line 119 adds ALL node
+    states to the selected rows, so `target_reference != "all"` is defined only when the reference ids name every node
+    once per row (R == N); anything else raises.  The result is then written back with `index_copy`, out of place: the
+    caller's tensor is not mutated (the reference assigns into it).
+
+    GPU tensors: dense.linear -> the fused block attention of csrc/block_attention.hip (the [n, n] scores never reach
+    HBM; dropout on P is the stateless hash mask) -> W_s with the residual -> LayerNorm -> Linear + ReLU -> W_o with the
+    residual -> LayerNorm, all HIP.  CPU tensors: torch_route.self_attention_message_passing."""
+
+    def __init__(self, input_state_dimension: int, key_query_dimension: int, value_dimension: int,
+                 output_dimension: int, intermediate_dimension: int, num_heads: int, dropout_rate: float = 0.0,
+                 target_reference: str = "all", max_num_nodes: int = 250):
+        super().__init__()
+        self.__num_heads = num_heads
+        self.__key_query_dim = key_query_dimension
+        self.__value_dim = value_dimension
+        self.__selfatt_head_transforms = nn.Linear(
+            in_features=input_state_dimension, out_features=num_heads * (2 * key_query_dimension + value_dimension),
+            bias=False)
+        self.__summarization_layer = nn.Linear(in_features=num_heads * value_dimension, out_features=output_dimension,
+                                               bias=False)
+        self.__intermediate_layer = nn.Linear(in_features=output_dimension, out_features=intermediate_dimension)
+        self.__output_layer = nn.Linear(in_features=intermediate_dimension, out_features=output_dimension)
+        self.__layer_norm1 = nn.LayerNorm(output_dimension)
+        self.__layer_norm2 = nn.LayerNorm(output_dimension)
+        self.__dropout_layer = nn.Dropout(p=dropout_rate)
+        self.__target_reference = target_reference
+        self.__max_num_nodes = max_num_nodes
+
+    def forward(self, node_states: torch.Tensor, adjacency_lists: Adj, node_to_graph_idx: torch.Tensor,
+                reference_node_ids: Dict[str, torch.Tensor],
+                reference_node_graph_idx: Dict[str, torch.Tensor],
+                edge_features: List[torch.Tensor]) -> torch.Tensor:
+        if self.__target_reference == "all":
+            return self.__transform(node_states, node_states, node_to_graph_idx)
+        ids = reference_node_ids[self.__target_reference]
+        if ids.shape[0] != node_states.shape[0]:
+            raise _lib.PtgnnAmdError(
+                f"MultiHeadSelfAttentionMessagePassing: target_reference {self.__target_reference!r} selects "
+                f"{ids.shape[0]} of {node_states.shape[0]} nodes, but selfattmessagepassing.py line 119 adds all node "
+                "states to the selected rows: the layer is only defined when the reference ids cover every node")
+        out = self.__transform(node_states[ids], node_states, reference_node_graph_idx[self.__target_reference])
+        return node_states.index_copy(0, ids, out)
+
+    def __transform(self, x: torch.Tensor, residual: torch.Tensor, graph_idx: torch.Tensor) -> torch.Tensor:
+        heads, dk, dv = self.__num_heads, self.__key_query_dim, self.__value_dim
+        w_h, w_s = self.__selfatt_head_transforms, self.__summarization_layer
+        w_i, w_o, ln1, ln2 = self.__intermediate_layer, self.__output_layer, self.__layer_norm1, self.__layer_norm2
+        if _on_host(x):
+            return torch_route.self_attention_message_passing(x, residual, graph_idx, w_h, w_s, w_i, w_o, ln1, ln2,
+                                                              self.__dropout_layer, heads, dk, dv, self.__max_num_nodes)
+        if x.dtype in _AMP_DTYPES:   # AMP: fp32 inside, the caller's dtype outside
+            return self.__transform(x.float(), residual.float(), graph_idx).to(x.dtype)
+        if x.dtype != torch.float32:
+            raise _lib.PtgnnAmdError("MultiHeadSelfAttentionMessagePassing: node states must be float32 / float16 / "
+                                     f"bfloat16 on the GPU (got {x.dtype})")
+        if x.dim() != 2 or x.shape[1] != w_h.in_features:
+            raise _lib.PtgnnAmdError(f"MultiHeadSelfAttentionMessagePassing: node states [N, {w_h.in_features}] expected "
+                                     f"(got {tuple(x.shape)})")
+        if not ops.block_attention_supported(dk, dv):
+            raise _lib.PtgnnAmdError(f"MultiHeadSelfAttentionMessagePassing: key_query_dimension {dk} / value_dimension "
+                                     f"{dv} outside the fused attention's 1..128 (there is no other GPU route)")
+        if w_o.out_features > 512:
+            raise _lib.PtgnnAmdError(f"MultiHeadSelfAttentionMessagePassing: output_dimension {w_o.out_features} exceeds "
+                                     "the 512 columns of the LayerNorm kernel (row_epilogue)")
+        if w_o.out_features != residual.shape[1]:
+            raise _lib.PtgnnAmdError(f"MultiHeadSelfAttentionMessagePassing: output_dimension {w_o.out_features} must "
+                                     f"equal the state dimension {residual.shape[1]} (the residual of line 119)")
+        training, p = self.training, float(self.__dropout_layer.p)
+        drop = p if training else 0.0
+        plan = _index_plan(graph_idx, _num_samples(graph_idx))
+        windows = ops.attention_windows(plan, self.__max_num_nodes)
+        seed = _dropout_seed() if drop > 0 else 0
+        params = [w_h.weight, w_s.weight, w_i.weight, w_i.bias, w_o.weight, w_o.bias, ln1.weight, ln1.bias, ln2.weight,
+                  ln2.bias]
+        if _no_grad_needed(x, residual, *params) and drop == 0:
+            kqv = ops.linear(x, w_h.weight)
+            values, _ = ops.block_attention(kqv, windows, self.__max_num_nodes, heads, dk, dv)
+            a = ops.row_epilogue(ops.linear_add(values, w_s.weight, residual), ops.EPI_LAYERNORM, ln1.weight, ln1.bias,
+                                 ln1.eps)
+            hidden = ops.linear(a, w_i.weight, w_i.bias, act="relu")
+            return ops.row_epilogue(ops.linear_add(hidden, w_o.weight, a, bias=w_o.bias), ops.EPI_LAYERNORM, ln2.weight,
+                                    ln2.bias, ln2.eps)
+        kqv = dense.linear(x, w_h.weight)
+        values = block_attention_autograd(kqv, windows, self.__max_num_nodes, heads, dk, dv, drop, seed)
+        a = dense.row_epilogue(self.__linear_dropout(values, w_s, None, drop) + residual, False, ln1)
+        hidden = self.__linear_dropout(a, w_i, "relu", 0.0)
+        return dense.row_epilogue(self.__linear_dropout(hidden, w_o, None, drop) + a, False, ln2)
+
+    @staticmethod
+    def __linear_dropout(x: torch.Tensor, lin: nn.Linear, act: Optional[str], p: float) -> torch.Tensor:
+        """dropout(act(Linear(x))) as one autograd node where the widths allow, else composed from the HIP Linear."""
+        y = dense.linear_act_dropout(x, lin.weight, lin.bias, act, p, p > 0)
+        if y is None:
+            y = dense.linear(x, lin.weight, lin.bias)
+            y = torch.relu(y) if act == "relu" else y
+            y = nn.functional.dropout(y, p, True) if p > 0 else y
+        return y
+
+    def forward_sharded(self, node_states: torch.Tensor, shard) -> torch.Tensor:
+        raise NotImplementedError("MultiHeadSelfAttentionMessagePassing is not supported under dst-range sharding "
+                                  "(ptgnn_amd.sharded): the nodes of a graph may span ranks, and attention among them is "
+                                  "not combined across ranks; run it unsharded")
+
+    @property
+    def input_state_dimension(self) -> int:
+        return self.__selfatt_head_transforms.in_features
+
+    @property
+    def output_state_dimension(self) -> int:
+        return self.__output_layer.out_features
 
 
 # ------------------------------------------------------------------------------------------------

@@ -44,7 +44,8 @@ def launch_counts(aggregation: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
-    attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward)."""
+    attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward, block_attention,
+    block_attention_backward)."""
     lib = _lib.load()
     out = {}
     for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
@@ -1808,6 +1809,96 @@ def graph_norm_backward(x: torch.Tensor, grad_y: torch.Tensor, gamma: torch.Tens
             gp[1].data_ptr(), gp[2].data_ptr(), ws.data_ptr(), ws_bytes, _stream(gx))
     _lib.check(rc, "ptgnn_amd_graph_norm_backward_f32")
     return gx, gp[0], gp[1], gp[2]
+
+
+# csrc/block_attention.hip: a workgroup owns 32, 64 or 128 rows of a window (1, 2 or 4 waves of 32 rows: the most whose
+# LDS stays within 64 KiB at the given dk / dv) and walks the window in tiles of 32 rows
+BLOCK_ATTENTION_ROW_TILES = (32, 64, 128)
+BLOCK_ATTENTION_COL_TILE = 32
+
+
+def block_attention_supported(dk: int, dv: int) -> bool:
+    """Whether the fused block attention takes these key / value widths (ptgnn_amd_block_attention_supported: 1..128)."""
+    return bool(_lib.load().ptgnn_amd_block_attention_supported(int(dk), int(dv)))
+
+
+def attention_windows(plan: GraphPlan, max_num_nodes: int) -> torch.Tensor:
+    """Window table of selfattmessagepassing.py:59-75 from the plan of a node -> graph map (ptgnn_amd_attention_windows):
+    int32 [bound + 1], bound = ceil(N / max_num_nodes) + G.  Entry w is the first row of window w for the W windows of
+    the batch (graph g owns the count_g rows after those of the graphs in front of it and is cut every max_num_nodes
+    rows; only the counts of the map matter), the entries from W on are N.  No host read-back."""
+    lib = _lib.load()
+    G, n = int(plan.num_nodes), int(plan.num_edges)
+    bound = int(lib.ptgnn_amd_attention_windows_bound(G, n, int(max_num_nodes)))
+    if bound < 0:
+        raise _lib.PtgnnAmdError(f"attention_windows: bad sizes (graphs {G}, rows {n}, max_num_nodes {max_num_nodes})")
+    if G == 0:
+        return torch.zeros(1, dtype=torch.int32, device=plan.rowptr.device)
+    windows = torch.empty(bound + 1, dtype=torch.int32, device=plan.rowptr.device)
+    plan.wait()
+    rc = lib.ptgnn_amd_attention_windows(plan.rowptr.data_ptr(), G, n, int(max_num_nodes), windows.data_ptr(),
+                                         bound + 1, _stream(windows))
+    _lib.check(rc, "ptgnn_amd_attention_windows")
+    return windows
+
+
+def _block_attention_args(kqv: torch.Tensor, windows: torch.Tensor, heads: int, dk: int, dv: int, what: str):
+    _require_cuda_f32("kqv", kqv)
+    kqv = _rowmajor(kqv)
+    if heads < 1 or dk < 1 or dv < 1 or kqv.shape[1] != heads * (2 * dk + dv):
+        raise _lib.PtgnnAmdError(f"{what}: kqv {tuple(kqv.shape)} is not [N, {heads} * (2 * {dk} + {dv})]")
+    if not block_attention_supported(dk, dv):
+        raise _lib.PtgnnAmdError(f"{what}: key / value dimensions ({dk}, {dv}) outside the kernels' 1..128")
+    if not windows.is_cuda or windows.dtype != torch.int32 or windows.dim() != 1 or windows.numel() < 1:
+        raise _lib.PtgnnAmdError(f"{what}: windows must be the int32 GPU table of attention_windows")
+    return kqv, windows.contiguous()
+
+
+def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int,
+                    p: float = 0.0, seed: int = 0):
+    """Softmax attention among the rows of every window, per head (ptgnn_amd_block_attention_f32;
+    selfattmessagepassing.py:104-117): kqv [N, heads (2 dk + dv)] read in place -> (out [N, heads dv], lse [N, heads]).
+    `p` > 0 applies the hash dropout mask of `seed` to the probabilities (row r heads + h, column j of a
+    [N heads, max_num_nodes rounded up to even] mask)."""
+    lib = _lib.load()
+    kqv, windows = _block_attention_args(kqv, windows, heads, dk, dv, "block_attention")
+    n = kqv.shape[0]
+    out = torch.empty(n, heads * dv, dtype=torch.float32, device=kqv.device)
+    lse = torch.empty(n, heads, dtype=torch.float32, device=kqv.device)
+    if n:
+        with _timed("block_attention", bytes=4.0 * n * heads * (2 * dk + 2 * dv + 1)):
+            rc = lib.ptgnn_amd_block_attention_f32(kqv.data_ptr(), _ld(kqv), windows.data_ptr(), windows.numel() - 1, n,
+                                                   int(max_num_nodes), heads, dk, dv, float(p), int(seed), out.data_ptr(),
+                                                   heads * dv, lse.data_ptr(), _stream(out))
+        _lib.check(rc, "ptgnn_amd_block_attention_f32")
+    return out, lse
+
+
+def block_attention_backward(kqv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, grad_out: torch.Tensor,
+                             windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int, p: float = 0.0,
+                             seed: int = 0) -> torch.Tensor:
+    """grad_kqv [N, heads (2 dk + dv)] of `block_attention` from grad_out = dL/dout and the forward's out / lse
+    (ptgnn_amd_block_attention_backward_f32: the probabilities are recomputed; deterministic, no float atomics)."""
+    lib = _lib.load()
+    kqv, windows = _block_attention_args(kqv, windows, heads, dk, dv, "block_attention_backward")
+    n = kqv.shape[0]
+    _require_cuda_f32("grad_out", grad_out)
+    grad_out, out, lse = _rowmajor(grad_out), out.contiguous(), lse.contiguous()
+    if tuple(grad_out.shape) != (n, heads * dv) or tuple(out.shape) != (n, heads * dv) or tuple(lse.shape) != (n, heads) \
+            or out.dtype != torch.float32 or lse.dtype != torch.float32:
+        raise _lib.PtgnnAmdError(f"block_attention_backward: grad_out {tuple(grad_out.shape)} / out {tuple(out.shape)} / "
+                                 f"lse {tuple(lse.shape)} do not match kqv {tuple(kqv.shape)}")
+    gkqv = torch.empty(n, heads * (2 * dk + dv), dtype=torch.float32, device=kqv.device)
+    if n:
+        ws_bytes = int(lib.ptgnn_amd_block_attention_backward_workspace_bytes(n, heads))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=kqv.device)
+        with _timed("block_attention_backward", bytes=4.0 * n * heads * (4 * dk + 5 * dv + 2)):
+            rc = lib.ptgnn_amd_block_attention_backward_f32(
+                kqv.data_ptr(), _ld(kqv), out.data_ptr(), heads * dv, lse.data_ptr(), grad_out.data_ptr(), _ld(grad_out),
+                windows.data_ptr(), windows.numel() - 1, n, int(max_num_nodes), heads, dk, dv, float(p), int(seed),
+                gkqv.data_ptr(), heads * (2 * dk + dv), ws.data_ptr(), ws_bytes, _stream(gkqv))
+        _lib.check(rc, "ptgnn_amd_block_attention_backward_f32")
+    return gkqv
 
 
 HEAD_EXPAND, HEAD_CONTRACT, HEAD_WEIGHT_GRAD = 0, 1, 2    # modes of ptgnn_amd_head_projection_f32

@@ -144,6 +144,30 @@ def graph_norm(x: torch.Tensor, gamma: torch.Tensor, alpha: torch.Tensor, bias: 
     return _GraphNorm.apply(x, gamma, alpha, bias, float(eps), plan)
 
 
+class _BlockAttention(torch.autograd.Function):
+    """The attention core of MultiHeadSelfAttentionMessagePassing (selfattmessagepassing.py:104-117) over a window table
+    as ONE node: forward and backward are the two entry points of csrc/block_attention.hip.  Saves kqv, out and the
+    log-sum-exp of every score row; the probabilities (and the dropout mask of `seed`) are recomputed in the backward."""
+
+    @staticmethod
+    def forward(ctx, kqv, windows, max_num_nodes, heads, dk, dv, p, seed):
+        out, lse = ops.block_attention(kqv, windows, max_num_nodes, heads, dk, dv, p, seed)
+        ctx.args = (windows, max_num_nodes, heads, dk, dv, p, seed)
+        ctx.save_for_backward(kqv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        kqv, out, lse = ctx.saved_tensors
+        return (ops.block_attention_backward(kqv, out, lse, grad_out, *ctx.args),) + (None,) * 7
+
+
+def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int,
+                    p: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """Differentiable fused softmax attention among the rows of every window of fp32 kqv [N, heads (2 dk + dv)]."""
+    return _BlockAttention.apply(kqv, windows, int(max_num_nodes), int(heads), int(dk), int(dv), float(p), int(seed))
+
+
 def _prepare(src: torch.Tensor, index: torch.Tensor, dim: int, out, dim_size):
     """Common argument handling of the torch_scatter-shaped entry points: 2-D (or 1-D) `src`, 1-D int64
     `index` along dim 0.  Anything else raises (no silent fallback)."""

@@ -113,6 +113,51 @@ def graph_norm(node_states: torch.Tensor, node_to_graph_idx: torch.Tensor, num_g
     return gamma * shifted / torch.sqrt(sigma_2[node_to_graph_idx]) + bias
 
 
+def attention_window_bounds(node_to_graph_idx: torch.Tensor, max_num_nodes: int):
+    """[(first row, end row)] of the windows of selfattmessagepassing.py:59-75: graph g owns the count_g rows after those
+    of the graphs in front of it (only the counts of the map are read) and is cut every max_num_nodes rows."""
+    counts = torch.bincount(node_to_graph_idx).tolist() if node_to_graph_idx.numel() else []
+    bounds, first = [], 0
+    for count in counts:
+        bounds += [(first + lo, first + min(lo + max_num_nodes, count)) for lo in range(0, count, max_num_nodes)]
+        first += count
+    return bounds
+
+
+def block_attention(kqv: torch.Tensor, bounds, num_heads: int, dk: int, dv: int, dropout_p: float = 0.0,
+                    training: bool = False) -> torch.Tensor:
+    """selfattmessagepassing.py:104-117 in the dtype of `kqv` [N, heads (2 dk + dv)]: per window and head
+    softmax_v(key_k . query_v / sqrt(dk)), dropout, times the values -> [N, heads dv]."""
+    n = kqv.shape[0]
+    per_head = kqv.reshape(n, num_heads, 2 * dk + dv).permute(1, 0, 2)             # [heads, N, 2 dk + dv]
+    pieces = []
+    for lo, hi in bounds:
+        block = per_head[:, lo:hi]
+        keys, queries, values = block[..., :dk], block[..., dk:2 * dk], block[..., 2 * dk:]
+        probs = torch.softmax(keys @ queries.transpose(1, 2) / dk ** 0.5, dim=-1)   # [heads, key, query]
+        probs = nn.functional.dropout(probs, dropout_p, training)
+        pieces.append(probs @ values)                                               # [heads, n, dv]
+    if not pieces:
+        return kqv.new_zeros(n, num_heads * dv)
+    return torch.cat(pieces, dim=1).permute(1, 0, 2).reshape(n, num_heads * dv)
+
+
+def self_attention_message_passing(node_states: torch.Tensor, residual_states: torch.Tensor,
+                                   node_to_graph_idx: torch.Tensor, head_transforms: nn.Linear, summarization: nn.Linear,
+                                   intermediate: nn.Linear, output: nn.Linear, layer_norm1: nn.LayerNorm,
+                                   layer_norm2: nn.LayerNorm, dropout: nn.Module, num_heads: int, dk: int, dv: int,
+                                   max_num_nodes: int) -> torch.Tensor:
+    """MultiHeadSelfAttentionMessagePassing.forward (selfattmessagepassing.py:92-123) on torch's operators, any dtype:
+    `node_states` are the rows that attend (line 89), `residual_states` what line 119 adds."""
+    _host_only(node_states, node_to_graph_idx)
+    kqv = head_transforms(node_states)
+    bounds = attention_window_bounds(node_to_graph_idx, max_num_nodes)
+    values = block_attention(kqv, bounds, num_heads, dk, dv, float(getattr(dropout, "p", 0.0)), dropout.training)
+    attention_output = layer_norm1(dropout(summarization(values)) + residual_states)
+    hidden = nn.functional.relu(intermediate(attention_output))
+    return layer_norm2(dropout(output(hidden)) + attention_output)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # torch_scatter-shaped entry points (any `dim`, 1-D or broadcastable index) for host tensors
 # ------------------------------------------------------------------------------------------------------------------
