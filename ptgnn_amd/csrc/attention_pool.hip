@@ -11,9 +11,10 @@
 // and the value / output Linears run on the [G, ...] pools.  The reference materialises keys [N, hidden] and the weighted
 // rows [N, heads * D] (8 KB per node at Graph2Seq's shape); here x is read once and G * heads * D floats are written.
 //
-// Layout of the pool.  Segments are cut into the 128-row chunks of weighted_pool.hip (counted from each segment's own
-// start); a workgroup walks one chunk in tiles of R rows staged through LDS (row stride D | 1: odd, so lanes reading 32
-// different rows at one column hit 32 different banks).  Per tile:
+// Layout of the pool.  Segments are cut into the 128-row chunks of segment_chunks.h (counted from each segment's own
+// start; chunk_locate, the chunk table and the chunk-order fold are that header's); a workgroup walks one chunk in
+// tiles of R rows staged through LDS (row stride D | 1: odd, so lanes reading 32 different rows at one column hit 32
+// different banks).  Per tile:
 //   1. score walk: thread (row r, part) dots ITS column slice of x_r with every head's u (u in LDS as [D][HP], read as
 //      broadcast float4): each x element read from LDS feeds HP FMAs, no cross-lane reduction;
 //   2. half-wave h owns head h: adds the parts of up to 64 rows in a fixed order, takes the tile max with 5 shuffles,
@@ -36,10 +37,7 @@
 // PTGNN_AMD_EUNSUPPORTED and the host composes the reference's operator sequence from the other HIP entry points.
 #include <math.h>
 
-#include <mutex>
-#include <unordered_map>
-
-#include "common.h"
+#include "segment_chunks.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -68,36 +66,6 @@ AttnLayout attn_layout(int dim, int heads, bool backward) {
     if (L.bytes <= 64 * 1024 || L.R == 16) break;
   }
   return L;
-}
-
-template <typename Kern>
-bool attn_set_lds(Kern kern, size_t bytes) {
-  if (bytes <= 64 * 1024) return true;
-  static std::mutex mu;
-  static std::unordered_map<uint64_t, size_t> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void *fn = reinterpret_cast<const void *>(kern);
-  const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)dev;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  done[key] = bytes;
-  return true;
-}
-
-// segment of workgroup b: chunk_start[seg] <= b < chunk_start[seg + 1] (workgroup-uniform binary search)
-__device__ __forceinline__ int attn_segment_of(int b, const int32_t *__restrict__ chunk_start, int num_segments) {
-  int seg = 0, hi = num_segments;
-  while (hi - seg > 1) {
-    const int mid = (seg + hi) >> 1;
-    if (chunk_start[mid] <= b) seg = mid; else hi = mid;
-  }
-  return seg;
 }
 
 // [dim][HP] image of the segment's [heads][dim] rows (padded heads 0)
@@ -183,21 +151,6 @@ __device__ __forceinline__ float half_wave_sum(float v) {
   return v;
 }
 
-// chunk b of its segment: rows [lo, hi) of the plan
-struct AttnChunk {
-  int seg, lo, hi;
-};
-
-__device__ __forceinline__ AttnChunk attn_chunk(int b, const int32_t *__restrict__ rowptr,
-                                                const int32_t *__restrict__ chunk_start, int num_segments) {
-  AttnChunk c;
-  c.seg = attn_segment_of(b, chunk_start, num_segments);
-  const int end = rowptr[c.seg + 1];
-  c.lo = rowptr[c.seg] + (b - chunk_start[c.seg]) * kPoolChunkRows;
-  c.hi = c.lo + kPoolChunkRows < end ? c.lo + kPoolChunkRows : end;
-  return c;
-}
-
 // LDS (floats): xs [R][S] | ut [dim][HP] | part [256][HP] | pt [R][HP] | alpha [8]
 template <int HP, int COLS>
 __global__ __launch_bounds__(kAttnThreads) void k_attn_pool_partial(
@@ -206,8 +159,8 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_pool_partial(
     const int32_t *__restrict__ chunk_start, bool vec4, float *__restrict__ partial, float *__restrict__ stat_partial) {
   extern __shared__ float lds[];
   const int b = blockIdx.x;
-  if (b >= chunk_start[num_segments]) return;          // the grid is the host's bound n / 128 + G
-  const AttnChunk ch = attn_chunk(b, rowptr, chunk_start, num_segments);
+  ChunkSpan ch;
+  if (!chunk_locate(rowptr, chunk_start, num_segments, b, ch)) return;
   const int parts = kAttnThreads / R;
   float *xs = lds;
   float *ut = xs + R * S;
@@ -349,8 +302,8 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_pool_backward(
     float *__restrict__ du_partial) {
   extern __shared__ float lds[];
   const int b = blockIdx.x;
-  if (b >= chunk_start[num_segments]) return;
-  const AttnChunk ch = attn_chunk(b, rowptr, chunk_start, num_segments);
+  ChunkSpan ch;
+  if (!chunk_locate(rowptr, chunk_start, num_segments, b, ch)) return;
   const int parts = kAttnThreads / R;
   float *xs = lds;
   float *ut = xs + R * S;
@@ -529,7 +482,7 @@ __global__ __launch_bounds__(256) void k_head_weight_grad(const float *__restric
 
 template <typename Kern, typename... Args>
 int attn_launch(Kern kern, const AttnLayout &L, unsigned grid, hipStream_t st, Args... args) {
-  PTGNN_REQUIRE(attn_set_lds(kern, L.bytes), PTGNN_AMD_EHIP, "attention_pool: %zu bytes of LDS refused", L.bytes);
+  PTGNN_REQUIRE(L.bytes <= 64 * 1024 || raise_dynamic_lds(kern, L.bytes), PTGNN_AMD_EHIP, "attention_pool: %zu bytes of LDS refused", L.bytes);
   kern<<<grid, kAttnThreads, L.bytes, st>>>(args...);
   PTGNN_LAUNCH_CHECK();
   return PTGNN_AMD_OK;
@@ -553,7 +506,32 @@ bool attn_supported(int dim, int heads) {
          attn_layout(dim, heads, true).bytes <= kAttnMaxLds;
 }
 
-size_t attn_align(size_t n) { return (n + 255) / 256 * 256; }
+// forward: the chunk table, the chunks' [heads, dim] accumulators and their (max | sum) per head; backward: the chunk
+// table and the chunks' [heads, dim] partial rows of du
+struct AttnWorkspace {
+  size_t chunk_start, partial, stat_partial, total;
+};
+
+AttnWorkspace attn_workspace(int64_t segments, int64_t elements, int dim, int heads, bool backward) {
+  const size_t bound = (size_t)chunk_count_bound(segments, elements);
+  Carve c;
+  AttnWorkspace w;
+  w.chunk_start = c.take(chunk_table_bytes(segments));
+  w.partial = c.take(bound * heads * dim * sizeof(float));
+  w.stat_partial = backward ? 0 : c.take(bound * 2 * heads * sizeof(float));
+  w.total = c.off;
+  return w;
+}
+
+// the argument checks the forward and the backward share; 0 when the arguments are fine
+int attn_check(const char *what, int64_t num_segments, int64_t num_elements, int32_t dim, int32_t num_heads) {
+  PTGNN_REQUIRE(num_heads > 0, PTGNN_AMD_EINVAL, "%s: bad sizes", what);
+  if (const int rc = chunked_segments_check(what, num_segments, num_elements, dim)) return rc;
+  PTGNN_REQUIRE(num_segments == 0 || attn_supported(dim, num_heads), PTGNN_AMD_EUNSUPPORTED,
+                "%s: dim %d / %d heads outside the kernel range (dim <= %d, heads <= %d)", what, dim, num_heads,
+                kAttnMaxDim, kAttnMaxHeads);
+  return PTGNN_AMD_OK;
+}
 
 }  // namespace
 }  // namespace ptgnn_amd
@@ -567,37 +545,26 @@ extern "C" int ptgnn_amd_attention_pool_supported(int32_t dim, int32_t num_heads
 extern "C" size_t ptgnn_amd_attention_pool_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim,
                                                            int32_t num_heads) {
   if (num_segments <= 0 || dim <= 0 || num_heads <= 0) return 0;
-  const int64_t bound = pool_chunk_count_bound(num_segments, num_elements);
-  return attn_align(pool_chunk_table_bytes(num_segments)) + attn_align((size_t)bound * num_heads * dim * sizeof(float)) +
-         (size_t)bound * 2 * num_heads * sizeof(float);
+  return attn_workspace(num_segments, num_elements, dim, num_heads, false).total;
 }
 
 extern "C" int ptgnn_amd_attention_pool_f32(const float *x, int64_t ld_x, const float *u, const int32_t *rowptr,
                                             const int32_t *perm, int64_t num_segments, int64_t num_elements,
                                             int32_t dim, int32_t num_heads, float *out, float *stats, void *workspace,
                                             size_t workspace_bytes, void *stream_) {
-  PTGNN_REQUIRE(num_segments >= 0 && num_elements >= 0 && dim > 0 && num_heads > 0, PTGNN_AMD_EINVAL,
-                "attention_pool: bad sizes");
+  if (const int rc = attn_check("attention_pool", num_segments, num_elements, dim, num_heads)) return rc;
   if (num_segments == 0) return PTGNN_AMD_OK;
   PTGNN_REQUIRE(u && rowptr && out && stats && (num_elements == 0 || (x && perm)), PTGNN_AMD_EINVAL,
                 "attention_pool: null pointer");
   PTGNN_REQUIRE(num_elements == 0 || ld_x >= dim, PTGNN_AMD_EINVAL, "attention_pool: bad leading dimension");
-  PTGNN_REQUIRE(attn_supported(dim, num_heads), PTGNN_AMD_EUNSUPPORTED,
-                "attention_pool: dim %d / %d heads outside the kernel range (dim <= %d, heads <= %d)", dim, num_heads,
-                kAttnMaxDim, kAttnMaxHeads);
-  const int64_t bound = pool_chunk_count_bound(num_segments, num_elements);
-  PTGNN_REQUIRE(bound < ((int64_t)1 << 31) && num_elements < ((int64_t)1 << 31) && num_segments < ((int64_t)1 << 31),
-                PTGNN_AMD_EUNSUPPORTED, "attention_pool: too many segments / elements");
-  const size_t need = ptgnn_amd_attention_pool_workspace_bytes(num_segments, num_elements, dim, num_heads);
-  PTGNN_REQUIRE(workspace && workspace_bytes >= need, PTGNN_AMD_EWORKSPACE,
-                "attention_pool: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  const AttnWorkspace ws = attn_workspace(num_segments, num_elements, dim, num_heads, false);
+  if (const int rc = workspace_check("attention_pool", workspace, workspace_bytes, ws.total)) return rc;
+  const int64_t bound = chunk_count_bound(num_segments, num_elements);
   hipStream_t st = (hipStream_t)stream_;
-  char *ws = static_cast<char *>(workspace);
-  int32_t *chunk_start = reinterpret_cast<int32_t *>(ws);
-  float *partial = reinterpret_cast<float *>(ws + attn_align(pool_chunk_table_bytes(num_segments)));
-  float *stat_partial = reinterpret_cast<float *>(reinterpret_cast<char *>(partial) +
-                                                  attn_align((size_t)bound * num_heads * dim * sizeof(float)));
-  launch_pool_chunk_starts(rowptr, (int)num_segments, chunk_start, st);
+  int32_t *chunk_start = carved<int32_t>(workspace, ws.chunk_start);
+  float *partial = carved<float>(workspace, ws.partial);
+  float *stat_partial = carved<float>(workspace, ws.stat_partial);
+  launch_chunk_starts(rowptr, (int)num_segments, chunk_start, st);
   PTGNN_LAUNCH_CHECK();
   const AttnLayout L = attn_layout(dim, num_heads, false);
   const bool vec4 = num_elements > 0 && dim % 4 == 0 && ld_x % 4 == 0 && aligned16(x);
@@ -618,8 +585,7 @@ extern "C" int ptgnn_amd_attention_pool_f32(const float *x, int64_t ld_x, const 
 extern "C" size_t ptgnn_amd_attention_pool_backward_workspace_bytes(int64_t num_segments, int64_t num_elements,
                                                                     int32_t dim, int32_t num_heads) {
   if (num_segments <= 0 || dim <= 0 || num_heads <= 0) return 0;
-  const int64_t bound = pool_chunk_count_bound(num_segments, num_elements);
-  return attn_align(pool_chunk_table_bytes(num_segments)) + (size_t)bound * num_heads * dim * sizeof(float);
+  return attn_workspace(num_segments, num_elements, dim, num_heads, true).total;
 }
 
 extern "C" int ptgnn_amd_attention_pool_backward_f32(const float *x, int64_t ld_x, const float *u,
@@ -628,27 +594,19 @@ extern "C" int ptgnn_amd_attention_pool_backward_f32(const float *x, int64_t ld_
                                                      const float *pooled, const float *stats, const float *grad_out,
                                                      float *grad_x, int64_t ld_gx, float *grad_u, void *workspace,
                                                      size_t workspace_bytes, void *stream_) {
-  PTGNN_REQUIRE(num_segments >= 0 && num_elements >= 0 && dim > 0 && num_heads > 0, PTGNN_AMD_EINVAL,
-                "attention_pool_backward: bad sizes");
+  if (const int rc = attn_check("attention_pool_backward", num_segments, num_elements, dim, num_heads)) return rc;
   if (num_segments == 0) return PTGNN_AMD_OK;
   PTGNN_REQUIRE(u && rowptr && pooled && stats && grad_out && grad_u && (num_elements == 0 || (x && perm && grad_x)),
                 PTGNN_AMD_EINVAL, "attention_pool_backward: null pointer");
   PTGNN_REQUIRE(num_elements == 0 || (ld_x >= dim && ld_gx >= dim), PTGNN_AMD_EINVAL,
                 "attention_pool_backward: bad leading dimension");
-  PTGNN_REQUIRE(attn_supported(dim, num_heads), PTGNN_AMD_EUNSUPPORTED,
-                "attention_pool_backward: dim %d / %d heads outside the kernel range (dim <= %d, heads <= %d)", dim,
-                num_heads, kAttnMaxDim, kAttnMaxHeads);
-  const int64_t bound = pool_chunk_count_bound(num_segments, num_elements);
-  PTGNN_REQUIRE(bound < ((int64_t)1 << 31) && num_elements < ((int64_t)1 << 31) && num_segments < ((int64_t)1 << 31),
-                PTGNN_AMD_EUNSUPPORTED, "attention_pool_backward: too many segments / elements");
-  const size_t need = ptgnn_amd_attention_pool_backward_workspace_bytes(num_segments, num_elements, dim, num_heads);
-  PTGNN_REQUIRE(workspace && workspace_bytes >= need, PTGNN_AMD_EWORKSPACE,
-                "attention_pool_backward: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  const AttnWorkspace ws = attn_workspace(num_segments, num_elements, dim, num_heads, true);
+  if (const int rc = workspace_check("attention_pool_backward", workspace, workspace_bytes, ws.total)) return rc;
+  const int64_t bound = chunk_count_bound(num_segments, num_elements);
   hipStream_t st = (hipStream_t)stream_;
-  char *ws = static_cast<char *>(workspace);
-  int32_t *chunk_start = reinterpret_cast<int32_t *>(ws);
-  float *partial = reinterpret_cast<float *>(ws + attn_align(pool_chunk_table_bytes(num_segments)));
-  launch_pool_chunk_starts(rowptr, (int)num_segments, chunk_start, st);
+  int32_t *chunk_start = carved<int32_t>(workspace, ws.chunk_start);
+  float *partial = carved<float>(workspace, ws.partial);
+  launch_chunk_starts(rowptr, (int)num_segments, chunk_start, st);
   PTGNN_LAUNCH_CHECK();
   const AttnLayout L = attn_layout(dim, num_heads, true);
   const bool vec4 = num_elements > 0 && dim % 4 == 0 && ld_x % 4 == 0 && aligned16(x);

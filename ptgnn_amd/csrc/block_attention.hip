@@ -35,9 +35,7 @@
 // Dropout is the stateless hash of dense_common.h: element (global row r, head h, window column j) takes the multiplier of
 // row r heads + h, column j of a [N heads, W] mask with W = max_num_nodes rounded up to even.
 #include "dense_common.h"
-
-#include <mutex>
-#include <unordered_map>
+#include "segment_chunks.h"   // SegmentScan: the window table is the chunk table's scan with another count
 
 namespace ptgnn_amd {
 namespace {
@@ -113,33 +111,18 @@ __device__ __forceinline__ bool ba_locate(const int32_t *__restrict__ windows, c
 __global__ __launch_bounds__(256) void k_attention_windows(const int32_t *__restrict__ rowptr, int num_graphs,
                                                            int max_nodes, int num_rows, int bound,
                                                            int32_t *__restrict__ windows) {
-  __shared__ int wsum[4];
-  __shared__ int carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  __shared__ SegmentScan<256> scan;
+  scan.begin();
   for (int base = 0; base < num_graphs; base += 256) {
     const int g = base + threadIdx.x;
     const int first = g < num_graphs ? rowptr[g] : 0;
     const int cnt = g < num_graphs ? rowptr[g + 1] - first : 0;
     const int c = cnt > 0 ? (cnt - 1) / max_nodes + 1 : 0;
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int run = carry + inc - c;
-    for (int v = 0; v < wave; ++v) run += wsum[v];
+    const int run = scan.step(c);
     for (int q = 0; q < c; ++q)
       if (run + q <= bound) windows[run + q] = first + q * max_nodes;
-    __syncthreads();
-    if (threadIdx.x == 255) carry = run + c;
-    __syncthreads();
   }
-  for (int i = carry + threadIdx.x; i <= bound; i += 256) windows[i] = num_rows;
+  for (int i = scan.total() + threadIdx.x; i <= bound; i += 256) windows[i] = num_rows;
 }
 
 // out[k, head dv + :] and lse[k, head] of the rows of one (window, head) row block
@@ -387,25 +370,9 @@ int ba_waves(int own_ld, int walk_ld, int extra) {
   return 1;
 }
 
+// a workgroup beyond 64 KiB of LDS (one wave at the widest heads) needs the kernel's limit raised first
 template <typename Kern>
-bool ba_set_lds(Kern kern, size_t bytes) {
-  if (bytes <= 64 * 1024) return true;
-  static std::mutex mu;
-  static std::unordered_map<uint64_t, size_t> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void *fn = reinterpret_cast<const void *>(kern);
-  const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)dev;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  done[key] = bytes;
-  return true;
-}
+bool ba_lds_ok(Kern kern, size_t bytes) { return bytes <= 64 * 1024 || raise_dynamic_lds(kern, bytes); }
 
 int64_t ba_windows_bound(int64_t num_graphs, int64_t num_rows, int64_t max_nodes) {
   return (num_rows + max_nodes - 1) / max_nodes + num_graphs;
@@ -459,7 +426,7 @@ int ba_launch_dqv(int dvt, dim3 grid, int nw, size_t bytes, hipStream_t st, cons
                   const DropoutParams &drop, float *gkqv, int64_t ld_g) {
   BA_TILES(dvt, {
     auto kern = k_block_attention_dqv<DKT, TT>;
-    PTGNN_REQUIRE(ba_set_lds(kern, bytes), PTGNN_AMD_EHIP, "block_attention_backward: %zu bytes of LDS refused", bytes);
+    PTGNN_REQUIRE(ba_lds_ok(kern, bytes), PTGNN_AMD_EHIP, "block_attention_backward: %zu bytes of LDS refused", bytes);
     kern<<<grid, 64 * nw, bytes, st>>>(kqv, ld, go, ld_go, lse, D, windows, sh, drop, gkqv, ld_g);
   })
   return PTGNN_AMD_OK;
@@ -520,7 +487,7 @@ extern "C" int ptgnn_amd_block_attention_f32(const float *kqv, int64_t ld_kqv, c
   hipStream_t st = (hipStream_t)stream_;
   BA_TILES(dvt, {
     auto kern = k_block_attention<TT>;
-    PTGNN_REQUIRE(ba_set_lds(kern, bytes), PTGNN_AMD_EHIP, "block_attention: %zu bytes of LDS refused", bytes);
+    PTGNN_REQUIRE(ba_lds_ok(kern, bytes), PTGNN_AMD_EHIP, "block_attention: %zu bytes of LDS refused", bytes);
     kern<<<grid, 64 * nw, bytes, st>>>(kqv, ld_kqv, windows, sh, drop, out, ld_out, lse);
   })
   PTGNN_LAUNCH_CHECK();
@@ -566,7 +533,7 @@ extern "C" int ptgnn_amd_block_attention_backward_f32(const float *kqv, int64_t 
   PTGNN_LAUNCH_CHECK();
   BA_TILES(dkt, {
     auto kern = k_block_attention_dkey<TT>;
-    PTGNN_REQUIRE(ba_set_lds(kern, bytes), PTGNN_AMD_EHIP, "block_attention_backward: %zu bytes of LDS refused", bytes);
+    PTGNN_REQUIRE(ba_lds_ok(kern, bytes), PTGNN_AMD_EHIP, "block_attention_backward: %zu bytes of LDS refused", bytes);
     kern<<<grid, 64 * nw, bytes, st>>>(kqv, ld_kqv, grad_out, ld_go, lse, D, windows, sh, drop, grad_kqv, ld_gkqv);
   })
   PTGNN_LAUNCH_CHECK();

@@ -58,15 +58,52 @@ inline int64_t xcd_padded_blocks(int64_t nblocks) {
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// Segment pools cut every segment of a plan into chunks of kPoolChunkRows rows counted from the segment's own start and
-// add the chunk partials in chunk order (weighted_pool.hip; attention_pool.hip uses the same chunk table and fold).
-constexpr int kPoolChunkRows = 128;
-int64_t pool_chunk_count_bound(int64_t segments, int64_t elements);   // upper bound of the chunks of a plan
-size_t pool_chunk_table_bytes(int64_t segments);                     // int32 chunk_start[segments + 1], padded
-// chunk_start[g] = chunks of the segments in front of g, chunk_start[G] = all chunks (one workgroup)
-void launch_pool_chunk_starts(const int32_t *rowptr, int num_segments, int32_t *chunk_start, hipStream_t st);
-// out[g, :dim] = partial rows chunk_start[g] .. chunk_start[g + 1] - 1 added in chunk order (0 for an empty segment)
-void launch_fold_segments(const float *partial, const int32_t *chunk_start, int dim, int64_t segments, float *out,
-                          int64_t ld_out, hipStream_t st);
+// Raise a kernel's dynamic-LDS limit to `bytes`, once per (kernel, device): the attribute call is not legal while a
+// stream is being captured into a hipGraph, and the warm-up launch outside the capture has made the call, so a launch
+// inside a capture finds the limit cached.  false when the runtime refuses (the caller decides what that means; `why`
+// then receives the runtime's error string).
+bool raise_dynamic_lds(const void *fn, size_t bytes, const char **why = nullptr);   // errors.cpp
+template <typename Kern>
+bool raise_dynamic_lds(Kern kern, size_t bytes, const char **why = nullptr) {
+  return raise_dynamic_lds(reinterpret_cast<const void *>(kern), bytes, why);
+}
+
+#ifdef __HIPCC__
+// Row math with a bitwise contract between its users: the fused inference epilogue (gather_reduce_core.h) and the training
+// pair (row_epilogue.hip) must round alike, so there is one copy.
+__device__ __forceinline__ float gelu_erf(float x) {
+  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
+}
+
+__device__ __forceinline__ float gelu_erf_grad(float x) {
+  // d/dx [x Phi(x)] = Phi(x) + x phi(x)
+  return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
+}
+
+// sum of `v` over the LPR consecutive lanes of a row group: xor butterfly, every lane ends with the same bits
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPR);
+  return v;
+}
+
+// VEC (4 or 1) consecutive floats of a row as one float4 or one float access
+template <int VEC>
+__device__ __forceinline__ void vec_load(const float *p, float (&o)[VEC]) {
+  if constexpr (VEC == 4) {
+    const float4 t = *reinterpret_cast<const float4 *>(p);
+    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+  } else {
+    o[0] = *p;
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void vec_store(float *p, const float (&o)[VEC]) {
+  if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(o[0], o[1], o[2], o[3]);
+  else *p = o[0];
+}
+#endif
 
 }  // namespace ptgnn_amd

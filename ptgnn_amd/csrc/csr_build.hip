@@ -31,8 +31,6 @@
 #include <string.h>
 
 #include <atomic>
-#include <mutex>
-#include <unordered_map>
 
 #include "common.h"
 
@@ -828,27 +826,6 @@ void layout(int64_t num_edges, const PlanPath &P, WsLayout *L) {
   L->total = o + 256;
 }
 
-// Raise a kernel's dynamic-LDS limit once per (device, kernel): the attribute call is not legal while a stream is
-// being captured into a hipGraph, and the warm-up launch outside the capture has made it.
-template <typename Kern>
-bool set_lds(Kern kern, size_t bytes) {
-  static std::mutex mu;
-  static std::unordered_map<uint64_t, size_t> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void *fn = reinterpret_cast<const void *>(kern);
-  const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)dev;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  done[key] = bytes;
-  return true;
-}
-
 }  // namespace
 }  // namespace ptgnn_amd
 
@@ -1053,7 +1030,7 @@ extern "C" int ptgnn_amd_csr_build(const int64_t *const *src_per_type,
     const int hub_thr = hubs ? hub_threshold : 0;
     if (P.big) {
       auto kern = k_plan_buckets<kBucketWaves, true>;
-      PTGNN_REQUIRE(set_lds(kern, P.bucket_lds), PTGNN_AMD_EHIP, "csr_build: %zu B of LDS refused", P.bucket_lds);
+      PTGNN_REQUIRE(raise_dynamic_lds(kern, P.bucket_lds), PTGNN_AMD_EHIP, "csr_build: %zu B of LDS refused", P.bucket_lds);
       kern<<<bgrid, kBucketWaves * 64, P.bucket_lds, stream>>>(out.recs, out.rpos, totals, P.bins, P.low_bits, num_nodes,
                                                               num_edges, rowptr, col, perm, hub_thr, 1024, hub_entries,
                                                               hub_count, 0);

@@ -3,8 +3,10 @@
 #include <stdio.h>
 
 #include <atomic>
+#include <mutex>
+#include <unordered_map>
 
-#include "../../include/ptgnn_amd.h"
+#include "common.h"
 
 namespace ptgnn_amd {
 static thread_local char g_err[512] = "";
@@ -28,6 +30,25 @@ static std::atomic<int64_t> *counter(int kernel_id) {
 }
 void count_launch(int kernel_id) {
   if (std::atomic<int64_t> *c = counter(kernel_id)) c->fetch_add(1, std::memory_order_relaxed);
+}
+
+bool raise_dynamic_lds(const void *fn, size_t bytes, const char **why) {
+  static std::mutex mu;
+  static std::unordered_map<uint64_t, size_t> done;     // (kernel, device): the attribute is per device
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)dev;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = done.find(key);
+  if (it != done.end() && it->second >= bytes) return true;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (why) *why = hipGetErrorString(e);
+    return false;
+  }
+  done[key] = bytes;
+  return true;
 }
 }  // namespace ptgnn_amd
 

@@ -69,17 +69,6 @@ namespace {
 constexpr int kHubChunk = 1024;  // CSR slots per hub chunk; hub_threshold must be >= 2 * kHubChunk
 constexpr int kLongRow = 256;    // rows beyond this many in-edges fold in their own launch (k_long_rows)
 
-__device__ __forceinline__ float gelu_erf(float x) {
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-}
-
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPR);
-  return v;
-}
-
 struct Args {
   const float *ysrc;
   const float *ydst;

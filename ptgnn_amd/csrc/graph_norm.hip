@@ -11,10 +11,10 @@
 // and one write of grad_x: HBM-bound streaming work whose re-reads fit the Infinity Cache at the benchmarked sizes
 // (116 k x 64 fp32 = 30 MB).
 //
-// Segments are graphs: few and long.  As in weighted_pool.hip every segment is cut into CHUNKS OF 128 ROWS COUNTED FROM
-// ITS OWN START (the shared chunk table of k_pool_chunk_starts), workgroup b folds chunk c of segment g, and a per-graph
-// launch adds the chunk partials of a segment IN CHUNK ORDER.  No float atomics: a graph's statistics and output rows are
-// a fixed function of ITS rows and their order, wherever the graph sits in the batch.
+// Segments are graphs: few and long.  Every segment is cut into the 128-row chunks of segment_chunks.h, counted from its
+// own start (chunk_locate and the chunk table are that header's, as for the pools), workgroup b folds chunk c of segment
+// g, and a per-graph launch adds the chunk partials of a segment IN CHUNK ORDER (chunk_fold).  No float atomics: a graph's
+// statistics and output rows are a fixed function of ITS rows and their order, wherever the graph sits in the batch.
 //
 // The variance is the reference's two-pass one over the ROUNDED s_i (not var + (1 - alpha)^2 mu^2, which loses y on
 // inputs whose mean dwarfs their spread), and every kernel forms s_i the same way: one rounded product alpha * mu[g],
@@ -34,60 +34,13 @@
 // accumulators (products of two floats are exact there; the pass stays memory-bound) and forms sig2, r, c, S in float64.  One pass over (x, gy) gives the chunk
 // partials, a per-graph fold gives c, gamma r, (alpha / n) S and the graph's three parameter-gradient terms, those are
 // added in GRAPH ORDER, and one streaming pass writes dx.  All outputs are overwritten and deterministic.
-#include "common.h"
+#include "segment_chunks.h"
 
 namespace ptgnn_amd {
 namespace {
 
 constexpr int kGnThreads = 256;
-constexpr int kGnChunk = kPoolChunkRows;   // rows of one chunk, counted from the start of its segment
 constexpr int kGnMaxDim = 1024;
-
-template <int VEC>
-__device__ __forceinline__ void gn_load(const float *p, float (&o)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-  } else {
-    o[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void gn_store(float *p, const float (&o)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(o[0], o[1], o[2], o[3]);
-  else *p = o[0];
-}
-
-// workgroup b -> its segment and the plan slots [lo, hi) of its chunk; false for a workgroup past the last chunk (the
-// grid is the host's upper bound n / 128 + G).  Workgroup-uniform.
-__device__ __forceinline__ bool gn_locate(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ chunk_start,
-                                          int num_segments, int b, int &seg, int &lo, int &hi) {
-  if (b >= chunk_start[num_segments]) return false;
-  seg = 0;
-  int hi_seg = num_segments;                           // chunk_start[seg] <= b < chunk_start[seg + 1]
-  while (hi_seg - seg > 1) {
-    const int mid = (seg + hi_seg) >> 1;
-    if (chunk_start[mid] <= b) seg = mid; else hi_seg = mid;
-  }
-  const int end = rowptr[seg + 1];
-  lo = rowptr[seg] + (b - chunk_start[seg]) * kGnChunk;
-  hi = lo + kGnChunk < end ? lo + kGnChunk : end;
-  return true;
-}
-
-// p[c0 * stride], p[(c0 + 1) * stride], ... added in that order (four loads in flight, one chain of additions)
-template <typename T>
-__device__ __forceinline__ T gn_fold(const T *__restrict__ p, int64_t stride, int c0, int c1) {
-  T t = 0;
-  int c = c0;
-  for (; c + 4 <= c1; c += 4) {
-    const T a0 = p[c * stride], a1 = p[(c + 1) * stride], a2 = p[(c + 2) * stride], a3 = p[(c + 3) * stride];
-    t += a0; t += a1; t += a2; t += a3;
-  }
-  for (; c < c1; ++c) t += p[c * stride];
-  return t;
-}
 
 enum { kGnSumX = 0, kGnSumSq = 1, kGnSumGrad = 2 };
 
@@ -110,8 +63,8 @@ __global__ __launch_bounds__(kGnThreads) void k_graph_norm_chunk_sums(
   using T = typename GnSums<MODE>::T;
   constexpr int NOUT = GnSums<MODE>::kOut;
   __shared__ __attribute__((aligned(16))) T lds[NOUT][kGnThreads * VEC];
-  int seg, lo, hi;
-  if (!gn_locate(rowptr, chunk_start, num_segments, blockIdx.x, seg, lo, hi)) return;
+  ChunkSpan ch;
+  if (!chunk_locate(rowptr, chunk_start, num_segments, blockIdx.x, ch)) return;
   const int groups = kGnThreads / lanes;
   const int grp = threadIdx.x / lanes, g = threadIdx.x % lanes;
   const int units = dim / VEC;
@@ -130,15 +83,15 @@ __global__ __launch_bounds__(kGnThreads) void k_graph_norm_chunk_sums(
     if (on) {
       if constexpr (MODE != kGnSumX) {
         float al[VEC], mu[VEC];
-        gn_load<VEC>(alpha + col, al);
-        gn_load<VEC>(mean + (int64_t)seg * dim + col, mu);
+        vec_load<VEC>(alpha + col, al);
+        vec_load<VEC>(mean + (int64_t)ch.seg * dim + col, mu);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) am[v] = __fmul_rn(al[v], mu[v]);
       }
-      for (int p = lo + grp; p < hi; p += groups) {
+      for (int p = ch.lo + grp; p < ch.hi; p += groups) {
         const int64_t r = perm[p];
         float xv[VEC];
-        gn_load<VEC>(x + r * ld_x + col, xv);
+        vec_load<VEC>(x + r * ld_x + col, xv);
         if constexpr (MODE == kGnSumX) {
 #pragma unroll
           for (int v = 0; v < VEC; ++v) acc[0][v] += xv[v];
@@ -150,7 +103,7 @@ __global__ __launch_bounds__(kGnThreads) void k_graph_norm_chunk_sums(
           }
         } else {
           float gv[VEC];
-          gn_load<VEC>(gy + r * ld_gy + col, gv);
+          vec_load<VEC>(gy + r * ld_gy + col, gv);
 #pragma unroll
           for (int v = 0; v < VEC; ++v) {
             const double s = (double)__fsub_rn(xv[v], am[v]), gd = (double)gv[v];
@@ -194,7 +147,7 @@ __global__ __launch_bounds__(256) void k_graph_norm_fold_mean(const float *__res
   const int64_t g = i / dim;
   const int col = (int)(i % dim);
   const int n = rowptr[g + 1] - rowptr[g];
-  const float t = gn_fold(partial + col, dim, chunk_start[g], chunk_start[g + 1]);
+  const float t = chunk_fold(partial + col, dim, chunk_start[g], chunk_start[g + 1]);
   mean[g * dim + col] = n > 0 ? t / (float)n : 0.0f;
 }
 
@@ -208,7 +161,7 @@ __global__ __launch_bounds__(256) void k_graph_norm_fold_var(const float *__rest
   const int64_t g = i / dim;
   const int col = (int)(i % dim);
   const int n = rowptr[g + 1] - rowptr[g];
-  const float sq = gn_fold(partial + col, dim, chunk_start[g], chunk_start[g + 1]);
+  const float sq = chunk_fold(partial + col, dim, chunk_start[g], chunk_start[g + 1]);
   const float sig2 = __fadd_rn(sq / (float)(n > 0 ? n : 1), eps);
   rinv[g * dim + col] = 1.0f / sqrtf(sig2);
 }
@@ -220,32 +173,32 @@ __global__ __launch_bounds__(kGnThreads) void k_graph_norm_apply(
     const float *__restrict__ bias, const float *__restrict__ mean, const float *__restrict__ rinv,
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ perm, int dim, int lanes, int num_segments,
     const int32_t *__restrict__ chunk_start, float *__restrict__ y, int64_t ld_y) {
-  int seg, lo, hi;
-  if (!gn_locate(rowptr, chunk_start, num_segments, blockIdx.x, seg, lo, hi)) return;
+  ChunkSpan ch;
+  if (!chunk_locate(rowptr, chunk_start, num_segments, blockIdx.x, ch)) return;
   const int groups = kGnThreads / lanes;
   const int grp = threadIdx.x / lanes, g = threadIdx.x % lanes;
   const int units = dim / VEC;
-  const float *mu_g = mean + (int64_t)seg * dim, *r_g = rinv + (int64_t)seg * dim;
+  const float *mu_g = mean + (int64_t)ch.seg * dim, *r_g = rinv + (int64_t)ch.seg * dim;
   for (int ubase = g; ubase < units; ubase += lanes) {
     const int col = ubase * VEC;
     float ga[VEC], al[VEC], bi[VEC], mu[VEC], r[VEC], am[VEC], gr[VEC];
-    gn_load<VEC>(gamma + col, ga);
-    gn_load<VEC>(alpha + col, al);
-    gn_load<VEC>(bias + col, bi);
-    gn_load<VEC>(mu_g + col, mu);
-    gn_load<VEC>(r_g + col, r);
+    vec_load<VEC>(gamma + col, ga);
+    vec_load<VEC>(alpha + col, al);
+    vec_load<VEC>(bias + col, bi);
+    vec_load<VEC>(mu_g + col, mu);
+    vec_load<VEC>(r_g + col, r);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       am[v] = __fmul_rn(al[v], mu[v]);
       gr[v] = ga[v] * r[v];
     }
-    for (int p = lo + grp; p < hi; p += groups) {
+    for (int p = ch.lo + grp; p < ch.hi; p += groups) {
       const int64_t row = perm[p];
       float xv[VEC], o[VEC];
-      gn_load<VEC>(x + row * ld_x + col, xv);
+      vec_load<VEC>(x + row * ld_x + col, xv);
 #pragma unroll
       for (int v = 0; v < VEC; ++v) o[v] = fmaf(__fsub_rn(xv[v], am[v]), gr[v], bi[v]);
-      gn_store<VEC>(y + row * ld_y + col, o);
+      vec_store<VEC>(y + row * ld_y + col, o);
     }
   }
 }
@@ -266,10 +219,10 @@ __global__ __launch_bounds__(256) void k_graph_norm_backward_fold(
   if (n > 0) {
     const int c0 = chunk_start[g], c1 = chunk_start[g + 1];
     const int64_t stride = 4 * (int64_t)dim;
-    const double A = gn_fold(partial + col, stride, c0, c1);
-    const double B = gn_fold(partial + dim + col, stride, c0, c1);
-    const double Q = gn_fold(partial + 2 * dim + col, stride, c0, c1);
-    const double C = gn_fold(partial + 3 * dim + col, stride, c0, c1);
+    const double A = chunk_fold(partial + col, stride, c0, c1);
+    const double B = chunk_fold(partial + dim + col, stride, c0, c1);
+    const double Q = chunk_fold(partial + 2 * dim + col, stride, c0, c1);
+    const double C = chunk_fold(partial + 3 * dim + col, stride, c0, c1);
     const double nd = (double)n, ga = (double)gamma[col], mu = (double)mean[g * dim + col];
     const double sig2 = Q / nd + (double)eps;
     const double r = 1.0 / sqrt(sig2);
@@ -296,7 +249,7 @@ __global__ __launch_bounds__(256) void k_graph_norm_param_fold(const double *__r
                                                                 float *__restrict__ grad_bias) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 3 * dim) return;
-  const double t = gn_fold(terms + i, 3 * (int64_t)dim, 0, segments);
+  const double t = chunk_fold(terms + i, 3 * (int64_t)dim, 0, segments);
   float *out = i < dim ? grad_gamma : (i < 2 * dim ? grad_alpha : grad_bias);
   out[i % dim] = (float)t;
 }
@@ -308,19 +261,19 @@ __global__ __launch_bounds__(kGnThreads) void k_graph_norm_backward_apply(
     const float *__restrict__ alpha, const float *__restrict__ mean, const double *__restrict__ coef,
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ perm, int dim, int lanes, int num_segments,
     const int32_t *__restrict__ chunk_start, float *__restrict__ gx, int64_t ld_gx) {
-  int seg, lo, hi;
-  if (!gn_locate(rowptr, chunk_start, num_segments, blockIdx.x, seg, lo, hi)) return;
+  ChunkSpan ch;
+  if (!chunk_locate(rowptr, chunk_start, num_segments, blockIdx.x, ch)) return;
   const int groups = kGnThreads / lanes;
   const int grp = threadIdx.x / lanes, g = threadIdx.x % lanes;
   const int units = dim / VEC;
-  const float *st = mean + (int64_t)seg * dim;
-  const double *cf = coef + (int64_t)seg * 3 * dim;
+  const float *st = mean + (int64_t)ch.seg * dim;
+  const double *cf = coef + (int64_t)ch.seg * 3 * dim;
   for (int ubase = g; ubase < units; ubase += lanes) {
     const int col = ubase * VEC;
     float al[VEC], mu[VEC], am[VEC];
     double c[VEC], gr[VEC], shift[VEC];
-    gn_load<VEC>(alpha + col, al);
-    gn_load<VEC>(st + col, mu);
+    vec_load<VEC>(alpha + col, al);
+    vec_load<VEC>(st + col, mu);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       am[v] = __fmul_rn(al[v], mu[v]);
@@ -328,15 +281,15 @@ __global__ __launch_bounds__(kGnThreads) void k_graph_norm_backward_apply(
       gr[v] = cf[dim + col + v];
       shift[v] = cf[2 * dim + col + v];
     }
-    for (int p = lo + grp; p < hi; p += groups) {
+    for (int p = ch.lo + grp; p < ch.hi; p += groups) {
       const int64_t row = perm[p];
       float xv[VEC], gv[VEC], o[VEC];
-      gn_load<VEC>(x + row * ld_x + col, xv);
-      gn_load<VEC>(gy + row * ld_gy + col, gv);
+      vec_load<VEC>(x + row * ld_x + col, xv);
+      vec_load<VEC>(gy + row * ld_gy + col, gv);
 #pragma unroll
       for (int v = 0; v < VEC; ++v)
         o[v] = (float)(fma(c[v], (double)__fsub_rn(xv[v], am[v]), gr[v] * (double)gv[v]) - shift[v]);
-      gn_store<VEC>(gx + row * ld_gx + col, o);
+      vec_store<VEC>(gx + row * ld_gx + col, o);
     }
   }
 }
@@ -349,20 +302,20 @@ int gn_lanes(int dim, bool vec4) {
   return lanes;
 }
 
-size_t gn_align(size_t n) { return (n + 255) / 256 * 256; }
-
+// the chunk table, the chunk partials and the two per-graph tables
 struct GnWorkspace {
-  size_t table, partial, a, b;     // byte sizes of the chunk table, the chunk partials and the two per-graph tables
-  size_t total() const { return table + partial + a + b; }
+  size_t chunk_start, partial, a, b, total;
 };
 
 // `partial_row`: bytes of one chunk's partial sums per column; `a_row` / `b_row`: bytes per graph and column
 GnWorkspace gn_workspace(int64_t segments, int64_t elements, int dim, size_t partial_row, size_t a_row, size_t b_row) {
+  Carve c;
   GnWorkspace w;
-  w.table = gn_align(pool_chunk_table_bytes(segments));
-  w.partial = gn_align((size_t)pool_chunk_count_bound(segments, elements) * dim * partial_row);
-  w.a = gn_align((size_t)segments * dim * a_row);
-  w.b = gn_align((size_t)segments * dim * b_row);
+  w.chunk_start = c.take(chunk_table_bytes(segments));
+  w.partial = c.take((size_t)chunk_count_bound(segments, elements) * dim * partial_row);
+  w.a = c.take((size_t)segments * dim * a_row);
+  w.b = c.take((size_t)segments * dim * b_row);
+  w.total = c.take(0);             // rounded up like the blocks in front: the size this op has always asked for
   return w;
 }
 
@@ -374,6 +327,14 @@ GnWorkspace gn_backward_workspace(int64_t segments, int64_t elements, int dim) {
   return gn_workspace(segments, elements, dim, 4 * sizeof(double), 3 * sizeof(double), 3 * sizeof(double));
 }
 
+// the argument checks the forward and the backward share; 0 when the arguments are fine
+int gn_check(const char *what, int64_t num_segments, int64_t num_elements, int32_t dim) {
+  if (const int rc = chunked_segments_check(what, num_segments, num_elements, dim, 3 * (int64_t)dim)) return rc;
+  PTGNN_REQUIRE(dim <= kGnMaxDim, PTGNN_AMD_EUNSUPPORTED, "%s: dim %d exceeds %d", what, dim, kGnMaxDim);
+  PTGNN_REQUIRE(num_segments > 0 || num_elements == 0, PTGNN_AMD_EINVAL, "%s: elements without segments", what);
+  return PTGNN_AMD_OK;
+}
+
 }  // namespace
 }  // namespace ptgnn_amd
 
@@ -383,39 +344,32 @@ extern "C" int ptgnn_amd_graph_norm_supported(int32_t dim) { return dim >= 1 && 
 
 extern "C" size_t ptgnn_amd_graph_norm_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim) {
   if (num_segments <= 0 || num_elements < 0 || dim <= 0) return 0;
-  return gn_forward_workspace(num_segments, num_elements, dim).total();
+  return gn_forward_workspace(num_segments, num_elements, dim).total;
 }
 
 extern "C" int ptgnn_amd_graph_norm_f32(const float *x, int64_t ld_x, const float *gamma, const float *alpha,
                                         const float *bias, float eps, const int32_t *rowptr, const int32_t *perm,
                                         int64_t num_segments, int64_t num_elements, int32_t dim, float *y, int64_t ld_y,
                                         float *mean, void *workspace, size_t workspace_bytes, void *stream_) {
-  PTGNN_REQUIRE(num_segments >= 0 && num_elements >= 0 && dim > 0, PTGNN_AMD_EINVAL, "graph_norm: bad sizes");
-  PTGNN_REQUIRE(dim <= kGnMaxDim, PTGNN_AMD_EUNSUPPORTED, "graph_norm: dim %d exceeds %d", dim, kGnMaxDim);
-  PTGNN_REQUIRE(num_segments > 0 || num_elements == 0, PTGNN_AMD_EINVAL, "graph_norm: elements without segments");
+  if (const int rc = gn_check("graph_norm", num_segments, num_elements, dim)) return rc;
   if (num_segments == 0) return PTGNN_AMD_OK;
   PTGNN_REQUIRE(gamma && alpha && bias && rowptr && (num_elements == 0 || (x && perm && y)), PTGNN_AMD_EINVAL,
                 "graph_norm: null pointer");
   PTGNN_REQUIRE(num_elements == 0 || (ld_x >= dim && ld_y >= dim), PTGNN_AMD_EINVAL, "graph_norm: bad leading dimension");
-  const int64_t bound = pool_chunk_count_bound(num_segments, num_elements);
-  PTGNN_REQUIRE(bound < ((int64_t)1 << 31) && num_elements < ((int64_t)1 << 31) &&
-                    num_segments * 3 * dim < ((int64_t)1 << 31),
-                PTGNN_AMD_EUNSUPPORTED, "graph_norm: too many segments / elements");
   const GnWorkspace w = gn_forward_workspace(num_segments, num_elements, dim);
-  PTGNN_REQUIRE(workspace && workspace_bytes >= w.total(), PTGNN_AMD_EWORKSPACE,
-                "graph_norm: workspace of %zu bytes, need %zu", workspace_bytes, w.total());
+  if (const int rc = workspace_check("graph_norm", workspace, workspace_bytes, w.total)) return rc;
+  const int64_t bound = chunk_count_bound(num_segments, num_elements);
   hipStream_t st = (hipStream_t)stream_;
-  char *ws = static_cast<char *>(workspace);
-  int32_t *chunk_start = reinterpret_cast<int32_t *>(ws);
-  float *partial = reinterpret_cast<float *>(ws + w.table);
-  float *rinv = reinterpret_cast<float *>(ws + w.table + w.partial);
-  if (!mean) mean = reinterpret_cast<float *>(ws + w.table + w.partial + w.a);
+  int32_t *chunk_start = carved<int32_t>(workspace, w.chunk_start);
+  float *partial = carved<float>(workspace, w.partial);
+  float *rinv = carved<float>(workspace, w.a);
+  if (!mean) mean = carved<float>(workspace, w.b);
   const bool vec4 = dim % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gamma) &&
                     aligned16(alpha) && aligned16(bias) && aligned16(mean) && aligned16(workspace);
   const int lanes = gn_lanes(dim, vec4);
   const unsigned grid = (unsigned)bound, fold_grid = (unsigned)((num_segments * dim + 255) / 256);
   const int G = (int)num_segments;
-  launch_pool_chunk_starts(rowptr, G, chunk_start, st);
+  launch_chunk_starts(rowptr, G, chunk_start, st);
   PTGNN_LAUNCH_CHECK();
   if (vec4)
     k_graph_norm_chunk_sums<4, kGnSumX><<<grid, kGnThreads, 0, st>>>(x, ld_x, nullptr, 0, alpha, mean, rowptr, perm, dim,
@@ -449,7 +403,7 @@ extern "C" int ptgnn_amd_graph_norm_f32(const float *x, int64_t ld_x, const floa
 extern "C" size_t ptgnn_amd_graph_norm_backward_workspace_bytes(int64_t num_segments, int64_t num_elements,
                                                                 int32_t dim) {
   if (num_segments <= 0 || num_elements < 0 || dim <= 0) return 0;
-  return gn_backward_workspace(num_segments, num_elements, dim).total();
+  return gn_backward_workspace(num_segments, num_elements, dim).total;
 }
 
 extern "C" int ptgnn_amd_graph_norm_backward_f32(const float *x, int64_t ld_x, const float *grad_y, int64_t ld_gy,
@@ -458,9 +412,7 @@ extern "C" int ptgnn_amd_graph_norm_backward_f32(const float *x, int64_t ld_x, c
                                                  int64_t num_elements, int32_t dim, float *grad_x, int64_t ld_gx,
                                                  float *grad_gamma, float *grad_alpha, float *grad_bias, void *workspace,
                                                  size_t workspace_bytes, void *stream_) {
-  PTGNN_REQUIRE(num_segments >= 0 && num_elements >= 0 && dim > 0, PTGNN_AMD_EINVAL, "graph_norm_backward: bad sizes");
-  PTGNN_REQUIRE(dim <= kGnMaxDim, PTGNN_AMD_EUNSUPPORTED, "graph_norm_backward: dim %d exceeds %d", dim, kGnMaxDim);
-  PTGNN_REQUIRE(num_segments > 0 || num_elements == 0, PTGNN_AMD_EINVAL, "graph_norm_backward: elements without segments");
+  if (const int rc = gn_check("graph_norm_backward", num_segments, num_elements, dim)) return rc;
   PTGNN_REQUIRE(grad_gamma && grad_alpha && grad_bias, PTGNN_AMD_EINVAL, "graph_norm_backward: null pointer");
   hipStream_t st = (hipStream_t)stream_;
   if (num_segments == 0) {
@@ -473,25 +425,20 @@ extern "C" int ptgnn_amd_graph_norm_backward_f32(const float *x, int64_t ld_x, c
                 PTGNN_AMD_EINVAL, "graph_norm_backward: null pointer");
   PTGNN_REQUIRE(num_elements == 0 || (ld_x >= dim && ld_gy >= dim && ld_gx >= dim), PTGNN_AMD_EINVAL,
                 "graph_norm_backward: bad leading dimension");
-  const int64_t bound = pool_chunk_count_bound(num_segments, num_elements);
-  PTGNN_REQUIRE(bound < ((int64_t)1 << 31) && num_elements < ((int64_t)1 << 31) &&
-                    num_segments * 3 * dim < ((int64_t)1 << 31),
-                PTGNN_AMD_EUNSUPPORTED, "graph_norm_backward: too many segments / elements");
   const GnWorkspace w = gn_backward_workspace(num_segments, num_elements, dim);
-  PTGNN_REQUIRE(workspace && workspace_bytes >= w.total(), PTGNN_AMD_EWORKSPACE,
-                "graph_norm_backward: workspace of %zu bytes, need %zu", workspace_bytes, w.total());
-  char *ws = static_cast<char *>(workspace);
-  int32_t *chunk_start = reinterpret_cast<int32_t *>(ws);
-  double *partial = reinterpret_cast<double *>(ws + w.table);
-  double *coef = reinterpret_cast<double *>(ws + w.table + w.partial);
-  double *terms = reinterpret_cast<double *>(ws + w.table + w.partial + w.a);
+  if (const int rc = workspace_check("graph_norm_backward", workspace, workspace_bytes, w.total)) return rc;
+  const int64_t bound = chunk_count_bound(num_segments, num_elements);
+  int32_t *chunk_start = carved<int32_t>(workspace, w.chunk_start);
+  double *partial = carved<double>(workspace, w.partial);
+  double *coef = carved<double>(workspace, w.a);
+  double *terms = carved<double>(workspace, w.b);
   const bool vec4 = dim % 4 == 0 && ld_x % 4 == 0 && ld_gy % 4 == 0 && ld_gx % 4 == 0 && aligned16(x) &&
                     aligned16(grad_y) && aligned16(grad_x) && aligned16(gamma) && aligned16(alpha) && aligned16(mean) &&
                     aligned16(workspace);
   const int lanes = gn_lanes(dim, vec4);
   const unsigned grid = (unsigned)bound, fold_grid = (unsigned)((num_segments * dim + 255) / 256);
   const int G = (int)num_segments;
-  launch_pool_chunk_starts(rowptr, G, chunk_start, st);
+  launch_chunk_starts(rowptr, G, chunk_start, st);
   PTGNN_LAUNCH_CHECK();
   if (vec4)
     k_graph_norm_chunk_sums<4, kGnSumGrad><<<grid, kGnThreads, 0, st>>>(x, ld_x, grad_y, ld_gy, alpha, mean, rowptr, perm,

@@ -24,22 +24,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ float gelu_erf(float x) {
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-}
-
-__device__ __forceinline__ float gelu_erf_grad(float x) {
-  // d/dx [x Phi(x)] = Phi(x) + x phi(x)
-  return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
-}
-
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPR);
-  return v;
-}
-
 struct RowArgs {
   const float *x; int64_t ld_x;
   const float *dy; int64_t ld_dy;

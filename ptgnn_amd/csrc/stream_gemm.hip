@@ -45,9 +45,6 @@
 //  profiles/r02_notes.md, r04_notes.md and DESIGN.md 9 hold its numbers.)
 #include <stdlib.h>
 
-#include <mutex>
-#include <unordered_map>
-
 #include "dense_common.h"
 #include <atomic>
 
@@ -1301,27 +1298,13 @@ bool debug_on() {
   return v == 1;
 }
 
-// Raise a kernel's dynamic-LDS limit once per (kernel, device, size): the attribute call is not legal while a
-// stream is being captured into a hipGraph, and the warm-up launch outside the capture has made it.
+// raise_dynamic_lds with this file's policy for a refusal: the caller falls back to the tile kernel
 template <typename Kern>
 bool set_lds(Kern kern, size_t bytes) {
-  static std::mutex mu;
-  static std::unordered_map<uint64_t, size_t> done;     // (kernel, device): the attribute is per device
-  const void *fn = reinterpret_cast<const void *>(kern);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)dev;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return true;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (debug_on()) fprintf(stderr, "[ptgnn_amd] stream kernel: %zu B of LDS refused (%s) -> tile kernel\n", bytes, hipGetErrorString(e));
-    return false;
-  }
-  done[key] = bytes;
-  return true;
+  const char *why = "";
+  if (raise_dynamic_lds(kern, bytes, &why)) return true;
+  if (debug_on()) fprintf(stderr, "[ptgnn_amd] stream kernel: %zu B of LDS refused (%s) -> tile kernel\n", bytes, why);
+  return false;
 }
 
 // runs per slab for the dense kernels: one 8-wave workgroup per CU

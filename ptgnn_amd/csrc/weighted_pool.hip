@@ -11,11 +11,12 @@
 // Segments are graphs: few (tens) and long (thousands of rows).  One lane group per segment folding in the reference's
 // serial order is what the package's ordinary segment sum does for rows of <= 2048 slots -- ~250 dependent round trips,
 // 0.36 ms per pool at cfg4, 60 % on top of the whole 8-layer forward (measured, round 6) -- and segments beyond 2048 rows
-// leave that order anyway (hub chunks).  So every segment is cut into CHUNKS OF 128 ROWS COUNTED FROM ITS OWN START:
-// workgroup b folds chunk c of segment g (k_pool_chunk_starts gives the (g, c) of every workgroup), a last launch adds the
-// chunk partials of a segment in chunk order.  No float atomics; the value of a segment is a fixed function of ITS rows
-// and their order -- independent of where the segment sits in the batch, so a sharded run that keeps whole graphs on a
-// rank reproduces the unsharded pool bit for bit.  The fold order is not the reference's serial one: a sum of ~2 000
+// leave that order anyway (hub chunks).  So every segment is cut into the 128-row chunks of segment_chunks.h, counted
+// from its own start: workgroup b folds chunk c of segment g, a last launch adds the chunk partials of a segment in chunk
+// order.  No float atomics; the value of a segment is a fixed function of ITS rows and their order -- independent of
+// where the segment sits in the batch, so a sharded run that keeps whole graphs on a rank reproduces the unsharded pool
+// bit for bit (the rule, and the two launches every chunked op shares -- k_pool_chunk_starts and k_fold_segments, defined
+// here -- are declared in segment_chunks.h).  The fold order is not the reference's serial one: a sum of ~2 000
 // fp32 rows of magnitude <= 1 differs by ~3e-5 between ANY two orders (the fp32 oracle itself sits 2e-5 from float64 on
 // such pools); the tests hold the pool, and the GRU update behind it, to "no further from float64 than 2 x the oracle".
 //
@@ -23,7 +24,7 @@
 //     d x_i = score_i go[g_i] + (go[g_i] . x_i) score_i (1 - score_i) w
 //     d w   = sum_i (go[g_i] . x_i) score_i (1 - score_i) x_i
 // one streaming pass for d x plus per-workgroup partial rows of d w that a second launch adds in a fixed order.
-#include "common.h"
+#include "segment_chunks.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -32,9 +33,8 @@ __device__ __forceinline__ float pool_sigmoid(float v) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
 }
 
-// sum of `v` over the `lanes` (power of two <= 64) consecutive lanes of a row group: xor butterfly, every lane of the
-// group ends with the same bits
-__device__ __forceinline__ float group_sum(float v, int lanes) {
+// group_sum of common.h for a lane count known only at run time (a power of two <= 64)
+__device__ __forceinline__ float lanes_sum(float v, int lanes) {
   for (int o = lanes >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
@@ -42,35 +42,18 @@ __device__ __forceinline__ float group_sum(float v, int lanes) {
 constexpr int kPoolThreads = 256;
 // COLS = chunks (float4 or float) of one row a lane holds: 1 for dim <= lanes * VEC (hidden 64 ... 256), up to 16
 
-constexpr int kPoolChunk = kPoolChunkRows;   // rows of one chunk, counted from the start of its segment
-
 // chunk_start[g] = chunks of the segments in front of g (chunk_start[G] = all chunks); one workgroup
 __global__ __launch_bounds__(1024) void k_pool_chunk_starts(const int32_t *__restrict__ rowptr, int num_segments,
                                                            int32_t *__restrict__ chunk_start) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  __shared__ SegmentScan<1024> scan;
+  scan.begin();
   for (int base = 0; base < num_segments; base += 1024) {
     const int gseg = base + threadIdx.x;
-    const int c = gseg < num_segments ? (rowptr[gseg + 1] - rowptr[gseg] + kPoolChunk - 1) / kPoolChunk : 0;
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int run = carry + inc - c;
-    for (int v = 0; v < wave; ++v) run += wsum[v];
+    const int c = gseg < num_segments ? (rowptr[gseg + 1] - rowptr[gseg] + kChunkRows - 1) / kChunkRows : 0;
+    const int run = scan.step(c);
     if (gseg < num_segments) chunk_start[gseg] = run;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = run + c;
-    __syncthreads();
   }
-  if (threadIdx.x == 0) chunk_start[num_segments] = carry;
+  if (threadIdx.x == 0) chunk_start[num_segments] = scan.total();
 }
 
 // x rows are read through `perm` (plan order -> element id): a sorted map (node_to_graph_idx) makes it the identity.
@@ -80,16 +63,8 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_partial(
     const int32_t *__restrict__ perm, int dim, int lanes, int num_segments, const int32_t *__restrict__ chunk_start,
     float *__restrict__ partial) {
   extern __shared__ float lds[];                       // [groups, dim] partial rows of the workgroup
-  const int b = blockIdx.x;
-  if (b >= chunk_start[num_segments]) return;          // the grid is the host's upper bound n / 128 + G
-  int seg = 0, hi_seg = num_segments;                  // chunk_start[seg] <= b < chunk_start[seg + 1] (workgroup-uniform)
-  while (hi_seg - seg > 1) {
-    const int mid = (seg + hi_seg) >> 1;
-    if (chunk_start[mid] <= b) seg = mid; else hi_seg = mid;
-  }
-  const int beg = rowptr[seg], end = rowptr[seg + 1];
-  const int lo = beg + (b - chunk_start[seg]) * kPoolChunk;
-  const int hi = lo + kPoolChunk < end ? lo + kPoolChunk : end;
+  ChunkSpan ch;
+  if (!chunk_locate(rowptr, chunk_start, num_segments, blockIdx.x, ch)) return;
   const int groups = kPoolThreads / lanes;
   const int grp = threadIdx.x / lanes, g = threadIdx.x % lanes;
   float wv[COLS][VEC], acc[COLS][VEC];
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_partial(
       acc[c][v] = 0.0f;
     }
   }
-  for (int p = lo + grp; p < hi; p += groups) {        // the loop bound is uniform per row group: shuffles stay in step
+  for (int p = ch.lo + grp; p < ch.hi; p += groups) {  // the loop bound is uniform per row group: shuffles stay in step
     const float *row = x + (int64_t)perm[p] * ld_x;
     float xv[COLS][VEC];
     float dot = 0.0f;
@@ -110,12 +85,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_partial(
     for (int c = 0; c < COLS; ++c) {
       const int col = (c * lanes + g) * VEC;
       if (col < dim) {
-        if constexpr (VEC == 4) {
-          const float4 t = *reinterpret_cast<const float4 *>(row + col);
-          xv[c][0] = t.x; xv[c][1] = t.y; xv[c][2] = t.z; xv[c][3] = t.w;
-        } else {
-          xv[c][0] = row[col];
-        }
+        vec_load<VEC>(row + col, xv[c]);
       } else {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) xv[c][v] = 0.0f;
@@ -123,7 +93,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_partial(
 #pragma unroll
       for (int v = 0; v < VEC; ++v) dot = fmaf(xv[c][v], wv[c][v], dot);
     }
-    const float s = pool_sigmoid(group_sum(dot, lanes));
+    const float s = pool_sigmoid(lanes_sum(dot, lanes));
 #pragma unroll
     for (int c = 0; c < COLS; ++c)
 #pragma unroll
@@ -153,9 +123,7 @@ __global__ __launch_bounds__(256) void k_fold_segments(const float *__restrict__
   if (i >= segments * dim) return;
   const int64_t g = i / dim;
   const int col = (int)(i % dim);
-  float t = 0.0f;
-  for (int c = chunk_start[g]; c < chunk_start[g + 1]; ++c) t += partial[(int64_t)c * dim + col];
-  out[g * ld_out + col] = t;
+  out[g * ld_out + col] = chunk_fold(partial + col, dim, chunk_start[g], chunk_start[g + 1]);
 }
 
 // out[r, :] = sum over the `parts` rows partial[r * parts + s, :], s ascending
@@ -165,10 +133,7 @@ __global__ __launch_bounds__(256) void k_fold_partials(const float *__restrict__
   if (i >= rows * dim) return;
   const int64_t r = i / dim;
   const int col = (int)(i % dim);
-  const float *p = partial + r * parts * dim + col;
-  float t = 0.0f;
-  for (int s = 0; s < parts; ++s) t += p[(int64_t)s * dim];
-  out[r * ld_out + col] = t;
+  out[r * ld_out + col] = chunk_fold(partial + r * parts * dim + col, dim, 0, parts);
 }
 
 constexpr int kBwdRowsPerBlock = 256;     // rows one workgroup of the backward walks
@@ -202,15 +167,8 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_backward(
     for (int c = 0; c < COLS; ++c) {
       const int col = (c * lanes + g) * VEC;
       if (col < dim) {
-        if constexpr (VEC == 4) {
-          const float4 t = *reinterpret_cast<const float4 *>(row + col);
-          const float4 u = *reinterpret_cast<const float4 *>(grow + col);
-          xv[c][0] = t.x; xv[c][1] = t.y; xv[c][2] = t.z; xv[c][3] = t.w;
-          gv[c][0] = u.x; gv[c][1] = u.y; gv[c][2] = u.z; gv[c][3] = u.w;
-        } else {
-          xv[c][0] = row[col];
-          gv[c][0] = grow[col];
-        }
+        vec_load<VEC>(row + col, xv[c]);
+        vec_load<VEC>(grow + col, gv[c]);
       } else {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) xv[c][v] = gv[c][v] = 0.0f;
@@ -221,8 +179,8 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_backward(
         gdot = fmaf(xv[c][v], gv[c][v], gdot);
       }
     }
-    const float s = pool_sigmoid(group_sum(dot, lanes));
-    const float ds = group_sum(gdot, lanes) * s * (1.0f - s);      // d loss / d (x_i . w)
+    const float s = pool_sigmoid(lanes_sum(dot, lanes));
+    const float ds = lanes_sum(gdot, lanes) * s * (1.0f - s);      // d loss / d (x_i . w)
 #pragma unroll
     for (int c = 0; c < COLS; ++c) {
       const int col = (c * lanes + g) * VEC;
@@ -232,10 +190,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_weighted_pool_backward(
         o[v] = fmaf(ds, wv[c][v], s * gv[c][v]);
         acc[c][v] = fmaf(ds, xv[c][v], acc[c][v]);
       }
-      if (col < dim) {
-        if constexpr (VEC == 4) *reinterpret_cast<float4 *>(gx + i * ld_gx + col) = make_float4(o[0], o[1], o[2], o[3]);
-        else gx[i * ld_gx + col] = o[0];
-      }
+      if (col < dim) vec_store<VEC>(gx + i * ld_gx + col, o);
     }
   }
 #pragma unroll
@@ -286,17 +241,23 @@ PoolShape pool_shape(int dim, bool aligned) {
     }                                                                                                       \
   } while (0)
 
-int64_t pool_chunk_bound(int64_t segments, int64_t elements) { return elements / kPoolChunk + segments; }
+// the chunk table and the [chunks, dim] partial rows
+struct PoolWorkspace {
+  size_t chunk_start, partial, total;
+};
 
-size_t pool_starts_bytes(int64_t segments) { return (size_t)((segments + 1 + 3) / 4 * 4) * sizeof(int32_t); }
+PoolWorkspace pool_workspace(int64_t segments, int64_t elements, int dim) {
+  Carve c;
+  PoolWorkspace w;
+  w.chunk_start = c.take(chunk_table_bytes(segments));
+  w.partial = c.take((size_t)chunk_count_bound(segments, elements) * dim * sizeof(float));
+  w.total = c.off;
+  return w;
+}
 
 }  // namespace
 
-int64_t pool_chunk_count_bound(int64_t segments, int64_t elements) { return pool_chunk_bound(segments, elements); }
-
-size_t pool_chunk_table_bytes(int64_t segments) { return pool_starts_bytes(segments); }
-
-void launch_pool_chunk_starts(const int32_t *rowptr, int num_segments, int32_t *chunk_start, hipStream_t st) {
+void launch_chunk_starts(const int32_t *rowptr, int num_segments, int32_t *chunk_start, hipStream_t st) {
   k_pool_chunk_starts<<<1, 1024, 0, st>>>(rowptr, num_segments, chunk_start);
 }
 
@@ -313,29 +274,26 @@ using namespace ptgnn_amd;
 
 extern "C" size_t ptgnn_amd_weighted_pool_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim) {
   if (num_segments <= 0 || dim <= 0) return 0;
-  return pool_starts_bytes(num_segments) + (size_t)pool_chunk_bound(num_segments, num_elements) * dim * sizeof(float);
+  return pool_workspace(num_segments, num_elements, dim).total;
 }
 
 extern "C" int ptgnn_amd_weighted_pool_f32(const float *x, int64_t ld_x, const float *w, const int32_t *rowptr,
                                            const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
                                            float *out, int64_t ld_out, void *workspace, size_t workspace_bytes,
                                            void *stream_) {
-  PTGNN_REQUIRE(num_segments >= 0 && num_elements >= 0 && dim > 0, PTGNN_AMD_EINVAL, "weighted_pool: bad sizes");
+  if (const int rc = chunked_segments_check("weighted_pool", num_segments, num_elements, dim)) return rc;
   if (num_segments == 0) return PTGNN_AMD_OK;
   PTGNN_REQUIRE(w && rowptr && out && (num_elements == 0 || (x && perm)), PTGNN_AMD_EINVAL, "weighted_pool: null pointer");
   PTGNN_REQUIRE(ld_out >= dim && (num_elements == 0 || ld_x >= dim), PTGNN_AMD_EINVAL, "weighted_pool: bad leading dimension");
   const PoolShape sh = pool_shape(dim, ld_x % 4 == 0 && aligned16(x));
   PTGNN_REQUIRE(sh.cols > 0, PTGNN_AMD_EUNSUPPORTED, "weighted_pool: dim %d exceeds 1024", dim);
-  const int64_t bound = pool_chunk_bound(num_segments, num_elements);
-  const size_t need = pool_starts_bytes(num_segments) + (size_t)bound * dim * sizeof(float);
-  PTGNN_REQUIRE(workspace && workspace_bytes >= need, PTGNN_AMD_EWORKSPACE, "weighted_pool: workspace of %zu bytes, need %zu",
-                workspace_bytes, need);
-  PTGNN_REQUIRE(bound < ((int64_t)1 << 31) && num_elements < ((int64_t)1 << 31) && num_segments < ((int64_t)1 << 31),
-                PTGNN_AMD_EUNSUPPORTED, "weighted_pool: too many segments / elements");
+  const PoolWorkspace ws = pool_workspace(num_segments, num_elements, dim);
+  if (const int rc = workspace_check("weighted_pool", workspace, workspace_bytes, ws.total)) return rc;
+  const int64_t bound = chunk_count_bound(num_segments, num_elements);
   hipStream_t st = (hipStream_t)stream_;
-  int32_t *chunk_start = static_cast<int32_t *>(workspace);
-  float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + pool_starts_bytes(num_segments));
-  k_pool_chunk_starts<<<1, 1024, 0, st>>>(rowptr, (int)num_segments, chunk_start);
+  int32_t *chunk_start = carved<int32_t>(workspace, ws.chunk_start);
+  float *partial = carved<float>(workspace, ws.partial);
+  launch_chunk_starts(rowptr, (int)num_segments, chunk_start, st);
   PTGNN_LAUNCH_CHECK();
   if (bound > 0) {
     const size_t lds = (size_t)(kPoolThreads / sh.lanes) * dim * sizeof(float);
@@ -343,8 +301,7 @@ extern "C" int ptgnn_amd_weighted_pool_f32(const float *x, int64_t ld_x, const f
                   (int)num_segments, chunk_start, partial);
     PTGNN_LAUNCH_CHECK();
   }
-  const int64_t total = num_segments * dim;
-  k_fold_segments<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(partial, chunk_start, dim, num_segments, out, ld_out);
+  launch_fold_segments(partial, chunk_start, dim, num_segments, out, ld_out, st);
   PTGNN_LAUNCH_CHECK();
   return PTGNN_AMD_OK;
 }
@@ -372,8 +329,7 @@ extern "C" int ptgnn_amd_weighted_pool_backward_f32(const float *x, int64_t ld_x
   PTGNN_REQUIRE(sh.cols > 0, PTGNN_AMD_EUNSUPPORTED, "weighted_pool_backward: dim %d exceeds 1024", dim);
   const int64_t blocks = (num_elements + kBwdRowsPerBlock - 1) / kBwdRowsPerBlock;
   const size_t need = (size_t)blocks * dim * sizeof(float);
-  PTGNN_REQUIRE(workspace && workspace_bytes >= need, PTGNN_AMD_EWORKSPACE,
-                "weighted_pool_backward: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  if (const int rc = workspace_check("weighted_pool_backward", workspace, workspace_bytes, need)) return rc;
   PTGNN_REQUIRE(blocks < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED, "weighted_pool_backward: too many elements");
   float *partial = static_cast<float *>(workspace);
   const size_t lds = (size_t)(kPoolThreads / sh.lanes) * dim * sizeof(float);

@@ -19,8 +19,6 @@
 //     type in a fixed order (deterministic, like every reduction of this library).
 // Shapes it takes: message and input widths that are multiples of 32 (tiles of 32 / 64 / 128 columns); the rest stays
 // on the tile kernel.
-#include <mutex>
-#include <unordered_map>
 
 #include "dense_common.h"
 #include "stream_gemm.h"
@@ -385,25 +383,6 @@ __global__ __launch_bounds__(256) void k_wgrad_stream_colsum(const float *__rest
   if (sub == 0) grad_b[m] = s;
 }
 
-template <typename Kern>
-bool set_lds(Kern kern, size_t bytes) {
-  static std::mutex mu;
-  static std::unordered_map<uint64_t, size_t> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void *fn = reinterpret_cast<const void *>(kern);
-  const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)dev;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  done[key] = bytes;
-  return true;
-}
-
 int blocks_for(int width) { return width % 128 == 0 ? 4 : (width % 64 == 0 ? 2 : (width % 32 == 0 ? 1 : 0)); }
 
 // (Sizing the launch for every workgroup the small tiles could keep resident -- 3 per CU at 64 x 64, 2 at 64 x 128 --
@@ -473,7 +452,7 @@ int stream_wgrad(const WsTable &tab_in, const float *x, int64_t ld_x, int64_t nu
   do {                                                                               \
     auto kern = gather ? k_wgrad_stream<NBA_, NBB_, DROP_, false, true>              \
                        : k_wgrad_stream<NBA_, NBB_, 0, CS_, false>;                  \
-    if (!set_lds(kern, lds)) return 0;                                               \
+    if (!raise_dynamic_lds(kern, lds)) return 0;                                     \
     kern<<<(unsigned)xcd_padded_blocks(total), kWavesPerWg * 64, lds, st>>>(p);                         \
   } while (0)
 #define PTGNN_WS_NBB(NBA_)                                                           \

@@ -148,6 +148,16 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _rows_arg(t: torch.Tensor, d: int):
+    """(data pointer, leading dimension) of an [n, d] operand of a library call: (None, d) when it has no rows."""
+    return (t.data_ptr(), _ld(t)) if t.numel() else (None, d)
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """Scratch bytes of one library call; never empty, so that its pointer is not NULL."""
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
 # ------------------------------------------------------------------------------------------------
 # graph plan
 # ------------------------------------------------------------------------------------------------
@@ -370,7 +380,7 @@ def _launch_unique_sources(plan: "GraphPlan") -> Optional[UniqueMessages]:
     counts = torch.empty(T + 1, dtype=torch.int64, device=dev)
     table = torch.empty(int(lib.ptgnn_amd_edge_table_bytes()), dtype=torch.uint8, device=dev)
     ws_bytes = int(lib.ptgnn_amd_unique_sources_workspace_bytes(ns, T))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     with _timed("unique_sources", bytes=E * 12.0 + ns * T / 4.0):
         rc = lib.ptgnn_amd_unique_sources(plan.col.data_ptr(), E, plan.type_bits, T, ns, slot_row.data_ptr(),
                                           unique_src.data_ptr(), cap, counts.data_ptr(), table.data_ptr(),
@@ -533,7 +543,7 @@ def build_plan(adjacency_lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], num
     col = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
     perm = torch.empty(max(E, 1), dtype=torch.int32, device=dev) if want_perm else None
     ws_bytes = lib.ptgnn_amd_csr_workspace_bytes(E, num_nodes)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     control = _plan_control(dev)
     hub_entries = hub_count = None
     if HUB_THRESHOLD > 0 and E > HUB_THRESHOLD:
@@ -605,7 +615,7 @@ def shard_index(adjacency_lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], lo
     need = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
     stats = torch.empty(world + 2 + T, dtype=torch.int64, device=dev)
     ws_bytes = int(lib.ptgnn_amd_shard_index_workspace_bytes(total_nodes))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     PtrArr, CntArr = ctypes.c_void_p * T, ctypes.c_int64 * T
     sp = PtrArr(*[s_.data_ptr() if s_.numel() else None for s_ in srcs])
     dp = PtrArr(*[d_.data_ptr() if d_.numel() else None for d_ in dsts])
@@ -1634,10 +1644,10 @@ def weighted_pool(x: torch.Tensor, w: torch.Tensor, plan: GraphPlan) -> torch.Te
     G = plan.num_nodes
     out = torch.empty(G, d, dtype=torch.float32, device=x.device)
     ws_bytes = int(lib.ptgnn_amd_weighted_pool_workspace_bytes(G, n, d))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     plan.wait()
     with _timed("weighted_pool", bytes=4.0 * (n * d + G * d + d) + 4.0 * n):
-        rc = lib.ptgnn_amd_weighted_pool_f32(x.data_ptr() if n else None, _ld(x) if n else d, w.data_ptr(),
+        rc = lib.ptgnn_amd_weighted_pool_f32(*_rows_arg(x, d), w.data_ptr(),
                                              plan.rowptr.data_ptr(), plan.perm.data_ptr(), G, n, d, out.data_ptr(), d,
                                              ws.data_ptr(), ws_bytes, _stream(out))
     _lib.check(rc, "ptgnn_amd_weighted_pool_f32")
@@ -1658,12 +1668,11 @@ def weighted_pool_backward(x: torch.Tensor, w: torch.Tensor, index: torch.Tensor
     gx = torch.empty(n, d, dtype=torch.float32, device=x.device)
     gw = torch.empty(d, dtype=torch.float32, device=x.device)
     ws_bytes = int(lib.ptgnn_amd_weighted_pool_backward_workspace_bytes(n, d))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     with _timed("weighted_pool_backward", bytes=4.0 * (3 * n * d) + 8.0 * n):
-        rc = lib.ptgnn_amd_weighted_pool_backward_f32(x.data_ptr() if n else None, _ld(x) if n else d, w.data_ptr(),
+        rc = lib.ptgnn_amd_weighted_pool_backward_f32(*_rows_arg(x, d), w.data_ptr(),
                                                       index.data_ptr() if n else None,
-                                                      grad_out.data_ptr() if grad_out.numel() else None,
-                                                      _ld(grad_out) if grad_out.numel() else d, n, d,
+                                                      *_rows_arg(grad_out, d), n, d,
                                                       gx.data_ptr() if n else None, d, gw.data_ptr(), ws.data_ptr(),
                                                       ws_bytes, _stream(gx))
     _lib.check(rc, "ptgnn_amd_weighted_pool_backward_f32")
@@ -1698,10 +1707,10 @@ def attention_pool(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan):
     if G == 0:
         return out, stats
     ws_bytes = int(lib.ptgnn_amd_attention_pool_workspace_bytes(G, n, d, H))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     plan.wait()
     with _timed("attention_pool", bytes=4.0 * (n * d + 2 * G * H * d) + 4.0 * n):
-        rc = lib.ptgnn_amd_attention_pool_f32(x.data_ptr() if n else None, _ld(x) if n else d, u.data_ptr(),
+        rc = lib.ptgnn_amd_attention_pool_f32(*_rows_arg(x, d), u.data_ptr(),
                                               plan.rowptr.data_ptr(), plan.perm.data_ptr() if n else None, G, n, d, H,
                                               out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws_bytes, _stream(out))
     _lib.check(rc, "ptgnn_amd_attention_pool_f32")
@@ -1724,11 +1733,11 @@ def attention_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, p
     if G == 0:
         return gx, gu
     ws_bytes = int(lib.ptgnn_amd_attention_pool_backward_workspace_bytes(G, n, d, H))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     plan.wait()
     with _timed("attention_pool_backward", bytes=4.0 * (2 * n * d + 4 * G * H * d) + 4.0 * n):
         rc = lib.ptgnn_amd_attention_pool_backward_f32(
-            x.data_ptr() if n else None, _ld(x) if n else d, u.data_ptr(), plan.rowptr.data_ptr(),
+            *_rows_arg(x, d), u.data_ptr(), plan.rowptr.data_ptr(),
             plan.perm.data_ptr() if n else None, G, n, d, H, pooled.data_ptr(), stats.data_ptr(), grad_out.data_ptr(),
             gx.data_ptr() if n else None, d, gu.data_ptr(), ws.data_ptr(), ws_bytes, _stream(gu))
     _lib.check(rc, "ptgnn_amd_attention_pool_backward_f32")
@@ -1768,10 +1777,10 @@ def graph_norm(x: torch.Tensor, gamma: torch.Tensor, alpha: torch.Tensor, bias: 
     mean = torch.empty(G, d, dtype=torch.float32, device=x.device) if with_mean else None
     if G > 0:
         ws_bytes = int(lib.ptgnn_amd_graph_norm_workspace_bytes(G, n, d))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        ws = _workspace(ws_bytes, x.device)
         plan.wait()
         with _timed("graph_norm", bytes=4.0 * (4 * n * d) + 3 * 4.0 * n):
-            rc = lib.ptgnn_amd_graph_norm_f32(x.data_ptr() if n else None, _ld(x) if n else d, gamma.data_ptr(),
+            rc = lib.ptgnn_amd_graph_norm_f32(*_rows_arg(x, d), gamma.data_ptr(),
                                               alpha.data_ptr(), bias.data_ptr(), float(eps), plan.rowptr.data_ptr(),
                                               plan.perm.data_ptr() if n else None, G, n, d,
                                               y.data_ptr() if n else None, d,
@@ -1799,11 +1808,11 @@ def graph_norm_backward(x: torch.Tensor, grad_y: torch.Tensor, gamma: torch.Tens
     gx = torch.empty(n, d, dtype=torch.float32, device=x.device)
     gp = torch.empty(3, d, dtype=torch.float32, device=x.device)
     ws_bytes = int(lib.ptgnn_amd_graph_norm_backward_workspace_bytes(G, n, d))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     plan.wait()
     with _timed("graph_norm_backward", bytes=4.0 * (5 * n * d) + 2 * 4.0 * n):
         rc = lib.ptgnn_amd_graph_norm_backward_f32(
-            x.data_ptr() if n else None, _ld(x) if n else d, grad_y.data_ptr() if n else None, _ld(grad_y) if n else d,
+            *_rows_arg(x, d), *_rows_arg(grad_y, d),
             gamma.data_ptr(), alpha.data_ptr(), float(eps), mean.data_ptr() if G else None, plan.rowptr.data_ptr(),
             plan.perm.data_ptr() if n else None, G, n, d, gx.data_ptr() if n else None, d, gp[0].data_ptr(),
             gp[1].data_ptr(), gp[2].data_ptr(), ws.data_ptr(), ws_bytes, _stream(gx))
@@ -1891,7 +1900,7 @@ def block_attention_backward(kqv: torch.Tensor, out: torch.Tensor, lse: torch.Te
     gkqv = torch.empty(n, heads * (2 * dk + dv), dtype=torch.float32, device=kqv.device)
     if n:
         ws_bytes = int(lib.ptgnn_amd_block_attention_backward_workspace_bytes(n, heads))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=kqv.device)
+        ws = _workspace(ws_bytes, kqv.device)
         with _timed("block_attention_backward", bytes=4.0 * n * heads * (4 * dk + 5 * dv + 2)):
             rc = lib.ptgnn_amd_block_attention_backward_f32(
                 kqv.data_ptr(), _ld(kqv), out.data_ptr(), heads * dv, lse.data_ptr(), grad_out.data_ptr(), _ld(grad_out),

@@ -1,6 +1,8 @@
 """The attention reducers on the MI355X: the fused HIP segment-softmax pool (csrc/attention_pool.hip) against the
 reference fixtures, a float64 restatement of the reference's operator order at D in {4, 6, 64, 256, 512} and the
-Graph2Seq shape, determinism, the no-[N, heads * D] guarantee, AMP dtypes and the global exchange around it."""
+Graph2Seq shape, determinism, the no-[N, heads * D] guarantee, AMP dtypes and the global exchange around it -- and, with
+the weighted-sum pool (csrc/weighted_pool.hip), the chunk rule the two pools share (csrc/segment_chunks.h): the 128-row
+chunk boundaries, and a sample pooling to the same bits alone and inside a batch."""
 import copy
 import math
 import types
@@ -104,9 +106,7 @@ def weights(module, dtype):
     return sd["key_layer.weight"], sd.get("value_layer.weight"), sd["output_layer.weight"]
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
-def test_float64_restatement(shape):
-    D, H, value, sizes, scale = shape
+def check_against_float64(D, H, value, sizes, scale):
     module, x, idx, G, gout = make_case(D, H, value, sizes, scale)
     module = module.to(DEV)
     xd, idxd, goutd = x.to(DEV).requires_grad_(True), idx.to(DEV), gout.to(DEV)
@@ -134,7 +134,81 @@ def test_float64_restatement(shape):
     for k, v in got.items():
         exact = res[torch.float64][k]
         assert attributed_ok(v, res[torch.float32][k], exact, TOL, max(1.0, float(exact.detach().abs().max()))), k
-    assert float(y[G - 1].abs().max()) == 0.0 and float(y[sizes.index(0)].abs().max()) == 0.0
+    return y
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
+def test_float64_restatement(shape):
+    y, sizes = check_against_float64(*shape), shape[3]
+    assert float(y[len(sizes)].abs().max()) == 0.0 and float(y[sizes.index(0)].abs().max()) == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the chunk rule of csrc/segment_chunks.h under both pools
+# ---------------------------------------------------------------------------------------------------------------------
+def ref_weighted(x, idx, G, w):
+    """varsizedsummary.py:68-81: sigmoid(Linear(D, 1)) scores, the scaled rows summed per sample; any dtype / device."""
+    score = 1.0 / (1.0 + torch.exp(-(x @ w.t()).squeeze(-1)))
+    return torch.zeros(G, x.shape[1], dtype=x.dtype, device=x.device).index_add(0, idx, x * score.unsqueeze(-1))
+
+
+def check_weighted_against_float64(D, sizes, shuffled):
+    g = torch.Generator().manual_seed(3000 + D * 11 + sum(sizes))
+    G = len(sizes)
+    idx = torch.repeat_interleave(torch.arange(G), torch.tensor(sizes))
+    if shuffled:
+        idx = idx[torch.randperm(idx.shape[0], generator=g)]
+    x, w = torch.randn(idx.shape[0], D, generator=g).to(DEV), (torch.randn(1, D, generator=g) / math.sqrt(D)).to(DEV)
+    gout, idx = torch.randn(G, D, generator=g).to(DEV), idx.to(DEV)
+    plan = ops.plan_for([(idx, idx)], G) if shuffled else ops.plan_from_sorted_index(idx, G)
+    got = {"out": ops.weighted_pool(x, w, plan)}
+    got["x"], got["w"] = ops.weighted_pool_backward(x, w, idx, gout)
+    res = {}
+    for dt in (torch.float32, torch.float64):
+        xr, wr = x.to(dt).clone().requires_grad_(True), w.to(dt).clone().requires_grad_(True)
+        out = ref_weighted(xr, idx, G, wr)
+        out.backward(gout.to(dt))
+        res[dt] = {"out": out.detach(), "x": xr.grad, "w": wr.grad.reshape(-1)}
+    for k, v in got.items():
+        exact = res[torch.float64][k]
+        print(f"weighted pool D={D} n={sum(sizes)} {k}: |got-fp32|={float((v - res[torch.float32][k]).abs().max()):.3e} "
+              f"|got-f64|={float((v.double() - exact).abs().max()):.3e} scale={float(exact.abs().max()):.3e}")
+        assert attributed_ok(v, res[torch.float32][k], exact, TOL, max(1.0, float(exact.abs().max()))), k
+
+
+@pytest.mark.parametrize("rows", [127, 128, 129, 255, 256, 257])
+def test_chunk_boundaries(rows):
+    check_weighted_against_float64(64, [rows], shuffled=False)
+    check_weighted_against_float64(6, [rows, 5], shuffled=True)      # a second sample, so that the shuffle moves rows
+    check_against_float64(64, 4, False, [rows], 1.0)
+    check_against_float64(6, 3, False, [rows], 1.0)
+
+
+@pytest.mark.parametrize("D", [64, 100])
+def test_a_sample_pools_to_the_same_bits_alone_and_inside_a_batch(D):
+    """Chunks are counted from a sample's own start, so its pool and its gradients do not depend on the samples around
+    it.  (Not the weighted pool's weight gradient: that folds 256-row blocks of the whole batch.)"""
+    sizes, H = [200, 57, 300, 40], 4
+    g = torch.Generator().manual_seed(4000 + D)
+    idx = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes)).to(DEV)
+    x, w = torch.randn(idx.shape[0], D, generator=g).to(DEV), (torch.randn(1, D, generator=g) / math.sqrt(D)).to(DEV)
+    u = (torch.randn(len(sizes), H, D, generator=g) / math.sqrt(D)).to(DEV)
+    gout, gpool = torch.randn(len(sizes), D, generator=g).to(DEV), torch.randn(len(sizes), H, D, generator=g).to(DEV)
+    rows = torch.nonzero(idx == 2).flatten()
+    x1, idx1 = x[rows].contiguous(), torch.zeros(rows.shape[0], dtype=torch.int64, device=DEV)
+    plan, plan1 = ops.plan_from_sorted_index(idx, len(sizes)), ops.plan_from_sorted_index(idx1, 1)
+
+    assert torch.equal(ops.weighted_pool(x, w, plan)[2], ops.weighted_pool(x1, w, plan1)[0])
+    gx, _ = ops.weighted_pool_backward(x, w, idx, gout)
+    gx1, _ = ops.weighted_pool_backward(x1, w, idx1, gout[2:3].contiguous())
+    assert torch.equal(gx[rows], gx1)
+
+    pooled, stats = ops.attention_pool(x, u, plan)
+    pooled1, stats1 = ops.attention_pool(x1, u[2:3].contiguous(), plan1)
+    assert torch.equal(pooled[2], pooled1[0]) and torch.equal(stats[2], stats1[0])
+    gx, gu = ops.attention_pool_backward(x, u, plan, pooled, stats, gpool)
+    gx1, gu1 = ops.attention_pool_backward(x1, u[2:3].contiguous(), plan1, pooled1, stats1, gpool[2:3].contiguous())
+    assert torch.equal(gx[rows], gx1) and torch.equal(gu[2], gu1[0])
 
 
 def test_two_runs_give_the_same_bits():
