@@ -137,6 +137,8 @@ enum {
   PTGNN_AMD_KERNEL_GRAPH_NORM_BACKWARD,     /* ptgnn_amd_graph_norm_backward_f32 */
   PTGNN_AMD_KERNEL_BLOCK_ATTENTION,          /* ptgnn_amd_block_attention_f32 */
   PTGNN_AMD_KERNEL_BLOCK_ATTENTION_BACKWARD, /* ptgnn_amd_block_attention_backward_f32 */
+  PTGNN_AMD_KERNEL_SEGMENT_SCORES,           /* ptgnn_amd_segment_scores_f32 */
+  PTGNN_AMD_KERNEL_SEGMENT_SCORES_BACKWARD,  /* ptgnn_amd_segment_scores_backward_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -672,6 +674,43 @@ int ptgnn_amd_head_projection_f32(int mode, const float *a /* nullable in mode 1
                                   const float *b /* nullable in mode 0 */, const float *w /* nullable in mode 2 */,
                                   int64_t num_rows, int32_t num_heads, int32_t head_dim, int32_t dim, float scale,
                                   float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Scores of elements against the `vectors` of their sample, and their per-sample log-sum-exp:
+ *   scores[i,l] = v[g,l,:] . y[i,:]  (g = map[i]),   lse[g,l] = log sum_{i : map[i] == g} exp(scores[i,l])
+ * Replaces: the copy attention of GruCopyingDecoder._compute_logprobs, ptgnn/neuralmodels/sequence/grucopydecoder.py:
+ *   the gather `output_states[input_memories_origin_idx]` that materialises [num_inputs, L, H] (:89-91), the einsum
+ *   "ilh,ih->il" (:95-97) and `scatter_logsumexp(copy_attention_scores, ..., eps=0)` (:122-124).  With dropout active the
+ *   rows y are dropout(memories_to_copy_attention(input_memories)) (:83-86) and v the GRU's output states; without it
+ *   the Linear moves onto the samples (v = W_c^T o) and y are the memories themselves.  One pass over y: running
+ *   (max, sum) per 128-row chunk counted from the sample's own start, chunks merged in chunk order (no float atomics;
+ *   a sample's lse has the same bits alone and inside a batch).
+ *   y [num_elements, dim] (ld_y), v [num_segments, vectors, dim] contiguous, rowptr / perm: the stable plan of the map
+ *   (as ptgnn_amd_weighted_pool_f32), scores [num_elements, vectors] contiguous in ELEMENT order, lse [num_segments,
+ *   vectors] (-inf for a sample without elements).
+ *   1 <= vectors <= 8 and dim <= 1024 (ptgnn_amd_segment_scores_supported), else EUNSUPPORTED.
+ *   workspace: ptgnn_amd_segment_scores_workspace_bytes.
+ * Backward (one pass over y; replaces the autograd of :89-97,122-124): from grad_scores [num_elements, vectors],
+ *   grad_lse [num_segments, vectors] and the forward's scores and lse,
+ *   t[i,l] = grad_scores[i,l] + grad_lse[g,l] exp(scores[i,l] - lse[g,l]),
+ *   grad_y[i,:] = sum_l t[i,l] v[g,l,:] (ld_gy; every element of the plan OVERWRITTEN) and
+ *   grad_v[g,l,:] = sum_{i in g} t[i,l] y[i,:] (deterministic: chunk partials folded in chunk order; 0 for a sample
+ *   without elements).  workspace: ptgnn_amd_segment_scores_backward_workspace_bytes.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_segment_scores_supported(int32_t dim, int32_t num_vectors);
+size_t ptgnn_amd_segment_scores_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim,
+                                                int32_t num_vectors);
+int ptgnn_amd_segment_scores_f32(const float *y, int64_t ld_y, const float *v, const int32_t *rowptr,
+                                 const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                 int32_t num_vectors, float *scores, float *lse, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t ptgnn_amd_segment_scores_backward_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim,
+                                                         int32_t num_vectors);
+int ptgnn_amd_segment_scores_backward_f32(const float *y, int64_t ld_y, const float *v, const int32_t *rowptr,
+                                          const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                          int32_t num_vectors, const float *scores, const float *lse,
+                                          const float *grad_scores, const float *grad_lse, float *grad_y, int64_t ld_gy,
+                                          float *grad_v, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * GraphNorm: per-graph normalisation of node states, per graph g with n_g nodes, per column, fp32:

@@ -7,3 +7,12 @@ gather/segment-reduce kernel, fp32-MFMA dense blocks, and `nn.Module`s that mirr
 from ptgnn_amd._lib import PtgnnAmdError  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # `from ptgnn_amd import GruCopyingDecoder`: resolved on first use, so that importing the package stays as light as
+    # it was (the layer modules are imported by their own names everywhere else)
+    if name == "GruCopyingDecoder":
+        from ptgnn_amd.sequence import GruCopyingDecoder
+        return GruCopyingDecoder
+    raise AttributeError(f"module 'ptgnn_amd' has no attribute {name!r}")

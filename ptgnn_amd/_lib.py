@@ -115,6 +115,13 @@ SIGNATURES = {
     "ptgnn_amd_attention_pool_backward_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp,
                                                          _vp, _vp, _i64, _vp, _vp, _c.c_size_t, _vp]),
     "ptgnn_amd_head_projection_f32": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "ptgnn_amd_segment_scores_supported": (_c.c_int, [_i32, _i32]),
+    "ptgnn_amd_segment_scores_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32, _i32]),
+    "ptgnn_amd_segment_scores_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp,
+                                                _c.c_size_t, _vp]),
+    "ptgnn_amd_segment_scores_backward_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32, _i32]),
+    "ptgnn_amd_segment_scores_backward_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp,
+                                                         _vp, _vp, _vp, _i64, _vp, _vp, _c.c_size_t, _vp]),
     "ptgnn_amd_graph_norm_supported": (_c.c_int, [_i32]),
     "ptgnn_amd_graph_norm_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32]),
     "ptgnn_amd_graph_norm_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp,

@@ -37,15 +37,11 @@
 // PTGNN_AMD_EUNSUPPORTED and the host composes the reference's operator sequence from the other HIP entry points.
 #include <math.h>
 
+#include "attention_tile.h"
 #include "segment_chunks.h"
 
 namespace ptgnn_amd {
 namespace {
-
-constexpr int kAttnThreads = 256;
-constexpr int kAttnMaxHeads = 8;
-constexpr int kAttnMaxDim = 1024;
-constexpr size_t kAttnMaxLds = 160 * 1024;     // LDS of one CU (gfx950)
 
 struct AttnLayout {
   int R, S, HP, cols;   // tile rows, LDS row stride, heads padded to a float4, columns per thread of the column walk
@@ -66,89 +62,6 @@ AttnLayout attn_layout(int dim, int heads, bool backward) {
     if (L.bytes <= 64 * 1024 || L.R == 16) break;
   }
   return L;
-}
-
-// [dim][HP] image of the segment's [heads][dim] rows (padded heads 0)
-template <int HP>
-__device__ __forceinline__ void attn_stage_heads(float *__restrict__ dst, const float *__restrict__ src, int dim,
-                                                 int heads) {
-  for (int e = threadIdx.x; e < dim * HP; e += kAttnThreads) {
-    const int d = e / HP, h = e % HP;
-    dst[e] = h < heads ? src[(int64_t)h * dim + d] : 0.0f;
-  }
-}
-
-// the tile's rows x[perm[t0 + r], :] -> xs[r * S + :]
-__device__ __forceinline__ void attn_stage_rows(float *__restrict__ xs, int S, const float *__restrict__ x, int64_t ld_x,
-                                                const int32_t *__restrict__ perm, int t0, int rows, int dim, bool vec4) {
-  if (vec4) {
-    // batches of kStageBatch loads in flight per thread before their LDS stores: one memory round trip per batch
-    // (a tile of 32 rows x 256 columns is 8 float4 per thread)
-    constexpr int kStageBatch = 8;
-    const int d4 = dim >> 2, total = rows * d4;
-    for (int base = threadIdx.x; base < total; base += kStageBatch * kAttnThreads) {
-      float4 v[kStageBatch];
-#pragma unroll
-      for (int k = 0; k < kStageBatch; ++k) {
-        const int e = base + k * kAttnThreads;
-        if (e < total) {
-          const int r = e / d4, c = (e - r * d4) << 2;
-          v[k] = *reinterpret_cast<const float4 *>(x + (int64_t)perm[t0 + r] * ld_x + c);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kStageBatch; ++k) {
-        const int e = base + k * kAttnThreads;
-        if (e < total) {
-          const int r = e / d4, c = (e - r * d4) << 2;
-          float *o = xs + r * S + c;
-          o[0] = v[k].x; o[1] = v[k].y; o[2] = v[k].z; o[3] = v[k].w;
-        }
-      }
-    }
-  } else {
-    for (int e = threadIdx.x; e < rows * dim; e += kAttnThreads) {
-      const int r = e / dim, c = e - r * dim;
-      xs[r * S + c] = x[(int64_t)perm[t0 + r] * ld_x + c];
-    }
-  }
-}
-
-// s[h] += x_r[d] m[d][h] over the column slice [d0, d1) (and a[h] with m2 when TWO)
-template <int HP, bool TWO>
-__device__ __forceinline__ void attn_score_walk(const float *__restrict__ xr, const float *__restrict__ m,
-                                                const float *__restrict__ m2, int d0, int d1, float (&s)[HP],
-                                                float (&a)[HP]) {
-  for (int d = d0; d < d1; ++d) {
-    const float xv = xr[d];
-#pragma unroll
-    for (int q = 0; q < HP / 4; ++q) {
-      const float4 w = *reinterpret_cast<const float4 *>(m + d * HP + 4 * q);
-      s[4 * q + 0] = fmaf(xv, w.x, s[4 * q + 0]);
-      s[4 * q + 1] = fmaf(xv, w.y, s[4 * q + 1]);
-      s[4 * q + 2] = fmaf(xv, w.z, s[4 * q + 2]);
-      s[4 * q + 3] = fmaf(xv, w.w, s[4 * q + 3]);
-      if constexpr (TWO) {
-        const float4 v = *reinterpret_cast<const float4 *>(m2 + d * HP + 4 * q);
-        a[4 * q + 0] = fmaf(xv, v.x, a[4 * q + 0]);
-        a[4 * q + 1] = fmaf(xv, v.y, a[4 * q + 1]);
-        a[4 * q + 2] = fmaf(xv, v.z, a[4 * q + 2]);
-        a[4 * q + 3] = fmaf(xv, v.w, a[4 * q + 3]);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float half_wave_max(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 32));
-  return v;
-}
-
-__device__ __forceinline__ float half_wave_sum(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-  return v;
 }
 
 // LDS (floats): xs [R][S] | ut [dim][HP] | part [256][HP] | pt [R][HP] | alpha [8]
@@ -482,10 +395,7 @@ __global__ __launch_bounds__(256) void k_head_weight_grad(const float *__restric
 
 template <typename Kern, typename... Args>
 int attn_launch(Kern kern, const AttnLayout &L, unsigned grid, hipStream_t st, Args... args) {
-  PTGNN_REQUIRE(L.bytes <= 64 * 1024 || raise_dynamic_lds(kern, L.bytes), PTGNN_AMD_EHIP, "attention_pool: %zu bytes of LDS refused", L.bytes);
-  kern<<<grid, kAttnThreads, L.bytes, st>>>(args...);
-  PTGNN_LAUNCH_CHECK();
-  return PTGNN_AMD_OK;
+  return tile_launch("attention_pool", kern, L.bytes, grid, st, args...);
 }
 
 // instantiate KERNEL<HP, COLS> for the layout and launch it

@@ -65,7 +65,8 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
   static const char *const agg_names[PTGNN_AMD_KERNEL_AGG_END_ - PTGNN_AMD_KERNEL_AGG_FIRST_] = {
       "k_gather_reduce", "egc_gather_combine", "egc_combine", "egc_combine_backward", "pna_aggregate",
       "pna_aggregate_backward", "attention_pool", "attention_pool_backward", "head_projection", "graph_norm",
-      "graph_norm_backward", "block_attention", "block_attention_backward"};
+      "graph_norm_backward", "block_attention", "block_attention_backward", "segment_scores",
+      "segment_scores_backward"};
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
     return agg_names[kernel_id - PTGNN_AMD_KERNEL_AGG_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;

@@ -1,5 +1,5 @@
-// The chunk walk of a node -> graph plan, shared by weighted_pool.hip, attention_pool.hip, graph_norm.hip and (the
-// workgroup scan only) block_attention.hip.
+// The chunk walk of a node -> graph plan, shared by weighted_pool.hip, attention_pool.hip, graph_norm.hip, segment_scores.hip
+// and (the workgroup scan only) block_attention.hip.
 //
 // Segments are graphs: few and long.  Every segment of a plan is cut into CHUNKS OF kChunkRows ROWS COUNTED FROM THE
 // SEGMENT'S OWN START; workgroup b works on one chunk, and a later launch adds the chunk partials of a segment IN CHUNK

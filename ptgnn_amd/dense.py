@@ -166,28 +166,37 @@ class _GruCell(torch.autograd.Function):
         return d_a, d_hx, d_wih, d_whh, d_bih, d_bhh
 
 
-def gru_cell(cell: torch.nn.GRUCell, a: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
-    """nn.GRUCell on the HIP kernels: the fused inference cell when nothing needs a gradient, else `_GruCell`."""
-    if not (_kernel_dims_ok(a, cell.weight_ih) and _kernel_dims_ok(h, cell.weight_hh)):
+def gru_cell_weights(a: torch.Tensor, h: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+                     b_ih: Optional[torch.Tensor] = None, b_hh: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One GRU step on the HIP kernels from the weights themselves (nn.GRUCell's weight_ih / ..., or one layer of an
+    nn.GRU: weight_ih_l0 / ...): the fused inference cell when nothing needs a gradient, else `_GruCell`."""
+    if not (_kernel_dims_ok(a, w_ih) and _kernel_dims_ok(h, w_hh)):
         raise _lib.PtgnnAmdError(f"dense.gru_cell needs 2-D float32 CUDA matrices (got {a.dtype} / {h.dtype} on "
                                  f"{a.device}); AMP dtypes are up-cast by the layers")
-    params = [cell.weight_ih, cell.weight_hh] + ([cell.bias_ih, cell.bias_hh] if cell.bias else [])
+    bias = b_ih is not None and b_hh is not None
+    params = [w_ih, w_hh] + ([b_ih, b_hh] if bias else [])
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [a, h] + params)
-    if cell.bias and not needs_grad:
-        return ops.gru_cell(a, h, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
-    if cell.bias and h.shape[1] % 4 == 0 and a.shape[1] % 4 == 0:
-        return _GruCell.apply(a, h, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
+    if bias and not needs_grad:
+        return ops.gru_cell(a, h, w_ih, w_hh, b_ih, b_hh)
+    if bias and h.shape[1] % 4 == 0 and a.shape[1] % 4 == 0:
+        return _GruCell.apply(a, h, w_ih, w_hh, b_ih, b_hh)
     # Shapes the fused cell does not tile (nn.GRUCell(bias=False); training with a state / message width that is
     # not a multiple of 4): the reference accepts them (gatedmessagepassing.py:25), so they run as the two gate
     # GEMMs on the differentiable HIP Linear (any width) + torch's elementwise gate math -- same arithmetic, on
     # the GPU, no vendor BLAS.
     hd = h.shape[1]
-    gi = linear(a, cell.weight_ih, cell.bias_ih if cell.bias else None)
-    gh = linear(h, cell.weight_hh, cell.bias_hh if cell.bias else None)
+    gi = linear(a, w_ih, b_ih if bias else None)
+    gh = linear(h, w_hh, b_hh if bias else None)
     r = torch.sigmoid(gi[:, :hd] + gh[:, :hd])
     z = torch.sigmoid(gi[:, hd:2 * hd] + gh[:, hd:2 * hd])
     n = torch.tanh(gi[:, 2 * hd:] + r * gh[:, 2 * hd:])
     return (1.0 - z) * n + z * h
+
+
+def gru_cell(cell: torch.nn.GRUCell, a: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    """nn.GRUCell on the HIP kernels (`gru_cell_weights` on the cell's tensors)."""
+    return gru_cell_weights(a, h, cell.weight_ih, cell.weight_hh, cell.bias_ih if cell.bias else None,
+                            cell.bias_hh if cell.bias else None)
 
 
 class _RowEpilogue(torch.autograd.Function):

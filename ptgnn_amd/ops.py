@@ -45,7 +45,7 @@ def launch_counts(aggregation: bool = False) -> dict:
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
     attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward, block_attention,
-    block_attention_backward)."""
+    block_attention_backward, segment_scores, segment_scores_backward)."""
     lib = _lib.load()
     out = {}
     for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
@@ -1742,6 +1742,75 @@ def attention_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, p
             gx.data_ptr() if n else None, d, gu.data_ptr(), ws.data_ptr(), ws_bytes, _stream(gu))
     _lib.check(rc, "ptgnn_amd_attention_pool_backward_f32")
     return gx, gu
+
+
+def segment_scores_supported(dim: int, num_vectors: int) -> bool:
+    """Whether the fused segment scores take (dim, vectors) (ptgnn_amd_segment_scores_supported: vectors <= 8,
+    dim <= 1024)."""
+    return bool(_lib.load().ptgnn_amd_segment_scores_supported(int(dim), int(num_vectors)))
+
+
+def _segment_scores_args(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, what: str):
+    _require_cuda_f32("y", y)
+    _require_cuda_f32("v", v, dims=3)
+    y = _rowmajor(y)
+    n, k = y.shape
+    G, L = plan.num_nodes, v.shape[1]
+    if n != plan.num_edges or tuple(v.shape) != (G, L, k) or plan.perm is None:
+        raise _lib.PtgnnAmdError(f"{what}: y {tuple(y.shape)}, v {tuple(v.shape)} do not fit a plan of "
+                                 f"{plan.num_edges} elements in {G} samples")
+    return y, v.contiguous(), n, k, G, L
+
+
+def segment_scores(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan):
+    """Scores of every element against the vectors of its sample over the plan of an element -> sample map, and their
+    per-sample log-sum-exp (ptgnn_amd_segment_scores_f32):
+        scores[i,l] = v[g(i),l] . y_i,   lse[g,l] = log sum_{i in g} exp(scores[i,l])   (-inf for an empty sample)
+    in one pass over y.  Returns (scores [n, L] in element order, lse [G, L])."""
+    lib = _lib.load()
+    y, v, n, k, G, L = _segment_scores_args(y, v, plan, "segment_scores")
+    scores = torch.empty(n, L, dtype=torch.float32, device=y.device)
+    lse = torch.empty(G, L, dtype=torch.float32, device=y.device)
+    ws_bytes = int(lib.ptgnn_amd_segment_scores_workspace_bytes(G, n, k, L))
+    ws = _workspace(ws_bytes, y.device)
+    plan.wait()
+    with _timed("segment_scores", bytes=4.0 * (n * k + n * L + G * L * (k + 1)) + 4.0 * n):
+        rc = lib.ptgnn_amd_segment_scores_f32(*_rows_arg(y, k), v.data_ptr() if G else None, plan.rowptr.data_ptr(),
+                                              plan.perm.data_ptr() if n else None, G, n, k, L,
+                                              scores.data_ptr() if n else None, lse.data_ptr() if G else None,
+                                              ws.data_ptr(), ws_bytes, _stream(lse))
+    _lib.check(rc, "ptgnn_amd_segment_scores_f32")
+    return scores, lse
+
+
+def segment_scores_backward(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, scores: torch.Tensor, lse: torch.Tensor,
+                            grad_scores: torch.Tensor, grad_lse: torch.Tensor):
+    """(grad_y [n, K], grad_v [G, L, K]) of `segment_scores` from grad_scores [n, L], grad_lse [G, L] and the forward's
+    scores and lse (ptgnn_amd_segment_scores_backward_f32: one pass over y, grad_v folded in a fixed order)."""
+    lib = _lib.load()
+    y, v, n, k, G, L = _segment_scores_args(y, v, plan, "segment_scores_backward")
+    _require_cuda_f32("grad_scores", grad_scores)
+    _require_cuda_f32("grad_lse", grad_lse)
+    scores, lse, grad_scores, grad_lse = (t.contiguous() for t in (scores, lse, grad_scores, grad_lse))
+    if tuple(scores.shape) != (n, L) or tuple(grad_scores.shape) != (n, L) or tuple(lse.shape) != (G, L) \
+            or tuple(grad_lse.shape) != (G, L):
+        raise _lib.PtgnnAmdError(f"segment_scores_backward: scores {tuple(scores.shape)} / grad_scores "
+                                 f"{tuple(grad_scores.shape)} / lse {tuple(lse.shape)} / grad_lse "
+                                 f"{tuple(grad_lse.shape)} do not match ({n}, {L}) and ({G}, {L})")
+    gy = torch.empty(n, k, dtype=torch.float32, device=y.device)
+    gv = torch.empty(G, L, k, dtype=torch.float32, device=y.device)
+    ws_bytes = int(lib.ptgnn_amd_segment_scores_backward_workspace_bytes(G, n, k, L))
+    ws = _workspace(ws_bytes, y.device)
+    plan.wait()
+    with _timed("segment_scores_backward", bytes=4.0 * (2 * n * k + 2 * n * L + 2 * G * L * (k + 1)) + 4.0 * n):
+        rc = lib.ptgnn_amd_segment_scores_backward_f32(
+            *_rows_arg(y, k), v.data_ptr() if G else None, plan.rowptr.data_ptr(),
+            plan.perm.data_ptr() if n else None, G, n, k, L, scores.data_ptr() if n else None,
+            lse.data_ptr() if G else None, grad_scores.data_ptr() if n else None,
+            grad_lse.data_ptr() if G else None, gy.data_ptr() if n else None, k, gv.data_ptr() if G else None,
+            ws.data_ptr(), ws_bytes, _stream(gv))
+    _lib.check(rc, "ptgnn_amd_segment_scores_backward_f32")
+    return gy, gv
 
 
 def graph_norm_supported(dim: int) -> bool:

@@ -168,6 +168,32 @@ def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int
     return _BlockAttention.apply(kqv, windows, int(max_num_nodes), int(heads), int(dk), int(dv), float(p), int(seed))
 
 
+class _SegmentScores(torch.autograd.Function):
+    """scores[i,l] = v[g(i),l] . y_i and lse[g,l] = log sum_{i in g} exp(scores[i,l]) over the plan of the element ->
+    sample map as ONE node (the copy attention of grucopydecoder.py:89-97,122-124): forward and backward are the two
+    passes of csrc/segment_scores.hip (no [n, L, K] gather of the vectors, deterministic grad_v)."""
+
+    @staticmethod
+    def forward(ctx, y, v, plan):
+        scores, lse = ops.segment_scores(y, v, plan)
+        ctx.plan = plan
+        ctx.save_for_backward(y, v, scores, lse)
+        return scores, lse
+
+    @staticmethod
+    def backward(ctx, grad_scores, grad_lse):
+        y, v, scores, lse = ctx.saved_tensors
+        grad_scores = torch.zeros_like(scores) if grad_scores is None else grad_scores.contiguous()
+        grad_lse = torch.zeros_like(lse) if grad_lse is None else grad_lse.contiguous()
+        gy, gv = ops.segment_scores_backward(y, v, ctx.plan, scores, lse, grad_scores, grad_lse)
+        return gy, gv, None
+
+
+def segment_scores(y: torch.Tensor, v: torch.Tensor, plan: "ops.GraphPlan"):
+    """Differentiable (scores [n, L], lse [G, L]) of fp32 rows y [n, K] against the vectors v [G, L, K] of their sample."""
+    return _SegmentScores.apply(y, v, plan)
+
+
 def _prepare(src: torch.Tensor, index: torch.Tensor, dim: int, out, dim_size):
     """Common argument handling of the torch_scatter-shaped entry points: 2-D (or 1-D) `src`, 1-D int64
     `index` along dim 0.  Anything else raises (no silent fallback)."""

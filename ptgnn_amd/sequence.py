@@ -1,0 +1,222 @@
+"""The copying decoder of the Graph2Seq task: mirror of ptgnn/neuralmodels/sequence/grucopydecoder.py:29-212
+(`GruCopyingDecoder`: same class name, constructor keywords, submodule / parameter creation order and name-mangled
+parameter names, so a reference state_dict loads strictly and the same seed gives the same initial values).
+`GruCopyingDecoderModel` -- vocabulary, tensorisation and the Python greedy-decode loop -- works unchanged around it.
+
+GPU route (L = decoding steps <= 8, memory and state widths <= 1024), with x the memories [I, Dm], g their sample, o the
+GRU's output states [B, L, H]:
+  * token embeddings by the HIP row gather (backward: the deterministic segment sum over a plan of the token ids), the GRU
+    as L calls of the fused cell -- no vendor RNN;
+  * standard attention: the memory Linear commutes with the pool, so u = W_s^T o on the samples, the fused attention pool
+    with heads := L (csrc/attention_pool.hip), A = W_s P on the samples -- no [I, H] projection, no [I, L, H] product;
+  * copy attention: scores and their per-sample log-sum-exp in one pass (csrc/segment_scores.hip).  Dropout sits between
+    the copy Linear and the dot product (grucopydecoder.py:83-97), so while it is active the rows are dropout(W_c x) and
+    the vectors o; otherwise W_c moves onto the samples too and the rows are x itself (greedy decoding: L = 1 per step);
+  * the vocabulary product as two HIP Linears, the joint normaliser and the loss arithmetic as torch glue on [B, L, V]
+    and [I, L] tensors.
+Shapes beyond that range compose the reference's operator sequence from the HIP Linear, the fused cell, the row gather
+and the facade's segment kernels.  CPU tensors take the reference's own operator order on torch (device dispatch as in
+every layer of the package); fp16 / bf16 inputs are up-cast on entry and the results cast back.
+"""
+import math
+
+import torch
+from torch import nn
+
+from ptgnn_amd import _lib, dense, ops, scatter as scatter_facade
+from ptgnn_amd.layers import _index_plan, _no_grad_needed
+from ptgnn_amd.reduceops import _AttentionPool
+from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_scores
+
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _rows(table: torch.Tensor, index: torch.Tensor, plan=None) -> torch.Tensor:
+    """table[index] on the HIP row gather; with autograd when something needs a gradient (`plan`: the plan of `index`
+    over the table's rows, built here when not given)."""
+    table = table.contiguous()
+    if _no_grad_needed(table):
+        return ops.gather_rows(table, index)
+    if plan is None:
+        plan = ops.plan_for([(index, index)], table.shape[0])
+    return gather_rows_autograd(table, index, plan)
+
+
+class GruCopyingDecoder(nn.Module):
+    def __init__(self, vocabulary_size: int, embedding_size: int, hidden_size: int, memories_hidden_dim: int,
+                 unk_id: int, dropout_rate: float):
+        super().__init__()
+        self.__embedding_layer = nn.Embedding(num_embeddings=vocabulary_size, embedding_dim=embedding_size)
+        self.__output_gru = nn.GRU(input_size=embedding_size, hidden_size=hidden_size, num_layers=1, batch_first=True)
+        self.__unk_id = unk_id
+        self.__memories_to_standard_attention = nn.Linear(in_features=memories_hidden_dim, out_features=hidden_size,
+                                                          bias=False)
+        self.__memories_to_copy_attention = nn.Linear(in_features=memories_hidden_dim, out_features=hidden_size,
+                                                      bias=False)
+        self.__hidden_to_vocab = nn.Parameter(0.01 * torch.randn((2 * hidden_size, embedding_size)))
+        self.__vocab_bias = nn.Parameter(torch.zeros(vocabulary_size))
+        self.__dropout = nn.Dropout(dropout_rate)
+
+    # --------------------------------------------------------------------------------------------------------------
+    # CPU tensors: grucopydecoder.py:70-142 in the reference's operator order
+    # --------------------------------------------------------------------------------------------------------------
+    def __host_logprobs(self, initial_states, input_memories, input_memories_origin_idx, input_token_ids):
+        num_samples = initial_states.shape[0]
+        target_token_embeddings = self.__dropout(self.__embedding_layer(input_token_ids))
+        output_states, output_gru_state = self.__output_gru(target_token_embeddings, initial_states.unsqueeze(0))
+        output_states = output_states.contiguous()                                         # [B, L, H]
+        standard_attention_reps = self.__memories_to_standard_attention(input_memories)    # [I, H]
+        copy_attention_reps = self.__dropout(self.__memories_to_copy_attention(input_memories))
+        output_states_per_input = output_states[input_memories_origin_idx]                 # [I, L, H]
+        standard_attention_scores = torch.einsum("ilh,ih->il", output_states_per_input, standard_attention_reps)
+        copy_attention_scores = torch.einsum("ilh,ih->il", output_states_per_input, copy_attention_reps)
+        standard_attention_logprobs = scatter_facade.scatter_log_softmax(
+            standard_attention_scores, index=input_memories_origin_idx, dim=0, eps=0, dim_size=num_samples)
+        standard_attention_mul = torch.einsum("il,ih->ilh", torch.exp(standard_attention_logprobs),
+                                              standard_attention_reps)
+        standard_attention_out = scatter_facade.scatter_add(standard_attention_mul, index=input_memories_origin_idx,
+                                                            dim=0, dim_size=num_samples)  # [B, L, H]
+        target_scores = torch.einsum(
+            "blh,hd,vd->blv", torch.cat((self.__dropout(standard_attention_out), output_states), dim=-1),
+            self.__hidden_to_vocab, self.__dropout(self.__embedding_layer.weight)) + self.__vocab_bias
+        total_copy_scores = scatter_facade.scatter_logsumexp(copy_attention_scores, index=input_memories_origin_idx,
+                                                             dim=0, dim_size=num_samples, eps=0)   # [B, L]
+        all_scores = torch.cat((target_scores, total_copy_scores.unsqueeze(-1)), dim=-1)
+        normalizing_const = torch.logsumexp(all_scores, dim=-1)                            # [B, L]
+        target_logprobs = target_scores - normalizing_const.unsqueeze(-1)
+        copy_logprobs = copy_attention_scores - normalizing_const[input_memories_origin_idx]
+        return copy_logprobs, target_logprobs, output_gru_state
+
+    # --------------------------------------------------------------------------------------------------------------
+    # GPU tensors
+    # --------------------------------------------------------------------------------------------------------------
+    def __gru_states(self, initial_states, input_token_ids):
+        """[B, L, H] output states of the GRU over the embedded tokens: the HIP row gather, then L fused cells."""
+        gru = self.__output_gru
+        B, L = input_token_ids.shape
+        step_major = input_token_ids.t().contiguous().reshape(-1)                          # row l * B + b
+        embedded = self.__dropout(_rows(self.__embedding_layer.weight, step_major))       # [L * B, E]
+        h, states = initial_states.contiguous(), []
+        for step in range(L):
+            h = dense.gru_cell_weights(embedded[step * B:(step + 1) * B], h, gru.weight_ih_l0, gru.weight_hh_l0,
+                                       gru.bias_ih_l0, gru.bias_hh_l0)
+            states.append(h)
+        return torch.stack(states, dim=1), h
+
+    def __vocabulary_scores(self, attention_out, output_states):
+        """grucopydecoder.py:111-119 on [B * L, .] matrices: two HIP Linears and the bias."""
+        hidden = torch.cat((self.__dropout(attention_out), output_states), dim=-1)         # [B * L, 2 H]
+        projected = dense.linear(hidden, self.__hidden_to_vocab.t())                       # [B * L, E]
+        return dense.linear(projected, self.__dropout(self.__embedding_layer.weight)) + self.__vocab_bias
+
+    def __composed_attention(self, x, index, plan, output_states):
+        """L > 8 or a width > 1024: the reference's operator sequence (grucopydecoder.py:79-124) on the HIP Linear, the
+        row gather and the facade's segment kernels."""
+        B, L, H = output_states.shape
+        standard_reps = dense.linear(x, self.__memories_to_standard_attention.weight)      # [I, H]
+        copy_reps = self.__dropout(dense.linear(x, self.__memories_to_copy_attention.weight))
+        states_per_input = _rows(output_states.reshape(B, L * H), index, plan).reshape(-1, L, H)
+        standard_scores = (states_per_input * standard_reps.unsqueeze(1)).sum(-1)          # [I, L]
+        copy_scores = (states_per_input * copy_reps.unsqueeze(1)).sum(-1)
+        probs = scatter_facade.scatter_log_softmax(standard_scores, index, dim=0, eps=0.0, dim_size=B).exp()
+        attention_out = scatter_facade.scatter_add(probs.unsqueeze(-1) * standard_reps.unsqueeze(1), index, dim=0,
+                                                   dim_size=B)                            # [B, L, H]
+        total_copy = scatter_facade.scatter_logsumexp(copy_scores, index, dim=0, dim_size=B, eps=0.0)
+        return attention_out.reshape(B * L, H), copy_scores, total_copy
+
+    def __device_logprobs(self, initial_states, x, index, input_token_ids):
+        if index.dtype != torch.int64 or not index.is_cuda or index.dim() != 1 or index.shape[0] != x.shape[0]:
+            raise _lib.PtgnnAmdError("GruCopyingDecoder: input_memories_origin_idx must be a CUDA int64 tensor with one "
+                                     "entry per memory")
+        w_s, w_c = self.__memories_to_standard_attention.weight, self.__memories_to_copy_attention.weight
+        H, Dm = w_s.shape
+        B, L = input_token_ids.shape
+        output_states, last_state = self.__gru_states(initial_states, input_token_ids)     # [B, L, H]
+        states = output_states.reshape(B * L, H)
+        x = x.contiguous()
+        plan = _index_plan(index, B)
+        drop = self.training and self.__dropout.p > 0.0
+        if not (ops.attention_pool_supported(Dm, L) and ops.segment_scores_supported(H if drop else Dm, L)):
+            attention_out, copy_scores, total_copy = self.__composed_attention(x, index, plan, output_states)
+        else:
+            queries = dense.linear(states, w_s.t()).reshape(B, L, Dm)                      # u_s = W_s^T o
+            pooled = _AttentionPool.apply(x, queries, plan)                                # [B, L, Dm]
+            attention_out = dense.linear(pooled.reshape(B * L, Dm), w_s)                   # A = W_s P
+            if drop:
+                rows = dense.linear_act_dropout(x, w_c, None, None, self.__dropout.p, True)
+                if rows is None:
+                    rows = self.__dropout(dense.linear(x, w_c))
+                vectors = output_states
+            else:
+                rows, vectors = x, dense.linear(states, w_c.t()).reshape(B, L, Dm)         # u_c = W_c^T o
+            copy_scores, total_copy = segment_scores(rows, vectors.contiguous(), plan)     # [I, L], [B, L]
+        target_scores = self.__vocabulary_scores(attention_out, states).reshape(B, L, -1)  # [B, L, V]
+        # logsumexp(cat(target_scores, total_copy)) without the [B, L, V + 1] copy
+        normalizing_const = torch.logaddexp(torch.logsumexp(target_scores, dim=-1), total_copy)
+        target_logprobs = target_scores - normalizing_const.unsqueeze(-1)
+        copy_logprobs = copy_scores - _rows(normalizing_const, index, plan)
+        return copy_logprobs, target_logprobs, last_state.unsqueeze(0)
+
+    def _compute_logprobs(self, initial_states, input_memories, input_memories_origin_idx, input_token_ids):
+        """
+        :param input_memories: [num-inputs-flattened, D]
+        :param input_memories_origin_idx: [num-inputs-flattened]
+        :param initial_states: [num-targets, H]
+        :param input_token_ids: [num-targets, max-seq-size-1]
+
+        :return: the logprobs for all copying locations [num-inputs-flattened, max-seq-size-1], the logprobs for all
+            elements in the vocabulary [num-targets, max-seq-size-1, vocab-size] and the GRU's last state [1, num-targets, H]
+        """
+        dt = input_memories.dtype
+        if dt in _HALF or initial_states.dtype in _HALF:         # AMP: fp32 inside, the caller's dtypes outside
+            copy_logprobs, target_logprobs, state = self._compute_logprobs(
+                initial_states.float(), input_memories.float(), input_memories_origin_idx, input_token_ids)
+            return copy_logprobs.to(dt), target_logprobs.to(dt), state.to(initial_states.dtype)
+        if not input_memories.is_cuda:    # device dispatch: CPU tensors take the reference's own operator order
+            return self.__host_logprobs(initial_states, input_memories, input_memories_origin_idx, input_token_ids)
+        return self.__device_logprobs(initial_states, input_memories, input_memories_origin_idx, input_token_ids)
+
+    def forward(self, *, input_memories, input_memories_origin_idx, initial_states, target_token_ids,
+                copyable_elements_idxs, copyable_elements_sample_idxs, target_lengths):
+        """
+        :param input_memories: [num-inputs-flattened, D]
+        :param input_memories_origin_idx: [num-inputs-flattened]
+        :param initial_states: [num-targets, H]
+        :param target_token_ids: [num-targets, max-seq-size]
+        :param target_lengths: [num-targets]
+        :param copyable_elements_idxs: [num-copyable-elements]
+        :param copyable_elements_sample_idxs: [num-copyable-elements]
+
+        :return: the loss (grucopydecoder.py:166-212; the segment sums are the facade's: HIP kernels on GPU tensors).
+        """
+        copy_logprobs, target_logprobs, _ = self._compute_logprobs(
+            initial_states, input_memories, input_memories_origin_idx, target_token_ids[:, :-1])
+        copy_logprobs, target_logprobs = copy_logprobs.float(), target_logprobs.float()
+        num_targets, num_steps = target_token_ids.shape[0], target_token_ids.shape[1] - 1
+
+        # UNKs are only predicted if we cannot copy.
+        num_valid_copy_actions = scatter_facade.scatter_add(
+            torch.ones_like(copyable_elements_sample_idxs), index=copyable_elements_sample_idxs, dim=0,
+            dim_size=num_targets * num_steps)
+        locations_with_valid_copy_actions = num_valid_copy_actions.reshape(num_targets, num_steps) > 0
+        unk_prediction_locations = target_token_ids[:, 1:] == self.__unk_id
+        mask = locations_with_valid_copy_actions & unk_prediction_locations
+
+        correct_generation_logprobs = torch.gather(target_logprobs, index=target_token_ids[:, 1:].unsqueeze(-1),
+                                                   dim=-1).squeeze(-1)                    # [num-targets, num-steps]
+        correct_generation_logprobs = correct_generation_logprobs.masked_fill(mask, -math.inf)
+
+        correct_copy_logprobs = scatter_facade.scatter_logsumexp(
+            copy_logprobs.flatten()[copyable_elements_idxs], index=copyable_elements_sample_idxs, dim=0,
+            dim_size=num_targets * num_steps, eps=0).view(num_targets, num_steps)
+
+        any_correct_action_logprob = torch.logsumexp(
+            torch.stack((correct_generation_logprobs, correct_copy_logprobs)), dim=0)     # [num-targets, num-steps]
+
+        mask = torch.arange(num_steps, device=target_lengths.device).unsqueeze(0) < target_lengths.unsqueeze(1)
+        per_seq_loss = (any_correct_action_logprob * mask.float()).sum(dim=-1) / mask.float().sum(dim=-1)
+        return -per_seq_loss.mean()
+
+    def forward_sharded(self, *args, **kwargs):
+        """The decoder attends over all memories of a sample: there is no sharded form (as for the attention reducers)."""
+        raise _lib.PtgnnAmdError("forward_sharded: cannot combine partial pools of GruCopyingDecoder")
