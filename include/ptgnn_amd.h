@@ -139,6 +139,8 @@ enum {
   PTGNN_AMD_KERNEL_BLOCK_ATTENTION_BACKWARD, /* ptgnn_amd_block_attention_backward_f32 */
   PTGNN_AMD_KERNEL_SEGMENT_SCORES,           /* ptgnn_amd_segment_scores_f32 */
   PTGNN_AMD_KERNEL_SEGMENT_SCORES_BACKWARD,  /* ptgnn_amd_segment_scores_backward_f32 */
+  PTGNN_AMD_KERNEL_EMBEDDING_BAG,            /* ptgnn_amd_embedding_bag_f32 */
+  PTGNN_AMD_KERNEL_EMBEDDING_BAG_BACKWARD,   /* ptgnn_amd_embedding_bag_backward_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -880,6 +882,47 @@ int ptgnn_amd_pna_aggregate_backward_f32(const float *msg, int64_t ld_msg, const
  * mlp_hidden_layers > 0) and for task heads (output_node_representations[node_idx_references]). */
 int ptgnn_amd_gather_rows_f32(const float *x, int64_t ld_x, const int64_t *idx, int64_t n_idx,
                               int32_t dim, float *out, int64_t ld_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Subtoken pool of SubtokenUnitEmbedder (embeddings/strelementrepresentationmodel.py:67-82: nn.Embedding over the
+ * [B, max_num_subtokens] ids, the length mask, the sum / mean / max over the slot axis), without the [B, S, D] tensor:
+ *   slot s of bag b is LIVE iff s < lengths[b]; dead slots are never read; ids are clamped into [0, vocab)
+ *   sum :  out[b] = live table rows added in slot order
+ *   mean:  that sum / (float(lengths[b]) + 1e-10f)   (fp32; the GIVEN length, also when it exceeds `slots`)
+ *   max :  the running maximum from -inf; arg[b, d] (nullable, int32 [B, dim] contiguous, max only) = the first slot
+ *          that attains it, -1 when none does
+ *   a bag without live slot: 0 (sum / mean), -inf (max) -- as the reference.
+ * table [vocab, dim] (ld_table), ids int64 [num_bags, slots] contiguous, lengths int64 [num_bags], out [num_bags, dim]
+ * (ld_out); mode = PTGNN_AMD_SUM / _MEAN / _MAX.  ptgnn_amd_embedding_bag_supported (pure host): dim % 4 == 0,
+ * 4 <= dim <= 1024, 1 <= slots <= 32; other shapes answer PTGNN_AMD_EUNSUPPORTED before any device work.
+ *
+ * Backward (autograd of the nn.Embedding at :67 through the mask and the reduction; deterministic, no float atomics):
+ * the bag is a one-edge-type graph, element e = b * slots + s with source b and destination ids[e].
+ *   ptgnn_amd_embedding_bag_keys: src[e] = b, key[e] = the clamped id of a live slot, `vocab` for a dead one -- the
+ *     adjacency pair of ptgnn_amd_csr_build (mode 0, num_nodes = vocab + 1, num_src_rows = num_bags), whose stable sort
+ *     lists the elements of every vocabulary row in element order and parks the padding in row `vocab`;
+ *   ptgnn_amd_embedding_bag_backward_f32: grad_table [vocab, dim] (ld_gt; OVERWRITTEN, rows nobody references exactly 0)
+ *     from grad = dL/dout [num_bags, dim] over that plan's rowptr [vocab + 2] / col / perm, walking rows [0, vocab) only
+ *     (padding costs no gather) with the row walk of ptgnn_amd_gather_reduce_f32 -- hub arguments as there, built with
+ *     the same threshold.  mean scales the gradient rows by 1 / (float(lengths[b]) + 1e-10f) first; max routes
+ *     grad[b, d] to slot arg[b, d] only (`arg` = the forward's; `perm` is read for max only).
+ *     workspace: ptgnn_amd_embedding_bag_backward_workspace_bytes(num_bags, slots, dim, mode) bytes (0 for sum).
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_embedding_bag_supported(int32_t dim, int32_t slots);
+int ptgnn_amd_embedding_bag_f32(const float *table, int64_t ld_table, int64_t vocab, const int64_t *ids,
+                                const int64_t *lengths, int64_t num_bags, int32_t slots, int32_t dim, int mode,
+                                float *out, int64_t ld_out, int32_t *arg /* nullable */, void *stream);
+int ptgnn_amd_embedding_bag_keys(const int64_t *ids, const int64_t *lengths, int64_t num_bags, int32_t slots,
+                                 int64_t vocab, int64_t *src, int64_t *key, void *stream);
+size_t ptgnn_amd_embedding_bag_backward_workspace_bytes(int64_t num_bags, int32_t slots, int32_t dim, int mode);
+int ptgnn_amd_embedding_bag_backward_f32(const float *grad, int64_t ld_grad, const int64_t *lengths,
+                                         const int32_t *arg /* max only */, int64_t num_bags, int32_t slots,
+                                         int64_t vocab, int32_t dim, int mode, const int32_t *rowptr,
+                                         const int32_t *col, const int32_t *perm, float *grad_table, int64_t ld_gt,
+                                         int32_t hub_threshold, const int32_t *hub_entries /* nullable */,
+                                         const int32_t *hub_count /* nullable */, void *hub_ws /* nullable */,
+                                         size_t hub_ws_bytes, int32_t *hub_tickets /* nullable */, void *workspace,
+                                         size_t workspace_bytes, void *stream);
 
 #pragma GCC visibility pop
 

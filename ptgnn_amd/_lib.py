@@ -138,6 +138,14 @@ SIGNATURES = {
     "ptgnn_amd_block_attention_backward_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32,
                                                           _i32, _i32, _i32, _f32, _c.c_uint64, _vp, _i64, _vp,
                                                           _c.c_size_t, _vp]),
+    "ptgnn_amd_embedding_bag_supported": (_c.c_int, [_i32, _i32]),
+    "ptgnn_amd_embedding_bag_f32": (_c.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _c.c_int, _vp, _i64, _vp,
+                                               _vp]),
+    "ptgnn_amd_embedding_bag_keys": (_c.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]),
+    "ptgnn_amd_embedding_bag_backward_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32, _c.c_int]),
+    "ptgnn_amd_embedding_bag_backward_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32, _c.c_int, _vp, _vp,
+                                                        _vp, _vp, _i64, _i32, _vp, _vp, _vp, _c.c_size_t, _vp, _vp,
+                                                        _c.c_size_t, _vp]),
 }
 
 # The header version this host was written against (include/ptgnn_amd.h: PTGNN_AMD_VERSION).  A stale .so with an

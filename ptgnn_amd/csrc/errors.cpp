@@ -66,7 +66,7 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "k_gather_reduce", "egc_gather_combine", "egc_combine", "egc_combine_backward", "pna_aggregate",
       "pna_aggregate_backward", "attention_pool", "attention_pool_backward", "head_projection", "graph_norm",
       "graph_norm_backward", "block_attention", "block_attention_backward", "segment_scores",
-      "segment_scores_backward"};
+      "segment_scores_backward", "embedding_bag", "embedding_bag_backward"};
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
     return agg_names[kernel_id - PTGNN_AMD_KERNEL_AGG_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;

@@ -1,0 +1,147 @@
+"""The node embedders every model of the reference starts its forward with (graphneuralnetwork.py:160): mirrors of
+ptgnn/neuralmodels/embeddings/strelementrepresentationmodel.py:16-89 (`TokenUnitEmbedder`, `SubtokenUnitEmbedder`: same
+class names, constructor keywords, submodule creation order, initialisers, `embedding_layer` property, forward signatures
+and name-mangled parameter names, so a reference state_dict loads strictly and the same seed gives the same initial
+values).  `StrElementRepresentationModel` -- vocabulary, tensorisation, minibatching -- works unchanged around them
+(a subclass overriding `build_neural_module`).
+
+GPU route:
+  * TokenUnitEmbedder: the HIP row gather (backward: the deterministic segment sum over a plan of the token ids), dropout;
+  * SubtokenUnitEmbedder: the fused embedding bag (csrc/embedding_bag.hip) as one autograd node -- no [B, S, D] tensor, the
+    table gradient a deterministic segment sum over the bag's plan, `arg` kept for max -- then the HIP Linear of the
+    output layer and dropout.
+Shapes beyond the bag's range (D not a multiple of 4, more than 32 subtokens) compose the reference's operator sequence
+from the HIP row gather and torch elementwise arithmetic.  CPU tensors take the reference's own operator order on torch
+(device dispatch as in every layer of the package); fp16 / bf16 tables are up-cast on entry and the result cast back.
+"""
+import math
+
+import torch
+from torch import nn
+
+from ptgnn_amd import _lib, dense, ops, torch_route
+from ptgnn_amd.sequence import _rows
+
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _check_ids(what: str, table: torch.Tensor, *index) -> None:
+    for t in index:
+        if not t.is_cuda or t.dtype != torch.int64:
+            raise _lib.PtgnnAmdError(f"{what}: the ids and lengths of a GPU table must be CUDA int64 tensors (got "
+                                     f"{t.dtype} on {t.device})")
+
+
+class _EmbeddingBag(torch.autograd.Function):
+    """sum / mean / max of table[ids[b, s]] over s < lengths[b] on the fused HIP bag; backward = the segment sum over the
+    bag's plan (ops.embedding_bag_backward), routed by the saved `arg` for max."""
+
+    @staticmethod
+    def forward(ctx, table, ids, lengths, kind):
+        need_grad = ctx.needs_input_grad[0]
+        res = ops.embedding_bag(table, ids, lengths, kind, return_arg=need_grad and kind == "max")
+        out, arg = res if isinstance(res, tuple) else (res, None)
+        ctx.save_for_backward(ids, lengths, arg)
+        ctx.kind, ctx.rows = kind, table.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ids, lengths, arg = ctx.saved_tensors
+        return ops.embedding_bag_backward(g.contiguous(), ids, lengths, ctx.kind, ctx.rows, arg=arg), None, None, None
+
+
+def embedding_bag(table: torch.Tensor, ids: torch.Tensor, lengths: torch.Tensor, kind: str) -> torch.Tensor:
+    """Differentiable (w.r.t. `table`) subtoken pool on the HIP kernels; `ops.embedding_bag_supported(D, S)` shapes only."""
+    return _EmbeddingBag.apply(table.contiguous(), ids, lengths, kind)
+
+
+def _composed_pool(table: torch.Tensor, ids: torch.Tensor, lengths: torch.Tensor, kind: str) -> torch.Tensor:
+    """strelementrepresentationmodel.py:67-82 on the HIP row gather plus torch elementwise arithmetic, for shapes outside
+    the fused bag.  Dead slots read row 0 (their ids may be anything) and are masked out."""
+    B, S = ids.shape
+    live = torch.arange(S, device=ids.device).unsqueeze(0) < lengths.unsqueeze(-1)            # [B, S]
+    flat = torch.where(live, ids, torch.zeros_like(ids)).clamp_(0, table.shape[0] - 1).reshape(-1)
+    embedded = _rows(table, flat).reshape(B, S, table.shape[1])
+    if kind == "max":
+        return embedded.masked_fill(~live.unsqueeze(-1), -math.inf).max(dim=-2)[0]
+    pooled = (embedded * live.unsqueeze(-1).float()).sum(dim=-2)
+    return pooled / (lengths.unsqueeze(-1).float() + 1e-10) if kind == "mean" else pooled
+
+
+class TokenUnitEmbedder(nn.Module):
+    def __init__(self, vocabulary_size: int, embedding_size: int, dropout_rate: float):
+        super().__init__()
+        self.__embeddings = nn.Embedding(num_embeddings=vocabulary_size, embedding_dim=embedding_size)
+        nn.init.xavier_uniform_(self.__embeddings.weight)
+        self.__dropout_layer = nn.Dropout(p=dropout_rate)
+
+    @property
+    def embedding_layer(self) -> nn.Embedding:
+        return self.__embeddings
+
+    def forward(self, token_idxs: torch.Tensor) -> torch.Tensor:
+        """:param token_idxs: [B] token ids;  :return: [B, D]"""
+        table = self.__embeddings.weight
+        if not table.is_cuda:             # device dispatch: CPU tensors take the reference's own operator order
+            return self.__dropout_layer(self.__embeddings(token_idxs))
+        _check_ids("TokenUnitEmbedder", table, token_idxs)
+        rows = _rows(table.float(), token_idxs.reshape(-1)).reshape(*token_idxs.shape, table.shape[1])
+        return self.__dropout_layer(rows.to(table.dtype))
+
+
+class SubtokenUnitEmbedder(nn.Module):
+    def __init__(self, vocabulary_size: int, embedding_size: int, dropout_rate: float, subtoken_combination_kind: str,
+                 use_dense_output: bool = True):
+        super().__init__()
+        assert subtoken_combination_kind in {"mean", "max", "sum"}
+        self.__subtoken_combination_kind = subtoken_combination_kind
+        self.__embeddings = nn.Embedding(num_embeddings=vocabulary_size, embedding_dim=embedding_size)
+        nn.init.uniform_(self.__embeddings.weight)
+        if use_dense_output:
+            self.__out_layer = nn.Linear(embedding_size, embedding_size, bias=False)
+            nn.init.xavier_uniform_(self.__out_layer.weight)
+        else:
+            self.__out_layer = None
+        self.__dropout_layer = nn.Dropout(p=dropout_rate)
+
+    @property
+    def embedding_layer(self) -> nn.Embedding:
+        return self.__embeddings
+
+    def __device_forward(self, token_idxs, lengths):
+        table, kind = self.__embeddings.weight, self.__subtoken_combination_kind
+        _check_ids("SubtokenUnitEmbedder", table, token_idxs, lengths)
+        if token_idxs.dim() != 2 or lengths.shape != token_idxs.shape[:1]:
+            raise _lib.PtgnnAmdError(f"SubtokenUnitEmbedder: token_idxs {tuple(token_idxs.shape)} / lengths "
+                                     f"{tuple(lengths.shape)} are not [B, max_num_subtokens] / [B]")
+        dt = table.dtype
+        if dt not in _HALF and dt != torch.float32:
+            raise _lib.PtgnnAmdError(f"SubtokenUnitEmbedder: no kernel for a {dt} table")
+        table32 = table.float()           # AMP tables: fp32 inside, the table's dtype outside
+        if ops.embedding_bag_supported(table.shape[1], token_idxs.shape[1]):
+            pooled = embedding_bag(table32, token_idxs, lengths, kind)
+        else:
+            pooled = _composed_pool(table32, token_idxs, lengths, kind)
+        drop = self.__dropout_layer
+        if self.__out_layer is None:
+            return drop(pooled.to(dt))
+        weight = self.__out_layer.weight.float()
+        out = dense.linear_act_dropout(pooled, weight, None, None, drop.p, self.training)
+        if out is None:
+            out = drop(dense.linear(pooled, weight))
+        return out.to(dt)
+
+    def forward(self, token_idxs: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        """
+        :param token_idxs: The subtoken ids in a [B, max_num_subtokens] matrix.
+        :param lengths: A [B]-sized vector containing the lengths
+        :return: a [B, D] matrix of D-sized representations, one per input example.
+        """
+        if self.__embeddings.weight.is_cuda:
+            return self.__device_forward(token_idxs, lengths)
+        embedded = torch_route.subtoken_embed(token_idxs, lengths, self.__embeddings.weight,
+                                              self.__subtoken_combination_kind)
+        if self.__out_layer is not None:
+            embedded = self.__out_layer(embedded)
+        return self.__dropout_layer(embedded)

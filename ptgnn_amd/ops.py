@@ -45,7 +45,7 @@ def launch_counts(aggregation: bool = False) -> dict:
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
     attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward, block_attention,
-    block_attention_backward, segment_scores, segment_scores_backward)."""
+    block_attention_backward, segment_scores, segment_scores_backward, embedding_bag, embedding_bag_backward)."""
     lib = _lib.load()
     out = {}
     for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
@@ -1811,6 +1811,95 @@ def segment_scores_backward(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, s
             ws.data_ptr(), ws_bytes, _stream(gv))
     _lib.check(rc, "ptgnn_amd_segment_scores_backward_f32")
     return gy, gv
+
+
+BAG_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def embedding_bag_supported(dim: int, slots: int) -> bool:
+    """Whether the fused embedding bag takes (dim, slots) (ptgnn_amd_embedding_bag_supported: dim % 4 == 0,
+    4 <= dim <= 1024, slots <= 32)."""
+    return bool(_lib.load().ptgnn_amd_embedding_bag_supported(int(dim), int(slots)))
+
+
+def _embedding_bag_args(table: torch.Tensor, ids: torch.Tensor, lengths: torch.Tensor, mode: str, what: str):
+    _require_cuda_f32("table", table)
+    if mode not in BAG_MODES:
+        raise ValueError(f"unknown subtoken combination {mode!r}")
+    for name, t, dims in (("ids", ids, 2), ("lengths", lengths, 1)):
+        if not t.is_cuda or t.dtype != torch.int64 or t.dim() != dims:
+            raise _lib.PtgnnAmdError(f"{what}: {name} must be a {dims}-D CUDA int64 tensor")
+    if lengths.shape[0] != ids.shape[0]:
+        raise _lib.PtgnnAmdError(f"{what}: {lengths.shape[0]} lengths for {ids.shape[0]} bags")
+    return _rowmajor(table), ids.contiguous(), lengths.contiguous()
+
+
+def embedding_bag(table: torch.Tensor, ids: torch.Tensor, lengths: torch.Tensor, mode: str, return_arg: bool = False):
+    """out[b] = sum / mean / max of table[ids[b, s]] over the slots s < lengths[b] (ptgnn_amd_embedding_bag_f32: the pool of
+    SubtokenUnitEmbedder without the [B, S, D] tensor).  `return_arg` (max): also the int32 [B, D] winning slots."""
+    lib = _lib.load()
+    table, ids, lengths = _embedding_bag_args(table, ids, lengths, mode, "embedding_bag")
+    (B, S), (V, D) = ids.shape, table.shape
+    out = torch.empty(B, D, dtype=torch.float32, device=table.device)
+    arg = torch.empty(B, D, dtype=torch.int32, device=table.device) if return_arg and mode == "max" else None
+    with _timed("embedding_bag", bytes=B * (8.0 * S + 8) + 4.0 * min(B * S, V) * D + 4.0 * B * D * (2 if arg is not None else 1)):
+        rc = lib.ptgnn_amd_embedding_bag_f32(table.data_ptr() if V else None, _ld(table), V, ids.data_ptr() if B else None,
+                                             lengths.data_ptr() if B else None, B, S, D, BAG_MODES[mode],
+                                             out.data_ptr() if B else None, D,
+                                             arg.data_ptr() if arg is not None and B else None, _stream(out))
+    _lib.check(rc, "ptgnn_amd_embedding_bag_f32")
+    return (out, arg) if return_arg else out
+
+
+def embedding_bag_plan(ids: torch.Tensor, lengths: torch.Tensor, vocabulary_size: int) -> GraphPlan:
+    """The backward plan of a bag: its elements as (bag, token) edges (ptgnn_amd_embedding_bag_keys), stably sorted by token
+    with the dead slots keyed to the extra row `vocabulary_size` (which no launch walks)."""
+    lib = _lib.load()
+    B, S = ids.shape
+    src = torch.empty(max(B * S, 1), dtype=torch.int64, device=ids.device)
+    key = torch.empty(max(B * S, 1), dtype=torch.int64, device=ids.device)
+    rc = lib.ptgnn_amd_embedding_bag_keys(ids.data_ptr() if B else None, lengths.data_ptr() if B else None, B, S,
+                                          int(vocabulary_size), src.data_ptr(), key.data_ptr(), _stream(src))
+    _lib.check(rc, "ptgnn_amd_embedding_bag_keys")
+    return build_plan([(src[:B * S], key[:B * S])], int(vocabulary_size) + 1, num_src_rows=max(B, 1))
+
+
+def embedding_bag_backward(grad: torch.Tensor, ids: torch.Tensor, lengths: torch.Tensor, mode: str, vocabulary_size: int,
+                           arg: Optional[torch.Tensor] = None, plan: Optional[GraphPlan] = None) -> torch.Tensor:
+    """dL/dtable [V, D] of `embedding_bag` from grad = dL/dout [B, D] (ptgnn_amd_embedding_bag_backward_f32): a segment sum
+    over the bag's plan (`embedding_bag_plan`, built here when not given), every vocabulary row folded in element order;
+    `arg`: the forward's winning slots (max)."""
+    lib = _lib.load()
+    _require_cuda_f32("grad", grad)
+    grad = _rowmajor(grad)
+    _, ids, lengths = _embedding_bag_args(grad, ids, lengths, mode, "embedding_bag_backward")
+    (B, S), D, V = ids.shape, grad.shape[1], int(vocabulary_size)
+    if grad.shape[0] != B:
+        raise _lib.PtgnnAmdError(f"embedding_bag_backward: grad {tuple(grad.shape)} for {B} bags")
+    if mode == "max":
+        if arg is None or tuple(arg.shape) != (B, D) or arg.dtype != torch.int32 or not arg.is_cuda:
+            raise _lib.PtgnnAmdError("embedding_bag_backward: max needs the forward's int32 [B, D] arg")
+        arg = arg.contiguous()
+    out = torch.empty(V, D, dtype=torch.float32, device=grad.device)
+    if V == 0:
+        return out
+    if not embedding_bag_supported(D, S):     # before the plan build: an unsupported shape does no device work
+        raise _lib.PtgnnAmdError(f"embedding_bag_backward: dim {D} / {S} slots outside the kernel range")
+    if plan is None:
+        plan = embedding_bag_plan(ids, lengths, V)
+    if plan.num_nodes != V + 1 or plan.num_edges != B * S:
+        raise _lib.PtgnnAmdError("embedding_bag_backward: the plan is not this bag's")
+    plan.wait()
+    ws_bytes = int(lib.ptgnn_amd_embedding_bag_backward_workspace_bytes(B, S, D, BAG_MODES[mode]))
+    ws = _workspace(ws_bytes, grad.device)
+    hub_ws, hub = _hub_args(plan, D, False, grad.device)
+    with _timed("embedding_bag_backward", bytes=B * S * (4.0 * D + 4) + V * (4.0 * D + 4)):
+        rc = lib.ptgnn_amd_embedding_bag_backward_f32(
+            grad.data_ptr() if B else None, _ld(grad) if B else D, lengths.data_ptr() if B else None,
+            arg.data_ptr() if mode == "max" and B else None, B, S, V, D, BAG_MODES[mode], plan.rowptr.data_ptr(),
+            plan.col.data_ptr(), plan.perm.data_ptr(), out.data_ptr(), D, *hub[1:], ws.data_ptr(), ws_bytes, _stream(out))
+    _lib.check(rc, "ptgnn_amd_embedding_bag_backward_f32")
+    return out
 
 
 def graph_norm_supported(dim: int) -> bool:

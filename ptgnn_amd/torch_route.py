@@ -389,3 +389,21 @@ def attention_summary(x: torch.Tensor, index: torch.Tensor, num_samples: int, qu
         outputs = probs.unsqueeze(-1) * x.unsqueeze(1)                             # [N, heads, D]
     per_sample = scatter(outputs.reshape(outputs.shape[0], -1), index, 0, None, n, "sum")
     return F.linear(per_sample, output_weight)
+
+
+def subtoken_embed(token_idxs: torch.Tensor, lengths: torch.Tensor, table: torch.Tensor, kind: str) -> torch.Tensor:
+    """The pool of SubtokenUnitEmbedder.forward (strelementrepresentationmodel.py:67-82) in the reference's operator order
+    on host tensors: [B, D] from the [B, max_num_subtokens] ids and the [B] lengths."""
+    _host_only(token_idxs, lengths, table)
+    embedded = nn.functional.embedding(token_idxs, table)                          # [B, max_num_subtokens, D]
+    mask = torch.arange(embedded.shape[1], device=lengths.device).unsqueeze(0) < lengths.unsqueeze(-1)
+    if kind == "mean":
+        embedded = embedded * mask.unsqueeze(-1).float()
+        return embedded.sum(dim=-2) / (lengths.unsqueeze(-1).float() + 1e-10)
+    if kind == "sum":
+        embedded = embedded * mask.unsqueeze(-1).float()
+        return embedded.sum(dim=-2)
+    if kind == "max":
+        embedded.masked_fill_(mask=~mask.unsqueeze(-1), value=-math.inf)
+        return embedded.max(dim=-2)[0]
+    raise ValueError(f'Unrecognized subtoken combination "{kind}".')
