@@ -143,6 +143,16 @@ enum {
   PTGNN_AMD_KERNEL_EMBEDDING_BAG_BACKWARD,   /* ptgnn_amd_embedding_bag_backward_f32 */
   PTGNN_AMD_KERNEL_AGG_END_
 };
+/* A third id range, past the aggregation range for the same reason: the kernels of the char-CNN embedder
+ * (csrc/char_conv.hip).  Its windowed GEMMs count under the GEMM families above. */
+enum {
+  PTGNN_AMD_KERNEL_CHAR_FIRST_ = 128,
+  PTGNN_AMD_KERNEL_CHAR_EMBED = PTGNN_AMD_KERNEL_CHAR_FIRST_, /* ptgnn_amd_char_embed_f32 */
+  PTGNN_AMD_KERNEL_CHAR_EMBED_BACKWARD,                       /* ptgnn_amd_char_embed_backward_f32 */
+  PTGNN_AMD_KERNEL_WINDOW_MAX,                                /* ptgnn_amd_window_max_f32 */
+  PTGNN_AMD_KERNEL_WINDOW_MAX_BACKWARD,                       /* ptgnn_amd_window_max_backward_f32 */
+  PTGNN_AMD_KERNEL_CHAR_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -923,6 +933,66 @@ int ptgnn_amd_embedding_bag_backward_f32(const float *grad, int64_t ld_grad, con
                                          const int32_t *hub_count /* nullable */, void *hub_ws /* nullable */,
                                          size_t hub_ws_bytes, int32_t *hub_tickets /* nullable */, void *workspace,
                                          size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The char-CNN of CharUnitEmbedder (embeddings/strelementrepresentationmodel.py:128-142: one_hot, three nn.Conv1d with
+ * ReLU between them, max over the positions), channel-last on ROW FRAMES: every activation / gradient matrix holds
+ * R = length - k1 + 1 rows per sample, sample b at rows [b R, (b + 1) R); layer i's valid positions are the first P_i
+ * rows of a sample (P1 = R, P2 = R - k2 + 1, P3 = P2 - k3 + 1), the rows behind them are computed and ignored.
+ *
+ * ptgnn_amd_char_embed_f32 (:133-137, one_hot + transpose + float + conv_l1, and the ReLU of :138): a convolution over a
+ *   one-hot input is a table sum,
+ *     out[b R + p, :] = act(bias + sum_{k < window} table[k num_chars + chars[b, p + k], :]),   p < R,
+ *   chars int64 [num_samples, length] contiguous, table [window num_chars, dim] contiguous with row k C + c = W1[:, c, k],
+ *   bias [dim] (nullable), out [num_samples R, dim] (ld_out), act = PTGNN_AMD_ACT_NONE / _RELU.  One launch; ids outside
+ *   [0, num_chars) are clamped into it.  ptgnn_amd_char_embed_supported (pure host): dim % 4 == 0, 4 <= dim <= 1024,
+ *   1 <= window <= 16 and (window num_chars + 1) * 256 bytes <= 160 KiB (the backward's LDS tile); other shapes answer
+ *   PTGNN_AMD_EUNSUPPORTED before any device work.
+ * ptgnn_amd_char_embed_backward_f32 (autograd of :133-138 w.r.t. conv_l1's weight and bias): from grad = dL/dout
+ *   [num_samples R, dim] (ld_grad) and the saved out = a1 (ld_a1; read for _RELU only: the mask a1 > 0) it OVERWRITES
+ *   grad_table [window num_chars, dim] and grad_bias [dim] (nullable).  Deterministic, no float atomics: a wave owns
+ *   ptgnn_amd_char_embed_backward_chunk() consecutive samples and 64 columns, adds them in row order into an LDS copy of
+ *   the table tile, and the chunks' tiles are folded in chunk order.  workspace:
+ *   ptgnn_amd_char_embed_backward_workspace_bytes(num_samples, num_chars, window, dim) bytes.
+ *
+ * ptgnn_amd_window_linear_f32 (nn.Conv1d at :138-139 on a channel-last frame, and its input gradient):
+ *     y[r, :] = act(W . x[r .. r + window - 1, :] + b),   r < rows,
+ *   x [rows + window - 1, c_in] with PACKED rows (ld_x == c_in unless window == 1) -- ALL rows + window - 1 rows are
+ *   read --, w [n_out, window c_in] with column j c_in + c = the conv weight [:, c, j], y [rows, n_out] (ld_y).  It is
+ *   ptgnn_amd_linear_f32 with k = window c_in and overlapping rows: same kernels, same launch counters, same bits.
+ * ptgnn_amd_window_weight_grad_f32: grad_w [n_out, window c_in] = sum_r grad_y[r]^T . x[r .. r + window - 1] and grad_b
+ *   [n_out] (nullable) = column sums of grad_y, on the kernels of ptgnn_amd_linear_weight_grad_f32 (its constraints:
+ *   c_in % 4 == 0, n_out % 4 == 0, 16-byte aligned rows); workspace: ptgnn_amd_edge_wgrad_workspace_bytes(rows, 1, n_out,
+ *   window c_in) bytes.
+ *
+ * ptgnn_amd_window_max_f32 (torch.max(l3_out, dim=-1) at :141): out[b, :] = max over the first `valid` of sample b's
+ *   rows_per_sample rows of x (ld_x); arg (nullable, int32 [num_samples, dim] contiguous) = the LOWEST position that
+ *   attains it (torch.max's rule; a NaN wins from its first position).  1 <= valid <= rows_per_sample.
+ * ptgnn_amd_window_max_backward_f32: writes EVERY row of grad_x [num_samples rows_per_sample, dim] (ld_gx): grad[b, d]
+ *   (ld_grad) at row arg[b, d] of sample b, exact zeros elsewhere.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_char_embed_supported(int32_t num_chars, int32_t window, int32_t dim);
+int ptgnn_amd_char_embed_f32(const int64_t *chars, int64_t num_samples, int32_t length, int32_t num_chars,
+                             int32_t window, const float *table, const float *bias /* nullable */, int32_t dim, int act,
+                             float *out, int64_t ld_out, void *stream);
+int32_t ptgnn_amd_char_embed_backward_chunk(void);
+size_t ptgnn_amd_char_embed_backward_workspace_bytes(int64_t num_samples, int32_t num_chars, int32_t window,
+                                                     int32_t dim);
+int ptgnn_amd_char_embed_backward_f32(const float *grad, int64_t ld_grad, const float *a1, int64_t ld_a1,
+                                      const int64_t *chars, int64_t num_samples, int32_t length, int32_t num_chars,
+                                      int32_t window, int32_t dim, int act, float *grad_table,
+                                      float *grad_bias /* nullable */, void *workspace, size_t workspace_bytes,
+                                      void *stream);
+int ptgnn_amd_window_linear_f32(const float *x, int64_t rows, int32_t c_in, int32_t window, int64_t ld_x,
+                                const float *w, int32_t n_out, const float *bias /* nullable */, int act, float *y,
+                                int64_t ld_y, void *stream);
+int ptgnn_amd_window_weight_grad_f32(const float *x, int64_t rows, int32_t c_in, int32_t window, const float *grad_y,
+                                     int64_t ld_grad_y, int32_t n_out, float *grad_w, float *grad_b /* nullable */,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+int ptgnn_amd_window_max_f32(const float *x, int64_t ld_x, int64_t num_samples, int32_t rows_per_sample, int32_t valid,
+                             int32_t dim, float *out, int64_t ld_out, int32_t *arg /* nullable */, void *stream);
+int ptgnn_amd_window_max_backward_f32(const float *grad, int64_t ld_grad, const int32_t *arg, int64_t num_samples,
+                                      int32_t rows_per_sample, int32_t dim, float *grad_x, int64_t ld_gx, void *stream);
 
 #pragma GCC visibility pop
 

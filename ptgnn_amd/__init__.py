@@ -15,7 +15,7 @@ def __getattr__(name):
     if name == "GruCopyingDecoder":
         from ptgnn_amd.sequence import GruCopyingDecoder
         return GruCopyingDecoder
-    if name in ("TokenUnitEmbedder", "SubtokenUnitEmbedder"):
+    if name in ("TokenUnitEmbedder", "SubtokenUnitEmbedder", "CharUnitEmbedder", "CnnConfig"):
         from ptgnn_amd import embeddings
         return getattr(embeddings, name)
     raise AttributeError(f"module 'ptgnn_amd' has no attribute {name!r}")

@@ -146,6 +146,17 @@ SIGNATURES = {
     "ptgnn_amd_embedding_bag_backward_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32, _c.c_int, _vp, _vp,
                                                         _vp, _vp, _i64, _i32, _vp, _vp, _vp, _c.c_size_t, _vp, _vp,
                                                         _c.c_size_t, _vp]),
+    "ptgnn_amd_char_embed_supported": (_c.c_int, [_i32, _i32, _i32]),
+    "ptgnn_amd_char_embed_f32": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _c.c_int, _vp, _i64, _vp]),
+    "ptgnn_amd_char_embed_backward_chunk": (_i32, []),
+    "ptgnn_amd_char_embed_backward_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32, _i32]),
+    "ptgnn_amd_char_embed_backward_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _c.c_int,
+                                                     _vp, _vp, _vp, _c.c_size_t, _vp]),
+    "ptgnn_amd_window_linear_f32": (_c.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _c.c_int, _vp, _i64, _vp]),
+    "ptgnn_amd_window_weight_grad_f32": (_c.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _c.c_size_t,
+                                                    _vp]),
+    "ptgnn_amd_window_max_f32": (_c.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "ptgnn_amd_window_max_backward_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
 }
 
 # The header version this host was written against (include/ptgnn_amd.h: PTGNN_AMD_VERSION).  A stale .so with an

@@ -398,13 +398,11 @@ static int linear_nj() {  // 0 = heuristic
 
 using namespace ptgnn_amd;
 
-extern "C" int ptgnn_amd_linear_f32(const float *x, int64_t rows, int32_t k, int64_t ld_x,
-                                    const float *w, int32_t n_out, const float *bias, int act,
-                                    float *y, int64_t ld_y, void *stream_) {
-  PTGNN_REQUIRE(rows >= 0 && k > 0 && n_out > 0, PTGNN_AMD_EINVAL, "linear: bad sizes");
-  PTGNN_REQUIRE(act >= 0 && act <= PTGNN_AMD_ACT_RELU, PTGNN_AMD_EINVAL, "linear: bad act");
-  if (rows == 0) return PTGNN_AMD_OK;
-  PTGNN_REQUIRE(x && w && y && ld_x >= k && ld_y >= n_out, PTGNN_AMD_EINVAL, "linear: null/ld");
+// y = act(x W^T + b) over rows of k floats that start ld_x floats apart: the launches behind ptgnn_amd_linear_f32
+// (ld_x >= k, checked there) and ptgnn_amd_window_linear_f32 (overlapping rows, ld_x < k).  Every operand load of the
+// streaming and the tile kernels addresses row r as x + r * ld_x, so the row stride is free.
+static int linear_launch(const float *x, int64_t rows, int32_t k, int64_t ld_x, const float *w, int32_t n_out,
+                         const float *bias, int act, float *y, int64_t ld_y, void *stream_) {
   if (stream_linear(x, rows, k, ld_x, w, n_out, bias, act, y, ld_y, (hipStream_t)stream_)) {
     PTGNN_LAUNCH_CHECK();
     return PTGNN_AMD_OK;
@@ -436,6 +434,32 @@ extern "C" int ptgnn_amd_linear_f32(const float *x, int64_t rows, int32_t k, int
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_TILE_LINEAR);
   return PTGNN_AMD_OK;
+}
+
+extern "C" int ptgnn_amd_linear_f32(const float *x, int64_t rows, int32_t k, int64_t ld_x,
+                                    const float *w, int32_t n_out, const float *bias, int act,
+                                    float *y, int64_t ld_y, void *stream_) {
+  PTGNN_REQUIRE(rows >= 0 && k > 0 && n_out > 0, PTGNN_AMD_EINVAL, "linear: bad sizes");
+  PTGNN_REQUIRE(act >= 0 && act <= PTGNN_AMD_ACT_RELU, PTGNN_AMD_EINVAL, "linear: bad act");
+  if (rows == 0) return PTGNN_AMD_OK;
+  PTGNN_REQUIRE(x && w && y && ld_x >= k && ld_y >= n_out, PTGNN_AMD_EINVAL, "linear: null/ld");
+  return linear_launch(x, rows, k, ld_x, w, n_out, bias, act, y, ld_y, stream_);
+}
+
+// The windowed Linear: row r of the input is the window * c_in contiguous floats that start at row r of the channel-last
+// matrix x, i.e. a Linear with k = window * c_in whose rows overlap (ld_x < k for window > 1).
+extern "C" int ptgnn_amd_window_linear_f32(const float *x, int64_t rows, int32_t c_in, int32_t window, int64_t ld_x,
+                                           const float *w, int32_t n_out, const float *bias, int act, float *y,
+                                           int64_t ld_y, void *stream_) {
+  PTGNN_REQUIRE(rows >= 0 && c_in > 0 && window > 0 && n_out > 0 && (int64_t)c_in * window < ((int64_t)1 << 31),
+                PTGNN_AMD_EINVAL, "window_linear: bad sizes");
+  PTGNN_REQUIRE(act >= 0 && act <= PTGNN_AMD_ACT_RELU, PTGNN_AMD_EINVAL, "window_linear: bad act");
+  if (rows == 0) return PTGNN_AMD_OK;
+  PTGNN_REQUIRE(x && w && y && ld_x >= c_in && ld_y >= n_out, PTGNN_AMD_EINVAL, "window_linear: null/ld");
+  PTGNN_REQUIRE(window == 1 || ld_x == c_in, PTGNN_AMD_EINVAL,
+                "window_linear: a window spans rows only where they are packed (ld_x=%lld, c_in=%d)", (long long)ld_x,
+                c_in);
+  return linear_launch(x, rows, c_in * window, ld_x, w, n_out, bias, act, y, ld_y, stream_);
 }
 
 // y = act(x W^T + b) + addend in ONE launch: the streaming kernels add the block in their store epilogue.  Shapes the

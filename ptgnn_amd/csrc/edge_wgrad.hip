@@ -451,3 +451,17 @@ extern "C" int ptgnn_amd_linear_weight_grad_f32(const float *x, int64_t ld_x, in
   return weight_grad_launch(x, ld_x, rows, k, nullptr, nullptr, counts, grad_y, ld_grad_y, 1, n_out, 0.f, 0,
                             grad_w, workspace, workspace_bytes, stream_, true, grad_b);
 }
+
+// grad_w [n_out, window * c_in] = sum_r grad_y[r]^T . x[r .. r + window - 1] (+ grad_b): the weight gradient of
+// ptgnn_amd_window_linear_f32 on the same kernels -- they address row r of x as x + r * ld_x, so rows of window * c_in
+// floats that start c_in floats apart are a row stride like any other.
+extern "C" int ptgnn_amd_window_weight_grad_f32(const float *x, int64_t rows, int32_t c_in, int32_t window,
+                                                const float *grad_y, int64_t ld_grad_y, int32_t n_out, float *grad_w,
+                                                float *grad_b, void *workspace, size_t workspace_bytes,
+                                                void *stream_) {
+  PTGNN_REQUIRE(rows >= 0 && c_in > 0 && window > 0 && n_out > 0 && (int64_t)c_in * window < ((int64_t)1 << 31),
+                PTGNN_AMD_EINVAL, "window_weight_grad: bad sizes");
+  const int64_t counts[1] = {rows};
+  return weight_grad_launch(x, c_in, rows, c_in * window, nullptr, nullptr, counts, grad_y, ld_grad_y, 1, n_out, 0.f, 0,
+                            grad_w, workspace, workspace_bytes, stream_, true, grad_b);
+}

@@ -1,7 +1,7 @@
 """The node embedders every model of the reference starts its forward with (graphneuralnetwork.py:160): mirrors of
-ptgnn/neuralmodels/embeddings/strelementrepresentationmodel.py:16-89 (`TokenUnitEmbedder`, `SubtokenUnitEmbedder`: same
-class names, constructor keywords, submodule creation order, initialisers, `embedding_layer` property, forward signatures
-and name-mangled parameter names, so a reference state_dict loads strictly and the same seed gives the same initial
+ptgnn/neuralmodels/embeddings/strelementrepresentationmodel.py:16-142 (`TokenUnitEmbedder`, `SubtokenUnitEmbedder`,
+`CnnConfig`, `CharUnitEmbedder`: same class names, constructor keywords, submodule creation order, initialisers,
+`embedding_layer` property, forward signatures and name-mangled parameter names, so a reference state_dict loads strictly and the same seed gives the same initial
 values).  `StrElementRepresentationModel` -- vocabulary, tensorisation, minibatching -- works unchanged around them
 (a subclass overriding `build_neural_module`).
 
@@ -9,17 +9,23 @@ GPU route:
   * TokenUnitEmbedder: the HIP row gather (backward: the deterministic segment sum over a plan of the token ids), dropout;
   * SubtokenUnitEmbedder: the fused embedding bag (csrc/embedding_bag.hip) as one autograd node -- no [B, S, D] tensor, the
     table gradient a deterministic segment sum over the bag's plan, `arg` kept for max -- then the HIP Linear of the
-    output layer and dropout.
+    output layer and dropout;
+  * CharUnitEmbedder: the first convolution over the one-hot input as one fused table sum (csrc/char_conv.hip: no one_hot,
+    no [B, L, C] tensor), the second and third as windowed Linears on the exact-fp32 MFMA GEMMs over channel-last row
+    frames (char_cnn.py: a Conv1d is a Linear whose rows overlap, forward and backward), the HIP window max, dropout.
+    Filter counts or an embedding size that are not multiples of 4, and char tables beyond the char-embed range, compose
+    the same sequence from the embedding bag (or the row gather), copied windows through `dense.linear` and the window max.
 Shapes beyond the bag's range (D not a multiple of 4, more than 32 subtokens) compose the reference's operator sequence
 from the HIP row gather and torch elementwise arithmetic.  CPU tensors take the reference's own operator order on torch
 (device dispatch as in every layer of the package); fp16 / bf16 tables are up-cast on entry and the result cast back.
 """
 import math
+from typing import NamedTuple
 
 import torch
 from torch import nn
 
-from ptgnn_amd import _lib, dense, ops, torch_route
+from ptgnn_amd import _lib, char_cnn, dense, ops, torch_route
 from ptgnn_amd.sequence import _rows
 
 _HALF = (torch.float16, torch.bfloat16)
@@ -145,3 +151,95 @@ class SubtokenUnitEmbedder(nn.Module):
         if self.__out_layer is not None:
             embedded = self.__out_layer(embedded)
         return self.__dropout_layer(embedded)
+
+
+class CnnConfig(NamedTuple):
+    l1_filters: int
+    l1_window_size: int
+    l2_filters: int
+    l2_window_size: int
+    lout_window_size: int
+
+
+def _conv_as_linear(weight: torch.Tensor) -> torch.Tensor:
+    """A Conv1d weight [F, C_in, w] as the [F, w * C_in] matrix of the windowed Linear (column k C_in + c = W[:, c, k]);
+    differentiable, so the gradient lands in Conv1d layout by autograd."""
+    return weight.permute(0, 2, 1).reshape(weight.shape[0], -1)
+
+
+class CharUnitEmbedder(nn.Module):
+    def __init__(self, num_chars: int, embedding_size: int, config: CnnConfig, dropout_rate: float = 0.0):
+        super().__init__()
+        self.__num_chars_in_vocabulary = num_chars
+        self.__conv_l1 = nn.Conv1d(in_channels=num_chars, out_channels=config.l1_filters,
+                                   kernel_size=config.l1_window_size)
+        self.__conv_l2 = nn.Conv1d(in_channels=config.l1_filters, out_channels=config.l2_filters,
+                                   kernel_size=config.l2_window_size)
+        self.__conv_l3 = nn.Conv1d(in_channels=config.l2_filters, out_channels=embedding_size,
+                                   kernel_size=config.lout_window_size, bias=False)
+        self.__dropout = nn.Dropout(p=dropout_rate)
+
+    def __windowed(self, chars, table, b1, w2, b2, w3, k1, k2, k3):
+        """Row frames (char_cnn.py): one char-embed launch, two windowed GEMMs, one window max."""
+        B, L = chars.shape
+        R, pad = L - k1 + 1, char_cnn.frame_pad(k2, k3)
+        a1 = char_cnn.char_window_embed(chars, table, b1, k1, pad)
+        a2 = char_cnn.window_linear(a1, _conv_as_linear(w2), b2, k2, pad, B * R, act="relu")
+        l3 = char_cnn.window_linear(a2, _conv_as_linear(w3), None, k3, pad, B * R)
+        return char_cnn.window_max(l3, pad, B, R, R - k2 - k3 + 2)
+
+    def __composed(self, chars, table, b1, w2, b2, w3, k1, k2, k3):
+        """The same sequence from the existing operators: window ids through the embedding bag (sum), windows materialised
+        by a copy in front of `dense.linear`, the HIP window max."""
+        B, L = chars.shape
+        C, R = self.__num_chars_in_vocabulary, L - k1 + 1
+        taps = torch.arange(k1, device=chars.device) * C
+        ids = (chars.clamp(0, C - 1).unfold(1, k1, 1) + taps).reshape(B * R, k1)
+        lengths = torch.full((B * R,), k1, dtype=torch.int64, device=chars.device)
+        if ops.embedding_bag_supported(table.shape[1], k1):
+            pooled = embedding_bag(table, ids, lengths, "sum")
+        else:
+            pooled = _composed_pool(table, ids, lengths, "sum")
+        act, rows = torch.relu(pooled + b1), R
+        for weight, bias, k, relu in ((w2, b2, k2, True), (w3, None, k3, False)):
+            width = act.shape[1]
+            windows = act.reshape(B, rows, width).unfold(1, k, 1).permute(0, 1, 3, 2).reshape(-1, k * width)
+            rows = rows - k + 1
+            act = dense.linear(windows, _conv_as_linear(weight).contiguous(), bias)
+            act = torch.relu(act) if relu else act
+        return char_cnn.window_max(act, 0, B, rows, rows)
+
+    def __device_forward(self, chars):
+        w1, b1 = self.__conv_l1.weight, self.__conv_l1.bias
+        w2, b2, w3 = self.__conv_l2.weight, self.__conv_l2.bias, self.__conv_l3.weight
+        if not chars.is_cuda or chars.dtype != torch.int64 or chars.dim() != 2:
+            raise _lib.PtgnnAmdError(f"CharUnitEmbedder: chars must be a CUDA int64 [B, max_num_chars] tensor (got "
+                                     f"{tuple(chars.shape)} {chars.dtype} on {chars.device})")
+        dt = w1.dtype
+        if dt not in _HALF and dt != torch.float32:
+            raise _lib.PtgnnAmdError(f"CharUnitEmbedder: no kernel for {dt} parameters")
+        k1, k2, k3 = w1.shape[2], w2.shape[2], w3.shape[2]
+        if chars.shape[1] < k1 + k2 + k3 - 2:
+            raise _lib.PtgnnAmdError(f"CharUnitEmbedder: {chars.shape[1]} chars are fewer than the {k1 + k2 + k3 - 2} that "
+                                     f"windows of {k1}, {k2}, {k3} need for one output position")
+        C, F1, F2, D = self.__num_chars_in_vocabulary, w1.shape[0], w2.shape[0], w3.shape[0]
+        # AMP parameters: fp32 inside, the parameters' dtype outside
+        table = w1.float().permute(2, 1, 0).reshape(k1 * C, F1)      # row k C + c = W1[:, c, k]
+        args = (chars, table, b1.float(), w2.float(), b2.float(), w3.float(), k1, k2, k3)
+        # the weight-gradient GEMMs read float4 rows of both operands: F1, F2 and D in fours (DESIGN section 2)
+        if F1 % 4 == 0 and F2 % 4 == 0 and D % 4 == 0 and ops.char_embed_supported(C, k1, F1):
+            summary = self.__windowed(*args)
+        else:
+            summary = self.__composed(*args)
+        return self.__dropout(summary.to(dt))
+
+    def forward(self, chars):
+        """
+        :param chars: [B, max_num_chars]
+        :return: [B, D]
+        """
+        if self.__conv_l1.weight.is_cuda:
+            return self.__device_forward(chars)
+        summary = torch_route.char_cnn(chars, self.__num_chars_in_vocabulary, self.__conv_l1, self.__conv_l2,
+                                       self.__conv_l3)                  # CPU tensors: the reference's operator order
+        return self.__dropout(summary)

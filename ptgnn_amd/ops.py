@@ -40,15 +40,19 @@ def get_gemm_mode() -> int:
 _AGG_FAMILY_FIRST = 64   # PTGNN_AMD_KERNEL_AGG_FIRST_: the aggregation families' id range (include/ptgnn_amd.h)
 
 
-def launch_counts(aggregation: bool = False) -> dict:
+_CHAR_FAMILY_FIRST = 128  # PTGNN_AMD_KERNEL_CHAR_FIRST_: the char-CNN kernels' id range
+
+
+def launch_counts(aggregation: bool = False, char_cnn: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
     attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward, block_attention,
-    block_attention_backward, segment_scores, segment_scores_backward, embedding_bag, embedding_bag_backward)."""
+    block_attention_backward, segment_scores, segment_scores_backward, embedding_bag, embedding_bag_backward);
+    `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward)."""
     lib = _lib.load()
     out = {}
-    for first in ((0, _AGG_FAMILY_FIRST) if aggregation else (0,)):
+    for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -61,7 +65,7 @@ def launch_counts(aggregation: bool = False) -> dict:
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True)
+    now = launch_counts(aggregation=True, char_cnn=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -1483,14 +1487,18 @@ def row_epilogue_backward(x: torch.Tensor, grad_y: torch.Tensor, flags: int, ln_
 
 
 def act_dropout_backward(grad: torch.Tensor, y: torch.Tensor, keep: Optional[torch.Tensor], scale: float,
-                         act: Optional[str]) -> torch.Tensor:
+                         act: Optional[str], out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """grad * (keep ? scale : 0) * act'(y) in one pass (ptgnn_amd_act_dropout_backward_f32); `y` is the activation's
-    output, `keep` the dropout's bool mask or None."""
+    output, `keep` the dropout's bool mask or None; `out`: optional contiguous fp32 destination of grad's size (the
+    rows of a gradient frame)."""
     lib = _lib.load()
     _require_cuda_f32("grad", grad)
     grad, y = grad.contiguous(), y.contiguous()
-    out = torch.empty_like(grad)
     n = grad.numel()
+    if out is None:
+        out = torch.empty_like(grad)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n):
+        raise _lib.PtgnnAmdError("act_dropout_backward: out must be a contiguous float32 CUDA tensor of grad's size")
     if keep is not None:
         keep = keep.contiguous()
         if keep.dtype != torch.bool or keep.numel() != n:
@@ -1900,6 +1908,219 @@ def embedding_bag_backward(grad: torch.Tensor, ids: torch.Tensor, lengths: torch
             plan.col.data_ptr(), plan.perm.data_ptr(), out.data_ptr(), D, *hub[1:], ws.data_ptr(), ws_bytes, _stream(out))
     _lib.check(rc, "ptgnn_amd_embedding_bag_backward_f32")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# char-CNN embedder (csrc/char_conv.hip and the windowed GEMM entries)
+# ------------------------------------------------------------------------------------------------
+def char_embed_supported(num_chars: int, window: int, dim: int) -> bool:
+    """Whether the char-embed kernels take the shape (ptgnn_amd_char_embed_supported: dim % 4 == 0, 4 <= dim <= 1024,
+    window <= 16, a table tile of (window * num_chars + 1) x 64 floats within one CU's LDS)."""
+    return bool(_lib.load().ptgnn_amd_char_embed_supported(int(num_chars), int(window), int(dim)))
+
+
+def char_embed_backward_chunk() -> int:
+    """Samples per chunk of the char-embed backward (ptgnn_amd_char_embed_backward_chunk)."""
+    return int(_lib.load().ptgnn_amd_char_embed_backward_chunk())
+
+
+def _char_args(chars: torch.Tensor, table: torch.Tensor, window: int, what: str):
+    _require_cuda_f32("table", table)
+    if not chars.is_cuda or chars.dtype != torch.int64 or chars.dim() != 2:
+        raise _lib.PtgnnAmdError(f"{what}: chars must be a 2-D CUDA int64 tensor")
+    window = int(window)
+    if window < 1 or table.shape[0] % window != 0 or chars.shape[1] < window:
+        raise _lib.PtgnnAmdError(f"{what}: a [{table.shape[0]}, {table.shape[1]}] table and {chars.shape[1]} chars do not "
+                                 f"fit a window of {window}")
+    return chars.contiguous(), table.contiguous(), window, table.shape[0] // window
+
+
+def _frame_rows(frame: torch.Tensor, first_row: int, rows: int, what: str) -> torch.Tensor:
+    """The contiguous [rows, width] block of `frame` that starts at `first_row` (the destination of a launch)."""
+    if not frame.is_contiguous() or first_row < 0 or first_row + rows > frame.shape[0]:
+        raise _lib.PtgnnAmdError(f"{what}: rows [{first_row}, {first_row + rows}) are not inside a contiguous frame of "
+                                 f"{frame.shape[0]} rows")
+    return frame[first_row:first_row + rows]
+
+
+def char_embed(chars: torch.Tensor, table: torch.Tensor, bias: Optional[torch.Tensor], window: int,
+               act: Optional[str] = "relu", out: Optional[torch.Tensor] = None, out_first_row: int = 0) -> torch.Tensor:
+    """a1[b R + p] = act(bias + sum_k table[k C + chars[b, p + k]]), R = L - window + 1 (ptgnn_amd_char_embed_f32: the first
+    convolution of CharUnitEmbedder over its one-hot input as a table sum).  `out`: a contiguous frame whose rows
+    [out_first_row, out_first_row + B R) receive the result (returned as a view); allocated when None."""
+    lib = _lib.load()
+    chars, table, window, C = _char_args(chars, table, window, "char_embed")
+    (B, L), D = chars.shape, table.shape[1]
+    R = L - window + 1
+    if out is None:
+        out, out_first_row = torch.empty(B * R, D, dtype=torch.float32, device=table.device), 0
+    _require_cuda_f32("out", out)
+    dst = _frame_rows(out, int(out_first_row), B * R, "char_embed")
+    if dst.shape[1] != D:
+        raise _lib.PtgnnAmdError(f"char_embed: the frame has {dst.shape[1]} columns, the table {D}")
+    if bias is not None:
+        _require_cuda_f32("bias", bias, 1)
+        if bias.shape[0] != D:
+            raise _lib.PtgnnAmdError(f"char_embed: a bias of {bias.shape[0]} entries for {D} columns")
+        bias = bias.contiguous()
+    with _timed("char_embed", bytes=8.0 * B * L + 4.0 * table.numel() + 4.0 * B * R * D):
+        rc = lib.ptgnn_amd_char_embed_f32(chars.data_ptr() if B else None, B, L, C, window, table.data_ptr(),
+                                          bias.data_ptr() if bias is not None else None, D, ACT_IDS[act],
+                                          dst.data_ptr() if B else None, D, _stream(out))
+    _lib.check(rc, "ptgnn_amd_char_embed_f32")
+    return dst
+
+
+def char_embed_backward(grad: torch.Tensor, a1: Optional[torch.Tensor], chars: torch.Tensor, num_chars: int, window: int,
+                        act: Optional[str] = "relu", want_bias: bool = True):
+    """(d table [window C, D], d bias [D] or None) of `char_embed` from grad = dL/da1 [B R, D] and the saved a1 (the ReLU
+    mask a1 > 0; not read for act None): ptgnn_amd_char_embed_backward_f32, deterministic."""
+    lib = _lib.load()
+    _require_cuda_f32("grad", grad)
+    grad = _rowmajor(grad)
+    D = grad.shape[1]
+    if not chars.is_cuda or chars.dtype != torch.int64 or chars.dim() != 2:
+        raise _lib.PtgnnAmdError("char_embed_backward: chars must be a 2-D CUDA int64 tensor")
+    chars = chars.contiguous()
+    B, L = chars.shape
+    window, C = int(window), int(num_chars)
+    R = L - window + 1
+    relu = ACT_IDS[act] != 0
+    if R < 1 or grad.shape[0] != B * R:
+        raise _lib.PtgnnAmdError(f"char_embed_backward: grad {tuple(grad.shape)} for {B} samples of {R} rows")
+    if relu:
+        _require_cuda_f32("a1", a1)
+        a1 = _rowmajor(a1)
+        if tuple(a1.shape) != (B * R, D):
+            raise _lib.PtgnnAmdError(f"char_embed_backward: a1 {tuple(a1.shape)} is not grad's shape")
+    g_table = torch.empty(window * C, D, dtype=torch.float32, device=grad.device)
+    g_bias = torch.empty(D, dtype=torch.float32, device=grad.device) if want_bias else None
+    ws_bytes = int(lib.ptgnn_amd_char_embed_backward_workspace_bytes(B, C, window, D))
+    ws = _workspace(ws_bytes, grad.device)
+    with _timed("char_embed_backward", bytes=8.0 * B * R * D + 8.0 * B * L + 2.0 * ws_bytes):
+        rc = lib.ptgnn_amd_char_embed_backward_f32(grad.data_ptr() if B else None, _ld(grad) if B else D,
+                                                   a1.data_ptr() if relu and B else None, _ld(a1) if relu and B else D,
+                                                   chars.data_ptr() if B else None, B, L, C, window, D, ACT_IDS[act],
+                                                   g_table.data_ptr(), g_bias.data_ptr() if want_bias else None,
+                                                   ws.data_ptr(), ws_bytes, _stream(g_table))
+    _lib.check(rc, "ptgnn_amd_char_embed_backward_f32")
+    return g_table, g_bias
+
+
+def _window_frame(x: torch.Tensor, first_row: int, rows: int, window: int, what: str):
+    _require_cuda_f32("x", x)
+    first_row, rows, window = int(first_row), int(rows), int(window)
+    if not x.is_contiguous():
+        raise _lib.PtgnnAmdError(f"{what}: the frame must be contiguous (a window spans packed rows; a strided view would "
+                                 "have to be copied)")
+    if window < 1 or rows < 0 or first_row < 0 or first_row + rows + window - 1 > x.shape[0]:
+        raise _lib.PtgnnAmdError(f"{what}: rows [{first_row}, {first_row + rows}) with a window of {window} reach outside "
+                                 f"the frame's {x.shape[0]} rows")
+    return first_row, rows, window
+
+
+def window_linear(x: torch.Tensor, first_row: int, rows: int, window: int, weight: torch.Tensor,
+                  bias: Optional[torch.Tensor] = None, act: Optional[str] = None, out: Optional[torch.Tensor] = None,
+                  out_first_row: int = 0) -> torch.Tensor:
+    """y[r] = act(W . x[first_row + r .. first_row + r + window - 1] + b) for r < rows (ptgnn_amd_window_linear_f32): a
+    Conv1d over the channel-last frame `x` [T, c_in] (the frame itself and the window, not an as_strided view), weight
+    [n_out, window * c_in].  `out`: a contiguous frame whose rows [out_first_row, out_first_row + rows) receive y."""
+    lib = _lib.load()
+    first_row, rows, window = _window_frame(x, first_row, rows, window, "window_linear")
+    _require_cuda_f32("weight", weight)
+    weight = weight.contiguous()
+    c_in, n_out = x.shape[1], weight.shape[0]
+    if weight.shape[1] != window * c_in:
+        raise _lib.PtgnnAmdError(f"window_linear: weight {tuple(weight.shape)} for a window of {window} x {c_in} columns")
+    if out is None:
+        out, out_first_row = torch.empty(rows, n_out, dtype=torch.float32, device=x.device), 0
+    _require_cuda_f32("out", out)
+    dst = _frame_rows(out, int(out_first_row), rows, "window_linear")
+    if dst.shape[1] != n_out:
+        raise _lib.PtgnnAmdError(f"window_linear: the output frame has {dst.shape[1]} columns, the weight {n_out} rows")
+    if bias is not None:
+        _require_cuda_f32("bias", bias, 1)
+        if bias.shape[0] != n_out:
+            raise _lib.PtgnnAmdError(f"window_linear: a bias of {bias.shape[0]} entries for {n_out} output columns")
+        bias = bias.contiguous()
+    k = window * c_in
+    with _timed("linear", flops=2.0 * rows * k * n_out, bytes=4.0 * (rows * c_in + n_out * k + rows * n_out)):
+        rc = lib.ptgnn_amd_window_linear_f32(x[first_row:].data_ptr() if rows else None, rows, c_in, window, c_in,
+                                             weight.data_ptr(), n_out, bias.data_ptr() if bias is not None else None,
+                                             ACT_IDS[act], dst.data_ptr() if rows else None, n_out, _stream(out))
+    _lib.check(rc, "ptgnn_amd_window_linear_f32")
+    return dst
+
+
+def window_weight_grad(x: torch.Tensor, first_row: int, rows: int, window: int, grad_y: torch.Tensor,
+                       want_bias: bool = False):
+    """grad_w [n_out, window * c_in] = sum_r grad_y[r]^T . x[first_row + r .. + window - 1] (and grad_b = column sums of
+    grad_y with `want_bias`): the weight gradient of `window_linear` (ptgnn_amd_window_weight_grad_f32)."""
+    lib = _lib.load()
+    first_row, rows, window = _window_frame(x, first_row, rows, window, "window_weight_grad")
+    _require_cuda_f32("grad_y", grad_y)
+    grad_y = _rowmajor(grad_y)
+    c_in, n_out = x.shape[1], grad_y.shape[1]
+    if grad_y.shape[0] != rows:
+        raise _lib.PtgnnAmdError("window_weight_grad: grad_y does not have `rows` rows")
+    k = window * c_in
+    if rows == 0:
+        gw = torch.zeros(n_out, k, dtype=torch.float32, device=x.device)
+        return (gw, torch.zeros(n_out, dtype=torch.float32, device=x.device)) if want_bias else gw
+    grad_w = torch.empty(n_out, k, dtype=torch.float32, device=x.device)
+    grad_b = torch.empty(n_out, dtype=torch.float32, device=x.device) if want_bias else None
+    ws_bytes = lib.ptgnn_amd_edge_wgrad_workspace_bytes(rows, 1, n_out, k)
+    ws = _workspace(ws_bytes, x.device)
+    with _timed("linear_weight_grad", flops=2.0 * rows * k * n_out, bytes=4.0 * (rows * c_in + rows * n_out + n_out * k)):
+        rc = lib.ptgnn_amd_window_weight_grad_f32(x[first_row:].data_ptr(), rows, c_in, window, grad_y.data_ptr(),
+                                                  _ld(grad_y), n_out, grad_w.data_ptr(),
+                                                  grad_b.data_ptr() if want_bias else None, ws.data_ptr(), ws_bytes,
+                                                  _stream(grad_w))
+    _lib.check(rc, "ptgnn_amd_window_weight_grad_f32")
+    return (grad_w, grad_b) if want_bias else grad_w
+
+
+def window_max(x: torch.Tensor, first_row: int, num_samples: int, rows_per_sample: int, valid: int,
+               return_arg: bool = False):
+    """out[b] = max over the first `valid` of the `rows_per_sample` rows of sample b, which start at row `first_row` of the
+    frame `x` (ptgnn_amd_window_max_f32); `return_arg`: also the int32 [B, D] lowest winning positions."""
+    lib = _lib.load()
+    _require_cuda_f32("x", x)
+    B, R, D = int(num_samples), int(rows_per_sample), x.shape[1]
+    src = _frame_rows(x, int(first_row), B * R, "window_max")
+    out = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    arg = torch.empty(B, D, dtype=torch.int32, device=x.device) if return_arg else None
+    with _timed("window_max", bytes=4.0 * B * int(valid) * D + 4.0 * B * D * (2 if return_arg else 1)):
+        rc = lib.ptgnn_amd_window_max_f32(src.data_ptr() if B else None, D, B, R, int(valid), D,
+                                          out.data_ptr() if B else None, D,
+                                          arg.data_ptr() if return_arg and B else None, _stream(out))
+    _lib.check(rc, "ptgnn_amd_window_max_f32")
+    return (out, arg) if return_arg else out
+
+
+def window_max_backward(grad: torch.Tensor, arg: torch.Tensor, rows_per_sample: int, out: Optional[torch.Tensor] = None,
+                        out_first_row: int = 0) -> torch.Tensor:
+    """The [B R, D] gradient rows of `window_max` (ptgnn_amd_window_max_backward_f32): grad[b, d] at row arg[b, d] of
+    sample b, exact zeros elsewhere; written into rows [out_first_row, out_first_row + B R) of the frame `out`."""
+    lib = _lib.load()
+    _require_cuda_f32("grad", grad)
+    grad = _rowmajor(grad)
+    (B, D), R = grad.shape, int(rows_per_sample)
+    if not arg.is_cuda or arg.dtype != torch.int32 or tuple(arg.shape) != (B, D):
+        raise _lib.PtgnnAmdError("window_max_backward: arg must be the forward's int32 [B, D] positions")
+    arg = arg.contiguous()
+    if out is None:
+        out, out_first_row = torch.empty(B * R, D, dtype=torch.float32, device=grad.device), 0
+    _require_cuda_f32("out", out)
+    dst = _frame_rows(out, int(out_first_row), B * R, "window_max_backward")
+    if dst.shape[1] != D:
+        raise _lib.PtgnnAmdError(f"window_max_backward: the frame has {dst.shape[1]} columns, grad {D}")
+    with _timed("window_max_backward", bytes=4.0 * B * R * D + 8.0 * B * D):
+        rc = lib.ptgnn_amd_window_max_backward_f32(grad.data_ptr() if B else None, _ld(grad) if B else D,
+                                                   arg.data_ptr() if B else None, B, R, D,
+                                                   dst.data_ptr() if B else None, D, _stream(out))
+    _lib.check(rc, "ptgnn_amd_window_max_backward_f32")
+    return dst
 
 
 def graph_norm_supported(dim: int) -> bool:

@@ -407,3 +407,14 @@ def subtoken_embed(token_idxs: torch.Tensor, lengths: torch.Tensor, table: torch
         embedded.masked_fill_(mask=~mask.unsqueeze(-1), value=-math.inf)
         return embedded.max(dim=-2)[0]
     raise ValueError(f'Unrecognized subtoken combination "{kind}".')
+
+
+def char_cnn(chars: torch.Tensor, num_chars: int, conv1: nn.Conv1d, conv2: nn.Conv1d, conv3: nn.Conv1d) -> torch.Tensor:
+    """The trunk of CharUnitEmbedder.forward (strelementrepresentationmodel.py:133-141) on host tensors, operator for
+    operator: one-hot characters as the channels of a [B, C, L] float signal, three convolutions with a ReLU in front of
+    the second and the third, the maximum over the remaining positions -> [B, D] (dropout is the caller's)."""
+    _host_only(chars, conv1.weight)
+    signal = nn.functional.one_hot(chars, num_chars).transpose(1, 2).float()      # [B, C, L]
+    for conv in (conv1, conv2):
+        signal = nn.functional.relu(conv(signal))                                  # [B, F, positions left]
+    return torch.max(conv3(signal), dim=-1)[0]
