@@ -12,6 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from ptgnn_amd import _lib
+from ptgnn_amd._readback import LOCK, Backoff, Readback, take_arrived
 
 REDUCE_IDS = {"sum": 0, "add": 0, "mean": 1, "max": 2, "min": 3}
 EPI_NONE, EPI_GELU, EPI_LAYERNORM, EPI_GELU_LAYERNORM = 0, 1, 2, 3
@@ -162,6 +163,35 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
 
 
+class _DeviceState:
+    """What the host keeps about ONE GPU between calls: the node-id guard's accumulator and its read-back (at most one
+    in flight), the shared-message and hub back-offs with the read-backs that drive them, the side stream of the
+    overlapped plan build and the plan-build control blocks per stream.  The back-offs, the pending lists and the guard's
+    read-back slot are changed under `_readback.LOCK` only.  Device objects are created on first use, outside the lock
+    (looking a state up touches no GPU); of two accumulators created at once the first one stored is the one used."""
+    __slots__ = ("device", "bad_ids", "bad_readback", "uniq_backoff", "uniq_pending", "hub_backoff", "hub_pending",
+                 "side_stream", "plan_control")
+
+    def __init__(self, index: int):
+        self.device = torch.device("cuda", index)
+        self.bad_ids = self.bad_readback = self.side_stream = None     # bad_ids: int32 [1] device accumulator
+        self.uniq_backoff, self.uniq_pending = Backoff(), []     # row counts in flight, tag = (edges, edge types)
+        self.hub_backoff, self.hub_pending = Backoff(), []       # hub counts in flight, tag = weakref to the plan
+        self.plan_control = {}                                   # stream handle -> zero-at-rest control block
+
+
+_STATES = {}    # device index -> _DeviceState
+
+
+def _device_state(device) -> _DeviceState:
+    key = torch.device(device).index or 0
+    st = _STATES.get(key)
+    if st is None:
+        with LOCK:
+            st = _STATES.setdefault(key, _DeviceState(key))
+    return st
+
+
 # ------------------------------------------------------------------------------------------------
 # graph plan
 # ------------------------------------------------------------------------------------------------
@@ -192,7 +222,7 @@ class GraphPlan:
         self.hub_entries = self.hub_count = None   # (chunk, row) pairs of rows > HUB_THRESHOLD
         self._slot_rows = self._ident = self._transposed = None
         self._uniq = None      # UniqueMessages | pending read-back | False (not worth it / not applicable)
-        self._hub_posted = False   # the hub count's asynchronous read-back has been posted (ops.gather_update_supported)
+        self._hub_posted = False   # the hub count's Readback is pending on the device's state (ops.gather_update_supported)
         self._has_hubs = None      # ... and has arrived: True / False (None = not known on the host)
 
     def may_have_hubs(self) -> bool:
@@ -301,27 +331,24 @@ class GraphPlan:
 class UniqueMessages:
     """slot_row int32 [E]: message row of every CSR slot; unique_src int64: source node of every message row
     (type-major); edge_table: the device-resident launch table of ptgnn_amd_edge_linear_shared_f32; capacity: rows the
-    message table must hold; counts: device int64 [T + 1] rows per type and in all."""
-    __slots__ = ("slot_row", "unique_src", "edge_table", "capacity", "counts", "num_edges", "num_types", "_host",
-                 "_event", "_counts")
+    message table must hold; counts: device int64 [T + 1] rows per type and in all (`_readback`: their Readback, posted
+    with the build unless it was captured)."""
+    __slots__ = ("slot_row", "unique_src", "edge_table", "capacity", "counts", "num_edges", "num_types", "_readback",
+                 "_counts")
 
     def __init__(self, slot_row, unique_src, edge_table, capacity, counts, num_edges, num_types):
         self.slot_row, self.unique_src, self.edge_table = slot_row, unique_src, edge_table
         self.capacity, self.counts, self.num_edges, self.num_types = capacity, counts, num_edges, num_types
-        self._host = self._event = self._counts = None
+        self._readback = self._counts = None
 
     def host_counts(self, wait: bool = False) -> Optional[List[int]]:
         """Rows per edge type + the total, once the asynchronous read-back has arrived (None before).  `wait` blocks
         on the read-back's own event -- not on the stream: work enqueued after the bookkeeping keeps running."""
-        if self._counts is None and self._event is not None:
-            if wait:
-                self._event.synchronize()
-            if self._event.query():
-                self._counts = [int(c) for c in self._host.tolist()]
-                _PINNED_FREE.setdefault(int(self._host.numel()), []).append(self._host)
-                self._host = self._event = None
-        elif self._counts is None and wait:     # built under graph capture: no read-back was posted
-            self._counts = [int(c) for c in self.counts.tolist()]
+        if self._counts is None:
+            if self._readback is not None:
+                self._counts = self._readback.values(wait)
+            elif wait:                          # built under graph capture: no read-back was posted
+                self._counts = [int(c) for c in self.counts.tolist()]
         return self._counts
 
     def rows(self, wait: bool = False) -> Optional[int]:
@@ -341,28 +368,17 @@ class UniqueMessages:
 
 # Sharing message rows costs ~6 small launches per minibatch.  Whether it pays is only known afterwards (the row counts
 # come back asynchronously): when the minibatches seen so far saved fewer than UNIQUE_MIN_SAVING of their rows, the
-# next UNIQUE_BACKOFF plans keep the per-edge form, then one is probed again.
+# next UNIQUE_BACKOFF plans of that device keep the per-edge form, then one is probed again.
 UNIQUE_MIN_SAVING = float(os.environ.get("PTGNN_AMD_UNIQUE_MIN_SAVING", "0.05"))
 UNIQUE_MIN_EDGES = int(os.environ.get("PTGNN_AMD_UNIQUE_MIN_EDGES", "65536"))
 UNIQUE_BACKOFF = 16
-_UNIQ_PENDING: List["UniqueMessages"] = []
-_UNIQ_SKIP = [0]
-_PINNED_FREE = {}    # words -> pinned int64 buffers not in flight (pinning host memory costs far more than the kernels)
 
 
-def _pinned_words(n: int) -> torch.Tensor:
-    free = _PINNED_FREE.setdefault(n, [])
-    return free.pop() if free else torch.empty(n, dtype=torch.int64).pin_memory()
-
-
-def _poll_unique_stats() -> None:
-    for u in list(_UNIQ_PENDING):
-        rows = u.rows()
-        if rows is not None:
-            _UNIQ_PENDING.remove(u)
-            if u.num_edges > 0 and rows > (1.0 - UNIQUE_MIN_SAVING) * u.num_edges:
-                _UNIQ_SKIP[0] = UNIQUE_BACKOFF
-    del _UNIQ_PENDING[:-8]
+def _poll_unique_stats(st: _DeviceState) -> None:
+    for readback in take_arrived(st.uniq_pending, keep=8):
+        num_edges, num_types = readback.tag
+        if num_edges > 0 and readback.values()[num_types] > (1.0 - UNIQUE_MIN_SAVING) * num_edges:
+            st.uniq_backoff.trip(UNIQUE_BACKOFF)
 
 
 def _launch_unique_sources(plan: "GraphPlan") -> Optional[UniqueMessages]:
@@ -371,13 +387,13 @@ def _launch_unique_sources(plan: "GraphPlan") -> Optional[UniqueMessages]:
     if plan._adj is None or E < UNIQUE_MIN_EDGES or T > 64:
         return None
     capturing = torch.cuda.is_current_stream_capturing()
+    dev = plan.col.device
+    st = _device_state(dev)
     if not capturing:
-        _poll_unique_stats()
-        if _UNIQ_SKIP[0] > 0:
-            _UNIQ_SKIP[0] -= 1
+        _poll_unique_stats(st)
+        if st.uniq_backoff.consume():
             return None
     plan.wait()
-    dev = plan.col.device
     cap = max(1, min(E, ns * T))
     slot_row = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
     unique_src = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -392,12 +408,9 @@ def _launch_unique_sources(plan: "GraphPlan") -> Optional[UniqueMessages]:
     _lib.check(rc, "ptgnn_amd_unique_sources")
     u = UniqueMessages(slot_row, unique_src, table, cap, counts, E, T)
     if not capturing:
-        u._host = _pinned_words(T + 1)
-        with torch.cuda.device(dev):
-            u._host.copy_(counts, non_blocking=True)
-            u._event = torch.cuda.Event()
-            u._event.record(torch.cuda.current_stream(dev))
-        _UNIQ_PENDING.append(u)
+        u._readback = Readback(counts, tag=(E, T))
+        with LOCK:
+            st.uniq_pending.append(u._readback)
     return u
 
 
@@ -440,27 +453,25 @@ def edge_linear_shared(x: torch.Tensor, uniq: UniqueMessages, weights: Sequence[
 # ------------------------------------------------------------------------------------------------
 # The reference device-asserts on an out-of-range node id (F.embedding, gatedmessagepassing.py:54-56).
 # Here the plan build clamps such ids to row 0 (nothing is ever read or written out of bounds) and counts
-# them in a per-device accumulator; the count travels back through a pinned host word WITHOUT a sync and
-# is looked at on later plan builds (or on demand: `check_indices(sync=True)`).  A non-zero count raises
+# them in a per-device accumulator (`_DeviceState.bad_ids`); the count travels back through a Readback WITHOUT a sync
+# and is looked at on later plan builds (or on demand: `check_indices(sync=True)`).  A non-zero count raises
 # PtgnnAmdError: the results of the offending minibatch are garbage, like the reference's would be.
-_BAD = {}    # device index -> {"dev": int32[1] accumulator, "host": pinned int32[1], "event": Event | None}
 VALIDATE_INDICES = os.environ.get("PTGNN_AMD_VALIDATE", "async")   # "async" | "sync" | "off"
 
 
-def _bad_state(device):
-    key = torch.device(device).index or 0
-    st = _BAD.get(key)
-    if st is None:
-        st = {"dev": torch.zeros(1, dtype=torch.int32, device=device),
-              "host": torch.zeros(1, dtype=torch.int32).pin_memory(), "event": None}
-        _BAD[key] = st
-    return st
+def _bad_accumulator(st: _DeviceState) -> torch.Tensor:
+    if st.bad_ids is None:
+        fresh = torch.zeros(1, dtype=torch.int32, device=st.device)
+        with LOCK:
+            if st.bad_ids is None:
+                st.bad_ids = fresh
+    return st.bad_ids
 
 
-def _raise_bad(st, count: int):
-    st["dev"].zero_()
-    st["host"].zero_()
-    st["event"] = None
+def _raise_bad(st: _DeviceState, count: int):
+    st.bad_ids.zero_()
+    with LOCK:
+        st.bad_readback = None      # one still in flight carries the count that is being reported here
     raise _lib.PtgnnAmdError(
         f"{count} node id(s) outside [0, num_nodes) reached the graph plan build (adjacency lists / scatter "
         "index / dim_size too small). They were clamped to row 0 so no memory was touched out of bounds, but "
@@ -468,35 +479,35 @@ def _raise_bad(st, count: int):
 
 
 def check_indices(device=None, sync: bool = False) -> None:
-    """Raise if a plan build on `device` saw an out-of-range node id.  sync=False only looks at read-backs
-    that have already completed (no host-device synchronisation)."""
-    for key, st in list(_BAD.items()):
-        if device is not None and (torch.device(device).index or 0) != key:
+    """Raise if a plan build on `device` (None: any device) saw an out-of-range node id.  sync=True reads the device's
+    accumulator; sync=False only looks at a read-back that has already arrived (no host-device synchronisation)."""
+    for st in list(_STATES.values()) if device is None else [_device_state(device)]:
+        if st.bad_ids is None:
             continue
         if sync:
-            n = int(st["dev"].item())
-            if n:
-                _raise_bad(st, n)
-            continue
-        ev = st["event"]
-        if ev is not None and ev.query():
-            st["event"] = None
-            n = int(st["host"][0])
-            if n:
-                _raise_bad(st, n)
+            n = int(st.bad_ids.item())
+        else:
+            rb = st.bad_readback
+            got = rb.values() if rb is not None else None
+            if got is None:
+                continue
+            with LOCK:
+                mine = st.bad_readback is rb
+                if mine:
+                    st.bad_readback = None
+            n = got[0] if mine else 0       # the thread that cleared the slot reports the count, no other
+        if n:
+            _raise_bad(st, n)
 
 
-def _post_plan_readback(st) -> None:
-    if st["event"] is None:   # one read-back in flight at a time
-        dev = st["dev"].device
-        with torch.cuda.device(dev):     # the copy and its event belong to the stream of the plan's device
-            st["host"].copy_(st["dev"], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-        st["event"] = ev
-
-
-_PLAN_CONTROL = {}   # (device index, stream handle) -> zero-at-rest control block of the plan build
+def _post_bad_readback(st: _DeviceState) -> None:
+    if st.bad_readback is None:     # one read-back in flight at a time
+        rb = Readback(st.bad_ids)   # (a HIP call: outside the lock)
+        with LOCK:
+            if st.bad_readback is None:
+                st.bad_readback = rb
+        # a thread that lost this race drops its copy of the same accumulator; its buffer is still being written, so it
+        # does not go back to the pool
 
 
 def _plan_control(dev: torch.device) -> torch.Tensor:
@@ -507,10 +518,10 @@ def _plan_control(dev: torch.device) -> torch.Tensor:
     nbytes = int(_lib.load().ptgnn_amd_csr_control_bytes())
     if torch.cuda.is_current_stream_capturing():
         return torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ctl = _PLAN_CONTROL.get(key)
+    blocks, key = _device_state(dev).plan_control, torch.cuda.current_stream(dev).cuda_stream
+    ctl = blocks.get(key)
     if ctl is None:
-        ctl = _PLAN_CONTROL[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        ctl = blocks.setdefault(key, torch.zeros(nbytes, dtype=torch.uint8, device=dev))
     return ctl
 
 
@@ -560,7 +571,7 @@ def build_plan(adjacency_lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], num
     bad = None
     capturing = torch.cuda.is_current_stream_capturing()
     if VALIDATE_INDICES != "off":
-        bad = _bad_state(dev)
+        bad = _device_state(dev)
         if not capturing:
             check_indices(dev)      # surfaces an earlier minibatch's bad ids (never blocks)
     # algorithmic bytes: read 16 B/edge (int64 src+dst), write 4 B/edge col (+4 perm) + rowptr
@@ -574,11 +585,11 @@ def build_plan(adjacency_lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], num
                                      HUB_THRESHOLD if hub_entries is not None else 0,
                                      hub_entries.data_ptr() if hub_entries is not None else None,
                                      hub_count.data_ptr() if hub_count is not None else None,
-                                     bad["dev"].data_ptr() if bad is not None else None,
+                                     _bad_accumulator(bad).data_ptr() if bad is not None else None,
                                      control.data_ptr(),
                                      ws.data_ptr(), ws_bytes, _stream(rowptr))
     if rc != 0:
-        _PLAN_CONTROL.clear()       # a build that stopped half-way may have left its control block non-zero
+        _device_state(dev).plan_control.clear()     # a build that stopped half-way may have left its block non-zero
     _lib.check(rc, "ptgnn_amd_csr_build")
     if bad is not None:
         if capturing:
@@ -586,7 +597,7 @@ def build_plan(adjacency_lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], num
         elif VALIDATE_INDICES == "sync":
             check_indices(dev, sync=True)
         else:
-            _post_plan_readback(bad)
+            _post_bad_readback(bad)
     # `ws`, `srcs`, `dsts` are stream-ordered: torch's caching allocator only hands their memory to
     # later work on the same stream, so dropping the references here is safe.
     # col/perm keep >= 1 element so their base pointer is never null (E == 0 batches are legal)
@@ -626,19 +637,19 @@ def shard_index(adjacency_lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], lo
     cn = CntArr(*counts)
     # global source ids outside [0, total_nodes) are counted like the plan build's bad ids (after the remap they are
     # ordinary own / halo rows, which that guard can no longer see)
-    bad = _bad_state(dev) if VALIDATE_INDICES != "off" else None
+    bad = _device_state(dev) if VALIDATE_INDICES != "off" else None
     with _timed("shard_index", bytes=E * 32.0 + total_nodes / 4.0):
         rc = lib.ptgnn_amd_shard_index(ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(dp, ctypes.c_void_p),
                                        ctypes.cast(cn, ctypes.c_void_p), T, int(lo), int(hi), bounds.data_ptr(), world,
                                        int(total_nodes), local_src.data_ptr(), local_dst.data_ptr(), need.data_ptr(),
-                                       cap, stats.data_ptr(), bad["dev"].data_ptr() if bad is not None else None,
+                                       cap, stats.data_ptr(), _bad_accumulator(bad).data_ptr() if bad is not None else None,
                                        ws.data_ptr(), ws_bytes, _stream(local_src))
     _lib.check(rc, "ptgnn_amd_shard_index")
     if bad is not None and not torch.cuda.is_current_stream_capturing():
         if VALIDATE_INDICES == "sync":
             check_indices(dev, sync=True)
         else:
-            _post_plan_readback(bad)
+            _post_bad_readback(bad)
     return local_src[:E], local_dst[:E], counts, need, stats
 
 
@@ -675,16 +686,13 @@ HUB_THRESHOLD = 2048
 # beside them): cfg2 0.411 -> 0.456 ms per step, cfg3 4.34 -> 4.39 ms -- the co-resident plan workgroups take LDS
 # bandwidth and issue slots from the MFMA kernel for longer than the plan build lasts on an idle chip.
 OVERLAP_PLAN_BUILD = os.environ.get("PTGNN_AMD_OVERLAP_PLAN", "0") not in ("", "0")
-_SIDE_STREAMS = {}
 
 
 def _side_stream(device) -> "torch.cuda.Stream":
-    key = torch.device(device).index
-    st = _SIDE_STREAMS.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _SIDE_STREAMS[key] = st
-    return st
+    st = _device_state(device)
+    if st.side_stream is None:
+        st.side_stream = torch.cuda.Stream(device=device)
+    return st.side_stream
 
 
 def _build_plan_overlapped(adjacency_lists, num_nodes: int) -> GraphPlan:
@@ -819,30 +827,25 @@ GATHER_UPDATE_MAX_EDGES = 1 << 21
 # ... and plans without hub rows: the fused kernel folds every row serially, so a row of > HUB_THRESHOLD in-edges (which the
 # unfused aggregation splits over chunk workgroups) would set its duration.  Whether a plan has such rows is known on the
 # device only (`plan.hub_count`); it is read back asynchronously once per plan, and a non-zero count sends the next
-# GATHER_UPDATE_BACKOFF calls to the unfused pair (both forms are exact: this is a speed decision, never a correctness one).
+# GATHER_UPDATE_BACKOFF calls on that device to the unfused pair (both forms are exact: this is a speed decision, never a
+# correctness one).
 GATHER_UPDATE_BACKOFF = 64
-_HUB_PENDING: List[Tuple["torch.cuda.Event", torch.Tensor, "weakref.ref"]] = []
-_HUB_SKIP = [0]
 
 
-def _poll_hub_counts() -> None:
-    for item in list(_HUB_PENDING):
-        ev, host, plan_ref = item
-        if ev.query():
-            _HUB_PENDING.remove(item)
-            hubs = int(host[0]) > 0
-            plan = plan_ref()
-            if plan is not None:
-                plan._has_hubs = hubs        # a fact of THIS plan: decides every later call over it
-            if hubs:
-                _HUB_SKIP[0] = GATHER_UPDATE_BACKOFF
-            _PINNED_FREE.setdefault(1, []).append(host)
-    del _HUB_PENDING[:-16]
+def _poll_hub_counts(st: _DeviceState) -> None:
+    for readback in take_arrived(st.hub_pending, keep=16):
+        hubs = readback.values()[0] > 0
+        plan = readback.tag()
+        if plan is not None:
+            plan._has_hubs = hubs            # a fact of THIS plan: decides every later call over it
+        if hubs:
+            st.hub_backoff.trip(GATHER_UPDATE_BACKOFF)
 
 
 def gather_update_supported(msg_dim: int, out_dim: int, plan: "GraphPlan") -> bool:
     """Whether the fused aggregation + update launch serves this call.  Callers evaluate their cheaper conditions
-    (gradients needed, dropout) FIRST: a True here may consume one step of the back-off below."""
+    (gradients needed, dropout) FIRST: a call whose plan does not know its own hub count yet consumes one step of the hub
+    back-off of the plan's device (`_DeviceState.hub_backoff`; under stream capture it is only looked at)."""
     if not (GATHER_UPDATE and plan.num_edges < GATHER_UPDATE_MAX_EDGES
             and bool(_lib.load().ptgnn_amd_gather_update_supported(int(msg_dim), int(out_dim)))):
         return False
@@ -850,26 +853,21 @@ def gather_update_supported(msg_dim: int, out_dim: int, plan: "GraphPlan") -> bo
         return True
     if plan._has_hubs is not None:          # the plan's own count has come back (a cached plan of full-graph inference)
         return not plan._has_hubs
+    st = _device_state(plan.hub_count.device)
     if torch.cuda.is_current_stream_capturing():
-        return _HUB_SKIP[0] == 0
-    _poll_hub_counts()
+        return st.hub_backoff.steps == 0
+    _poll_hub_counts(st)
     if plan._has_hubs is not None:
         return not plan._has_hubs
-    if not plan._hub_posted:
-        plan._hub_posted = True
+    with LOCK:
+        post, plan._hub_posted = not plan._hub_posted, True
+    if post:
         plan.wait()
-        dev = plan.hub_count.device
-        host = _pinned_words(1)
-        with torch.cuda.device(dev):
-            host.copy_(plan.hub_count.to(torch.int64), non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-        _HUB_PENDING.append((ev, host, weakref.ref(plan)))
-    # this plan's count is still in flight: go by what the recent plans reported
-    if _HUB_SKIP[0] > 0:
-        _HUB_SKIP[0] -= 1
-        return False
-    return True
+        readback = Readback(plan.hub_count, tag=weakref.ref(plan))
+        with LOCK:
+            st.hub_pending.append(readback)
+    # this plan's count is still in flight: go by what the recent plans of this device reported
+    return not st.hub_backoff.consume()
 
 
 def gather_update(msgs: torch.Tensor, plan: GraphPlan, reduce: str, col: torch.Tensor, type_bits: int, epilogue: int,

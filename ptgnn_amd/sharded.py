@@ -28,6 +28,7 @@ import torch
 import torch.distributed as dist
 
 from ptgnn_amd import ops
+from ptgnn_amd._readback import Readback
 
 Adj = List[Tuple[torch.Tensor, torch.Tensor]]
 
@@ -90,7 +91,7 @@ class ExchangePlanner:
         self.send_caps: Optional[List[int]] = None      # rows this rank sends per peer
         self.global_stats: Tuple[int, int, int] = (0, 0, 0)
         self.ever_cut = False
-        self._pending = None                              # (host tensor, event | None) of the previous build
+        self._pending: Optional[Readback] = None          # the previous build's counts, on their way to the host
         self._layout = None                               # device tensors derived from the capacities (rebuilt on growth)
         self.builds = self.exact_builds = self.overflows = 0
         self.last_overflow = 0
@@ -116,29 +117,17 @@ class ExchangePlanner:
         self.ever_cut = self.ever_cut or int(stats[0]) > 0
 
     def post(self, values: torch.Tensor) -> None:
-        """Start the asynchronous copy of this build's counts to the host (read by the next build)."""
-        if values.is_cuda:
-            host = ops._pinned_words(int(values.numel()))       # pooled: pinning fresh host memory costs more than the build
-            with torch.cuda.device(values.device):
-                host.copy_(values, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(values.device))
-            self._pending = (host, ev)
-        else:
-            self._pending = (values.clone(), None)
+        """Start the asynchronous copy of this build's counts to the host (read by the next build; CPU counts, as under
+        gloo, are there at once)."""
+        self._pending = Readback(values)
 
     def collect(self, world: int) -> None:
         """Look at the previous build's counts (posted one minibatch ago): learn from them; an overflow raises."""
-        if self._pending is None:
+        pending, self._pending = self._pending, None
+        if pending is None:
             return
-        host, ev = self._pending
-        self._pending = None
-        if ev is not None:
-            ev.synchronize()       # recorded a whole minibatch ago: already complete, the host does not wait
+        vals = pending.values(wait=True)    # posted a whole minibatch ago: already there, the host does not wait
         HOST_READS["late"] += 1
-        vals = [int(v) for v in host.tolist()]
-        if ev is not None:
-            ops._PINNED_FREE.setdefault(int(host.numel()), []).append(host)
         stats, need, got = vals[:5], vals[5: 5 + world], vals[5 + world: 5 + 2 * world]
         self.learn(need, got, stats)
         self.last_overflow = stats[4]

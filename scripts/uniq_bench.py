@@ -17,7 +17,7 @@ adj.append((ar, ar))
 for i in range(12):
     ops.clear_plan_cache()
     plan = ops.plan_for(adj, N)
-    ops._UNIQ_SKIP[0] = 0
+    ops._device_state("cuda").uniq_backoff.trip(0)
     u = plan.unique_messages()
 torch.cuda.synchronize()
 print("rows", u.rows(wait=True), "edges", plan.num_edges)

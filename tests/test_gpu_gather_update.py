@@ -88,7 +88,8 @@ def test_mlp_layer_hidden_64_takes_the_fused_kernel_and_matches_the_oracle(agg, 
     layer = layer.cuda()
     cadj = to_cuda_adj(adj)
     outs = {}
-    monkeypatch.setattr(ops, "_HUB_SKIP", [0])       # an earlier test's hub plan must not send this one to the unfused pair
+    # an earlier test's hub plan must not send this one to the unfused pair
+    monkeypatch.setattr(ops._device_state("cuda").hub_backoff, "steps", 0)
     for fused in (True, False):
         monkeypatch.setattr(ops, "GATHER_UPDATE", fused)
         ops.clear_plan_cache()
@@ -160,15 +161,16 @@ def test_a_plan_with_hub_rows_sends_the_following_calls_to_the_unfused_pair(monk
     """The fused kernel folds every row serially; a plan that reports hub rows (count read back asynchronously, no host
     synchronisation on the hot path) switches the next GATHER_UPDATE_BACKOFF decisions to gather_reduce + linear."""
     from ptgnn_amd import ops
-    monkeypatch.setattr(ops, "_HUB_SKIP", [0])
-    monkeypatch.setattr(ops, "_HUB_PENDING", [])
+    st = ops._device_state("cuda")
+    monkeypatch.setattr(st.hub_backoff, "steps", 0)
+    monkeypatch.setattr(st, "hub_pending", [])
     g = torch.Generator().manual_seed(2)
     N, E = 20_000, 60_000
     src, dst = torch.randint(0, N, (E,), generator=g), torch.randint(0, N, (E,), generator=g)
     plain = ops.build_plan(to_cuda_adj([(src, dst)]), N)
     assert ops.gather_update_supported(64, 64, plain)
     torch.cuda.synchronize()
-    assert ops.gather_update_supported(64, 64, plain) and ops._HUB_SKIP[0] == 0
+    assert ops.gather_update_supported(64, 64, plain) and st.hub_backoff.steps == 0
     dst2 = dst.clone()
     dst2[: ops.HUB_THRESHOLD + 500] = 7                       # one hub row
     hubby = ops.build_plan(to_cuda_adj([(src, dst2)]), N)
@@ -176,13 +178,13 @@ def test_a_plan_with_hub_rows_sends_the_following_calls_to_the_unfused_pair(monk
     torch.cuda.synchronize()
     fresh = ops.build_plan(to_cuda_adj([(src, dst)]), N)     # a plan whose own count is still unknown ...
     assert not ops.gather_update_supported(64, 64, fresh)    # ... goes by the recent plans: the read-back has arrived, back off
-    assert ops._HUB_SKIP[0] == ops.GATHER_UPDATE_BACKOFF - 1
+    assert st.hub_backoff.steps == ops.GATHER_UPDATE_BACKOFF - 1
     # what a plan reported about ITSELF decides its later calls, whatever the back-off says: the hub-free plan
     # stays fused, the hub plan never takes the serial fold again -- also after the back-off has run out
     assert plain._has_hubs is False and hubby._has_hubs is True
-    assert ops.gather_update_supported(64, 64, plain) and ops._HUB_SKIP[0] == ops.GATHER_UPDATE_BACKOFF - 1
-    monkeypatch.setattr(ops, "_HUB_SKIP", [0])
+    assert ops.gather_update_supported(64, 64, plain) and st.hub_backoff.steps == ops.GATHER_UPDATE_BACKOFF - 1
+    st.hub_backoff.trip(0)
     assert not ops.gather_update_supported(64, 64, hubby) and ops.gather_update_supported(64, 64, plain)
-    monkeypatch.setattr(ops, "_HUB_SKIP", [1])
+    st.hub_backoff.trip(1)
     other = ops.build_plan(to_cuda_adj([(src, dst)]), N)
     assert not ops.gather_update_supported(64, 64, other) and ops.gather_update_supported(64, 64, other)

@@ -1017,7 +1017,7 @@ def test_unique_sources_equal_the_numpy_bookkeeping(n, counts, src_pool, monkeyp
     g = torch.Generator().manual_seed(n + len(counts))
     adj = [(torch.randint(0, src_pool or n, (c,), generator=g), torch.randint(0, n, (c,), generator=g)) for c in counts]
     monkeypatch.setattr(ops, "UNIQUE_MIN_EDGES", 0)
-    monkeypatch.setattr(ops, "_UNIQ_SKIP", [0])
+    monkeypatch.setattr(ops._device_state("cuda").uniq_backoff, "steps", 0)
     ops.clear_plan_cache()
     plan = ops.plan_for(to_cuda_adj(adj), n)
     uq = plan.unique_messages()
@@ -1071,7 +1071,7 @@ def test_ggnn_layer_with_shared_message_rows_gives_the_same_bits(agg, mode, monk
     cadj = to_cuda_adj(adj)
     monkeypatch.setattr(L, "EDGE_PATH_BIAS", 1e-9)
     monkeypatch.setattr(ops, "UNIQUE_MIN_EDGES", 0)
-    monkeypatch.setattr(ops, "_UNIQ_SKIP", [0])
+    monkeypatch.setattr(ops._device_state("cuda").uniq_backoff, "steps", 0)
     prev_mode = ops.set_gemm_mode(mode)
     outs, rows = {}, {}
     try:
@@ -2006,6 +2006,28 @@ def test_plan_build_flags_out_of_range_ids_without_touching_memory():
     assert int(good.rowptr[-1]) == 5000
 
 
+def test_out_of_range_ids_surface_through_the_asynchronous_read_back():
+    """The guard's default mode: the count posted by the offending plan build is picked up by a later NON-blocking
+    `check_indices()` once it has arrived, the raise clears the accumulator and the read-back, and builds go on."""
+    from ptgnn_amd import _lib, ops
+    N = 1000
+    g = torch.Generator().manual_seed(3)
+    src = torch.randint(0, N, (5000,), generator=g)
+    dst = torch.randint(0, N, (5000,), generator=g)
+    dst[17] = N + 5
+    src[99] = -3
+    ops.clear_plan_cache()
+    ops.check_indices(sync=True)            # clean slate
+    ops.build_plan([(src.cuda(), dst.cuda())], N)
+    torch.cuda.synchronize()
+    with pytest.raises(_lib.PtgnnAmdError, match="outside"):
+        ops.check_indices()
+    ops.check_indices()                     # reported once
+    ops.check_indices(sync=True)            # the counter was reset by the raise
+    good = ops.build_plan([(src.clamp(0, N - 1).cuda(), dst.clamp(0, N - 1).cuda())], N)
+    assert int(good.rowptr[-1]) == 5000
+
+
 def test_pooling_accepts_an_unsorted_element_to_sample_map():
     """varsizedsummary.py:28-41 is a plain scatter: any element -> sample map must work, sorted or not."""
     from oracle.scatter_ref import scatter
@@ -2300,7 +2322,7 @@ def test_sharded_two_block_overlap_mode_equals_unsharded(case, monkeypatch):
         want = layer(x, cadj, None, {}, {}, empty_feats(cadj, "cuda"))
     monkeypatch.setattr(L, "UNIQUE_MESSAGES", True)       # ... the shards (GGNN edge form): one per (type, source) pair
     monkeypatch.setattr(ops, "UNIQUE_MIN_EDGES", 0)
-    monkeypatch.setattr(ops, "_UNIQ_SKIP", [0])
+    monkeypatch.setattr(ops._device_state("cuda").uniq_backoff, "steps", 0)
     indeg = torch.zeros(n, dtype=torch.int64)
     for _, d in adj:
         indeg += torch.bincount(d, minlength=n)

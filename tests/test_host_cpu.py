@@ -4,6 +4,8 @@ properties, loud failure on CPU tensors)."""
 import ctypes
 import os
 import re
+import threading
+import time
 
 import pytest
 import torch
@@ -255,6 +257,7 @@ def test_shared_message_rows_entry_points_validate_and_back_off(lib, monkeypatch
     checks happen before any HIP call; the launch table has the size the Python wrapper allocates; the bookkeeping
     backs off for UNIQUE_BACKOFF plans after a minibatch whose (type, source) pairs were (nearly) all distinct."""
     from ptgnn_amd import ops
+    from ptgnn_amd._readback import Readback
     assert lib.ptgnn_amd_edge_table_bytes() == 3 * 64 * 8 + 65 * 8 + 2 * 65 * 4 + 8       # StreamEdgeTable, 8-aligned
     assert lib.ptgnn_amd_unique_sources_workspace_bytes(1000, 3) > 3000                   # >= a flag byte per pair
     assert lib.ptgnn_amd_unique_sources(None, 10, 2, 3, 100, None, None, 10, None, None, None, 0, None) == -1
@@ -266,19 +269,161 @@ def test_shared_message_rows_entry_points_validate_and_back_off(lib, monkeypatch
     assert lib.ptgnn_amd_edge_linear_shared_supported(128, 128, 65) == 0       # one table holds 64 edge types
     assert lib.ptgnn_amd_edge_linear_shared_supported(100, 128, 17) == 0       # not a shape of the streaming edge GEMM
 
-    class Fake:
-        def __init__(self, edges, rows):
-            self.num_edges, self._r = edges, rows
+    class InFlight:
+        def query(self):
+            return False
 
-        def rows(self):
-            return self._r
-    monkeypatch.setattr(ops, "_UNIQ_PENDING", [Fake(1000, None), Fake(1000, 800)])
-    monkeypatch.setattr(ops, "_UNIQ_SKIP", [0])
-    ops._poll_unique_stats()
-    assert ops._UNIQ_SKIP[0] == 0 and len(ops._UNIQ_PENDING) == 1          # 20 % saved: keep going; one still in flight
-    ops._UNIQ_PENDING.append(Fake(1000, 990))
-    ops._poll_unique_stats()
-    assert ops._UNIQ_SKIP[0] == ops.UNIQUE_BACKOFF                          # 1 % saved: skip the next plans
+    def Fake(edges, rows):        # the row counts of a 1-type plan on their way back; rows=None: still in flight
+        return Readback(torch.tensor([rows or 0, rows or 0]), event=None if rows else InFlight(), tag=(edges, 1))
+    monkeypatch.setattr(ops, "_STATES", {})
+    st = ops._device_state("cuda:0")
+    st.uniq_pending[:] = [Fake(1000, None), Fake(1000, 800)]
+    ops._poll_unique_stats(st)
+    assert st.uniq_backoff.steps == 0 and len(st.uniq_pending) == 1        # 20 % saved: keep going; one still in flight
+    st.uniq_pending.append(Fake(1000, 990))
+    ops._poll_unique_stats(st)
+    assert st.uniq_backoff.steps == ops.UNIQUE_BACKOFF                      # 1 % saved: skip the next plans
+
+
+@pytest.fixture
+def host_pool(monkeypatch):
+    """The read-back pool on plain host memory (pinning needs a device), with every buffer it hands out or takes back
+    recorded: `live` = ids out of the pool right now, `handed` / `returned` = counts, `errors` = a buffer handed to two
+    live read-backs, or returned twice."""
+    from ptgnn_amd import _readback as RB
+    track = threading.Lock()
+
+    class Free(list):                          # the free list of one (dtype, size); the sleep hands the GIL over in the
+        def pop(self):                         # middle of a critical section, where only a missing lock can hurt
+            time.sleep(1e-6)
+            return pool.out(list.pop(self))
+
+        def append(self, buf):
+            with track:
+                if id(buf) not in pool.live:
+                    pool.errors.append("a buffer came back twice")
+                pool.live.discard(id(buf))
+                pool.returned += 1
+            list.append(self, buf)
+
+    class Pool(dict):
+        live, handed, returned, errors = set(), 0, 0, []
+
+        def setdefault(self, key, default=None):
+            return dict.setdefault(self, key, Free())
+
+        def out(self, buf):
+            with track:
+                if id(buf) in self.live:
+                    self.errors.append("a buffer was handed to two live read-backs")
+                self.live.add(id(buf))
+                self.handed += 1
+            return buf
+
+    pool = Pool()
+    monkeypatch.setattr(RB, "_POOL", pool)
+    monkeypatch.setattr(RB, "_allocate", lambda dtype, n, pinned: pool.out(torch.empty(n, dtype=dtype)))
+    return pool
+
+
+def test_readback_of_a_cpu_tensor_is_ready_at_once_and_returns_its_buffer_once(host_pool):
+    from ptgnn_amd._readback import Readback
+    rb = Readback(torch.tensor([3, 1, 4, 1, 5]))
+    assert rb.ready() and host_pool.handed == 1 and host_pool.returned == 0
+    assert rb.values() == [3, 1, 4, 1, 5] and all(type(v) is int for v in rb.values())
+    assert rb.values(wait=True) == [3, 1, 4, 1, 5] and host_pool.returned == 1 and not host_pool.errors
+    again = Readback(torch.tensor([7, 7, 7, 7, 7]))                   # same dtype and size: the pooled buffer is reused
+    assert host_pool.handed == 2 and len(host_pool.live) == 1 and again.values() == [7] * 5
+
+    class Stub:                                                        # an event that has not happened yet
+        done = False
+
+        def query(self):
+            return self.done
+
+        def synchronize(self):
+            raise AssertionError("a non-blocking look synchronised")
+    ev = Stub()
+    late = Readback(torch.tensor([9], dtype=torch.int32), event=ev)
+    assert not late.ready() and late.values() is None and host_pool.returned == 2     # nothing taken, nothing blocked
+    ev.done = True
+    assert late.ready() and late.values() == [9] and late.values() == [9]
+    assert host_pool.returned == 3 and not host_pool.live and not host_pool.errors
+
+
+def test_backoffs_are_per_device_and_count_down_to_zero(monkeypatch):
+    from ptgnn_amd import ops
+    monkeypatch.setattr(ops, "_STATES", {})
+    a, b = ops._device_state("cuda:0"), ops._device_state("cuda:1")
+    assert a is ops._device_state(torch.device("cuda", 0)) and a is not b
+    a.hub_backoff.trip(ops.GATHER_UPDATE_BACKOFF)
+    assert a.hub_backoff.steps == ops.GATHER_UPDATE_BACKOFF and b.hub_backoff.steps == 0 and a.uniq_backoff.steps == 0
+    assert not b.hub_backoff.consume() and b.hub_backoff.steps == 0
+    assert [a.hub_backoff.consume() for _ in range(ops.GATHER_UPDATE_BACKOFF + 2)] == \
+        [True] * ops.GATHER_UPDATE_BACKOFF + [False, False]
+    assert a.hub_backoff.steps == 0                                    # ... and stops there
+
+
+def test_two_threads_share_the_readback_pool_a_pending_list_and_a_backoff(host_pool):
+    """The host bookkeeping of a layer call from two threads at once (threaded minibatch iterators): post, poll, take,
+    look at the values, back off.  The stub event, the instrumented pool and the pending list give the GIL away inside
+    the critical sections, so the threads interleave there in every round (without the lock both take the same
+    read-back off the list).  No thread raises, no buffer is ever held by two live read-backs or returned twice, each
+    read-back is taken by one thread, both threads get the same values from it, and what was handed out and has not
+    come back is exactly what is still pending."""
+    import collections
+    import sys
+    from ptgnn_amd._readback import LOCK, Backoff, Readback, take_arrived
+    class Pending(list):                        # ... and so does the pending list, between "is it still here" and its removal
+        def __contains__(self, item):
+            time.sleep(1e-6)
+            return list.__contains__(self, item)
+    pending, backoff, failures, taken = Pending(), Backoff(), [], [0, 0]
+    recent = collections.deque(maxlen=4)        # read-backs one thread has taken; BOTH threads ask them for their values
+    rounds, start = 600, threading.Barrier(2)
+
+    class Arrived:
+        def query(self):
+            time.sleep(1e-6)
+            return True
+
+    def worker(k):
+        try:
+            start.wait(10)
+            for i in range(rounds):
+                rb = Readback(torch.tensor([k, i]), event=Arrived())
+                with LOCK:
+                    pending.append(rb)
+                for got in take_arrived(pending, keep=16) if i % 3 else ():       # every third round leaves its own behind
+                    recent.append(got)
+                    vals = got.values()
+                    assert vals == got.values() and vals[0] in (0, 1) and 0 <= vals[1] < rounds, vals
+                    taken[k] += 1
+                    if vals[1] % 7 == 0:
+                        backoff.trip(5)
+                for other in list(recent):
+                    vals = other.values()
+                    assert vals is other.values() and vals[0] in (0, 1) and 0 <= vals[1] < rounds, vals
+                backoff.consume()
+        except BaseException as exc:        # noqa: BLE001 -- reported by the main thread
+            failures.append(repr(exc))
+            start.abort()
+
+    interval = sys.getswitchinterval()
+    sys.setswitchinterval(1e-6)
+    try:
+        threads = [threading.Thread(target=worker, args=(k,)) for k in (0, 1)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join(60)
+    finally:
+        sys.setswitchinterval(interval)
+    assert not failures and not host_pool.errors, (failures[:3], host_pool.errors[:3])
+    assert not any(t.is_alive() for t in threads) and sum(taken) > rounds // 2
+    assert 0 <= backoff.steps <= 5
+    assert sum(taken) + len(pending) == 2 * rounds                     # nothing was taken twice, nothing was lost
+    assert host_pool.handed - host_pool.returned == len(pending) == len(host_pool.live)
 
 
 def test_committed_bench_line_keeps_the_driver_contract():

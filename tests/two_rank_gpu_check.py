@@ -295,11 +295,7 @@ def case_fuzz(rank, world):
             got = run()
         # did THIS build overflow?  its count is known one build late: look now (a blocking look is fine in a test)
         pending = planner._pending
-        over = 0
-        if pending is not None:
-            if pending[1] is not None:
-                pending[1].synchronize()
-            over = int(pending[0][4])
+        over = pending.values(wait=True)[4] if pending is not None else 0
         if over:
             try:
                 got = run()                         # raises (capacities grown) ...
