@@ -342,6 +342,31 @@ int ptgnn_amd_gather_reduce_rows_f32(const float *ysrc, int64_t ld_ysrc,
                                      const int32_t *hub_count /* nullable */, void *hub_ws /* nullable */,
                                      size_t hub_ws_bytes, int32_t *hub_tickets /* nullable */,
                                      int64_t row_begin, int64_t row_end, void *stream);
+/* Row headers: the first eight `col` entries of every destination row at an address that depends on the row alone.
+ *   hdr int32 [num_rows, 8], 32-byte aligned:  hdr[r, k] = entries[min(rowptr[r] + k, rowptr[r + 1] - 1)]
+ *   (slots past the row's end repeat its last entry -- the clamped duplicates the aggregation's groups of 8 load
+ *   anyway); all zeros for an empty row, never read.  `entries` is whatever the aggregation will be given as `col`:
+ *   the plan's col, its perm, or the slot_row of ptgnn_amd_unique_sources.  One launch, no host synchronisation.
+ * ptgnn_amd_gather_reduce_hdr_f32 is ptgnn_amd_gather_reduce_rows_f32 with that array (`row_hdr`, nullable = the same
+ * call): a lane group requests its row's record together with the rowptr pair and starts the first eight message
+ * rows from it, so a row of up to eight in-edges is two dependent memory round trips instead of three (rowptr -> col
+ * -> rows).  Later groups of a longer row read `col` as before.  Slots fold in the same order: the output bits do
+ * not depend on `row_hdr`.  Used by the plain walks in groups of eight (16-byte-aligned rows, msg_dim <= 256, no
+ * destination term, no argout); every other call ignores it.  Hub and long rows are left to their kernels as
+ * without it. */
+int ptgnn_amd_row_headers(const int32_t *rowptr, const int32_t *entries, int64_t num_rows, int32_t *hdr, void *stream);
+int ptgnn_amd_gather_reduce_hdr_f32(const float *ysrc, int64_t ld_ysrc,
+                                    const float *ydst /* nullable */, int64_t ld_ydst,
+                                    const int32_t *rowptr, const int32_t *col,
+                                    int32_t type_bits, int64_t num_nodes, int32_t msg_dim,
+                                    int reduce, int epilogue, const float *ln_gamma,
+                                    const float *ln_beta, float ln_eps, float *out, int64_t ld_out,
+                                    int32_t *argout /* nullable */, int64_t num_edges,
+                                    int32_t hub_threshold, const int32_t *hub_entries /* nullable */,
+                                    const int32_t *hub_count /* nullable */, void *hub_ws /* nullable */,
+                                    size_t hub_ws_bytes, int32_t *hub_tickets /* nullable */,
+                                    int64_t row_begin, int64_t row_end,
+                                    const int32_t *row_hdr /* nullable */, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * MlpMessagePassingLayer, aggregation AND node update in one launch (mlpmessagepassing.py:107-117 with the update

@@ -202,8 +202,25 @@ extern "C" int ptgnn_amd_gather_reduce_rows_f32(const float *ysrc, int64_t ld_y,
                                                 const int32_t *hub_count, void *hub_ws,
                                                 size_t hub_ws_bytes, int32_t *hub_tickets, int64_t row_begin,
                                                 int64_t row_end, void *stream_) {
+  return ptgnn_amd_gather_reduce_hdr_f32(ysrc, ld_y, ydst, ld_yd, rowptr, col, type_bits, num_nodes, msg_dim, reduce,
+                                         epilogue, ln_gamma, ln_beta, ln_eps, out, ld_out, argout, num_edges,
+                                         hub_threshold, hub_entries, hub_count, hub_ws, hub_ws_bytes, hub_tickets,
+                                         row_begin, row_end, nullptr, stream_);
+}
+
+extern "C" int ptgnn_amd_gather_reduce_hdr_f32(const float *ysrc, int64_t ld_y, const float *ydst,
+                                               int64_t ld_yd, const int32_t *rowptr, const int32_t *col,
+                                               int32_t type_bits, int64_t num_nodes, int32_t msg_dim,
+                                               int reduce, int epilogue, const float *ln_gamma,
+                                               const float *ln_beta, float ln_eps, float *out,
+                                               int64_t ld_out, int32_t *argout, int64_t num_edges,
+                                               int32_t hub_threshold, const int32_t *hub_entries,
+                                               const int32_t *hub_count, void *hub_ws,
+                                               size_t hub_ws_bytes, int32_t *hub_tickets, int64_t row_begin,
+                                               int64_t row_end, const int32_t *row_hdr, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   PTGNN_REQUIRE(num_nodes >= 0 && msg_dim > 0 && num_edges >= 0, PTGNN_AMD_EINVAL, "gather_reduce: bad sizes");
+  PTGNN_REQUIRE(((uintptr_t)row_hdr & 31) == 0, PTGNN_AMD_EINVAL, "gather_reduce: row_hdr must be 32-byte aligned");
   PTGNN_REQUIRE(row_begin >= 0 && row_begin <= row_end && row_end <= num_nodes, PTGNN_AMD_EINVAL,
                 "gather_reduce: row range [%lld, %lld) outside [0, %lld]", (long long)row_begin, (long long)row_end,
                 (long long)num_nodes);
@@ -226,6 +243,7 @@ extern "C" int ptgnn_amd_gather_reduce_rows_f32(const float *ysrc, int64_t ld_y,
   a.rowptr = rowptr; a.col = col; a.type_bits = type_bits; a.num_nodes = row_end; a.row_begin = row_begin; a.msg_dim = msg_dim;
   a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.ln_eps = ln_eps; a.out = out; a.ld_out = ld_out;
   a.argout = argout; a.epi = epilogue;
+  a.hdr = row_hdr;   // read by the walks in groups of 8 only (gather_reduce_core.h); every other variant ignores it
   const int rc = setup_hub(a, num_edges, hub_threshold, hub_entries, hub_count, hub_ws, hub_ws_bytes,
                            hub_tickets, argout != nullptr);
   if (rc != PTGNN_AMD_OK) return rc;
@@ -314,6 +332,40 @@ extern "C" int ptgnn_amd_gather_reduce_masked_f32(const float *grad, int64_t ld_
     return launch_all<decltype(V)::value, decltype(L)::value, decltype(C)::value, PTGNN_AMD_SUM, false, false,
                       true>(a, col_blocks, stream);
   });
+}
+
+// ---------------------------------------------------------------------------------------------
+// row headers of a plan: hdr[r, k] = entries[min(rowptr[r] + k, rowptr[r + 1] - 1)], zeros for an empty row
+// ---------------------------------------------------------------------------------------------
+namespace ptgnn_amd {
+namespace {
+// one thread per header entry: the eight threads of a row read the same rowptr pair (one 8-byte request after
+// coalescing) and write one 32-byte record; ~4 MB of traffic for the 116 k rows of BASELINE config 3
+__global__ __launch_bounds__(256) void k_row_headers(const int32_t *__restrict__ rowptr,
+                                                     const int32_t *__restrict__ entries, int64_t num_rows,
+                                                     int32_t *__restrict__ hdr) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r = i >> 3;
+  if (r >= num_rows) return;
+  const int k = (int)(i & 7);
+  const int beg = rowptr[r], end = rowptr[r + 1];
+  int32_t v = 0;
+  if (end > beg) v = entries[beg + k < end ? beg + k : end - 1];
+  hdr[i] = v;
+}
+}  // namespace
+}  // namespace ptgnn_amd
+
+extern "C" int ptgnn_amd_row_headers(const int32_t *rowptr, const int32_t *entries, int64_t num_rows, int32_t *hdr,
+                                     void *stream_) {
+  PTGNN_REQUIRE(num_rows >= 0 && num_rows < ((int64_t)1 << 31), PTGNN_AMD_EINVAL, "row_headers: bad sizes");
+  if (num_rows == 0) return PTGNN_AMD_OK;
+  PTGNN_REQUIRE(rowptr && entries && hdr, PTGNN_AMD_EINVAL, "row_headers: null pointer");
+  PTGNN_REQUIRE(((uintptr_t)hdr & 31) == 0, PTGNN_AMD_EINVAL, "row_headers: hdr must be 32-byte aligned");
+  const int64_t blocks = (num_rows * 8 + 255) / 256;
+  k_row_headers<<<(unsigned)blocks, 256, 0, (hipStream_t)stream_>>>(rowptr, entries, num_rows, hdr);
+  PTGNN_LAUNCH_CHECK();
+  return PTGNN_AMD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

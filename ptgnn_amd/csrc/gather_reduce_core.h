@@ -76,6 +76,7 @@ struct Args {
   int64_t ld_yd;
   const int32_t *rowptr;
   const int32_t *col;
+  const int32_t *hdr;        // nullable [num rows, 8]: col[rowptr[r] + k] clamped to the row's last slot (row_hdr of the ABI)
   int32_t type_bits;
   int64_t num_nodes;         // one past the last row of this launch
   int64_t row_begin;         // first row of this launch (0 unless a row range was asked for); pointers stay absolute
@@ -338,6 +339,65 @@ struct RowOp {
     }
   }
 
+  // The header-first walk of the main kernel: the fold of reduce_pf<U>(row, beg, end, 1) with the first group's U
+  // entries already in registers -- `first`, the row's header record (Args::hdr), requested together with the rowptr
+  // pair: the same clamped entries reduce_pf fetches once `beg` is known, one dependent round trip earlier.  That group
+  // is folded on its own, ahead of the loop (one loop body fed from the header on entry and from `col` on the back
+  // edge makes the compiler wait for every row load before it issues the next).  The further groups of a longer row
+  // (8 % of the rows of a code graph) fetch their entries at the top of the group, which is also where the compiler
+  // puts reduce_pf's prefetch: no entries carried across the fold keeps this walk inside the plain one's registers.
+  // Slots past the row's end are not loaded here (reduce_pf loads a duplicate of the last slot): the lanes of a slot
+  // load under the mask they already have for the column bound, and the slot folds the value that changes nothing --
+  // 0 into a sum, as there; the accumulator's initial value into a max / min, which a strict compare never takes,
+  // exactly like a duplicate of a value that is already folded.  Same slots, same order: same bits, and a row of 3
+  // in-edges has 3 row loads in flight, not 8.
+  template <int U>
+  __device__ __forceinline__ void reduce_hdr(int beg, int end, const int32_t (&first)[U]) {
+    static_assert(VEC == 4 && !MASKED && !HAS_ARG && !HAS_DST, "the header walk serves plain float4 rows");
+    if (beg >= end) return;
+    fold_group<U>(first, beg, end);
+    for (int i = beg + U; i < end; i += U) {
+      int32_t pk[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) pk[u] = a.col[i + u < end ? i + u : end - 1];
+      fold_group<U>(pk, i, end);
+    }
+  }
+
+  // reduce_hdr: the slots i, i + 1, ... < end of a group of U whose col entries are `pk` (clamped, so every address is
+  // a valid one): all row loads issued before any is used, then folded in slot order
+  template <int U>
+  __device__ __forceinline__ void fold_group(const int32_t (&pk)[U], int i, int end) {
+    constexpr bool kMinMax = REDUCE == PTGNN_AMD_MAX || REDUCE == PTGNN_AMD_MIN;
+    float m[U][CH][VEC];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t s = pk[u] >> a.type_bits;
+      const int t = pk[u] & tmask;
+      const float *base = a.ysrc + s * a.ld_y + (int64_t)t * M;
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        const int colx = cbase + (g + c * LPR) * VEC;
+        if (colx < M && i + u < end) {
+          const float4 v = *reinterpret_cast<const float4 *>(base + colx);
+          m[u][c][0] = v.x; m[u][c][1] = v.y; m[u][c][2] = v.z; m[u][c][3] = v.w;
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) m[u][c][v] = 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool valid = i + u < end;
+#pragma unroll
+      for (int c = 0; c < CH; ++c)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) m[u][c][v] = valid ? m[u][c][v] : (kMinMax ? kInit : 0.f);
+      fold(m[u], i + u);
+    }
+  }
+
   __device__ __forceinline__ void store(float *orow, int32_t *arow) const {
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
@@ -592,7 +652,7 @@ __global__ __launch_bounds__(256) void k_hub_chunks(Args a) {
 // main kernel: one row per lane group
 // ------------------------------------------------------------------------------------------------
 template <int VEC, int LPR, int CH, int REDUCE, bool HAS_DST, bool HAS_ARG, bool MASKED, bool DST1 = false,
-          bool HUBF = hub_fuses<CH, HAS_DST, HAS_ARG, MASKED>(), bool COMB = false>
+          bool HUBF = hub_fuses<CH, HAS_DST, HAS_ARG, MASKED>(), bool COMB = false, bool HDR = false>
 __global__ __launch_bounds__(256) void k_gather_reduce(Args a) {
   constexpr int ROWS_PER_BLOCK = 256 / LPR;
   // the first `hub_blocks` workgroups (a multiple of 8: the XCD mapping of the row tiles is unchanged) walk the plan's
@@ -609,18 +669,41 @@ __global__ __launch_bounds__(256) void k_gather_reduce(Args a) {
   if (tile >= a.num_tiles) return;
   const int64_t row = a.row_begin + tile * ROWS_PER_BLOCK + threadIdx.x / LPR;
   if (row >= a.num_nodes) return;  // whole lane-group exits together (no cross-group shuffles)
-  const int beg = a.rowptr[row], end = a.rowptr[row + 1];
-  if (a.hub_threshold > 0 && end - beg > a.hub_threshold) return;  // hub: the chunk kernel owns it
-  if (a.long_threshold > 0 && end - beg > a.long_threshold) return;  // long row: k_long_rows owns it
-  // column block (only > 0 when msg_dim exceeds LPR*VEC*CH; epilogues are then disabled by host)
-  RowOp<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, COMB> op(a, threadIdx.x % LPR,
-                                                               blockIdx.y * (LPR * VEC * CH));
   // plain rows fold in prefetched groups of 8 (4 when a lane owns two column chunks); so do rows with a
   // destination term when there is ONE edge type (DST1: the term is loaded once per row).  A per-slot destination
   // term (several edge types) stays on groups of 4: its second row set per slot would cost the occupancy the
   // wider group buys.
   constexpr int UP = (VEC == 4 && !MASKED && (!HAS_DST || DST1)) ? (CH == 1 ? 8 : 4) : 0;
+  // HDR, the header-first walk (groups of 8 only; launch_main picks it when the caller gave row headers): the row's
+  // header record holds the first group's eight col entries at an address that depends on `row` alone, so it is
+  // requested TOGETHER with the rowptr pair and the first payload group starts one round trip earlier
+  // (rowptr + header -> rows, instead of rowptr -> col -> rows).
+  static_assert(!HDR || UP == 8, "row headers serve the walks in groups of 8");
+  int32_t pk[HDR ? 8 : 1];
+  int beg, end;
+  if constexpr (HDR) {
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    const i32x4 *rec = reinterpret_cast<const i32x4 *>(a.hdr + row * 8);
+    i32x4 h0 = rec[0], h1 = rec[1];
+    beg = a.rowptr[row];
+    end = a.rowptr[row + 1];
+    // No instruction: the record and the rowptr pair are all "used" here, ahead of the branches on the row's degree.
+    // Without it the compiler sinks the record's loads to their first use, behind the wait for the rowptr pair --
+    // the dependent round trip the record is there to remove.
+    asm volatile("" : "+v"(h0), "+v"(h1), "+v"(beg), "+v"(end));
+    pk[0] = h0.x; pk[1] = h0.y; pk[2] = h0.z; pk[3] = h0.w;
+    pk[4] = h1.x; pk[5] = h1.y; pk[6] = h1.z; pk[7] = h1.w;
+  } else {
+    beg = a.rowptr[row];
+    end = a.rowptr[row + 1];
+  }
+  if (a.hub_threshold > 0 && end - beg > a.hub_threshold) return;  // hub: the chunk kernel owns it
+  if (a.long_threshold > 0 && end - beg > a.long_threshold) return;  // long row: k_long_rows owns it
+  // column block (only > 0 when msg_dim exceeds LPR*VEC*CH; epilogues are then disabled by host)
+  RowOp<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, COMB> op(a, threadIdx.x % LPR,
+                                                               blockIdx.y * (LPR * VEC * CH));
   if constexpr (UP == 0) op.reduce(row, beg, end, 1);
+  else if constexpr (HDR) op.template reduce_hdr<8>(beg, end, pk);
   else op.template reduce_pf<UP, HAS_DST && DST1>(row, beg, end, 1);
   op.finish_and_store(row, end - beg);
 }
@@ -662,6 +745,28 @@ __global__ __launch_bounds__(256) void k_long_rows(Args a) {
 // ------------------------------------------------------------------------------------------------
 // launch plumbing
 // ------------------------------------------------------------------------------------------------
+// Which main-kernel variants have a header-first instantiation: plain float4 rows in one column chunk, walked in groups
+// of 8, without mask, destination term or arg output.  Their header form keeps or gains waves per SIMD against the plain
+// one (the compiler's kernel-resource-usage remarks, tabulated in profiles/row_headers_notes.md).  Every other variant
+// ignores Args::hdr.  Left on the plain walk because a header form cost them waves when it was built: max / min with
+// an arg output (63 -> 74 VGPRs, 8 -> 6 waves per SIMD) and every variant with a destination term (62-79 -> 236-238
+// VGPRs, 2 waves).
+template <int VEC, int CH, bool HAS_DST, bool HAS_ARG, bool MASKED, bool COMB>
+constexpr bool hdr_walk() {
+  return VEC == 4 && CH == 1 && !MASKED && !COMB && !HAS_ARG && !HAS_DST;
+}
+
+template <int VEC, int LPR, int CH, int REDUCE, bool HAS_DST, bool HAS_ARG, bool MASKED, bool DST1, bool HUBF, bool COMB>
+void launch_main(const Args &a, dim3 grid, hipStream_t stream) {
+  if constexpr (hdr_walk<VEC, CH, HAS_DST, HAS_ARG, MASKED, COMB>()) {
+    if (a.hdr != nullptr) {
+      k_gather_reduce<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, DST1, HUBF, COMB, true><<<grid, 256, 0, stream>>>(a);
+      return;
+    }
+  }
+  k_gather_reduce<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, DST1, HUBF, COMB, false><<<grid, 256, 0, stream>>>(a);
+}
+
 // COMB: the rows finish with the EGC combine (egc_combine.hip; one column block, no destination term, no mask)
 template <int VEC, int LPR, int CH, int REDUCE, bool HAS_DST, bool HAS_ARG, bool MASKED, bool COMB = false>
 int launch_all(const Args &a0, int col_blocks, hipStream_t stream) {
@@ -724,17 +829,17 @@ int launch_all(const Args &a0, int col_blocks, hipStream_t stream) {
   if constexpr (kFuseSmall) {
     if (a.hub_blocks > 0) {      // the small-plan instantiation that walks the hub list itself
       if (kDst1Variant && a.type_bits == 0)
-        k_gather_reduce<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, kDst1Variant, true><<<grid, 256, 0, stream>>>(a);
+        launch_main<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, kDst1Variant, true, false>(a, grid, stream);
       else
-        k_gather_reduce<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, false, true><<<grid, 256, 0, stream>>>(a);
+        launch_main<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, false, true, false>(a, grid, stream);
       PTGNN_LAUNCH_CHECK();
       return PTGNN_AMD_OK;
     }
   }
   if (kDst1Variant && a.type_bits == 0)
-    k_gather_reduce<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, kDst1Variant, kHubF, COMB><<<grid, 256, 0, stream>>>(a);
+    launch_main<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, kDst1Variant, kHubF, COMB>(a, grid, stream);
   else
-    k_gather_reduce<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, false, kHubF, COMB><<<grid, 256, 0, stream>>>(a);
+    launch_main<VEC, LPR, CH, REDUCE, HAS_DST, HAS_ARG, MASKED, false, kHubF, COMB>(a, grid, stream);
   PTGNN_LAUNCH_CHECK();
   if (side) {   // join: the caller's stream continues once the hub and long rows are written too
     PTGNN_HIP(hipStreamWaitEvent(stream, side->join, 0));

@@ -205,7 +205,7 @@ class GraphPlan:
     __slots__ = ("rowptr", "col", "perm", "type_bits", "num_nodes", "num_edges", "num_types",
                  "num_src_rows", "_backward", "_adj", "_adj_refs", "_inv_perm", "_ready", "_waited",
                  "_hub_tickets", "hub_entries", "hub_count", "_slot_rows", "_ident", "_transposed", "_uniq", "_hub_posted",
-                 "_has_hubs", "__weakref__")
+                 "_has_hubs", "_hdrs", "__weakref__")
 
     def __init__(self, rowptr, col, perm, type_bits, num_nodes, num_edges, num_types):
         self.rowptr, self.col, self.perm = rowptr, col, perm
@@ -224,6 +224,7 @@ class GraphPlan:
         self._uniq = None      # UniqueMessages | pending read-back | False (not worth it / not applicable)
         self._hub_posted = False   # the hub count's Readback is pending on the device's state (ops.gather_update_supported)
         self._has_hubs = None      # ... and has arrived: True / False (None = not known on the host)
+        self._hdrs = {}            # "col" / "perm" -> row headers int32 [N, 8] of that slot array (row_header)
 
     def may_have_hubs(self) -> bool:
         """Only plans with more edges than the threshold can contain a hub row (whether they do is
@@ -251,6 +252,31 @@ class GraphPlan:
             if cur.cuda_stream not in self._waited:
                 cur.wait_event(self._ready)
                 self._waited.add(cur.cuda_stream)
+
+    def row_header(self, entries: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """int32 [N, 8] row headers of a forward plan for the slot array the aggregation is about to read (`entries`:
+        the plan's col -- the default --, its perm, or the slot_row of its UniqueMessages): hdr[r, k] is the entry of slot
+        rowptr[r] + k, clamped to the row's last slot, zeros for an empty row (ptgnn_amd_row_headers).  One launch on the
+        first call per slot array, behind the plan build, shared by every layer of the minibatch; no host
+        synchronisation.  None for the plans that keep the plain walk (backward, transposed, pooling) and for a slot
+        array the plan does not know."""
+        if self._adj is None:
+            return None
+        uniq = self._uniq or None
+        if entries is None or entries is self.col:
+            key, entries = "col", self.col
+        elif entries is self.perm:
+            key = "perm"
+        elif uniq is not None and entries is uniq.slot_row:
+            if uniq.hdr is None:
+                uniq.hdr = _launch_row_headers(self, entries)
+            return uniq.hdr
+        else:
+            return None
+        hdr = self._hdrs.get(key)
+        if hdr is None:
+            hdr = self._hdrs[key] = _launch_row_headers(self, entries)
+        return hdr
 
     def unique_messages(self) -> Optional["UniqueMessages"]:
         """Message rows of the layers whose message depends on (edge type, source) only (GGNN without edge features /
@@ -332,14 +358,15 @@ class UniqueMessages:
     """slot_row int32 [E]: message row of every CSR slot; unique_src int64: source node of every message row
     (type-major); edge_table: the device-resident launch table of ptgnn_amd_edge_linear_shared_f32; capacity: rows the
     message table must hold; counts: device int64 [T + 1] rows per type and in all (`_readback`: their Readback, posted
-    with the build unless it was captured)."""
+    with the build unless it was captured); hdr: the row headers of slot_row (GraphPlan.row_header), None until an
+    aggregation asks for them."""
     __slots__ = ("slot_row", "unique_src", "edge_table", "capacity", "counts", "num_edges", "num_types", "_readback",
-                 "_counts")
+                 "_counts", "hdr")
 
     def __init__(self, slot_row, unique_src, edge_table, capacity, counts, num_edges, num_types):
         self.slot_row, self.unique_src, self.edge_table = slot_row, unique_src, edge_table
         self.capacity, self.counts, self.num_edges, self.num_types = capacity, counts, num_edges, num_types
-        self._readback = self._counts = None
+        self._readback = self._counts = self.hdr = None
 
     def host_counts(self, wait: bool = False) -> Optional[List[int]]:
         """Rows per edge type + the total, once the asynchronous read-back has arrived (None before).  `wait` blocks
@@ -412,6 +439,23 @@ def _launch_unique_sources(plan: "GraphPlan") -> Optional[UniqueMessages]:
         with LOCK:
             st.uniq_pending.append(u._readback)
     return u
+
+
+# Row headers (GraphPlan.row_header): the aggregation's lane groups request a row's first eight slot entries together
+# with its rowptr pair.  PTGNN_AMD_ROW_HEADERS=0 (or ops.ROW_HEADERS = False, looked at per call) keeps the plain walk:
+# same bits, one more dependent round trip per row (A/B + tests).
+ROW_HEADERS = os.environ.get("PTGNN_AMD_ROW_HEADERS", "1") not in ("", "0")
+
+
+def _launch_row_headers(plan: "GraphPlan", entries: torch.Tensor) -> torch.Tensor:
+    N = plan.num_nodes
+    plan.wait()
+    hdr = torch.empty(max(N, 1), 8, dtype=torch.int32, device=plan.rowptr.device)
+    with _timed("row_headers", bytes=N * (32.0 + 4) + 4.0 * min(plan.num_edges, 8 * N)):
+        rc = _lib.load().ptgnn_amd_row_headers(plan.rowptr.data_ptr(), entries.data_ptr(), N, hdr.data_ptr(),
+                                               _stream(hdr))
+    _lib.check(rc, "ptgnn_amd_row_headers")
+    return hdr
 
 
 def edge_linear_shared_supported(state_dim: int, msg_dim: int, num_types: int) -> bool:
@@ -806,16 +850,22 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
                                      "written) and returns no arg")
         nbytes *= (hi - lo) / max(N, 1)
     hub_ws, hub = _hub_args(plan, msg_dim, arg is not None, ysrc.device)
+    # the kernel variants with a header-first walk (gather_reduce_core.h, hdr_walk): float4 rows in one column chunk,
+    # no destination term, no arg output -- every other call would build a header that its kernel ignores
+    hdr = None
+    if (ROW_HEADERS and ydst is None and arg is None and msg_dim % 4 == 0 and msg_dim <= 256 and ld_y % 4 == 0
+            and ysrc.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0):
+        hdr = plan.row_header(colt)
     with _timed("gather_reduce", bytes=nbytes):
-        rc = lib.ptgnn_amd_gather_reduce_rows_f32(
+        rc = lib.ptgnn_amd_gather_reduce_hdr_f32(
             _ptr_or(ysrc, plan.rowptr), ld_y, ydst.data_ptr() if ydst is not None else None, ld_yd,
             plan.rowptr.data_ptr(), colt.data_ptr(), tb, N, msg_dim,
             REDUCE_IDS[reduce], epilogue,
             ln_weight.data_ptr() if ln_weight is not None else None,
             ln_bias.data_ptr() if ln_bias is not None else None, float(ln_eps),
             out.data_ptr(), msg_dim, arg.data_ptr() if arg is not None else None,
-            *hub, lo, hi, _stream(out))
-    _lib.check(rc, "ptgnn_amd_gather_reduce_rows_f32")
+            *hub, lo, hi, hdr.data_ptr() if hdr is not None else None, _stream(out))
+    _lib.check(rc, "ptgnn_amd_gather_reduce_hdr_f32")
     return (out, arg) if return_arg else out
 
 
