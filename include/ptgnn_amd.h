@@ -153,6 +153,15 @@ enum {
   PTGNN_AMD_KERNEL_WINDOW_MAX_BACKWARD,                       /* ptgnn_amd_window_max_backward_f32 */
   PTGNN_AMD_KERNEL_CHAR_END_
 };
+/* A fourth id range: the task heads (csrc/task_heads.hip).  Their Linears count under the GEMM families above. */
+enum {
+  PTGNN_AMD_KERNEL_HEAD_FIRST_ = 192,
+  PTGNN_AMD_KERNEL_LOGIT_LOSS = PTGNN_AMD_KERNEL_HEAD_FIRST_, /* ptgnn_amd_logit_loss_f32 */
+  PTGNN_AMD_KERNEL_LOGIT_LOSS_BACKWARD,                       /* ptgnn_amd_logit_loss_backward_f32 */
+  PTGNN_AMD_KERNEL_CANDIDATE_SCORES,                          /* ptgnn_amd_candidate_scores_f32 */
+  PTGNN_AMD_KERNEL_CANDIDATE_SCORES_BACKWARD,                 /* ptgnn_amd_candidate_scores_backward_f32 */
+  PTGNN_AMD_KERNEL_HEAD_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1018,6 +1027,108 @@ int ptgnn_amd_window_max_f32(const float *x, int64_t ld_x, int64_t num_samples, 
                              int32_t dim, float *out, int64_t ld_out, int32_t *arg /* nullable */, void *stream);
 int ptgnn_amd_window_max_backward_f32(const float *grad, int64_t ld_grad, const int32_t *arg, int64_t num_samples,
                                       int32_t rows_per_sample, int32_t dim, float *grad_x, int64_t ld_gx, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Task heads (csrc/task_heads.hip): what the three benchmarked models run after their GNN.  Exact fp32, no float
+ * atomics, every sum over rows or slots folded in a fixed order; no entry point synchronises.
+ *
+ * TOTALS BLOCK, written by every forward call that has targets: PTGNN_AMD_HEAD_TOTALS_BYTES bytes, 8-byte aligned,
+ * eight 8-byte slots
+ *   slot 0  float64  the loss sum (softmax: sum of lse - logit[target] over live rows; sigmoid: sum over all
+ *                    elements; candidates: sum over slots of score[correct] - lse)
+ *   slot 1  int64    the denominator of the loss: live rows (softmax), rows (sigmoid), slots (candidates)
+ *   slot 2  int64    softmax: rows whose arg-max is their target | sigmoid: true positives  | candidates: slots whose
+ *                    arg-max candidate is the correct one
+ *   slot 3  int64    softmax: targets outside [0, C) other than -100 | sigmoid: false positives | candidates: correct
+ *                    indices that are not a candidate of their slot
+ *   slot 4  int64    softmax: 0 | sigmoid: false negatives | candidates: node ids outside [0, num_nodes)
+ *   slot 5  int64    rows / candidates of the call;  slots 6, 7: 0
+ * The backward entry points read slot 1 from the device; the host never needs it.
+ *
+ * METRICS BLOCK, optional (NULL: none), PTGNN_AMD_HEAD_METRICS_BYTES bytes, 8-byte aligned, caller-owned and
+ * PERSISTENT: the merge step of a forward call ADDS into it, so a module accumulates its metrics over minibatches
+ * without a launch of its own and reads them when somebody asks.  The caller zeroes it to reset.
+ *   softmax, candidates:  int64 correct | int64 samples (live rows / slots) | int64 skipped targets | unused
+ *   sigmoid:              float64 sum precision * rows | float64 sum recall * rows | float64 sum F * rows | int64 rows
+ * (precision, recall and F from tp, fp, fn converted to fp32, in the fp32 expression of ppi.py:50-52, 1e-10 terms
+ * included).  Like the plan build's control block and the node-id guard's accumulator, a metrics block belongs to ONE
+ * stream at a time: calls that add into it from two streams at once race.
+ * ---------------------------------------------------------------------------------------- */
+#define PTGNN_AMD_HEAD_TOTALS_BYTES 64
+#define PTGNN_AMD_HEAD_METRICS_BYTES 32
+enum { PTGNN_AMD_LOSS_SOFTMAX = 0, PTGNN_AMD_LOSS_SIGMOID = 1 };
+
+/* Row loss over logits [rows, classes] (ld), any classes >= 1, any rows >= 0 (rows == 0 launches nothing); every
+ * logit is read once.
+ *
+ * mode PTGNN_AMD_LOSS_SOFTMAX replaces nn.CrossEntropyLoss, torch.argmax and torch.softmax + torch.max of
+ *   graph2class.py:91-102.  targets: int64 [rows], or NULL (predict: per-row outputs only, no loss, no totals).
+ *   Per row: lse [rows] (required; the backward reads it), argmax int64 [rows] (lowest index on ties), max_prob
+ *   [rows] = exp(max - lse), row_loss [rows] = lse - logit[target] (all three nullable).  A target outside [0, C)
+ *   makes the row an IGNORED row -- no loss, no gradient, not in the denominator, never used as an index; -100 is
+ *   nn.CrossEntropyLoss's ignore_index, any other such value is counted in slot 3.  Logits of any spread: a running
+ *   maximum.  loss[0] = slot 0 / slot 1 (nan when every row is ignored, as the reference).
+ * mode PTGNN_AMD_LOSS_SIGMOID replaces torch.sigmoid(l) >= 0.5, the three masked sums, precision / recall / F and
+ *   binary_cross_entropy_with_logits(reduction="none").sum(-1).mean() of ppi.py:43-62.  targets: uint8 [rows,
+ *   classes] (ld_t; torch.bool storage), required.  Per element max(l, 0) - l t + log1p(exp(-|l|)), prediction
+ *   l >= 0; row_loss [rows] nullable; lse, argmax, max_prob unused.  loss[0] = slot 0 / rows.
+ * workspace: ptgnn_amd_logit_loss_workspace_bytes(rows), 8-byte aligned. */
+size_t ptgnn_amd_logit_loss_workspace_bytes(int64_t rows);
+int ptgnn_amd_logit_loss_f32(const float *logits, int64_t ld, int64_t rows, int32_t classes, int mode,
+                             const void *targets /* nullable in mode 0 */, int64_t ld_t, float *lse,
+                             int64_t *argmax /* nullable */, float *max_prob /* nullable */,
+                             float *row_loss /* nullable */, float *loss, void *totals, void *metrics /* nullable */,
+                             void *workspace, size_t workspace_bytes, void *stream);
+/* grad_logits [rows, classes] (ld_g), every element written: grad_loss[0] / slot 1 * (exp(l - lse) - onehot), zeros
+ * for ignored rows (softmax); grad_loss[0] / rows * (sigmoid(l) - t) (sigmoid).  grad_loss [1] and totals are DEVICE
+ * memory: the upstream scalar and the denominator never visit the host. */
+int ptgnn_amd_logit_loss_backward_f32(const float *logits, int64_t ld, int64_t rows, int32_t classes, int mode,
+                                      const void *targets, int64_t ld_t, const float *lse /* mode 0 */,
+                                      const void *totals, const float *grad_loss, float *grad_logits, int64_t ld_g,
+                                      void *stream);
+
+/* Candidate scoring of varmisuse.py:63-91 over the segment plan (rowptr int32 [num_slots + 1], perm int32
+ * [num_candidates]: the candidates of slot g are perm[rowptr[g] .. rowptr[g + 1])) of the candidate -> slot map
+ * cand_slot int64 [num_candidates]:
+ *     scores[c] = x[cand_idx[c]] . w[:dim] + x[slot_idx[cand_slot[c]]] . w[dim:]        [num_candidates]
+ *     lse[g]    = log sum_{c in g} exp(scores[c])        (-inf for a slot without candidates: eps = 0)
+ *     argmax[g] = the POSITION c of the slot's best candidate, lowest on ties, num_candidates for an empty slot
+ *                 (what torch_scatter.scatter_max reports)
+ *     loss[0]   = -(1 / num_slots) sum_g (scores[correct[g]] - lse[g])
+ * replacing the two row gathers, the [num_candidates, 2 dim] torch.cat, nn.Linear(2 dim, 1), scatter_log_softmax and
+ * scatter_max: neither the concatenation nor a gathered copy exists.  correct int64 [num_slots] is nullable (scores,
+ * lse, argmax only).  correct[g] must be a candidate OF SLOT g (the reference's one-slot-per-graph assumption,
+ * varmisuse.py:61): any other value -- outside [0, num_candidates) or a candidate of another slot -- contributes
+ * nothing, is counted in slot 3 and never indexes memory.  Node ids outside [0, num_nodes) are clamped and counted
+ * (slot 4), like every row gather of the library.
+ * Supported: dim a multiple of 4, 4 <= dim <= 1024 (ptgnn_amd_candidate_scores_supported); others answer
+ * PTGNN_AMD_EUNSUPPORTED before any device work.  num_slots == 0 launches nothing.
+ * workspace: ptgnn_amd_candidate_scores_workspace_bytes(num_slots). */
+int ptgnn_amd_candidate_scores_supported(int32_t dim);
+size_t ptgnn_amd_candidate_scores_workspace_bytes(int64_t num_slots);
+int ptgnn_amd_candidate_scores_f32(const float *x, int64_t ld_x, int64_t num_nodes, const int64_t *cand_idx,
+                                   const int64_t *slot_idx, const int64_t *cand_slot, const int32_t *rowptr,
+                                   const int32_t *perm, int64_t num_candidates, int64_t num_slots, int32_t dim,
+                                   const float *w, const int64_t *correct /* nullable */, float *scores, float *lse,
+                                   int64_t *argmax, float *loss, void *totals, void *metrics /* nullable */,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+/* With t[c] = grad_loss[0] / num_slots * (exp(scores[c] - lse[g]) - [c == correct[g]]) + grad_scores[c]  (g the slot of
+ * c; grad_loss [1] on the DEVICE, nullable = 0; grad_scores [num_candidates] nullable = 0; a skipped correct[g] gives
+ * its slot no loss gradient):
+ *     row_grad[c, :]                  = t[c] w[:dim]                      row_grad is [num_candidates + num_slots, dim],
+ *     row_grad[num_candidates + g, :] = (sum_{c in g} t[c]) w[dim:]       the rows of cat(cand_idx, slot_idx)
+ *     grad_w[:dim] = sum_c t[c] x[cand_idx[c]],  grad_w[dim:] = sum_g (sum_{c in g} t[c]) x[slot_idx[g]]
+ * grad_w from per-slot partials added in slot order.  The host turns row_grad into d x with ONE segment sum over the
+ * plan of cat(cand_idx, slot_idx).  Rows of candidates the plan does not hold are not written.
+ * workspace: ptgnn_amd_candidate_scores_backward_workspace_bytes(num_slots, dim). */
+size_t ptgnn_amd_candidate_scores_backward_workspace_bytes(int64_t num_slots, int32_t dim);
+int ptgnn_amd_candidate_scores_backward_f32(const float *x, int64_t ld_x, int64_t num_nodes, const int64_t *cand_idx,
+                                            const int64_t *slot_idx, const int64_t *cand_slot, const int32_t *rowptr,
+                                            const int32_t *perm, int64_t num_candidates, int64_t num_slots, int32_t dim,
+                                            const float *w, const int64_t *correct /* nullable */, const float *scores,
+                                            const float *lse, const float *grad_loss /* nullable */,
+                                            const float *grad_scores /* nullable */, float *row_grad, float *grad_w,
+                                            void *workspace, size_t workspace_bytes, void *stream);
 
 #pragma GCC visibility pop
 

@@ -15,7 +15,10 @@ def __getattr__(name):
     if name == "GruCopyingDecoder":
         from ptgnn_amd.sequence import GruCopyingDecoder
         return GruCopyingDecoder
-    if name in ("TokenUnitEmbedder", "SubtokenUnitEmbedder", "CharUnitEmbedder", "CnnConfig"):
+    if name in ("Graph2ClassModule", "VarMisuseGraphModel", "PPIClassification"):
+        from ptgnn_amd import heads
+        return getattr(heads, name)
+    if name in ("TokenUnitEmbedder", "SubtokenUnitEmbedder", "CharUnitEmbedder", "CnnConfig", "LinearFeatureEmbedder"):
         from ptgnn_amd import embeddings
         return getattr(embeddings, name)
     raise AttributeError(f"module 'ptgnn_amd' has no attribute {name!r}")

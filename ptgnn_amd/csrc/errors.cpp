@@ -23,12 +23,15 @@ void set_error(const char *fmt, ...) {
 static std::atomic<int64_t> g_launches[PTGNN_AMD_KERNEL_COUNT_];
 static std::atomic<int64_t> g_agg_launches[PTGNN_AMD_KERNEL_AGG_END_ - PTGNN_AMD_KERNEL_AGG_FIRST_];
 static std::atomic<int64_t> g_char_launches[PTGNN_AMD_KERNEL_CHAR_END_ - PTGNN_AMD_KERNEL_CHAR_FIRST_];
+static std::atomic<int64_t> g_head_launches[PTGNN_AMD_KERNEL_HEAD_END_ - PTGNN_AMD_KERNEL_HEAD_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
     return &g_agg_launches[kernel_id - PTGNN_AMD_KERNEL_AGG_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_CHAR_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_CHAR_END_)
     return &g_char_launches[kernel_id - PTGNN_AMD_KERNEL_CHAR_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_HEAD_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HEAD_END_)
+    return &g_head_launches[kernel_id - PTGNN_AMD_KERNEL_HEAD_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -76,6 +79,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "char_embed", "char_embed_backward", "window_max", "window_max_backward"};
   if (kernel_id >= PTGNN_AMD_KERNEL_CHAR_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_CHAR_END_)
     return char_names[kernel_id - PTGNN_AMD_KERNEL_CHAR_FIRST_];
+  static const char *const head_names[PTGNN_AMD_KERNEL_HEAD_END_ - PTGNN_AMD_KERNEL_HEAD_FIRST_] = {
+      "logit_loss", "logit_loss_backward", "candidate_scores", "candidate_scores_backward"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_HEAD_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HEAD_END_)
+    return head_names[kernel_id - PTGNN_AMD_KERNEL_HEAD_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

@@ -15,12 +15,14 @@ GPU route:
     frames (char_cnn.py: a Conv1d is a Linear whose rows overlap, forward and backward), the HIP window max, dropout.
     Filter counts or an embedding size that are not multiples of 4, and char tables beyond the char-embed range, compose
     the same sequence from the embedding bag (or the row gather), copied windows through `dense.linear` and the window max.
+  * LinearFeatureEmbedder (linearmapembedding.py:13-29, the node embedder of the PPI model): `dense.linear`, with Tanh / ReLU
+    in the GEMM epilogue where the fused node takes the widths and any other activation module applied after.
 Shapes beyond the bag's range (D not a multiple of 4, more than 32 subtokens) compose the reference's operator sequence
 from the HIP row gather and torch elementwise arithmetic.  CPU tensors take the reference's own operator order on torch
 (device dispatch as in every layer of the package); fp16 / bf16 tables are up-cast on entry and the result cast back.
 """
 import math
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -243,3 +245,34 @@ class CharUnitEmbedder(nn.Module):
         summary = torch_route.char_cnn(chars, self.__num_chars_in_vocabulary, self.__conv_l1, self.__conv_l2,
                                        self.__conv_l3)                  # CPU tensors: the reference's operator order
         return self.__dropout(summary)
+
+
+class LinearFeatureEmbedder(nn.Module):
+    def __init__(self, input_element_size: int, output_embedding_size: int, activation: Optional[nn.Module] = None):
+        super().__init__()
+        self.__linear_map = nn.Linear(input_element_size, output_embedding_size, bias=False)
+        nn.init.xavier_uniform_(self.__linear_map.weight)
+        self.__activation = activation
+
+    def forward(self, features):
+        weight, act = self.__linear_map.weight, self.__activation
+        if not features.is_cuda:          # device dispatch: CPU tensors take the reference's own operator order
+            mapped_features = self.__linear_map(features)
+            return act(mapped_features) if act is not None else mapped_features
+        dt = features.dtype
+        if (dt not in _HALF and dt != torch.float32) or features.dim() != 2:
+            raise _lib.PtgnnAmdError(f"LinearFeatureEmbedder: features must be a 2-D float matrix (got "
+                                     f"{tuple(features.shape)} {dt})")
+        x, w = features.float(), weight.float()           # AMP: fp32 inside, the features' dtype outside
+        fused = {nn.Tanh: "tanh", nn.ReLU: "relu"}.get(type(act))
+        if fused is not None and x.shape[0] > 0:
+            out = dense.linear_act_dropout(x, w, None, fused, 0.0, False)
+            if out is not None:
+                return out.to(dt)
+        if x.shape[0] == 0:
+            mapped_features = x.new_zeros(0, w.shape[0])
+        else:
+            mapped_features = dense.linear(x, w)
+        if act is not None:
+            mapped_features = act(mapped_features)
+        return mapped_features.to(dt)

@@ -44,16 +44,21 @@ _AGG_FAMILY_FIRST = 64   # PTGNN_AMD_KERNEL_AGG_FIRST_: the aggregation families
 _CHAR_FAMILY_FIRST = 128  # PTGNN_AMD_KERNEL_CHAR_FIRST_: the char-CNN kernels' id range
 
 
-def launch_counts(aggregation: bool = False, char_cnn: bool = False) -> dict:
+_HEAD_FAMILY_FIRST = 192  # PTGNN_AMD_KERNEL_HEAD_FIRST_: the task heads' id range
+
+
+def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
     attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward, block_attention,
     block_attention_backward, segment_scores, segment_scores_backward, embedding_bag, embedding_bag_backward);
-    `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward)."""
+    `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward);
+    `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward)."""
     lib = _lib.load()
     out = {}
-    for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()):
+    for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
+            + ((_HEAD_FAMILY_FIRST,) if heads else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -66,7 +71,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False) -> dict:
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True, char_cnn=True)
+    now = launch_counts(aggregation=True, char_cnn=True, heads=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2399,3 +2404,227 @@ def head_weight_grad(a: torch.Tensor, b: torch.Tensor, num_heads: int, scale: fl
         raise _lib.PtgnnAmdError(f"head_weight_grad: a {tuple(a.shape)} and b {tuple(b.shape)} do not match")
     out = torch.empty(hidden, b.shape[2], dtype=torch.float32, device=a.device)
     return _head_projection(HEAD_WEIGHT_GRAD, a, b, None, G, H, dk, b.shape[2], scale, out)
+
+
+# ------------------------------------------------------------------------------------------------
+# task heads (csrc/task_heads.hip)
+# ------------------------------------------------------------------------------------------------
+LOSS_MODES = {"softmax": 0, "sigmoid": 1}
+HEAD_TOTALS_SLOTS = 8     # PTGNN_AMD_HEAD_TOTALS_BYTES / 8: loss sum (float64 bits) | denominator | three counts | rows | 0 | 0
+HEAD_METRICS_SLOTS = 4    # PTGNN_AMD_HEAD_METRICS_BYTES / 8
+
+
+def head_metrics_block(device) -> torch.Tensor:
+    """A zeroed persistent metrics block (int64 [4]; the sigmoid mode keeps float64 bits in the first three slots, read
+    them with `.view(torch.float64)`).  The merge step of `logit_loss` / `candidate_scores` adds into it; it belongs to
+    one stream at a time."""
+    return torch.zeros(HEAD_METRICS_SLOTS, dtype=torch.int64, device=device)
+
+
+def _metrics_ptr(metrics: Optional[torch.Tensor], device):
+    if metrics is None:
+        return None
+    if not metrics.is_cuda or metrics.device != device or metrics.dtype != torch.int64 \
+            or metrics.numel() != HEAD_METRICS_SLOTS or not metrics.is_contiguous():
+        raise _lib.PtgnnAmdError("a head metrics block is a contiguous CUDA int64 [4] tensor on the logits' device "
+                                 "(ops.head_metrics_block)")
+    return metrics.data_ptr()
+
+
+def _head_targets(logits: torch.Tensor, targets: Optional[torch.Tensor], mode: int, what: str):
+    """(targets as the kernel reads them, their leading dimension)."""
+    R, C = logits.shape
+    if targets is None:
+        if mode != 0:
+            raise _lib.PtgnnAmdError(f"{what}: the sigmoid mode needs targets")
+        return None, 0
+    if not targets.is_cuda or targets.device != logits.device:
+        raise _lib.PtgnnAmdError(f"{what}: targets must live on the logits' GPU (got {targets.device})")
+    if mode == 0:
+        if targets.dtype != torch.int64 or tuple(targets.shape) != (R,):
+            raise _lib.PtgnnAmdError(f"{what}: softmax targets are int64 [{R}] (got {targets.dtype} "
+                                     f"{tuple(targets.shape)})")
+        return targets.contiguous(), 0
+    if targets.dtype not in (torch.bool, torch.uint8) or tuple(targets.shape) != (R, C):
+        raise _lib.PtgnnAmdError(f"{what}: sigmoid targets are bool [{R}, {C}] (got {targets.dtype} "
+                                 f"{tuple(targets.shape)})")
+    targets = targets.contiguous()
+    return (targets.view(torch.uint8) if targets.dtype == torch.bool else targets), C
+
+
+def logit_loss(logits: torch.Tensor, targets: Optional[torch.Tensor], mode: str = "softmax",
+               metrics: Optional[torch.Tensor] = None):
+    """Row loss over fp32 logits [R, C] in one pass (ptgnn_amd_logit_loss_f32; graph2class.py:91-102, ppi.py:43-62).
+    "softmax": int64 targets [R] (None: predict) -> cross-entropy over the live rows; "sigmoid": bool targets [R, C] ->
+    BCE-with-logits summed per row, tp / fp / fn.  Returns (loss [] -- nan without rows or targets --, lse [R], argmax
+    int64 [R], max_prob [R], totals int64 [8]); the three per-row tensors are None in the sigmoid mode.  `metrics`: a
+    block of `head_metrics_block` to add this call's figures into.  Nothing here waits for the device."""
+    lib = _lib.load()
+    _require_cuda_f32("logits", logits)
+    logits = _rowmajor(logits)
+    R, C = logits.shape
+    if mode not in LOSS_MODES:
+        raise _lib.PtgnnAmdError(f"logit_loss: unknown mode {mode!r} (have {sorted(LOSS_MODES)})")
+    m = LOSS_MODES[mode]
+    if C < 1:
+        raise _lib.PtgnnAmdError("logit_loss: logits need at least one class")
+    dev = logits.device
+    tg, ld_t = _head_targets(logits, targets, m, "logit_loss")
+    mptr = _metrics_ptr(metrics, dev)
+    lse = argmax = maxp = None
+    if m == 0:
+        lse = torch.empty(R, dtype=torch.float32, device=dev)
+        argmax = torch.empty(R, dtype=torch.int64, device=dev)
+        maxp = torch.empty(R, dtype=torch.float32, device=dev)
+    if R == 0 or tg is None:
+        loss = torch.full((1,), float("nan"), dtype=torch.float32, device=dev)
+        totals = torch.zeros(HEAD_TOTALS_SLOTS, dtype=torch.int64, device=dev)
+        if R == 0:
+            return loss.view(()), lse, argmax, maxp, totals
+    else:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        totals = torch.empty(HEAD_TOTALS_SLOTS, dtype=torch.int64, device=dev)
+    ws_bytes = int(lib.ptgnn_amd_logit_loss_workspace_bytes(R))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    with _timed("logit_loss", bytes=4.0 * R * C + (8.0 * R if m == 0 else 1.0 * R * C) + 20.0 * R):
+        rc = lib.ptgnn_amd_logit_loss_f32(logits.data_ptr(), _ld(logits), R, C, m, tg.data_ptr() if tg is not None else None,
+                                          ld_t, lse.data_ptr() if lse is not None else None,
+                                          argmax.data_ptr() if argmax is not None else None,
+                                          maxp.data_ptr() if maxp is not None else None, None, loss.data_ptr(),
+                                          totals.data_ptr(), mptr, ws.data_ptr(), ws.numel() * 8, _stream(loss))
+    _lib.check(rc, "ptgnn_amd_logit_loss_f32")
+    return loss.view(()), lse, argmax, maxp, totals
+
+
+def _device_scalar(t: torch.Tensor, device, what: str) -> torch.Tensor:
+    if not t.is_cuda or t.numel() != 1:
+        raise _lib.PtgnnAmdError(f"{what} must be a one-element CUDA tensor (it is read on the device)")
+    return t.detach().to(device=device, dtype=torch.float32).reshape(1).contiguous()
+
+
+def logit_loss_backward(logits: torch.Tensor, targets: torch.Tensor, mode: str, lse: Optional[torch.Tensor],
+                        totals: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
+    """grad_logits [R, C] of `logit_loss` from the upstream scalar `grad_loss` and the forward's lse and totals, all read
+    on the device (ptgnn_amd_logit_loss_backward_f32)."""
+    lib = _lib.load()
+    _require_cuda_f32("logits", logits)
+    logits = _rowmajor(logits)
+    R, C = logits.shape
+    m = LOSS_MODES[mode]
+    tg, ld_t = _head_targets(logits, targets, m, "logit_loss_backward")
+    if tg is None:
+        raise _lib.PtgnnAmdError("logit_loss_backward: a call without targets has no loss to differentiate")
+    if not totals.is_cuda or totals.dtype != torch.int64 or totals.numel() != HEAD_TOTALS_SLOTS:
+        raise _lib.PtgnnAmdError("logit_loss_backward: totals must be the forward's CUDA int64 [8] block")
+    if m == 0 and (lse is None or not lse.is_cuda or tuple(lse.shape) != (R,)):
+        raise _lib.PtgnnAmdError(f"logit_loss_backward: lse must be the forward's CUDA [{R}] tensor")
+    g = _device_scalar(grad_loss, logits.device, "logit_loss_backward: grad_loss")
+    grad = torch.empty(R, C, dtype=torch.float32, device=logits.device)
+    if R == 0:
+        return grad
+    with _timed("logit_loss_backward", bytes=8.0 * R * C + (8.0 * R if m == 0 else 1.0 * R * C)):
+        rc = lib.ptgnn_amd_logit_loss_backward_f32(logits.data_ptr(), _ld(logits), R, C, m, tg.data_ptr(), ld_t,
+                                                   lse.contiguous().data_ptr() if m == 0 else None,
+                                                   totals.contiguous().data_ptr(), g.data_ptr(), grad.data_ptr(), C,
+                                                   _stream(grad))
+    _lib.check(rc, "ptgnn_amd_logit_loss_backward_f32")
+    return grad
+
+
+def candidate_scores_supported(dim: int) -> bool:
+    """Whether the fused candidate scoring takes node states of width `dim` (a multiple of 4, 4 <= dim <= 1024)."""
+    return bool(_lib.load().ptgnn_amd_candidate_scores_supported(int(dim)))
+
+
+def _candidate_args(x, cand_idx, slot_idx, cand_slot, plan, w, correct, what):
+    _require_cuda_f32("x", x)
+    x = _rowmajor(x)
+    N, D = x.shape
+    for name, t in (("cand_idx", cand_idx), ("slot_idx", slot_idx), ("cand_slot", cand_slot), ("correct", correct)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1):
+            raise _lib.PtgnnAmdError(f"{what}: {name} must be a 1-D CUDA int64 tensor")
+    Cn, G = cand_idx.shape[0], slot_idx.shape[0]
+    if cand_slot.shape[0] != Cn or plan.num_nodes != G or plan.num_edges != Cn or plan.perm is None \
+            or (correct is not None and correct.shape[0] != G):
+        raise _lib.PtgnnAmdError(f"{what}: {Cn} candidates / {G} slots do not fit cand_slot {tuple(cand_slot.shape)}, a plan "
+                                 f"of {plan.num_edges} elements in {plan.num_nodes} segments or correct")
+    if not w.is_cuda or w.dtype != torch.float32 or w.numel() != 2 * D:
+        raise _lib.PtgnnAmdError(f"{what}: w must hold 2 * {D} CUDA float32 values")
+    return (x, cand_idx.contiguous(), slot_idx.contiguous(), cand_slot.contiguous(), w.detach().reshape(-1).contiguous(),
+            correct.contiguous() if correct is not None else None, N, D, Cn, G)
+
+
+def candidate_scores(x: torch.Tensor, cand_idx: torch.Tensor, slot_idx: torch.Tensor, cand_slot: torch.Tensor,
+                     plan: GraphPlan, w: torch.Tensor, correct: Optional[torch.Tensor] = None,
+                     metrics: Optional[torch.Tensor] = None):
+    """scores[c] = x[cand_idx[c]] . w[:D] + x[slot_idx[cand_slot[c]]] . w[D:], their per-slot log-sum-exp and arg-max
+    position over `plan` (the segment plan of cand_slot), and -mean_g(scores[correct[g]] - lse[g]) in one launch plus a
+    merge (ptgnn_amd_candidate_scores_f32; varmisuse.py:63-91).  Returns (loss [] -- nan without slots or `correct` --,
+    scores [Cn], lse [G], argmax int64 [G], totals int64 [8]).  Nothing here waits for the device."""
+    lib = _lib.load()
+    x, cand_idx, slot_idx, cand_slot, w, correct, N, D, Cn, G = _candidate_args(
+        x, cand_idx, slot_idx, cand_slot, plan, w, correct, "candidate_scores")
+    dev = x.device
+    mptr = _metrics_ptr(metrics, dev)
+    scores = torch.empty(Cn, dtype=torch.float32, device=dev)
+    lse = torch.empty(G, dtype=torch.float32, device=dev)
+    argmax = torch.empty(G, dtype=torch.int64, device=dev)
+    if G == 0 or correct is None:
+        loss = torch.full((1,), float("nan"), dtype=torch.float32, device=dev)
+    else:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    totals = torch.zeros(HEAD_TOTALS_SLOTS, dtype=torch.int64, device=dev) if G == 0 else \
+        torch.empty(HEAD_TOTALS_SLOTS, dtype=torch.int64, device=dev)
+    if not lib.ptgnn_amd_candidate_scores_supported(D):
+        raise _lib.PtgnnAmdError(f"candidate_scores: node states of width {D} are outside the kernel range (a multiple of 4 "
+                                 "up to 1024); compose gather_rows / dense.linear / the scatter facade instead")
+    if G == 0:
+        return loss.view(()), scores, lse, argmax, totals
+    ws_bytes = int(lib.ptgnn_amd_candidate_scores_workspace_bytes(G))
+    ws = _workspace(ws_bytes, dev)
+    plan.wait()
+    with _timed("candidate_scores", bytes=4.0 * (Cn + G) * D + 8.0 * D + 24.0 * Cn + 28.0 * G):
+        rc = lib.ptgnn_amd_candidate_scores_f32(
+            x.data_ptr() if N else None, _ld(x), N, cand_idx.data_ptr() if Cn else None, slot_idx.data_ptr(),
+            cand_slot.data_ptr() if Cn else None, plan.rowptr.data_ptr(), plan.perm.data_ptr() if Cn else None, Cn, G, D,
+            w.data_ptr(), correct.data_ptr() if correct is not None else None, scores.data_ptr() if Cn else None,
+            lse.data_ptr(), argmax.data_ptr(), loss.data_ptr(), totals.data_ptr(), mptr, ws.data_ptr(), ws_bytes,
+            _stream(loss))
+    _lib.check(rc, "ptgnn_amd_candidate_scores_f32")
+    return loss.view(()), scores, lse, argmax, totals
+
+
+def candidate_scores_backward(x: torch.Tensor, cand_idx: torch.Tensor, slot_idx: torch.Tensor, cand_slot: torch.Tensor,
+                              plan: GraphPlan, w: torch.Tensor, correct: Optional[torch.Tensor], scores: torch.Tensor,
+                              lse: torch.Tensor, grad_loss: Optional[torch.Tensor],
+                              grad_scores: Optional[torch.Tensor] = None):
+    """(row_grad [Cn + G, D] -- the gradient rows of cat(cand_idx, slot_idx), to be segment-summed onto the nodes --,
+    grad_w [2 D]) of `candidate_scores` from the upstream scalar `grad_loss` (read on the device; None = 0) and an optional
+    extra gradient `grad_scores` [Cn] of the scores (ptgnn_amd_candidate_scores_backward_f32)."""
+    lib = _lib.load()
+    x, cand_idx, slot_idx, cand_slot, w, correct, N, D, Cn, G = _candidate_args(
+        x, cand_idx, slot_idx, cand_slot, plan, w, correct, "candidate_scores_backward")
+    dev = x.device
+    if tuple(scores.shape) != (Cn,) or tuple(lse.shape) != (G,) or not scores.is_cuda or not lse.is_cuda:
+        raise _lib.PtgnnAmdError(f"candidate_scores_backward: scores / lse must be the forward's CUDA [{Cn}] / [{G}] tensors")
+    g = _device_scalar(grad_loss, dev, "candidate_scores_backward: grad_loss") if grad_loss is not None else None
+    if grad_scores is not None:
+        _require_cuda_f32("grad_scores", grad_scores, dims=1)
+        if grad_scores.shape[0] != Cn:
+            raise _lib.PtgnnAmdError(f"candidate_scores_backward: grad_scores must have {Cn} entries")
+        grad_scores = grad_scores.contiguous()
+    row_grad = torch.zeros(Cn + G, D, dtype=torch.float32, device=dev)
+    grad_w = torch.empty(2 * D, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.ptgnn_amd_candidate_scores_backward_workspace_bytes(G, D))
+    ws = _workspace(ws_bytes, dev)
+    plan.wait()
+    with _timed("candidate_scores_backward", bytes=4.0 * (Cn + G) * D * 2 + 8.0 * G * D + 24.0 * Cn):
+        rc = lib.ptgnn_amd_candidate_scores_backward_f32(
+            x.data_ptr() if N else None, _ld(x), N, cand_idx.data_ptr() if Cn else None, slot_idx.data_ptr() if G else None,
+            cand_slot.data_ptr() if Cn else None, plan.rowptr.data_ptr(), plan.perm.data_ptr() if Cn else None, Cn, G, D,
+            w.data_ptr(), correct.data_ptr() if correct is not None else None,
+            scores.contiguous().data_ptr() if Cn else None, lse.contiguous().data_ptr() if G else None,
+            g.data_ptr() if g is not None else None, grad_scores.data_ptr() if grad_scores is not None and Cn else None,
+            row_grad.data_ptr() if Cn + G else None, grad_w.data_ptr(), ws.data_ptr(), ws_bytes, _stream(grad_w))
+    _lib.check(rc, "ptgnn_amd_candidate_scores_backward_f32")
+    return row_grad, grad_w
