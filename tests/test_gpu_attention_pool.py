@@ -15,6 +15,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 from agg_paths import TOL, attributed_ok
 from attnpool_cases import CASES, NUM_SAMPLES, build
 from ptgnn_amd import _lib, ops, reduceops as R
+from segment_batches import ref_multihead, ref_weighted
 
 pytestmark = pytest.mark.gpu
 
@@ -51,25 +52,7 @@ def test_reference_fixtures_forward_and_gradients_on_the_gpu(name, spec):
         assert rel_err(p.grad, fx["grad." + k]) <= FIXTURE_TOL, k
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# float64 restatement of varsizedsummary.py:140-178 with a `max` query (hidden = D), any dtype / device
-# ---------------------------------------------------------------------------------------------------------------------
-def ref_multihead(x, idx, G, wk, wv, wo, H):
-    n, D = x.shape
-    q = torch.zeros(G, D, dtype=x.dtype, device=x.device).scatter_reduce(0, idx.unsqueeze(1).expand(-1, D), x, "amax",
-                                                                         include_self=False)
-    keys = (x @ wk.t()).reshape(n, H, -1)
-    scores = (q[idx].reshape(n, H, -1) * keys).sum(-1) / math.sqrt(keys.shape[-1])
-    top = torch.full((G, H), float("-inf"), dtype=x.dtype, device=x.device).scatter_reduce(
-        0, idx.unsqueeze(1).expand(-1, H), scores.detach(), "amax")
-    e = (scores - top[idx]).exp()
-    total = torch.zeros(G, H, dtype=x.dtype, device=x.device).index_add(0, idx, e)
-    p = e / total[idx]
-    vals = (x @ wv.t()).reshape(n, H, -1) if wv is not None else x.unsqueeze(1)
-    rows = (p.unsqueeze(-1) * vals).reshape(n, -1)
-    per = torch.zeros(G, rows.shape[1], dtype=x.dtype, device=x.device).index_add(0, idx, rows)
-    return per @ wo.t(), scores
-
+# the float64 restatement of varsizedsummary.py:140-178 with a `max` query (hidden = D) is segment_batches.ref_multihead
 
 # (D, heads, value layer, sizes of the samples, scale of x); every shape ends with an empty sample
 SHAPES = [(4, h, False, [300, 1, 0, 57, 129, 4], 1.0) for h in (1, 2, 4)]
@@ -146,12 +129,6 @@ def test_float64_restatement(shape):
 # ---------------------------------------------------------------------------------------------------------------------
 # the chunk rule of csrc/segment_chunks.h under both pools
 # ---------------------------------------------------------------------------------------------------------------------
-def ref_weighted(x, idx, G, w):
-    """varsizedsummary.py:68-81: sigmoid(Linear(D, 1)) scores, the scaled rows summed per sample; any dtype / device."""
-    score = 1.0 / (1.0 + torch.exp(-(x @ w.t()).squeeze(-1)))
-    return torch.zeros(G, x.shape[1], dtype=x.dtype, device=x.device).index_add(0, idx, x * score.unsqueeze(-1))
-
-
 def check_weighted_against_float64(D, sizes, shuffled):
     g = torch.Generator().manual_seed(3000 + D * 11 + sum(sizes))
     G = len(sizes)

@@ -14,6 +14,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 from agg_paths import TOL, attributed_ok
 from decoder_cases import CASES, build, inputs_of, load, make_inputs, ref_logprobs, ref_loss, state_of, weights_of
 from ptgnn_amd import ops, sequence
+from segment_batches import segment_lse
 
 pytestmark = pytest.mark.gpu
 
@@ -127,14 +128,6 @@ def test_reference_fixtures_forward_and_gradients_on_the_gpu(name, spec):
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. the kernel against float64
 # ---------------------------------------------------------------------------------------------------------------------
-def segment_lse(scores, index, n):
-    top = torch.full((n, scores.shape[1]), -INF, dtype=scores.dtype, device=scores.device).scatter_reduce(
-        0, index.unsqueeze(1).expand_as(scores), scores.detach(), "amax")
-    safe = torch.where(top == -INF, torch.zeros_like(top), top)
-    total = torch.zeros_like(top).index_add(0, index, (scores - safe[index]).exp())
-    return torch.where(top == -INF, top, total.log() + safe)
-
-
 def kernel_case(K, Lv, sizes, scale=1.0, shuffled=True):
     """idx over len(sizes) + 1 samples (the last one empty), rows y, vectors v, the two output gradients."""
     g = torch.Generator().manual_seed(7000 + 13 * K + Lv + sum(sizes))

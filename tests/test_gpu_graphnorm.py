@@ -14,6 +14,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 from agg_paths import TOL, attributed_ok
 from graphnorm_cases import CASES, build
 from ptgnn_amd import gnn as G, layers as L, ops
+from segment_batches import ref_graphnorm
 
 pytestmark = pytest.mark.gpu
 
@@ -62,23 +63,7 @@ def test_reference_fixtures_forward_and_gradients_on_the_gpu(name, spec):
         assert ok(got[k], fx["grad." + k], fx["grad64." + k], k), k
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# restatement of graphnorm.py:36-46 (scatter_mean = index_add / max(count, 1)), any dtype / device
-# ---------------------------------------------------------------------------------------------------------------------
-def ref_graphnorm(x, idx, gamma, alpha, bias, eps):
-    D, n_graphs = x.shape[1], int(idx.max()) + 1
-    count = torch.zeros(n_graphs, dtype=x.dtype, device=x.device).index_add_(
-        0, idx, torch.ones(idx.shape[0], dtype=x.dtype, device=x.device)).clamp(min=1).unsqueeze(1)
-
-    def scatter_mean(v):
-        return torch.zeros(n_graphs, D, dtype=x.dtype, device=x.device).index_add(0, idx, v) / count
-
-    per_graph_mean = scatter_mean(x)
-    shifted = x - alpha * per_graph_mean[idx]
-    sigma_2 = scatter_mean(torch.pow(shifted, 2)) + eps
-    return gamma * shifted / torch.sqrt(sigma_2[idx]) + bias
-
-
+# the restatement of graphnorm.py:36-46 (scatter_mean = index_add / max(count, 1)) is segment_batches.ref_graphnorm
 def make_case(D, sizes, scale=1.0, offset=0.0, shuffled=True, eps=1e-10):
     g = torch.Generator().manual_seed(2000 + D * 13 + sum(sizes) + len(sizes))
     idx = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes))

@@ -13,6 +13,7 @@ from agg_paths import TOL, attributed_ok
 from head_cases import ALL_HEAD_CASES, LFE_CASES, StubGnn, build, build_lfe, call_args, inputs_of, load, state_of
 from ptgnn_amd import embeddings, heads, ops
 from ptgnn_amd.gnn import GnnOutput
+from segment_batches import candidate_ref, sigmoid_ref, softmax_ref, softmax_targets
 
 pytestmark = pytest.mark.gpu
 
@@ -151,34 +152,55 @@ def test_forward_backward_and_predict_never_block_the_host(kind, name, spec):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. the logit-loss kernel against float64
 # ---------------------------------------------------------------------------------------------------------------------
-def softmax_ref(logits, targets, dtype):
-    """(loss, lse, per-row loss) of the softmax mode in `dtype`: rows whose target is outside [0, C) are ignored."""
-    l = logits.detach().to(dtype).requires_grad_(True)
-    C = l.shape[1]
-    lse = torch.logsumexp(l, dim=-1)
-    live = (targets >= 0) & (targets < C)
-    picked = l.gather(1, targets.clamp(0, C - 1).unsqueeze(1)).squeeze(1)
-    rows = torch.where(live, lse - picked, torch.zeros_like(lse))
-    return rows.sum() / live.sum(), lse, l
-
-
-def sigmoid_ref(logits, targets, dtype):
-    l = logits.detach().to(dtype).requires_grad_(True)
-    t = targets.to(dtype)
-    # ppi.py:59-62 itself: max(l, 0) - l t + log1p(exp(-|l|)) with the analytic gradient sigmoid(l) - t (spelled with clamp
-    # and abs, autograd takes a subgradient at a logit that is exactly 0 -- 1 - t instead of 0.5 - t)
-    rows = nn.functional.binary_cross_entropy_with_logits(l, t, reduction="none").sum(-1)
-    return rows.mean(), None, l
-
-
-def softmax_targets(R, C, gen):
-    t = torch.randint(0, C, (R,), generator=gen)
-    t[0], t[R - 1] = 0, C - 1
-    if R >= 3:
-        t[1] = -100                   # nn.CrossEntropyLoss's ignore_index
-    if R >= 4:
-        t[2] = C                      # the reference device-asserts; skipped and counted here
-    return t
+def check_logit_loss_kernel(R, C, mode, gen):
+    """One [R, C] call of `heads.logit_loss` with backward against float64; every integer total and the metrics block exactly
+    (shared with tests/test_gpu_many_segments.py, which takes R past one run of chunks per merge thread)."""
+    if mode == "softmax":
+        logits = ((torch.rand(R, C, generator=gen) - 0.5) * 200.0).to(DEV)          # a spread of 200
+        targets = softmax_targets(R, C, gen).to(DEV)
+        ref = softmax_ref
+    else:
+        logits = ((torch.rand(R, C, generator=gen) - 0.5) * 120.0).to(DEV)          # +-60
+        targets = (torch.rand(R, C, generator=gen) < 0.4).to(DEV)
+        ref = sigmoid_ref
+    g = torch.tensor(2.5, device=DEV)                                                # a non-unit upstream scalar
+    live_logits = logits.clone().requires_grad_(True)
+    metrics = ops.head_metrics_block(DEV)
+    before = ops.launch_counts(heads=True)
+    loss = heads.logit_loss(live_logits, targets, mode, metrics)
+    (loss * g).backward()
+    assert ops.launches_since(before) == {"logit_loss": 1, "logit_loss_backward": 1}
+    want32, lse32, l32 = ref(logits, targets, torch.float32)
+    exact, lse64, l64 = ref(logits, targets, torch.float64)
+    (want32 * g).backward()
+    (exact * g.double()).backward()
+    print(f"  {mode} R={R} C={C}")
+    assert attributed(loss, want32, exact, "loss")
+    assert attributed(live_logits.grad, l32.grad, l64.grad, "grad_logits")
+    _, lse, argmax, max_prob, totals = ops.logit_loss(logits, targets, mode)
+    totals = totals.cpu()
+    counts = totals.tolist()
+    if mode == "softmax":
+        assert attributed(lse, lse32, lse64, "lse")
+        live = (targets >= 0) & (targets < C)
+        assert torch.equal(argmax, logits.argmax(dim=-1))                            # random floats: no ties
+        assert attributed(max_prob, (logits.max(-1)[0] - lse32).exp(), (logits.double().max(-1)[0] - lse64).exp(), "max prob")
+        assert counts[1:6] == [int(live.sum()), int(((argmax == targets) & live).sum()),
+                               int((~live & (targets != -100)).sum()), 0, R]
+        assert not bool(live_logits.grad[~live].any())                               # ignored rows: exact zeros
+        assert metrics.tolist() == [counts[2], counts[1], counts[3], 0]
+    else:
+        pred, t = logits >= 0, targets
+        tp, fp, fn = int((pred & t).sum()), int((pred & ~t).sum()), int((~pred & t).sum())
+        assert counts[1:6] == [R, tp, fp, fn, R]
+        tpf, fpf, fnf = (torch.tensor(float(v), dtype=torch.float32) for v in (tp, fp, fn))
+        pr, re = tpf / (tpf + fpf + 1e-10), tpf / (tpf + fnf + 1e-10)
+        f1 = 2 * pr * re / (pr + re + 1e-10)
+        sums = metrics.cpu().view(torch.float64)
+        for got, want in zip(sums[:3].tolist(), (pr, re, f1)):
+            assert abs(got - float(want) * R) <= 1e-6 * R, (got, float(want) * R)    # fp32 expression: a few ulp of <= 1
+        assert int(metrics[3]) == R
+    assert float(totals[:1].view(torch.float64)) == pytest.approx(float(exact) * counts[1], rel=1e-5)
 
 
 @pytest.mark.parametrize("mode", ["softmax", "sigmoid"])
@@ -186,52 +208,7 @@ def softmax_targets(R, C, gen):
 def test_logit_loss_kernel_against_float64(C, mode):
     gen = torch.Generator().manual_seed(1000 + C)
     for R in (1, 127, 128, 129, 300):
-        if mode == "softmax":
-            logits = ((torch.rand(R, C, generator=gen) - 0.5) * 200.0).to(DEV)          # a spread of 200
-            targets = softmax_targets(R, C, gen).to(DEV)
-            ref = softmax_ref
-        else:
-            logits = ((torch.rand(R, C, generator=gen) - 0.5) * 120.0).to(DEV)          # +-60
-            targets = (torch.rand(R, C, generator=gen) < 0.4).to(DEV)
-            ref = sigmoid_ref
-        g = torch.tensor(2.5, device=DEV)                                                # a non-unit upstream scalar
-        live_logits = logits.clone().requires_grad_(True)
-        metrics = ops.head_metrics_block(DEV)
-        before = ops.launch_counts(heads=True)
-        loss = heads.logit_loss(live_logits, targets, mode, metrics)
-        (loss * g).backward()
-        assert ops.launches_since(before) == {"logit_loss": 1, "logit_loss_backward": 1}
-        want32, lse32, l32 = ref(logits, targets, torch.float32)
-        exact, lse64, l64 = ref(logits, targets, torch.float64)
-        (want32 * g).backward()
-        (exact * g.double()).backward()
-        print(f"  {mode} R={R} C={C}")
-        assert attributed(loss, want32, exact, "loss")
-        assert attributed(live_logits.grad, l32.grad, l64.grad, "grad_logits")
-        _, lse, argmax, max_prob, totals = ops.logit_loss(logits, targets, mode)
-        totals = totals.cpu()
-        counts = totals.tolist()
-        if mode == "softmax":
-            assert attributed(lse, lse32, lse64, "lse")
-            live = (targets >= 0) & (targets < C)
-            assert torch.equal(argmax, logits.argmax(dim=-1))                            # random floats: no ties
-            assert attributed(max_prob, (logits.max(-1)[0] - lse32).exp(), (logits.double().max(-1)[0] - lse64).exp(), "max prob")
-            assert counts[1:6] == [int(live.sum()), int(((argmax == targets) & live).sum()),
-                                   int((~live & (targets != -100)).sum()), 0, R]
-            assert not bool(live_logits.grad[~live].any())                               # ignored rows: exact zeros
-            assert metrics.tolist() == [counts[2], counts[1], counts[3], 0]
-        else:
-            pred, t = logits >= 0, targets
-            tp, fp, fn = int((pred & t).sum()), int((pred & ~t).sum()), int((~pred & t).sum())
-            assert counts[1:6] == [R, tp, fp, fn, R]
-            tpf, fpf, fnf = (torch.tensor(float(v), dtype=torch.float32) for v in (tp, fp, fn))
-            pr, re = tpf / (tpf + fpf + 1e-10), tpf / (tpf + fnf + 1e-10)
-            f1 = 2 * pr * re / (pr + re + 1e-10)
-            sums = metrics.cpu().view(torch.float64)
-            for got, want in zip(sums[:3].tolist(), (pr, re, f1)):
-                assert abs(got - float(want) * R) <= 1e-6 * R, (got, float(want) * R)    # fp32 expression: a few ulp of <= 1
-            assert int(metrics[3]) == R
-        assert float(totals[:1].view(torch.float64)) == pytest.approx(float(exact) * counts[1], rel=1e-5)
+        check_logit_loss_kernel(R, C, mode, gen)
 
 
 def test_logit_loss_all_rows_ignored_and_ties():
@@ -272,28 +249,6 @@ def candidate_batch(D, gen, N=700):
     x = torch.randn(N, D, generator=gen)
     w = torch.randn(1, 2 * D, generator=gen) / math.sqrt(D)
     return x, w, cand_idx, slot_idx, cand_slot, correct
-
-
-def candidate_ref(x, w, cand_idx, slot_idx, cand_slot, correct, cot, g, dtype):
-    """(loss, scores, lse, argmax, x, w) in `dtype`; the backward of g * loss + sum(cot * scores) has run."""
-    x = x.detach().to(dtype).requires_grad_(True)
-    w = w.detach().to(dtype).requires_grad_(True)
-    D, G, Cn = x.shape[1], slot_idx.shape[0], cand_idx.shape[0]
-    scores = x[cand_idx] @ w[0, :D] + (x[slot_idx] @ w[0, D:])[cand_slot]
-    top = torch.full((G,), -INF, dtype=dtype, device=x.device).scatter_reduce(0, cand_slot, scores.detach(), "amax")
-    safe = torch.where(top == -INF, torch.zeros_like(top), top)
-    total = torch.zeros(G, dtype=dtype, device=x.device).index_add(0, cand_slot, (scores - safe[cand_slot]).exp())
-    lse = torch.where(top == -INF, top, total.log() + safe)
-    position = torch.arange(Cn, device=x.device)
-    best = torch.where(scores.detach() == top[cand_slot], position, torch.full_like(position, Cn))
-    argmax = torch.full((G,), Cn, dtype=torch.int64, device=x.device).scatter_reduce(0, cand_slot, best, "amin")
-    ok = (correct >= 0) & (correct < Cn)
-    ok = ok & (cand_slot[correct.clamp(0, Cn - 1)] == torch.arange(G, device=x.device))
-    terms = torch.where(ok, scores[correct.clamp(0, Cn - 1)] - torch.where(ok, lse, torch.zeros_like(lse)),
-                        torch.zeros_like(lse))
-    loss = -terms.sum() / G
-    (loss * g.to(dtype) + (scores * cot.to(dtype)).sum()).backward()
-    return loss, scores, lse, argmax, x, w
 
 
 @pytest.mark.parametrize("D", [4, 60, 128, 1024])

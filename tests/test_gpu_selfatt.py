@@ -13,6 +13,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 from agg_paths import TOL, attributed_ok
 from helpers import dropout_keep_scale
 from ptgnn_amd import PtgnnAmdError, gnn as G, layers as L, ops
+from segment_batches import ref_attention, window_offsets
 from selfatt_cases import CASES, build, call, load
 
 pytestmark = pytest.mark.gpu
@@ -57,36 +58,8 @@ def test_reference_fixtures_forward_and_gradients_on_the_gpu(name, spec):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # restatement of selfattmessagepassing.py:104-117 with a padded mask: windows as rows of a [W, L] batch
+# (segment_batches.ref_attention / window_offsets), computed once per configuration
 # ---------------------------------------------------------------------------------------------------------------------
-def window_offsets(counts, max_num_nodes):
-    offs, first = [], 0
-    for c in counts:
-        offs += [first + lo for lo in range(0, c, max_num_nodes)]
-        first += c
-    return offs + [first]
-
-
-def ref_attention(kqv, counts, max_num_nodes, heads, dk, dv, mask=None):
-    """out [N, heads dv] in the dtype of kqv; `mask` [N heads, W]: the dropout multiplier of (row r heads + h, column j)."""
-    n = kqv.shape[0]
-    offs = window_offsets(counts, max_num_nodes)
-    lens = torch.tensor([b - a for a, b in zip(offs[:-1], offs[1:])])
-    W, Lmax = lens.shape[0], int(lens.max())
-    pos = torch.arange(Lmax)
-    valid = pos[None, :] < lens[:, None]                                           # [W, L]
-    rows = (torch.tensor(offs[:-1])[:, None] + pos[None, :]).clamp(max=n - 1)      # [W, L]
-    x = kqv.reshape(n, heads, 2 * dk + dv)[rows]                                   # [W, L, heads, :]
-    keys, queries, values = x[..., :dk], x[..., dk:2 * dk], x[..., 2 * dk:]
-    scores = torch.einsum("wkhd,wvhd->wkhv", keys, queries) / dk ** 0.5
-    scores = scores.masked_fill(~valid[:, None, None, :], float("-inf"))
-    probs = torch.softmax(scores, dim=-1)
-    if mask is not None:
-        m = mask.reshape(n, heads, -1)[rows][..., :Lmax]                          # [W, L(k), heads, L(v)]
-        probs = probs * m.to(probs.dtype)
-    out = torch.einsum("wkhv,wvhd->wkhd", probs, values)                           # [W, L, heads, dv]
-    return out[valid].reshape(n, heads * dv)
-
-
 REFS = {}
 
 
