@@ -162,6 +162,14 @@ enum {
   PTGNN_AMD_KERNEL_CANDIDATE_SCORES_BACKWARD,                 /* ptgnn_amd_candidate_scores_backward_f32 */
   PTGNN_AMD_KERNEL_HEAD_END_
 };
+/* A fifth id range: the loss of the copying decoder (csrc/vocab_loss.hip). */
+enum {
+  PTGNN_AMD_KERNEL_SEQ_FIRST_ = 256,
+  PTGNN_AMD_KERNEL_VOCAB_LOSS = PTGNN_AMD_KERNEL_SEQ_FIRST_, /* ptgnn_amd_vocab_loss_f32 */
+  PTGNN_AMD_KERNEL_VOCAB_LOSS_BACKWARD,                      /* ptgnn_amd_vocab_loss_backward_f32 */
+  PTGNN_AMD_KERNEL_COPY_LOSS_FINISH,                         /* ptgnn_amd_copy_loss_finish_f32 */
+  PTGNN_AMD_KERNEL_SEQ_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1129,6 +1137,62 @@ int ptgnn_amd_candidate_scores_backward_f32(const float *x, int64_t ld_x, int64_
                                             const float *lse, const float *grad_loss /* nullable */,
                                             const float *grad_scores /* nullable */, float *row_grad, float *grad_w,
                                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The loss of the copying decoder (csrc/vocab_loss.hip), replacing ptgnn/neuralmodels/sequence/
+ * grucopydecoder.py:118-135, 171-212: the `+ vocab_bias`, torch.logsumexp over cat(target_scores, total_copy_scores),
+ * `target_logprobs = target_scores - normalizing_const` [B, L, V], the torch.gather of the correct tokens and, for the
+ * third entry, the UNK mask, the stacked logsumexp, the length mask and the two means.  The [B L, V] log-probabilities
+ * never exist.  rows = B L decoding locations; s[r, v] = scores[r, v] + bias[v].  Exact fp32, no float atomics, fixed
+ * fold orders (two calls give the same bits); rows == 0 launches nothing.
+ *
+ * ptgnn_amd_vocab_loss_f32: scores [rows, vocab] (ld >= vocab; rows of any alignment) is the raw output of the second
+ *   vocabulary Linear, bias [vocab] nullable, extra [rows] nullable (the per-location copy normaliser, -inf for a
+ *   sample without memories), targets int64 [rows] nullable.
+ *     norm[r]   = logaddexp(log sum_v exp s[r, v], extra[r])     (extra[r] = -inf: the vocabulary term bit for bit)
+ *     picked[r] = s[r, targets[r]] - norm[r]                      (targets given; nan for a target outside [0, vocab),
+ *                                                                  which is never used as an index)
+ *     stats[r]  = (M, log_sum) with norm[r] = M + log_sum: the maximum over the row and extra[r], and the log of the sum
+ *                 relative to it ([rows, 2], 8-byte aligned).  The sum norm[r] is rounded at the magnitude of the logits,
+ *                 the pair is not: picked and the backward entry work from the pair.
+ *   Every score is read once, under a running maximum.  The columns of a row are split over workgroups; the
+ *   per-(row, column chunk) partials are merged in chunk order.
+ * ptgnn_amd_vocab_loss_backward_f32: stats [rows, 2] of the forward; g_norm [rows], g_picked [rows] DEVICE memory,
+ *   nullable = 0.
+ *     grad_scores[r, v] = (g_norm[r] - g_picked[r]) exp(s[r, v] - norm[r]) + g_picked[r] [v == targets[r]]     (ld_g)
+ *     grad_extra[r]     = (g_norm[r] - g_picked[r]) exp(extra[r] - norm[r])       nullable; 0 for extra[r] = -inf
+ *     grad_bias[v]      = sum_r grad_scores[r, v]                                 nullable
+ *   One pass: scores read once, gradients written once, grad_bias from per-row-block partials of that pass added in
+ *   row-block order (workspace; needed only with grad_bias, 16-byte aligned).
+ * ptgnn_amd_copy_loss_finish_f32 (grucopydecoder.py:171-212, after the two per-location terms exist): gen [B L] the
+ *   picked generation log-probabilities, copied [B L] the per-location log-sum-exp of the correct copy log-probabilities
+ *   (-inf: nothing to copy), rowptr int32 [B L + 1] nullable: the row pointer of the plan of
+ *   copyable_elements_sample_idxs over the locations (a location has a copy when its row is not empty), targets int64
+ *   [B L], lengths int64 [B].
+ *     gen'    = has_copy && targets == unk_id ? -inf : gen
+ *     any     = logsumexp(stack(gen', copied))
+ *     loss[0] = -mean_b( sum_{l} any[b, l] * [l < lengths[b]] / sum_l [l < lengths[b]] )
+ *   in the reference's arithmetic (the mask is a product; steps in step order, samples in sample order), and d_gen,
+ *   d_copied [B L] = d loss / d gen, d loss / d copied (0 where masked or -inf).  One launch of one workgroup.
+ * ---------------------------------------------------------------------------------------- */
+size_t ptgnn_amd_vocab_loss_workspace_bytes(int64_t rows, int32_t vocab);
+int ptgnn_amd_vocab_loss_f32(const float *scores, int64_t ld, int64_t rows, int32_t vocab,
+                             const float *bias /* nullable */, const float *extra /* nullable */,
+                             const int64_t *targets /* nullable */, float *norm, float *picked /* with targets */,
+                             float *stats, void *workspace, size_t workspace_bytes, void *stream);
+size_t ptgnn_amd_vocab_loss_backward_workspace_bytes(int64_t rows, int32_t vocab);
+int ptgnn_amd_vocab_loss_backward_f32(const float *scores, int64_t ld, int64_t rows, int32_t vocab,
+                                      const float *bias /* nullable */, const float *extra /* nullable */,
+                                      const int64_t *targets /* nullable */, const float *stats,
+                                      const float *g_norm /* nullable */, const float *g_picked /* nullable */,
+                                      float *grad_scores, int64_t ld_g, float *grad_extra /* nullable */,
+                                      float *grad_bias /* nullable */, void *workspace, size_t workspace_bytes,
+                                      void *stream);
+size_t ptgnn_amd_copy_loss_finish_workspace_bytes(int64_t num_samples);
+int ptgnn_amd_copy_loss_finish_f32(const float *gen, const float *copied, const int32_t *rowptr /* nullable */,
+                                   const int64_t *targets, int64_t unk_id, const int64_t *lengths, int64_t num_samples,
+                                   int32_t steps, float *loss, float *d_gen, float *d_copied, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 
 #pragma GCC visibility pop
 

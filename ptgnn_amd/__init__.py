@@ -15,7 +15,7 @@ def __getattr__(name):
     if name == "GruCopyingDecoder":
         from ptgnn_amd.sequence import GruCopyingDecoder
         return GruCopyingDecoder
-    if name in ("Graph2ClassModule", "VarMisuseGraphModel", "PPIClassification"):
+    if name in ("Graph2ClassModule", "VarMisuseGraphModel", "PPIClassification", "Graph2SeqModule"):
         from ptgnn_amd import heads
         return getattr(heads, name)
     if name in ("TokenUnitEmbedder", "SubtokenUnitEmbedder", "CharUnitEmbedder", "CnnConfig", "LinearFeatureEmbedder"):

@@ -174,6 +174,15 @@ SIGNATURES = {
     "ptgnn_amd_candidate_scores_backward_f32": (_c.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32,
                                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t,
                                                            _vp]),
+    "ptgnn_amd_vocab_loss_workspace_bytes": (_c.c_size_t, [_i64, _i32]),
+    "ptgnn_amd_vocab_loss_f32": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t,
+                                            _vp]),
+    "ptgnn_amd_vocab_loss_backward_workspace_bytes": (_c.c_size_t, [_i64, _i32]),
+    "ptgnn_amd_vocab_loss_backward_f32": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                                     _vp, _vp, _c.c_size_t, _vp]),
+    "ptgnn_amd_copy_loss_finish_workspace_bytes": (_c.c_size_t, [_i64]),
+    "ptgnn_amd_copy_loss_finish_f32": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                                                  _c.c_size_t, _vp]),
 }
 
 # The header version this host was written against (include/ptgnn_amd.h: PTGNN_AMD_VERSION).  A stale .so with an

@@ -24,6 +24,7 @@ static std::atomic<int64_t> g_launches[PTGNN_AMD_KERNEL_COUNT_];
 static std::atomic<int64_t> g_agg_launches[PTGNN_AMD_KERNEL_AGG_END_ - PTGNN_AMD_KERNEL_AGG_FIRST_];
 static std::atomic<int64_t> g_char_launches[PTGNN_AMD_KERNEL_CHAR_END_ - PTGNN_AMD_KERNEL_CHAR_FIRST_];
 static std::atomic<int64_t> g_head_launches[PTGNN_AMD_KERNEL_HEAD_END_ - PTGNN_AMD_KERNEL_HEAD_FIRST_];
+static std::atomic<int64_t> g_seq_launches[PTGNN_AMD_KERNEL_SEQ_END_ - PTGNN_AMD_KERNEL_SEQ_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -32,6 +33,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_char_launches[kernel_id - PTGNN_AMD_KERNEL_CHAR_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_HEAD_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HEAD_END_)
     return &g_head_launches[kernel_id - PTGNN_AMD_KERNEL_HEAD_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_SEQ_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_SEQ_END_)
+    return &g_seq_launches[kernel_id - PTGNN_AMD_KERNEL_SEQ_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -83,6 +86,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "logit_loss", "logit_loss_backward", "candidate_scores", "candidate_scores_backward"};
   if (kernel_id >= PTGNN_AMD_KERNEL_HEAD_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HEAD_END_)
     return head_names[kernel_id - PTGNN_AMD_KERNEL_HEAD_FIRST_];
+  static const char *const seq_names[PTGNN_AMD_KERNEL_SEQ_END_ - PTGNN_AMD_KERNEL_SEQ_FIRST_] = {
+      "vocab_loss", "vocab_loss_backward", "copy_loss_finish"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_SEQ_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_SEQ_END_)
+    return seq_names[kernel_id - PTGNN_AMD_KERNEL_SEQ_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

@@ -1,9 +1,10 @@
-"""The task heads of the three benchmarked models: the `ModuleWithMetrics` that owns the GNN, turns node states into a
-loss and keeps the accuracy figures.  Mirrors of
+"""The task heads of the three benchmarked models and of Graph2Seq: the `ModuleWithMetrics` that owns the GNN, turns node
+states into a loss and keeps the accuracy figures.  Mirrors of
 
     Graph2ClassModule     ptgnn/implementations/typilus/graph2class.py:63-102
     VarMisuseGraphModel   ptgnn/implementations/varmisuse/varmisuse.py:41-91
     PPIClassification     ptgnn/implementations/ppi/ppi.py:13-62
+    Graph2SeqModule       ptgnn/implementations/graph2seq/graph2seq.py:36-81
 
 with the same class names, constructor keywords, RNG draws in the same order, name-mangled parameter names (a reference
 state_dict loads strictly, both ways), forward signatures and metric names.  `gnn` is any module with
@@ -17,6 +18,9 @@ GPU route (node states on the GPU; csrc/task_heads.hip):
   * VarMisuse: ONE autograd node around the candidate kernel (no [Cn, 2H] concatenation, no gathered copies; d x by one
     segment sum over the plan of the candidate and slot ids).  Node states whose width is not a multiple of 4 up to 1024
     compose the HIP row gather, `dense.linear` and the facade's scatter_log_softmax / scatter_max.
+  * Graph2Seq: the backbone nodes' states by the differentiable HIP row gather, the summariser of `reduceops`, and the
+    decoder's loss on the fused vocabulary-loss kernels (`sequence.GruCopyingDecoder.fused_loss`, csrc/vocab_loss.hip);
+    the loss is added into a per-device accumulator tensor, read in `_module_metrics` only.
   * fp16 / bf16 node states and parameters are up-cast; the loss is fp32.
   * NO call of `forward` or `predict` waits for the device.  The metrics live in a lazily allocated per-device block that
     the kernels' merge step adds into; they reach the host in `_module_metrics` / `report_metrics` only, where the
@@ -30,8 +34,10 @@ from typing import Any, Dict, Tuple
 import torch
 from torch import nn
 
-from ptgnn_amd import dense, ops, scatter
+from ptgnn_amd import dense, ops, scatter, sequence
+from ptgnn_amd._lib import PtgnnAmdError
 from ptgnn_amd.gnn import GnnOutput, ModuleWithMetrics
+from ptgnn_amd.reduceops import ElementsToSummaryRepresentationInput
 
 _NAN = float("nan")
 
@@ -318,3 +324,68 @@ class PPIClassification(ModuleWithMetrics):
         losses = nn.functional.binary_cross_entropy_with_logits(input=target_logits, target=targets.float(),
                                                                 reduction="none")
         return losses.sum(dim=-1).mean()
+
+
+class Graph2SeqModule(ModuleWithMetrics):
+    """graph2seq/graph2seq.py:36-81: the GNN, the summariser that turns the nodes of a graph into the decoder's initial
+    state, and the copying decoder over the states of the backbone nodes."""
+
+    # `ptgnn_amd.sequence.GruCopyingDecoder.fused_loss` instead of the decoder's `forward`; any other decoder module is
+    # called as the reference calls it.  profiles/graph2seq_notes.md holds the comparison behind the default.
+    use_fused_loss = True
+
+    def __init__(self, gnn: nn.Module, decoder: nn.Module, node_to_graph_representation: nn.Module):
+        super().__init__()
+        self._gnn = gnn
+        self._decoder = decoder
+        self.__node_to_graph_representation = node_to_graph_representation
+
+    def _reset_module_metrics(self) -> None:
+        self.__loss_sum = 0.0
+        self.__num_mbs = 0
+        self.__device_loss_sums = {}       # device -> float64 [] accumulator; dropped (no launch) on reset
+
+    def _module_metrics(self) -> Dict[str, Any]:
+        loss_sum = self.__loss_sum
+        for acc in self.__device_loss_sums.values():       # the blocking reads: only here, where the reference reads too
+            loss_sum += float(acc.cpu())
+        return {"loss": loss_sum / self.__num_mbs}
+
+    def _get_initial_decoder_states(self, gnn_output: GnnOutput):
+        inputs, outputs = gnn_output.input_node_representations, gnn_output.output_node_representations
+        if outputs.is_cuda:
+            inputs, outputs = _f32(inputs), _f32(outputs)
+        return self.__node_to_graph_representation(ElementsToSummaryRepresentationInput(
+            element_embeddings=torch.cat((inputs, outputs), dim=-1),
+            element_to_sample_map=gnn_output.node_to_graph_idx, num_samples=gnn_output.num_graphs))
+
+    def forward(self, *, encoder_mb_data: Dict[str, Any], decoder_mb_data: Dict[str, Any]):
+        gnn_output: GnnOutput = self._gnn(**encoder_mb_data)
+        states = gnn_output.output_node_representations
+        backbone = gnn_output.node_idx_references["backbone_nodes"]
+        if not states.is_cuda:             # device dispatch: CPU tensors take the reference's own operator order
+            memories = states[backbone]
+        elif backbone.shape[0] == 0:       # no backbone nodes: nothing is launched
+            memories = _f32(states).new_zeros(0, states.shape[1]) + _f32(states).sum() * 0.0
+        else:
+            memories = sequence._rows(_f32(states), backbone)
+        decoder = self._decoder
+        fused = self.use_fused_loss and isinstance(decoder, sequence.GruCopyingDecoder)
+        loss = (decoder.fused_loss if fused else decoder)(
+            input_memories=memories, input_memories_origin_idx=gnn_output.node_graph_idx_reference["backbone_nodes"],
+            initial_states=self._get_initial_decoder_states(gnn_output), **decoder_mb_data)
+        with torch.no_grad():
+            if loss.is_cuda:               # no call of forward waits for the device
+                acc = self.__device_loss_sums.get(loss.device)
+                if acc is None:
+                    self.__device_loss_sums[loss.device] = loss.detach().double()
+                else:
+                    acc.add_(loss.detach())
+            else:
+                self.__loss_sum += float(loss.detach())
+            self.__num_mbs += 1
+        return loss
+
+    def forward_sharded(self, *args, **kwargs):
+        """The decoder attends over all memories of a sample: there is no sharded form."""
+        raise PtgnnAmdError("forward_sharded: cannot combine partial pools of Graph2SeqModule")

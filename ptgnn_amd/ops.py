@@ -47,18 +47,23 @@ _CHAR_FAMILY_FIRST = 128  # PTGNN_AMD_KERNEL_CHAR_FIRST_: the char-CNN kernels' 
 _HEAD_FAMILY_FIRST = 192  # PTGNN_AMD_KERNEL_HEAD_FIRST_: the task heads' id range
 
 
-def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False) -> dict:
+_SEQ_FAMILY_FIRST = 256  # PTGNN_AMD_KERNEL_SEQ_FIRST_: the copying decoder's loss kernels
+
+
+def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
+                  sequence: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
     attention_pool, attention_pool_backward, head_projection, graph_norm, graph_norm_backward, block_attention,
     block_attention_backward, segment_scores, segment_scores_backward, embedding_bag, embedding_bag_backward);
     `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward);
-    `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward)."""
+    `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward);
+    `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
-            + ((_HEAD_FAMILY_FIRST,) if heads else ()):
+            + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -71,7 +76,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True, char_cnn=True, heads=True)
+    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2628,3 +2633,113 @@ def candidate_scores_backward(x: torch.Tensor, cand_idx: torch.Tensor, slot_idx:
             row_grad.data_ptr() if Cn + G else None, grad_w.data_ptr(), ws.data_ptr(), ws_bytes, _stream(grad_w))
     _lib.check(rc, "ptgnn_amd_candidate_scores_backward_f32")
     return row_grad, grad_w
+
+
+# ------------------------------------------------------------------------------------------------
+# the copying decoder's loss (csrc/vocab_loss.hip)
+# ------------------------------------------------------------------------------------------------
+def _vocab_args(scores: torch.Tensor, bias, extra, targets, what: str):
+    _require_cuda_f32("scores", scores)
+    scores = _rowmajor(scores)
+    R, V = scores.shape
+    if V < 1:
+        raise _lib.PtgnnAmdError(f"{what}: scores need at least one column")
+    dev = scores.device
+    for name, t, n, dt in (("bias", bias, V, torch.float32), ("extra", extra, R, torch.float32),
+                           ("targets", targets, R, torch.int64)):
+        if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,)):
+            raise _lib.PtgnnAmdError(f"{what}: {name} must be a CUDA {dt} [{n}] tensor on the scores' device (got "
+                                     f"{t.dtype} {tuple(t.shape)} on {t.device})")
+    return scores, *(t.contiguous() if t is not None else None for t in (bias, extra, targets)), R, V
+
+
+def _opt_ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def vocab_loss(scores: torch.Tensor, bias: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None,
+               targets: Optional[torch.Tensor] = None):
+    """(norm [R], picked [R] or None, stats [R, 2]) over raw vocabulary scores [R, V] (ptgnn_amd_vocab_loss_f32;
+    grucopydecoder.py:118-135): with s = scores + bias, norm = logaddexp(logsumexp_v s, extra) and picked =
+    s[r, targets[r]] - norm (nan for a target outside [0, V)); stats = (maximum, log of the sum relative to it) with norm =
+    their sum, which `vocab_loss_backward` takes.  One read of the scores; the [R, V] log-probabilities are never formed."""
+    lib = _lib.load()
+    scores, bias, extra, targets, R, V = _vocab_args(scores, bias, extra, targets, "vocab_loss")
+    dev = scores.device
+    norm = torch.empty(R, dtype=torch.float32, device=dev)
+    picked = torch.empty(R, dtype=torch.float32, device=dev) if targets is not None else None
+    stats = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    if R == 0:
+        return norm, picked, stats
+    ws_bytes = int(lib.ptgnn_amd_vocab_loss_workspace_bytes(R, V))
+    ws = _workspace(ws_bytes, dev)
+    with _timed("vocab_loss", bytes=4.0 * R * V + 4.0 * V + 24.0 * R):
+        rc = lib.ptgnn_amd_vocab_loss_f32(scores.data_ptr(), _ld(scores), R, V, _opt_ptr(bias), _opt_ptr(extra),
+                                          _opt_ptr(targets), norm.data_ptr(), _opt_ptr(picked), stats.data_ptr(),
+                                          ws.data_ptr(), ws_bytes, _stream(norm))
+    _lib.check(rc, "ptgnn_amd_vocab_loss_f32")
+    return norm, picked, stats
+
+
+def vocab_loss_backward(scores: torch.Tensor, bias: Optional[torch.Tensor], extra: Optional[torch.Tensor],
+                        targets: Optional[torch.Tensor], stats: torch.Tensor, g_norm: Optional[torch.Tensor],
+                        g_picked: Optional[torch.Tensor], want_bias: bool = True):
+    """(grad_scores [R, V], grad_extra [R] or None, grad_bias [V] or None) of `vocab_loss` from its `stats` and the gradients of
+    its norm and picked outputs (device tensors, None = 0) in one pass (ptgnn_amd_vocab_loss_backward_f32): grad_bias comes from the pass's own
+    per-row-block column sums, added in row-block order."""
+    lib = _lib.load()
+    scores, bias, extra, targets, R, V = _vocab_args(scores, bias, extra, targets, "vocab_loss_backward")
+    dev = scores.device
+    for name, t, shape in (("stats", stats, (R, 2)), ("g_norm", g_norm, (R,)), ("g_picked", g_picked, (R,))):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise _lib.PtgnnAmdError(f"vocab_loss_backward: {name} must be a CUDA float32 {list(shape)} tensor")
+    stats, g_norm, g_picked = (t.contiguous() if t is not None else None for t in (stats, g_norm, g_picked))
+    grad = torch.empty(R, V, dtype=torch.float32, device=dev)
+    grad_extra = torch.empty(R, dtype=torch.float32, device=dev) if extra is not None else None
+    if R == 0:
+        return grad, grad_extra, torch.zeros(V, dtype=torch.float32, device=dev) if want_bias else None
+    grad_bias = torch.empty(V, dtype=torch.float32, device=dev) if want_bias else None
+    ws_bytes = int(lib.ptgnn_amd_vocab_loss_backward_workspace_bytes(R, V)) if want_bias else 0
+    ws = _workspace(ws_bytes, dev)
+    with _timed("vocab_loss_backward", bytes=8.0 * R * V + (8.0 * ((R + 7) // 8) * V if want_bias else 0.0) + 24.0 * R):
+        rc = lib.ptgnn_amd_vocab_loss_backward_f32(scores.data_ptr(), _ld(scores), R, V, _opt_ptr(bias), _opt_ptr(extra),
+                                                   _opt_ptr(targets), stats.data_ptr(), _opt_ptr(g_norm), _opt_ptr(g_picked),
+                                                   grad.data_ptr(), V, _opt_ptr(grad_extra), _opt_ptr(grad_bias),
+                                                   ws.data_ptr(), ws_bytes, _stream(grad))
+    _lib.check(rc, "ptgnn_amd_vocab_loss_backward_f32")
+    return grad, grad_extra, grad_bias
+
+
+def copy_loss_finish(gen: torch.Tensor, copied: torch.Tensor, rowptr: Optional[torch.Tensor], targets: torch.Tensor,
+                     unk_id: int, lengths: torch.Tensor):
+    """(loss [], d_gen [B, L], d_copied [B, L]) of the decoder's [B, L] tail (ptgnn_amd_copy_loss_finish_f32;
+    grucopydecoder.py:171-212): gen / copied [B, L] the correct generation / copy log-probabilities, `rowptr` int32
+    [B L + 1] the row pointer of the plan of the copyable locations (None: nothing to copy anywhere), targets int64 [B, L],
+    lengths int64 [B].  One launch; the two derivatives are those of the returned loss."""
+    lib = _lib.load()
+    _require_cuda_f32("gen", gen)
+    _require_cuda_f32("copied", copied)
+    B, L = gen.shape
+    dev = gen.device
+    if tuple(copied.shape) != (B, L) or tuple(targets.shape) != (B, L) or targets.dtype != torch.int64 \
+            or not targets.is_cuda or tuple(lengths.shape) != (B,) or lengths.dtype != torch.int64 or not lengths.is_cuda:
+        raise _lib.PtgnnAmdError(f"copy_loss_finish: copied float32 / targets int64 must be CUDA [{B}, {L}] tensors and "
+                                 f"lengths a CUDA int64 [{B}] tensor")
+    if rowptr is not None and (not rowptr.is_cuda or rowptr.dtype != torch.int32 or rowptr.numel() != B * L + 1):
+        raise _lib.PtgnnAmdError(f"copy_loss_finish: rowptr must be a CUDA int32 [{B * L + 1}] tensor")
+    gen, copied, targets, lengths = (t.contiguous() for t in (gen, copied, targets, lengths))
+    d_gen = torch.empty(B, L, dtype=torch.float32, device=dev)
+    d_copied = torch.empty(B, L, dtype=torch.float32, device=dev)
+    if B == 0 or L == 0:
+        return torch.full((), float("nan"), dtype=torch.float32, device=dev), d_gen, d_copied
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.ptgnn_amd_copy_loss_finish_workspace_bytes(B))
+    ws = _workspace(ws_bytes, dev)
+    with _timed("copy_loss_finish", bytes=28.0 * B * L + 12.0 * B):
+        rc = lib.ptgnn_amd_copy_loss_finish_f32(gen.data_ptr(), copied.data_ptr(),
+                                                rowptr.contiguous().data_ptr() if rowptr is not None else None,
+                                                targets.data_ptr(), int(unk_id), lengths.data_ptr(), B, L, loss.data_ptr(),
+                                                d_gen.data_ptr(), d_copied.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                _stream(loss))
+    _lib.check(rc, "ptgnn_amd_copy_loss_finish_f32")
+    return loss.view(()), d_gen, d_copied

@@ -12,8 +12,15 @@ GRU's output states [B, L, H]:
   * copy attention: scores and their per-sample log-sum-exp in one pass (csrc/segment_scores.hip).  Dropout sits between
     the copy Linear and the dot product (grucopydecoder.py:83-97), so while it is active the rows are dropout(W_c x) and
     the vectors o; otherwise W_c moves onto the samples too and the rows are x itself (greedy decoding: L = 1 per step);
-  * the vocabulary product as two HIP Linears, the joint normaliser and the loss arithmetic as torch glue on [B, L, V]
-    and [I, L] tensors.
+  * the vocabulary product as two HIP Linears; in `forward` / `_compute_logprobs` (greedy decoding needs the whole
+    `target_logprobs`) the joint normaliser and the loss arithmetic are torch glue on [B, L, V] and [I, L] tensors;
+  * `fused_loss` (the training loss, what `heads.Graph2SeqModule` calls) keeps the same GRU, attention and copy scores and
+    replaces that glue by csrc/vocab_loss.hip: `_VocabLoss` reads the RAW second Linear's output once -- bias, running
+    maximum, joint normaliser with the copy term, the correct tokens' entries -- and its one-pass backward writes the
+    gradient of the raw scores and the bias gradient; the correct copy entries are [C]-sized gathers off the copy scores
+    minus the normaliser of their own (sample of the memory, step), their per-location log-sum-exp runs on the facade's
+    segment kernels, and `_CopyLossFinish` is the [B, L] tail in one launch.  Neither `target_logprobs` [B, L, V] nor
+    `copy_logprobs` [I, L] exists on that route; on shapes beyond the fused range only its attention part is composed.
 Shapes beyond that range compose the reference's operator sequence from the HIP Linear, the fused cell, the row gather
 and the facade's segment kernels.  CPU tensors take the reference's own operator order on torch (device dispatch as in
 every layer of the package); fp16 / bf16 inputs are up-cast on entry and the results cast back.
@@ -40,6 +47,54 @@ def _rows(table: torch.Tensor, index: torch.Tensor, plan=None) -> torch.Tensor:
     if plan is None:
         plan = ops.plan_for([(index, index)], table.shape[0])
     return gather_rows_autograd(table, index, plan)
+
+
+class _VocabLoss(torch.autograd.Function):
+    """(norm [R], picked [R]) = ops.vocab_loss(raw scores [R, V], bias, total_copy [R], targets [R]) as one node: the joint
+    normaliser of grucopydecoder.py:124-130 and the correct tokens' log-probabilities of :178-181 without the [R, V]
+    log-probabilities.  The backward is the kernel's second entry point; its grad_scores flows into dense._Linear."""
+
+    @staticmethod
+    def forward(ctx, raw_scores, bias, total_copy, targets):
+        norm, picked, stats = ops.vocab_loss(raw_scores, bias, total_copy, targets)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raw_scores, bias, total_copy, targets, stats)
+        return norm, picked
+
+    @staticmethod
+    def backward(ctx, g_norm, g_picked):
+        raw_scores, bias, total_copy, targets, stats = ctx.saved_tensors
+        grad, g_extra, g_bias = ops.vocab_loss_backward(raw_scores, bias, total_copy, targets, stats, g_norm, g_picked,
+                                                        want_bias=bias is not None and ctx.needs_input_grad[1])
+        return grad, g_bias, g_extra if ctx.needs_input_grad[2] else None, None
+
+
+class _CopyLossFinish(torch.autograd.Function):
+    """loss = ops.copy_loss_finish(gen [B, L], copied [B, L], ...) as one node (grucopydecoder.py:171-212).  The launch
+    writes the derivatives of its own loss; the backward scales them by the upstream scalar on the device."""
+
+    @staticmethod
+    def forward(ctx, gen, copied, rowptr, targets, unk_id, lengths):
+        loss, d_gen, d_copied = ops.copy_loss_finish(gen, copied, rowptr, targets, unk_id, lengths)
+        ctx.save_for_backward(d_gen, d_copied)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d_gen, d_copied = ctx.saved_tensors
+        return d_gen * g, d_copied * g, None, None, None, None
+
+
+def _plan_logsumexp(x: torch.Tensor, index: torch.Tensor, plan) -> torch.Tensor:
+    """scatter_logsumexp(x [C, 1], index, eps=0) over the given plan of `index` (the facade's own sequence,
+    scatter.scatter_logsumexp, without a second plan build): -inf for a segment without elements."""
+    with torch.no_grad():
+        vals, slot = ops.gather_reduce(x.detach(), plan, 1, "max", return_arg=True, type_bits=0, col=plan.perm)
+        top = torch.where(slot >= 0, vals, torch.full_like(vals, -math.inf))
+        shift = ops.gather_rows(top, index)
+    rec = x - shift
+    rec = rec.masked_fill(rec.isnan(), -math.inf)
+    return scatter_facade.segment_reduce(rec.exp(), plan, "sum").log() + top
 
 
 class GruCopyingDecoder(nn.Module):
@@ -103,11 +158,15 @@ class GruCopyingDecoder(nn.Module):
             states.append(h)
         return torch.stack(states, dim=1), h
 
-    def __vocabulary_scores(self, attention_out, output_states):
-        """grucopydecoder.py:111-119 on [B * L, .] matrices: two HIP Linears and the bias."""
+    def __raw_vocabulary_scores(self, attention_out, output_states):
+        """grucopydecoder.py:111-118 on [B * L, .] matrices: two HIP Linears, the bias not added."""
         hidden = torch.cat((self.__dropout(attention_out), output_states), dim=-1)         # [B * L, 2 H]
         projected = dense.linear(hidden, self.__hidden_to_vocab.t())                       # [B * L, E]
-        return dense.linear(projected, self.__dropout(self.__embedding_layer.weight)) + self.__vocab_bias
+        return dense.linear(projected, self.__dropout(self.__embedding_layer.weight))
+
+    def __vocabulary_scores(self, attention_out, output_states):
+        """grucopydecoder.py:111-119: the raw scores and the bias."""
+        return self.__raw_vocabulary_scores(attention_out, output_states) + self.__vocab_bias
 
     def __composed_attention(self, x, index, plan, output_states):
         """L > 8 or a width > 1024: the reference's operator sequence (grucopydecoder.py:79-124) on the HIP Linear, the
@@ -124,7 +183,9 @@ class GruCopyingDecoder(nn.Module):
         total_copy = scatter_facade.scatter_logsumexp(copy_scores, index, dim=0, dim_size=B, eps=0.0)
         return attention_out.reshape(B * L, H), copy_scores, total_copy
 
-    def __device_logprobs(self, initial_states, x, index, input_token_ids):
+    def __device_attention(self, initial_states, x, index, input_token_ids):
+        """What both GPU routes share: (GRU states [B L, H], attention output [B L, H], copy scores [I, L], their
+        per-sample log-sum-exp [B, L], the GRU's last state [B, H], the plan of `index` over the samples)."""
         if index.dtype != torch.int64 or not index.is_cuda or index.dim() != 1 or index.shape[0] != x.shape[0]:
             raise _lib.PtgnnAmdError("GruCopyingDecoder: input_memories_origin_idx must be a CUDA int64 tensor with one "
                                      "entry per memory")
@@ -150,6 +211,12 @@ class GruCopyingDecoder(nn.Module):
             else:
                 rows, vectors = x, dense.linear(states, w_c.t()).reshape(B, L, Dm)         # u_c = W_c^T o
             copy_scores, total_copy = segment_scores(rows, vectors.contiguous(), plan)     # [I, L], [B, L]
+        return states, attention_out, copy_scores, total_copy, last_state, plan
+
+    def __device_logprobs(self, initial_states, x, index, input_token_ids):
+        B, L = input_token_ids.shape
+        states, attention_out, copy_scores, total_copy, last_state, plan = self.__device_attention(
+            initial_states, x, index, input_token_ids)
         target_scores = self.__vocabulary_scores(attention_out, states).reshape(B, L, -1)  # [B, L, V]
         # logsumexp(cat(target_scores, total_copy)) without the [B, L, V + 1] copy
         normalizing_const = torch.logaddexp(torch.logsumexp(target_scores, dim=-1), total_copy)
@@ -216,6 +283,43 @@ class GruCopyingDecoder(nn.Module):
         mask = torch.arange(num_steps, device=target_lengths.device).unsqueeze(0) < target_lengths.unsqueeze(1)
         per_seq_loss = (any_correct_action_logprob * mask.float()).sum(dim=-1) / mask.float().sum(dim=-1)
         return -per_seq_loss.mean()
+
+    def fused_loss(self, *, input_memories, input_memories_origin_idx, initial_states, target_token_ids,
+                   copyable_elements_idxs, copyable_elements_sample_idxs, target_lengths):
+        """The loss of `forward` (same keyword arguments, same value) on the fused vocabulary-loss kernels
+        (csrc/vocab_loss.hip): neither `target_logprobs` [B, L, V] nor `copy_logprobs` [I, L] exists.  The GRU states, the
+        attention and the copy scores are those of `_compute_logprobs`; the raw vocabulary product goes through
+        `_VocabLoss` (bias, joint normaliser with the copy term, the correct tokens' entries), the correct copy entries
+        are read off the copy scores as [C] tensors, and `_CopyLossFinish` is the [B, L] tail in one launch.  CPU tensors
+        and B = 0 / L = 0 are handed to `forward`."""
+        B, L = target_token_ids.shape[0], target_token_ids.shape[1] - 1
+        if not input_memories.is_cuda or B == 0 or L <= 0:
+            return self.forward(
+                input_memories=input_memories, input_memories_origin_idx=input_memories_origin_idx,
+                initial_states=initial_states, target_token_ids=target_token_ids,
+                copyable_elements_idxs=copyable_elements_idxs,
+                copyable_elements_sample_idxs=copyable_elements_sample_idxs, target_lengths=target_lengths)
+        if input_memories.dtype in _HALF or initial_states.dtype in _HALF:       # AMP: fp32 inside, an fp32 loss
+            input_memories, initial_states = input_memories.float(), initial_states.float()
+        index = input_memories_origin_idx
+        states, attention_out, copy_scores, total_copy, _, _ = self.__device_attention(
+            initial_states, input_memories, index, target_token_ids[:, :-1])
+        targets = target_token_ids[:, 1:].contiguous()                                     # [B, L]
+        raw_scores = self.__raw_vocabulary_scores(attention_out, states)                   # [B * L, V]: the only one
+        norm, picked = _VocabLoss.apply(raw_scores, self.__vocab_bias, total_copy.reshape(B * L), targets.reshape(B * L))
+        if copyable_elements_idxs.shape[0] == 0:
+            copied, rowptr = torch.full((B, L), -math.inf, dtype=torch.float32, device=norm.device), None
+        else:
+            # entry e = memory * L + step of the flattened copy scores; its normaliser is that of (sample of the memory,
+            # step), whatever location the caller files the entry under
+            memory = torch.div(copyable_elements_idxs, L, rounding_mode="floor")
+            own_location = index[memory] * L + (copyable_elements_idxs - memory * L)
+            correct = _rows(copy_scores.reshape(-1, 1), copyable_elements_idxs) \
+                - _rows(norm.reshape(-1, 1), own_location)                                 # [C, 1]
+            plan = _index_plan(copyable_elements_sample_idxs, B * L)
+            copied = _plan_logsumexp(correct, copyable_elements_sample_idxs, plan).reshape(B, L)
+            rowptr = plan.rowptr
+        return _CopyLossFinish.apply(picked.reshape(B, L), copied, rowptr, targets, self.__unk_id, target_lengths.long())
 
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form (as for the attention reducers)."""
