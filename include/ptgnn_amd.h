@@ -170,6 +170,12 @@ enum {
   PTGNN_AMD_KERNEL_COPY_LOSS_FINISH,                         /* ptgnn_amd_copy_loss_finish_f32 */
   PTGNN_AMD_KERNEL_SEQ_END_
 };
+/* A sixth id range: the greedy-decoding step of the copying decoder (csrc/decode_step.hip). */
+enum {
+  PTGNN_AMD_KERNEL_DECODE_FIRST_ = 320,
+  PTGNN_AMD_KERNEL_DECODE_STEP = PTGNN_AMD_KERNEL_DECODE_FIRST_, /* ptgnn_amd_decode_step_f32 */
+  PTGNN_AMD_KERNEL_DECODE_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1193,6 +1199,42 @@ int ptgnn_amd_copy_loss_finish_f32(const float *gen, const float *copied, const 
                                    const int64_t *targets, int64_t unk_id, const int64_t *lengths, int64_t num_samples,
                                    int32_t steps, float *loss, float *d_gen, float *d_copied, void *workspace,
                                    size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * One step of the copying decoder's greedy decoding (csrc/decode_step.hip), replacing the per-step host work of
+ * ptgnn/neuralmodels/sequence/grucopydecoder.py:375-457: `target_logprobs`, torch.topk, the three .cpu() copies, the
+ * Python dict merge of copy and vocabulary probabilities, the arg-max and the next token tensor.  One launch, one
+ * workgroup per sample, no host read-back; the [B, V] log-probabilities never exist.
+ *   scores [B, vocab] (ld >= vocab) the RAW output of the second vocabulary Linear, bias [vocab] nullable,
+ *   copy_scores [num_memories] and total_copy [B] (their per-sample log-sum-exp, -inf for a sample without memories) as
+ *   ptgnn_amd_segment_scores_f32 leaves them for one vector per sample.
+ *   The value grouping of the call: rowptr int32 [B + 1], slot_memory int32 [num_memories] (the memory of a slot) and
+ *   slot_ids int64 [num_memories] (its value id), the slots of sample b being rowptr[b] .. rowptr[b + 1] - 1 with
+ *   ascending ids.  An id < vocab is a vocabulary id; any other id is the caller's key of an out-of-vocabulary value.
+ * Per sample b with done[b] == 0, s[v] = scores[b, v] + bias[v] and norm = logaddexp(log sum_v exp s[v], total_copy[b]):
+ *   every run of equal ids g is an entry  log sum_{slots of the run} exp(copy_scores[.] - norm), merged by logaddexp with
+ *   s[g] - norm when g < vocab and s[g] is one of the top_k largest of the row; the other entry is the row's largest,
+ *   s[v*] - norm.  The prediction is the largest entry.  Exact ties: among equal scores of the row the lower index is
+ *   the larger (top-1 and the top_k-th place alike), the row's entry goes before a run of equal value, and of two runs
+ *   the lower id.
+ *     logprobs[b] += the entry;  prediction == end_id: done[b] = 1;  else tokens[b, step] = prediction, lengths[b] += 1
+ *     next_tokens[b] = prediction < vocab ? prediction : unk_id
+ * A sample with done[b] != 0 gets next_tokens[b] = end_id and nothing else.  tokens is [B, max_steps].
+ * slot_memory entries outside [0, num_memories) and negative ids are clamped to 0 and counted in bad[0] (int32, DEVICE
+ * memory, nullable), like every row gather of the library.  Exact fp32, no float atomics: two calls give the same
+ * bits.  vocab < 1, top_k < 1, a step outside [0, max_steps) or unk_id / end_id outside the vocabulary answer
+ * PTGNN_AMD_EINVAL before any device work; num_samples == 0 launches nothing.
+ * workspace: ptgnn_amd_decode_step_workspace_bytes(num_samples, vocab, top_k) -- 0 today (a sample's partial results stay
+ * in the LDS of its workgroup), 0 for sizes the entry refuses.
+ * ---------------------------------------------------------------------------------------- */
+size_t ptgnn_amd_decode_step_workspace_bytes(int64_t num_samples, int32_t vocab, int32_t top_k);
+int ptgnn_amd_decode_step_f32(const float *scores, int64_t ld, const float *bias /* nullable */,
+                              const float *copy_scores, const float *total_copy, const int32_t *slot_memory,
+                              const int32_t *rowptr, const int64_t *slot_ids, int64_t num_samples,
+                              int64_t num_memories, int32_t vocab, int32_t top_k, int64_t unk_id, int64_t end_id,
+                              int32_t step, int32_t max_steps, int32_t *done, int64_t *lengths, float *logprobs,
+                              int64_t *tokens, int64_t *next_tokens, int32_t *bad /* nullable */, void *workspace,
+                              size_t workspace_bytes, void *stream);
 
 #pragma GCC visibility pop
 

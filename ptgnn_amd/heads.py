@@ -359,7 +359,8 @@ class Graph2SeqModule(ModuleWithMetrics):
             element_embeddings=torch.cat((inputs, outputs), dim=-1),
             element_to_sample_map=gnn_output.node_to_graph_idx, num_samples=gnn_output.num_graphs))
 
-    def forward(self, *, encoder_mb_data: Dict[str, Any], decoder_mb_data: Dict[str, Any]):
+    def __decoder_inputs(self, encoder_mb_data: Dict[str, Any]) -> Dict[str, Any]:
+        """The GNN, the backbone gather and the summariser: what the decoder is given besides its own minibatch data."""
         gnn_output: GnnOutput = self._gnn(**encoder_mb_data)
         states = gnn_output.output_node_representations
         backbone = gnn_output.node_idx_references["backbone_nodes"]
@@ -369,11 +370,14 @@ class Graph2SeqModule(ModuleWithMetrics):
             memories = _f32(states).new_zeros(0, states.shape[1]) + _f32(states).sum() * 0.0
         else:
             memories = sequence._rows(_f32(states), backbone)
+        return dict(input_memories=memories,
+                    input_memories_origin_idx=gnn_output.node_graph_idx_reference["backbone_nodes"],
+                    initial_states=self._get_initial_decoder_states(gnn_output))
+
+    def forward(self, *, encoder_mb_data: Dict[str, Any], decoder_mb_data: Dict[str, Any]):
         decoder = self._decoder
         fused = self.use_fused_loss and isinstance(decoder, sequence.GruCopyingDecoder)
-        loss = (decoder.fused_loss if fused else decoder)(
-            input_memories=memories, input_memories_origin_idx=gnn_output.node_graph_idx_reference["backbone_nodes"],
-            initial_states=self._get_initial_decoder_states(gnn_output), **decoder_mb_data)
+        loss = (decoder.fused_loss if fused else decoder)(**self.__decoder_inputs(encoder_mb_data), **decoder_mb_data)
         with torch.no_grad():
             if loss.is_cuda:               # no call of forward waits for the device
                 acc = self.__device_loss_sums.get(loss.device)
@@ -385,6 +389,15 @@ class Graph2SeqModule(ModuleWithMetrics):
                 self.__loss_sum += float(loss.detach())
             self.__num_mbs += 1
         return loss
+
+    def greedy_decode(self, *, encoder_mb_data: Dict[str, Any], input_element_ids, start_id: int, end_id: int,
+                      max_seq_len: int, top_k: int = 100):
+        """graph2seq.py:175-204 without the host loop: the decoder inputs exactly as `forward` forms them, under
+        torch.no_grad(), handed to `sequence.GruCopyingDecoder.greedy_decode` (its argument and result conventions;
+        `input_element_ids` has one id per backbone node)."""
+        with torch.no_grad():
+            return self._decoder.greedy_decode(**self.__decoder_inputs(encoder_mb_data), input_element_ids=input_element_ids,
+                                               start_id=start_id, end_id=end_id, max_seq_len=max_seq_len, top_k=top_k)
 
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form."""

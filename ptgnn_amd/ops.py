@@ -50,8 +50,11 @@ _HEAD_FAMILY_FIRST = 192  # PTGNN_AMD_KERNEL_HEAD_FIRST_: the task heads' id ran
 _SEQ_FAMILY_FIRST = 256  # PTGNN_AMD_KERNEL_SEQ_FIRST_: the copying decoder's loss kernels
 
 
+_DECODE_FAMILY_FIRST = 320  # PTGNN_AMD_KERNEL_DECODE_FIRST_: the copying decoder's greedy-decoding step
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
-                  sequence: bool = False) -> dict:
+                  sequence: bool = False, decode: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -59,11 +62,13 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     block_attention_backward, segment_scores, segment_scores_backward, embedding_bag, embedding_bag_backward);
     `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward);
     `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward);
-    `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish)."""
+    `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish);
+    `decode=True` its greedy-decoding step (decode_step)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
-            + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()):
+            + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()) \
+            + ((_DECODE_FAMILY_FIRST,) if decode else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -76,7 +81,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True)
+    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2743,3 +2748,83 @@ def copy_loss_finish(gen: torch.Tensor, copied: torch.Tensor, rowptr: Optional[t
                                                 _stream(loss))
     _lib.check(rc, "ptgnn_amd_copy_loss_finish_f32")
     return loss.view(()), d_gen, d_copied
+
+
+# ------------------------------------------------------------------------------------------------
+# the copying decoder's greedy-decoding step (csrc/decode_step.hip)
+# ------------------------------------------------------------------------------------------------
+def value_groups(index: torch.Tensor, ids: torch.Tensor, num_samples: int, num_ids: int):
+    """The memories of a decode call ordered by (sample, value id): (rowptr int32 [B + 1], slot_memory int32 [I],
+    slot_ids int64 [I]) with the slots of sample b at rowptr[b] .. rowptr[b + 1] - 1, ascending ids inside a sample and
+    the memories of one (sample, id) in memory order -- a value group is a run of equal ids.  Two passes of the stable
+    plan build: by id (`num_ids` > every id), then by sample over that order.  Built once per call, no host read-back."""
+    I = int(index.shape[0])
+    if not (index.is_cuda and ids.is_cuda and index.dtype == torch.int64 and ids.dtype == torch.int64
+            and index.dim() == 1 and tuple(ids.shape) == (I,)):
+        raise _lib.PtgnnAmdError("value_groups: index and ids must be CUDA int64 tensors with one entry per memory")
+    ids = ids.contiguous()
+    by_id = plan_for([(ids, ids)], int(num_ids))
+    by_id.wait()
+    order = by_id.perm[:I].to(torch.int64)                     # memories by id, equal ids in memory order
+    index_by_id = index[order]
+    by_sample = plan_for([(index_by_id, index_by_id)], int(num_samples))
+    by_sample.wait()
+    slot_memory = order[by_sample.perm[:I].to(torch.int64)]
+    return by_sample.rowptr, slot_memory.to(torch.int32), ids[slot_memory]
+
+
+def decode_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores: torch.Tensor, total_copy: torch.Tensor,
+                groups, top_k: int, unk_id: int, end_id: int, step: int, done: torch.Tensor, lengths: torch.Tensor,
+                logprobs: torch.Tensor, tokens: torch.Tensor, next_tokens: torch.Tensor) -> None:
+    """One greedy-decoding step of the copying decoder in one launch (ptgnn_amd_decode_step_f32;
+    grucopydecoder.py:375-457): from the raw vocabulary scores [B, V], the copy scores [I] with their per-sample
+    log-sum-exp [B] and `groups = value_groups(...)` to the prediction of every sample that is not done.  Updates the
+    state IN PLACE: done int32 [B], lengths int64 [B], logprobs float32 [B], tokens int64 [B, T] (column `step`),
+    next_tokens int64 [B].  No host read-back; ids the kernel had to clamp are counted like the plan build's."""
+    lib = _lib.load()
+    _require_cuda_f32("scores", scores)
+    scores = _rowmajor(scores)
+    B, V = scores.shape
+    dev = scores.device
+    rowptr, slot_memory, slot_ids = groups
+    I = int(slot_memory.shape[0])
+    copy_scores = copy_scores.reshape(-1)
+    T = int(tokens.shape[1]) if tokens.dim() == 2 else -1
+    for name, t, shape, dt in (("bias", bias, (V,), torch.float32), ("copy_scores", copy_scores, (I,), torch.float32),
+                               ("total_copy", total_copy, (B,), torch.float32), ("rowptr", rowptr, (B + 1,), torch.int32),
+                               ("slot_memory", slot_memory, (I,), torch.int32), ("slot_ids", slot_ids, (I,), torch.int64),
+                               ("done", done, (B,), torch.int32), ("lengths", lengths, (B,), torch.int64),
+                               ("logprobs", logprobs, (B,), torch.float32), ("tokens", tokens, (B, T), torch.int64),
+                               ("next_tokens", next_tokens, (B,), torch.int64)):
+        if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != shape):
+            raise _lib.PtgnnAmdError(f"decode_step: {name} must be a CUDA {dt} {list(shape)} tensor on the scores' device "
+                                     f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+    for name, t in (("done", done), ("lengths", lengths), ("logprobs", logprobs), ("tokens", tokens),
+                    ("next_tokens", next_tokens)):
+        if not t.is_contiguous():
+            raise _lib.PtgnnAmdError(f"decode_step: {name} is updated in place and must be contiguous")
+    if V < 1 or top_k < 1:
+        raise _lib.PtgnnAmdError(f"decode_step: needs at least one column and top_k >= 1 (got V = {V}, top_k = {top_k})")
+    if B == 0:
+        return
+    bias, copy_scores, total_copy, rowptr, slot_memory, slot_ids = (
+        t.contiguous() if t is not None else None for t in (bias, copy_scores, total_copy, rowptr, slot_memory, slot_ids))
+    K = int(min(top_k, V))
+    bad = _bad_accumulator(_device_state(dev)) if VALIDATE_INDICES != "off" else None
+    ws_bytes = int(lib.ptgnn_amd_decode_step_workspace_bytes(B, V, K))
+    ws = _workspace(ws_bytes, dev)
+    with _timed("decode_step", bytes=4.0 * B * V * (1 if K >= V else 5) + 4.0 * V + 16.0 * I + 40.0 * B):
+        rc = lib.ptgnn_amd_decode_step_f32(scores.data_ptr(), _ld(scores), _opt_ptr(bias), _opt_ptr(copy_scores),
+                                           total_copy.data_ptr(), _opt_ptr(slot_memory), rowptr.data_ptr(),
+                                           _opt_ptr(slot_ids), B, I, V, K, int(unk_id), int(end_id), int(step), T,
+                                           done.data_ptr(), lengths.data_ptr(), logprobs.data_ptr(), tokens.data_ptr(),
+                                           next_tokens.data_ptr(), bad.data_ptr() if bad is not None else None,
+                                           ws.data_ptr(), ws_bytes, _stream(done))
+    _lib.check(rc, "ptgnn_amd_decode_step_f32")
+
+
+def post_index_check(device) -> None:
+    """Send the device's bad-index count on its way to the host (no synchronisation); a later plan build or
+    `check_indices` raises on it.  For launches that count into the accumulator without a plan build behind them."""
+    if VALIDATE_INDICES != "off" and not torch.cuda.is_current_stream_capturing():
+        _post_bad_readback(_device_state(device))

@@ -1,7 +1,9 @@
 """The copying decoder of the Graph2Seq task: mirror of ptgnn/neuralmodels/sequence/grucopydecoder.py:29-212
 (`GruCopyingDecoder`: same class name, constructor keywords, submodule / parameter creation order and name-mangled
 parameter names, so a reference state_dict loads strictly and the same seed gives the same initial values).
-`GruCopyingDecoderModel` -- vocabulary, tensorisation and the Python greedy-decode loop -- works unchanged around it.
+`GruCopyingDecoderModel` -- vocabulary, tensorisation and the Python greedy-decode loop -- works unchanged around it;
+`GruCopyingDecoder.greedy_decode` is that loop (grucopydecoder.py:375-457) on device tensors, one HIP launch of
+csrc/decode_step.hip per step in place of `target_logprobs`, torch.topk, the three host copies and the dict merge.
 
 GPU route (L = decoding steps <= 8, memory and state widths <= 1024), with x the memories [I, Dm], g their sample, o the
 GRU's output states [B, L, H]:
@@ -12,8 +14,13 @@ GRU's output states [B, L, H]:
   * copy attention: scores and their per-sample log-sum-exp in one pass (csrc/segment_scores.hip).  Dropout sits between
     the copy Linear and the dot product (grucopydecoder.py:83-97), so while it is active the rows are dropout(W_c x) and
     the vectors o; otherwise W_c moves onto the samples too and the rows are x itself (greedy decoding: L = 1 per step);
-  * the vocabulary product as two HIP Linears; in `forward` / `_compute_logprobs` (greedy decoding needs the whole
-    `target_logprobs`) the joint normaliser and the loss arithmetic are torch glue on [B, L, V] and [I, L] tensors;
+  * the vocabulary product as two HIP Linears; in `forward` / `_compute_logprobs` the joint normaliser and the loss
+    arithmetic are torch glue on [B, L, V] and [I, L] tensors;
+  * `greedy_decode` keeps the hidden state, the next tokens, the done flags, the lengths, the log-probabilities and the
+    token matrix on the device for all `max_seq_len` steps: per step the GRU cell, the attention pool and the copy scores
+    with L = 1, the RAW vocabulary product, and `ops.decode_step`, which reads those scores and the copy scores and writes
+    the prediction.  The memories ordered by (sample, value id) -- `ops.value_groups`, two stable plan builds -- and the
+    plan of the memory -> sample map are built once per call.  Nothing is read back inside the loop;
   * `fused_loss` (the training loss, what `heads.Graph2SeqModule` calls) keeps the same GRU, attention and copy scores and
     replaces that glue by csrc/vocab_loss.hip: `_VocabLoss` reads the RAW second Linear's output once -- bias, running
     maximum, joint normaliser with the copy term, the correct tokens' entries -- and its one-pass backward writes the
@@ -36,6 +43,7 @@ from ptgnn_amd.reduceops import _AttentionPool
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_scores
 
 _HALF = (torch.float16, torch.bfloat16)
+_MAX_ELEMENT_ID = 1 << 22    # greedy_decode: the value ids of a call index one plan build (a row pointer of that length)
 
 
 def _rows(table: torch.Tensor, index: torch.Tensor, plan=None) -> torch.Tensor:
@@ -320,6 +328,119 @@ class GruCopyingDecoder(nn.Module):
             copied = _plan_logsumexp(correct, copyable_elements_sample_idxs, plan).reshape(B, L)
             rowptr = plan.rowptr
         return _CopyLossFinish.apply(picked.reshape(B, L), copied, rowptr, targets, self.__unk_id, target_lengths.long())
+
+    # --------------------------------------------------------------------------------------------------------------
+    # greedy decoding (grucopydecoder.py:375-457)
+    # --------------------------------------------------------------------------------------------------------------
+    def __host_greedy_step(self, copy_logprobs, target_logprobs, index, ids, top_k, end_id, step, state):
+        """One step of the reference's dict merge on torch operators, on [B, V] / [I] log-probabilities: the K largest
+        vocabulary entries (equal values: the lower id first), every (sample, value id) group of copy log-probabilities
+        merged onto its vocabulary entry where that is one of the K and onto -inf elsewhere, the arg-max (the
+        vocabulary's top-1 before a group of equal value, of two groups the lower id), the state update."""
+        done, lengths, logprobs, tokens, next_tokens = state
+        B, V = target_logprobs.shape
+        order = torch.sort(target_logprobs, dim=-1, descending=True, stable=True).indices
+        in_top = torch.zeros(B, V, dtype=torch.bool, device=order.device).scatter_(1, order[:, :min(top_k, V)], True)
+        best_id = order[:, 0]
+        best = target_logprobs.gather(1, best_id.unsqueeze(1)).squeeze(1)
+        if index.shape[0]:
+            span = int(ids.max()) + 1
+            keys, group = torch.unique(index * span + ids, return_inverse=True)        # sorted by (sample, id)
+            sample, gid = torch.div(keys, span, rounding_mode="floor"), keys % span
+            G = keys.shape[0]
+            top = torch.full((G,), -math.inf, dtype=copy_logprobs.dtype).scatter_reduce(
+                0, group, copy_logprobs, "amax", include_self=True)
+            shift = torch.where(top == -math.inf, torch.zeros_like(top), top)
+            merged = torch.zeros(G, dtype=copy_logprobs.dtype).index_add(
+                0, group, (copy_logprobs - shift[group]).exp()).log() + shift
+            column = gid.clamp(max=V - 1)
+            vocabulary = torch.where((gid < V) & in_top[sample, column], target_logprobs[sample, column],
+                                     torch.full_like(merged, -math.inf))
+            merged = torch.logaddexp(vocabulary, merged)
+            group_best = torch.full((B,), -math.inf, dtype=merged.dtype).scatter_reduce(
+                0, sample, merged, "amax", include_self=True)
+            position = torch.where(merged == group_best[sample], torch.arange(G), torch.full((G,), G))
+            first = torch.full((B,), G, dtype=torch.int64).scatter_reduce(0, sample, position, "amin", include_self=True)
+            copied = group_best > best
+            predicted = torch.where(copied, gid[first.clamp(max=G - 1)], best_id)
+            value = torch.where(copied, group_best, best)
+        else:
+            predicted, value = best_id, best
+        live = ~done
+        ends = predicted == end_id
+        logprobs += torch.where(live, value.float(), torch.zeros_like(logprobs))
+        append = live & ~ends
+        tokens[:, step] = torch.where(append, predicted, tokens[:, step])
+        lengths += append.long()
+        next_tokens.copy_(torch.where(live, torch.where(predicted < V, predicted, torch.full_like(predicted, self.__unk_id)),
+                                      torch.full_like(predicted, end_id)))
+        done |= live & ends
+
+    def greedy_decode(self, *, input_memories, input_memories_origin_idx, initial_states, input_element_ids, start_id: int,
+                      end_id: int, max_seq_len: int, top_k: int = 100):
+        """The greedy decoding of GruCopyingDecoderModel.greedy_decode (grucopydecoder.py:375-457) without its host loop.
+
+        :param input_memories: [num-inputs-flattened, D]
+        :param input_memories_origin_idx: [num-inputs-flattened]
+        :param initial_states: [num-targets, H]
+        :param input_element_ids: int64 [num-inputs-flattened], standing in for the reference's `input_concrete_values`:
+            an id < vocabulary size is the vocabulary id of the memory's string, any other id is the caller's key of a
+            string that is not in the vocabulary (equal strings, equal keys; keys below 2 ** 22)
+        :param start_id, end_id: the vocabulary ids of START and END
+        :param top_k: the vocabulary candidates per step (the reference's 100)
+
+        :return: token_ids int64 [num-targets, max_seq_len] (row b holds the lengths[b] predicted tokens of sample b in the
+            extended id space, END not included, then -1), lengths int64 [num-targets], logprobs float32 [num-targets]
+            (the sum of the chosen log-probabilities, END's included).
+
+        Exact ties, which the reference leaves to torch.topk and to dict order: of equal vocabulary scores the lower id
+        counts as the larger (for the top-1 and at the K-th place), the vocabulary's top-1 goes before a copy group of
+        equal value, and of two groups the lower id.  The module is treated as in eval(): dropout must be inactive."""
+        x, index, h, ids = input_memories, input_memories_origin_idx, initial_states, input_element_ids
+        if self.training and self.__dropout.p > 0.0:
+            raise _lib.PtgnnAmdError("greedy_decode: dropout is active (call eval() first)")
+        V = self.__vocab_bias.shape[0]
+        B, T, I = int(h.shape[0]), int(max_seq_len), int(x.shape[0])
+        if ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] != I or ids.device != x.device:
+            raise _lib.PtgnnAmdError("greedy_decode: input_element_ids must be an int64 tensor with one entry per memory, on "
+                                     "the memories' device")
+        if top_k < 1 or T < 0 or not (0 <= start_id < V and 0 <= end_id < V):
+            raise _lib.PtgnnAmdError(f"greedy_decode: needs top_k >= 1, max_seq_len >= 0 and start_id / end_id inside the "
+                                     f"vocabulary of {V} (got {top_k}, {T}, {start_id}, {end_id})")
+        dev = x.device
+        tokens = torch.full((B, T), -1, dtype=torch.int64, device=dev)
+        lengths = torch.zeros(B, dtype=torch.int64, device=dev)
+        logprobs = torch.zeros(B, dtype=torch.float32, device=dev)
+        if B == 0 or T == 0:
+            return tokens, lengths, logprobs
+        span = 1
+        if I:
+            low, high = (int(v) for v in torch.aminmax(ids))     # the one read-back of the call, before the loop
+            if low < 0 or high >= _MAX_ELEMENT_ID:
+                raise _lib.PtgnnAmdError(f"greedy_decode: input_element_ids must lie in [0, {_MAX_ELEMENT_ID}) (got "
+                                         f"{low} .. {high})")
+            span = high + 1
+        next_tokens = torch.full((B,), int(start_id), dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            x, h = x.float(), h.float()                          # AMP: fp32 inside, as everywhere
+            if not x.is_cuda:    # device dispatch: CPU tensors take the same algorithm on torch operators
+                done = torch.zeros(B, dtype=torch.bool)
+                for step in range(T):
+                    copy_logprobs, target_logprobs, state = self._compute_logprobs(h, x, index, next_tokens.unsqueeze(1))
+                    h = state.squeeze(0)
+                    self.__host_greedy_step(copy_logprobs.squeeze(1), target_logprobs.squeeze(1), index, ids, top_k, end_id,
+                                            step, (done, lengths, logprobs, tokens, next_tokens))
+                return tokens, lengths, logprobs
+            done = torch.zeros(B, dtype=torch.int32, device=dev)
+            groups = ops.value_groups(index, ids, B, span)
+            for step in range(T):
+                states, attention_out, copy_scores, total_copy, h, _ = self.__device_attention(
+                    h, x, index, next_tokens.unsqueeze(1))
+                raw_scores = self.__raw_vocabulary_scores(attention_out, states)           # [B, V]
+                ops.decode_step(raw_scores, self.__vocab_bias, copy_scores, total_copy.reshape(B), groups, top_k,
+                                self.__unk_id, end_id, step, done, lengths, logprobs, tokens, next_tokens)
+            ops.post_index_check(dev)
+        return tokens, lengths, logprobs
 
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form (as for the attention reducers)."""
