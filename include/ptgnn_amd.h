@@ -176,6 +176,12 @@ enum {
   PTGNN_AMD_KERNEL_DECODE_STEP = PTGNN_AMD_KERNEL_DECODE_FIRST_, /* ptgnn_amd_decode_step_f32 */
   PTGNN_AMD_KERNEL_DECODE_END_
 };
+/* A seventh id range: the beam-search step of the copying decoder (csrc/beam_step.hip; its two kernels count as one). */
+enum {
+  PTGNN_AMD_KERNEL_BEAM_FIRST_ = 384,
+  PTGNN_AMD_KERNEL_BEAM_STEP = PTGNN_AMD_KERNEL_BEAM_FIRST_, /* ptgnn_amd_beam_step_f32 */
+  PTGNN_AMD_KERNEL_BEAM_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1235,6 +1241,51 @@ int ptgnn_amd_decode_step_f32(const float *scores, int64_t ld, const float *bias
                               int32_t step, int32_t max_steps, int32_t *done, int64_t *lengths, float *logprobs,
                               int64_t *tokens, int64_t *next_tokens, int32_t *bad /* nullable */, void *workspace,
                               size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * One step of the copying decoder's beam search (csrc/beam_step.hip): the step above widened from the best entry of a
+ * sample to the W = beam_width best continuations of its W hypotheses ("slots").  The reference has no beam search; the
+ * semantics extend its greedy dictionary (grucopydecoder.py:406-442) and equal the step above for W = 1.  No host
+ * read-back; the [B W, V] log-probabilities never exist.
+ *   scores [B W, vocab] (ld >= vocab; row b W + j is slot j of sample b), bias [vocab] nullable, copy_scores
+ *   [num_memories, W] and total_copy [B, W] as ptgnn_amd_segment_scores_f32 leaves them for W vectors per sample, the
+ *   value grouping (rowptr, slot_memory, slot_ids) of the step above.
+ *   The state IN: beam_scores_in float [B, W], done_in int32 [B, W], lengths_in int64 [B, W], tokens_in int64
+ *   [B, W, max_steps]; the state OUT in buffers of the same shapes that do not overlap them (slots are reordered: the
+ *   caller swaps the two sets between steps); next_tokens int64 [B W]; parent_rows int64 [B W] = b W + parent of the slot,
+ *   the index of the row gather that reorders the hidden states.
+ * Per sample, slot j with done_in == 0 has the ENTRIES of the step above, from its own row, its own column of the copy
+ * scores and norm_j: the top_k largest s_j[v] - norm_j, merged with every run of equal ids (onto the vocabulary entry
+ * where g < vocab and s_j[g] is one of the top_k, else onto -inf).  Entry e is the candidate (parent j, id e, score
+ * beam_scores_in[j] + entry); a slot with done_in != 0 is one candidate, itself, score unchanged.  The W candidates of the
+ * sample that come first in this order become the slots 0 .. W - 1 of the state out, in that order:
+ *   1. higher score;  2. lower parent;  3. inside a parent the entries whose id is one of its W best vocabulary columns
+ *   (of equal scores of a row the lower index is the larger, as above) before its other entries;  4. lower id.
+ * Candidates that are all -inf are ordered by 2.-4. for a parent whose score is finite; a live parent whose score is
+ * -inf (slots 1 .. W - 1 before the first step) offers the ids 0 .. W - 1 at -inf without a look at its row -- with
+ * beam_width <= min(top_k, vocab) and finite scores at least W candidates are finite and these are never taken.
+ *   id == end_id: done_out = 1, the score includes END's entry, nothing is appended;  a finished parent: copied;
+ *   otherwise tokens_out[.., step] = id after the parent's history, lengths_out = lengths_in[parent] + 1.
+ *   next_tokens = end_id for a finished slot, else id < vocab ? id : unk_id.
+ * slot_memory entries outside [0, num_memories) and negative ids are clamped to 0 and counted in bad[0] (int32, DEVICE
+ * memory, nullable), once per slot and call.  Exact fp32, no float atomics, fixed fold orders: two calls give the same
+ * bits.  Before any device work: vocab < 1, top_k < 1, beam_width outside [1, 8] or above min(top_k, vocab), a step
+ * outside [0, max_steps), unk_id / end_id outside the vocabulary, a null required pointer or a workspace below
+ * ptgnn_amd_beam_step_workspace_bytes(...) answer PTGNN_AMD_EINVAL, sizes beyond int32 indexing PTGNN_AMD_EUNSUPPORTED;
+ * num_samples == 0 launches nothing.  The workspace holds one float per (memory, slot) and the W W candidates of every
+ * sample between the two kernels of the entry; its size is 0 for sizes the entry refuses.
+ * ---------------------------------------------------------------------------------------- */
+size_t ptgnn_amd_beam_step_workspace_bytes(int64_t num_samples, int64_t num_memories, int32_t vocab, int32_t top_k,
+                                           int32_t beam_width);
+int ptgnn_amd_beam_step_f32(const float *scores, int64_t ld, const float *bias /* nullable */, const float *copy_scores,
+                            const float *total_copy, const int32_t *slot_memory, const int32_t *rowptr,
+                            const int64_t *slot_ids, int64_t num_samples, int64_t num_memories, int32_t vocab,
+                            int32_t top_k, int32_t beam_width, int64_t unk_id, int64_t end_id, int32_t step,
+                            int32_t max_steps, const float *beam_scores_in, const int32_t *done_in,
+                            const int64_t *lengths_in, const int64_t *tokens_in, float *beam_scores_out,
+                            int32_t *done_out, int64_t *lengths_out, int64_t *tokens_out, int64_t *next_tokens,
+                            int64_t *parent_rows, int32_t *bad /* nullable */, void *workspace, size_t workspace_bytes,
+                            void *stream);
 
 #pragma GCC visibility pop
 

@@ -186,6 +186,10 @@ SIGNATURES = {
     "ptgnn_amd_decode_step_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
     "ptgnn_amd_decode_step_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i64,
                                              _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
+    "ptgnn_amd_beam_step_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32, _i32, _i32]),
+    "ptgnn_amd_beam_step_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64,
+                                           _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _c.c_size_t, _vp]),
 }
 
 # The header version this host was written against (include/ptgnn_amd.h: PTGNN_AMD_VERSION).  A stale .so with an

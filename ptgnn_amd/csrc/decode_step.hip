@@ -27,75 +27,10 @@
 //   4. Thread 0 updates the state.  A sample that is done is fed end_id and changes nothing else.
 // Exact ties are the one place where the reference leaves the outcome open (to torch.topk and to dict order); here they
 // are decided as above.  No float atomics, fixed fold orders: two launches give the same bits.
-#include <math.h>
-
-#include "segment_chunks.h"
+#include "decode_common.h"
 
 namespace ptgnn_amd {
 namespace {
-
-constexpr int kDecThreads = 1024;
-constexpr int kDecWaves = kDecThreads / kWave;
-
-// running soft-max state: the maximum and sum exp(. - maximum); (-inf, 0) is empty
-struct MaxSum {
-  float m, s;
-};
-
-// commutative: combine(a, b) and combine(b, a) have the same bits
-__device__ __forceinline__ MaxSum combine(const MaxSum &a, const MaxSum &b) {
-  MaxSum o;
-  o.m = fmaxf(a.m, b.m);
-  const float sa = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - o.m);
-  const float sb = b.m == -INFINITY ? 0.0f : b.s * expf(b.m - o.m);
-  o.s = sa + sb;
-  return o;
-}
-
-__device__ __forceinline__ void push(MaxSum &a, float v) {
-  if (v > a.m) {
-    a.s = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - v);
-    a.m = v;
-  }
-  if (a.m != -INFINITY) a.s += expf(v - a.m);
-}
-
-// a candidate of the arg-max: `rank` orders equal values (-1 the row's top-1, else the slot that starts the run)
-struct Cand {
-  float v;
-  int rank;
-  int64_t id;
-};
-
-__device__ __forceinline__ bool better(const Cand &a, const Cand &b) {
-  return a.v > b.v || (a.v == b.v && a.rank < b.rank);
-}
-
-__device__ __forceinline__ Cand shfl_xor_cand(const Cand &a, int o) {
-  Cand b;
-  b.v = __shfl_xor(a.v, o, kWave);
-  b.rank = __shfl_xor(a.rank, o, kWave);
-  const int lo = __shfl_xor((int)(uint32_t)(uint64_t)a.id, o, kWave);
-  const int hi = __shfl_xor((int)(uint32_t)((uint64_t)a.id >> 32), o, kWave);
-  b.id = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  return b;
-}
-
-// larger float <=> larger key; -0 and +0 share a key
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t u = __float_as_uint(v == 0.0f ? 0.0f : v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float score_at(const float *__restrict__ row, const float *__restrict__ bias, int c) {
-  return row[c] + (bias ? bias[c] : 0.0f);
-}
-
-__device__ __forceinline__ float log_add_exp(float a, float b) {
-  const float hi = fmaxf(a, b), lo = fminf(a, b);
-  if (lo == -INFINITY) return hi;
-  return hi + log1pf(expf(lo - hi));
-}
 
 __global__ __launch_bounds__(kDecThreads) void k_decode_step(
     const float *__restrict__ scores, int64_t ld, const float *__restrict__ bias, const float *__restrict__ copy,
@@ -105,10 +40,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
     int64_t *__restrict__ tokens, int64_t *__restrict__ next_tokens, int32_t *__restrict__ bad) {
   __shared__ MaxSum s_ms[kDecWaves];
   __shared__ Cand s_cand[kDecWaves];
-  __shared__ int s_hist[256];
-  __shared__ uint32_t s_prefix;
-  __shared__ int s_want, s_cut, s_equal;
-  __shared__ SegmentScan<kDecThreads> s_scan;
+  __shared__ RadixSelect s_select;
   const int b = blockIdx.x;
   const int t = threadIdx.x;
   const int lane = t & (kWave - 1), wave = t >> 6;
@@ -150,47 +82,11 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
   best.rank = -1;
   __syncthreads();                                           // s_cand is written again in step 3
 
-  // 2. the K-th largest key of the row; s_cut = the highest index with that key that is still one of the K
+  // 2. the K-th largest key of the row; cut = the highest index with that key that is still one of the K
   const bool all_in = top_k >= vocab;
   uint32_t kth = 0;
   int cut = INT32_MAX;
-  if (!all_in) {
-    if (t == 0) s_prefix = 0, s_want = top_k, s_cut = INT32_MAX;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (t < 256) s_hist[t] = 0;
-      __syncthreads();
-      const uint32_t prefix = s_prefix;
-      for (int c = t; c < vocab; c += kDecThreads) {
-        const uint32_t key = order_key(score_at(row, bias, c));
-        if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
-      }
-      __syncthreads();
-      // bins from the largest down: thread t < 256 has bin 255 - t; the bin where the running count reaches `want`
-      const int count = t < 256 ? s_hist[255 - t] : 0;
-      const int want = s_want;
-      s_scan.begin();
-      const int before = s_scan.step(count);
-      if (t < 256 && before < want && before + count >= want) {
-        s_prefix = prefix | ((uint32_t)(255 - t) << shift);
-        s_want = want - before;
-        s_equal = count;                                     // after the last pass: the entries with the K-th key
-      }
-      __syncthreads();
-    }
-    kth = s_prefix;
-    const int want = s_want;                                 // how many of the entries with key == kth are in the K
-    if (want < s_equal) {                                  // workgroup-uniform: an exact tie at the K-th place
-      s_scan.begin();
-      for (int base = 0; base < vocab; base += kDecThreads) {
-        const int c = base + t;
-        const int hit = c < vocab && order_key(score_at(row, bias, c)) == kth ? 1 : 0;
-        const int before = s_scan.step(hit);
-        if (hit && before == want - 1) s_cut = c;
-      }
-      __syncthreads();
-    }
-    cut = s_cut;
-  }
+  if (!all_in) s_select.select(row, bias, vocab, top_k, kth, cut);   // csrc/decode_common.h
 
   // 3. the sample's value groups
   const int lo = rowptr[b], hi = rowptr[b + 1];

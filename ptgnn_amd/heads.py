@@ -399,6 +399,15 @@ class Graph2SeqModule(ModuleWithMetrics):
             return self._decoder.greedy_decode(**self.__decoder_inputs(encoder_mb_data), input_element_ids=input_element_ids,
                                                start_id=start_id, end_id=end_id, max_seq_len=max_seq_len, top_k=top_k)
 
+    def beam_decode(self, *, encoder_mb_data: Dict[str, Any], input_element_ids, start_id: int, end_id: int,
+                    max_seq_len: int, beam_width: int, top_k: int = 100):
+        """Beam search on the decoder inputs `greedy_decode` forms, handed to `sequence.GruCopyingDecoder.beam_decode`
+        (its argument and result conventions: the `beam_width` best sequences of every sample)."""
+        with torch.no_grad():
+            return self._decoder.beam_decode(**self.__decoder_inputs(encoder_mb_data), input_element_ids=input_element_ids,
+                                             start_id=start_id, end_id=end_id, max_seq_len=max_seq_len,
+                                             beam_width=beam_width, top_k=top_k)
+
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form."""
         raise PtgnnAmdError("forward_sharded: cannot combine partial pools of Graph2SeqModule")

@@ -53,8 +53,11 @@ _SEQ_FAMILY_FIRST = 256  # PTGNN_AMD_KERNEL_SEQ_FIRST_: the copying decoder's lo
 _DECODE_FAMILY_FIRST = 320  # PTGNN_AMD_KERNEL_DECODE_FIRST_: the copying decoder's greedy-decoding step
 
 
+_BEAM_FAMILY_FIRST = 384  # PTGNN_AMD_KERNEL_BEAM_FIRST_: the copying decoder's beam-search step
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
-                  sequence: bool = False, decode: bool = False) -> dict:
+                  sequence: bool = False, decode: bool = False, beam: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -63,12 +66,12 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward);
     `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward);
     `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish);
-    `decode=True` its greedy-decoding step (decode_step)."""
+    `decode=True` its greedy-decoding step (decode_step); `beam=True` its beam-search step (beam_step)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
             + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()) \
-            + ((_DECODE_FAMILY_FIRST,) if decode else ()):
+            + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -81,7 +84,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True)
+    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2821,6 +2824,77 @@ def decode_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores:
                                            next_tokens.data_ptr(), bad.data_ptr() if bad is not None else None,
                                            ws.data_ptr(), ws_bytes, _stream(done))
     _lib.check(rc, "ptgnn_amd_decode_step_f32")
+
+
+def beam_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores: torch.Tensor, total_copy: torch.Tensor,
+              groups, top_k: int, unk_id: int, end_id: int, step: int, state_in, state_out, next_tokens: torch.Tensor,
+              parent_rows: torch.Tensor) -> None:
+    """One beam-search step of the copying decoder (ptgnn_amd_beam_step_f32): from the raw vocabulary scores [B W, V] (row
+    b W + j: slot j of sample b), the copy scores [I, W] with their per-sample log-sum-exp [B, W] and `groups =
+    value_groups(...)` to the W best continuations of every sample.  `state_in` = (scores float32 [B, W], done int32
+    [B, W], lengths int64 [B, W], tokens int64 [B, W, T]) is read, `state_out` (the same shapes, other buffers: the slots
+    are reordered) is written, with next_tokens int64 [B W] and parent_rows int64 [B W] = b W + the slot's parent, the
+    index of the row gather that reorders the hidden states.  No host read-back; clamped ids are counted like the plan
+    build's."""
+    lib = _lib.load()
+    _require_cuda_f32("scores", scores)
+    scores = _rowmajor(scores)
+    R, V = scores.shape
+    dev = scores.device
+    rowptr, slot_memory, slot_ids = groups
+    I = int(slot_memory.shape[0])
+    beam_in, done_in, lengths_in, tokens_in = state_in
+    beam_out, done_out, lengths_out, tokens_out = state_out
+    if beam_in.dim() != 2 or beam_in.shape[1] < 1 or R % int(beam_in.shape[1]):
+        raise _lib.PtgnnAmdError(f"beam_step: the beam scores must be [B, W] with B W = {R} rows of vocabulary scores "
+                                 f"(got {tuple(beam_in.shape)})")
+    B, W = (int(v) for v in beam_in.shape)
+    T = int(tokens_in.shape[2]) if tokens_in.dim() == 3 else -1
+    for name, t, shape, dt in (("bias", bias, (V,), torch.float32), ("copy_scores", copy_scores, (I, W), torch.float32),
+                               ("total_copy", total_copy, (B, W), torch.float32),
+                               ("rowptr", rowptr, (B + 1,), torch.int32), ("slot_memory", slot_memory, (I,), torch.int32),
+                               ("slot_ids", slot_ids, (I,), torch.int64), ("scores in", beam_in, (B, W), torch.float32),
+                               ("done in", done_in, (B, W), torch.int32), ("lengths in", lengths_in, (B, W), torch.int64),
+                               ("tokens in", tokens_in, (B, W, T), torch.int64),
+                               ("scores out", beam_out, (B, W), torch.float32), ("done out", done_out, (B, W), torch.int32),
+                               ("lengths out", lengths_out, (B, W), torch.int64),
+                               ("tokens out", tokens_out, (B, W, T), torch.int64),
+                               ("next_tokens", next_tokens, (B * W,), torch.int64),
+                               ("parent_rows", parent_rows, (B * W,), torch.int64)):
+        if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != shape):
+            raise _lib.PtgnnAmdError(f"beam_step: {name} must be a CUDA {dt} {list(shape)} tensor on the scores' device "
+                                     f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+    for name, t in (("scores in", beam_in), ("done in", done_in), ("lengths in", lengths_in), ("tokens in", tokens_in),
+                    ("scores out", beam_out), ("done out", done_out), ("lengths out", lengths_out),
+                    ("tokens out", tokens_out), ("next_tokens", next_tokens), ("parent_rows", parent_rows)):
+        if not t.is_contiguous():
+            raise _lib.PtgnnAmdError(f"beam_step: {name} is read or written in place and must be contiguous")
+    for a, b in zip(state_in, state_out):
+        if a.data_ptr() == b.data_ptr() and a.numel():
+            raise _lib.PtgnnAmdError("beam_step: the state out must not share buffers with the state in (slots are reordered)")
+    K = int(min(top_k, V))
+    if V < 1 or top_k < 1 or not 1 <= W <= min(K, 8):
+        raise _lib.PtgnnAmdError(f"beam_step: needs top_k >= 1 and 1 <= beam width <= min(top_k, V, 8), the head limit of "
+                                 f"the fused attention pool (got V = {V}, top_k = {top_k}, beam width {W})")
+    if B == 0:
+        return
+    bias, copy_scores, total_copy, rowptr, slot_memory, slot_ids = (
+        t.contiguous() if t is not None else None for t in (bias, copy_scores, total_copy, rowptr, slot_memory, slot_ids))
+    bad = _bad_accumulator(_device_state(dev)) if VALIDATE_INDICES != "off" else None
+    ws_bytes = int(lib.ptgnn_amd_beam_step_workspace_bytes(B, I, V, K, W))
+    ws = _workspace(ws_bytes, dev)
+    passes = 2 + (4 if W < V else 0) + (4 if K < V and K != W else 0)      # normaliser, collect, the radix selects
+    with _timed("beam_step", bytes=4.0 * R * V * passes + 4.0 * V + (12.0 + 8.0 * W) * I * W + 20.0 * R * W
+                + (16.0 * T + 48.0) * R):
+        rc = lib.ptgnn_amd_beam_step_f32(scores.data_ptr(), _ld(scores), _opt_ptr(bias), _opt_ptr(copy_scores),
+                                         total_copy.data_ptr(), _opt_ptr(slot_memory), rowptr.data_ptr(),
+                                         _opt_ptr(slot_ids), B, I, V, K, W, int(unk_id), int(end_id), int(step), T,
+                                         beam_in.data_ptr(), done_in.data_ptr(), lengths_in.data_ptr(),
+                                         tokens_in.data_ptr(), beam_out.data_ptr(), done_out.data_ptr(),
+                                         lengths_out.data_ptr(), tokens_out.data_ptr(), next_tokens.data_ptr(),
+                                         parent_rows.data_ptr(), bad.data_ptr() if bad is not None else None,
+                                         ws.data_ptr(), ws_bytes, _stream(beam_out))
+    _lib.check(rc, "ptgnn_amd_beam_step_f32")
 
 
 def post_index_check(device) -> None:

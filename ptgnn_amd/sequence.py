@@ -3,7 +3,8 @@
 parameter names, so a reference state_dict loads strictly and the same seed gives the same initial values).
 `GruCopyingDecoderModel` -- vocabulary, tensorisation and the Python greedy-decode loop -- works unchanged around it;
 `GruCopyingDecoder.greedy_decode` is that loop (grucopydecoder.py:375-457) on device tensors, one HIP launch of
-csrc/decode_step.hip per step in place of `target_logprobs`, torch.topk, the three host copies and the dict merge.
+csrc/decode_step.hip per step in place of `target_logprobs`, torch.topk, the three host copies and the dict merge;
+`GruCopyingDecoder.beam_decode` extends its dictionary to a beam search, which the reference does not have.
 
 GPU route (L = decoding steps <= 8, memory and state widths <= 1024), with x the memories [I, Dm], g their sample, o the
 GRU's output states [B, L, H]:
@@ -21,6 +22,10 @@ GRU's output states [B, L, H]:
     with L = 1, the RAW vocabulary product, and `ops.decode_step`, which reads those scores and the copy scores and writes
     the prediction.  The memories ordered by (sample, value id) -- `ops.value_groups`, two stable plan builds -- and the
     plan of the memory -> sample map are built once per call.  Nothing is read back inside the loop;
+  * `beam_decode` is that loop for W <= 8 hypotheses per sample: the GRU cell and the vocabulary product on B W rows, the
+    attention pool and the copy scores with L := W (the hypotheses of a sample are its heads), `ops.beam_step`
+    (csrc/beam_step.hip), which writes the W best continuations of every sample, their parents and the reordered
+    token histories into a second set of state buffers, and the row gather of the new hidden states by parent;
   * `fused_loss` (the training loss, what `heads.Graph2SeqModule` calls) keeps the same GRU, attention and copy scores and
     replaces that glue by csrc/vocab_loss.hip: `_VocabLoss` reads the RAW second Linear's output once -- bias, running
     maximum, joint normaliser with the copy term, the correct tokens' entries -- and its one-pass backward writes the
@@ -191,34 +196,46 @@ class GruCopyingDecoder(nn.Module):
         total_copy = scatter_facade.scatter_logsumexp(copy_scores, index, dim=0, dim_size=B, eps=0.0)
         return attention_out.reshape(B * L, H), copy_scores, total_copy
 
-    def __device_attention(self, initial_states, x, index, input_token_ids):
-        """What both GPU routes share: (GRU states [B L, H], attention output [B L, H], copy scores [I, L], their
-        per-sample log-sum-exp [B, L], the GRU's last state [B, H], the plan of `index` over the samples)."""
+    @staticmethod
+    def __check_index(x, index):
         if index.dtype != torch.int64 or not index.is_cuda or index.dim() != 1 or index.shape[0] != x.shape[0]:
             raise _lib.PtgnnAmdError("GruCopyingDecoder: input_memories_origin_idx must be a CUDA int64 tensor with one "
                                      "entry per memory")
+
+    def __attend(self, output_states, x, index, plan):
+        """The attention / copy part of the GPU routes, for L vectors per sample (the L steps of a target, or the L
+        hypotheses of a beam): output states [B, L, H] -> (attention output [B L, H], copy scores [I, L], their per-sample
+        log-sum-exp [B, L])."""
         w_s, w_c = self.__memories_to_standard_attention.weight, self.__memories_to_copy_attention.weight
         H, Dm = w_s.shape
-        B, L = input_token_ids.shape
-        output_states, last_state = self.__gru_states(initial_states, input_token_ids)     # [B, L, H]
+        B, L = output_states.shape[:2]
         states = output_states.reshape(B * L, H)
-        x = x.contiguous()
-        plan = _index_plan(index, B)
         drop = self.training and self.__dropout.p > 0.0
         if not (ops.attention_pool_supported(Dm, L) and ops.segment_scores_supported(H if drop else Dm, L)):
-            attention_out, copy_scores, total_copy = self.__composed_attention(x, index, plan, output_states)
+            return self.__composed_attention(x, index, plan, output_states)
+        queries = dense.linear(states, w_s.t()).reshape(B, L, Dm)                          # u_s = W_s^T o
+        pooled = _AttentionPool.apply(x, queries, plan)                                    # [B, L, Dm]
+        attention_out = dense.linear(pooled.reshape(B * L, Dm), w_s)                       # A = W_s P
+        if drop:
+            rows = dense.linear_act_dropout(x, w_c, None, None, self.__dropout.p, True)
+            if rows is None:
+                rows = self.__dropout(dense.linear(x, w_c))
+            vectors = output_states
         else:
-            queries = dense.linear(states, w_s.t()).reshape(B, L, Dm)                      # u_s = W_s^T o
-            pooled = _AttentionPool.apply(x, queries, plan)                                # [B, L, Dm]
-            attention_out = dense.linear(pooled.reshape(B * L, Dm), w_s)                   # A = W_s P
-            if drop:
-                rows = dense.linear_act_dropout(x, w_c, None, None, self.__dropout.p, True)
-                if rows is None:
-                    rows = self.__dropout(dense.linear(x, w_c))
-                vectors = output_states
-            else:
-                rows, vectors = x, dense.linear(states, w_c.t()).reshape(B, L, Dm)         # u_c = W_c^T o
-            copy_scores, total_copy = segment_scores(rows, vectors.contiguous(), plan)     # [I, L], [B, L]
+            rows, vectors = x, dense.linear(states, w_c.t()).reshape(B, L, Dm)             # u_c = W_c^T o
+        copy_scores, total_copy = segment_scores(rows, vectors.contiguous(), plan)         # [I, L], [B, L]
+        return attention_out, copy_scores, total_copy
+
+    def __device_attention(self, initial_states, x, index, input_token_ids):
+        """What the loss and greedy decoding share: (GRU states [B L, H], attention output [B L, H], copy scores [I, L],
+        their per-sample log-sum-exp [B, L], the GRU's last state [B, H], the plan of `index` over the samples)."""
+        self.__check_index(x, index)
+        B, L = input_token_ids.shape
+        output_states, last_state = self.__gru_states(initial_states, input_token_ids)     # [B, L, H]
+        states = output_states.reshape(B * L, output_states.shape[2])
+        x = x.contiguous()
+        plan = _index_plan(index, B)
+        attention_out, copy_scores, total_copy = self.__attend(output_states, x, index, plan)
         return states, attention_out, copy_scores, total_copy, last_state, plan
 
     def __device_logprobs(self, initial_states, x, index, input_token_ids):
@@ -441,6 +458,167 @@ class GruCopyingDecoder(nn.Module):
                                 self.__unk_id, end_id, step, done, lengths, logprobs, tokens, next_tokens)
             ops.post_index_check(dev)
         return tokens, lengths, logprobs
+
+    # --------------------------------------------------------------------------------------------------------------
+    # beam search: greedy decoding's dictionary, the W best continuations of W hypotheses per sample
+    # --------------------------------------------------------------------------------------------------------------
+    def __host_beam_step(self, copy_logprobs, target_logprobs, row_of_memory, ids, top_k, W, end_id, step, state):
+        """One beam step on torch operators, on [B W, V] / [W I] log-probabilities (row b W + j: slot j of sample b; the
+        memories repeated once per slot, `row_of_memory` their rows): per live row the W best vocabulary entries -- with
+        the row's value group merged in where the id has one -- and the row's other groups, merged as in
+        `__host_greedy_step`; per finished row itself.  The candidates are sorted by (sample, higher score, lower parent,
+        the W best vocabulary ids first, lower id) with stable sorts from the last key to the first, and the first W of
+        a sample are its new slots.  Returns (state, next tokens [B W], parent rows [B W])."""
+        beam, done, lengths, tokens = state
+        R, V = target_logprobs.shape
+        B = R // W
+        K = min(top_k, V)
+        order = torch.sort(target_logprobs, dim=-1, descending=True, stable=True).indices
+        in_top = torch.zeros(R, V, dtype=torch.bool).scatter_(1, order[:, :K], True)
+        best_w = order[:, :W]                                                           # [R, W]
+        in_best = torch.zeros(R, V, dtype=torch.bool).scatter_(1, best_w, True)
+        entries = target_logprobs.clone()
+        rows = torch.arange(R)
+        cand_row, cand_id = [rows.repeat_interleave(W)], [best_w.reshape(-1)]
+        cand_class, cand_value = [torch.zeros(R * W, dtype=torch.int64)], []
+        if row_of_memory.shape[0]:
+            span = int(ids.max()) + 1
+            keys, group = torch.unique(row_of_memory * span + ids, return_inverse=True)  # sorted by (row, id)
+            row, gid = torch.div(keys, span, rounding_mode="floor"), keys % span
+            G = keys.shape[0]
+            top = torch.full((G,), -math.inf, dtype=copy_logprobs.dtype).scatter_reduce(
+                0, group, copy_logprobs, "amax", include_self=True)
+            shift = torch.where(top == -math.inf, torch.zeros_like(top), top)
+            merged = torch.zeros(G, dtype=copy_logprobs.dtype).index_add(
+                0, group, (copy_logprobs - shift[group]).exp()).log() + shift
+            column = gid.clamp(max=V - 1)
+            vocabulary = torch.where((gid < V) & in_top[row, column], target_logprobs[row, column],
+                                     torch.full_like(merged, -math.inf))
+            merged = torch.logaddexp(vocabulary, merged)
+            replaces = (gid < V) & in_best[row, column]              # the group's entry IS that vocabulary entry
+            entries[row[replaces], column[replaces]] = merged[replaces]
+            cand_row.append(row[~replaces])
+            cand_id.append(gid[~replaces])
+            cand_class.append(torch.ones(int((~replaces).sum()), dtype=torch.int64))
+            cand_value.append(merged[~replaces])
+        cand_value.insert(0, entries.gather(1, best_w).reshape(-1))
+        cand_row, cand_id, cand_class = torch.cat(cand_row), torch.cat(cand_id), torch.cat(cand_class)
+        cand_value = torch.cat(cand_value).float()
+        live = ~done.reshape(-1)
+        keep = live[cand_row]
+        finished = rows[~live]
+        cand_row = torch.cat((cand_row[keep], finished))
+        cand_id = torch.cat((cand_id[keep], torch.full_like(finished, -1)))
+        cand_class = torch.cat((cand_class[keep], torch.zeros_like(finished)))
+        score = beam.reshape(-1)[cand_row] + torch.cat((cand_value[keep], torch.zeros(finished.shape[0])))
+        perm = torch.sort(cand_id, stable=True).indices
+        for key, descending in ((cand_class, False), (cand_row % W, False), (score, True),
+                                (torch.div(cand_row, W, rounding_mode="floor"), False)):
+            perm = perm[torch.sort(key[perm], descending=descending, stable=True).indices]
+        sample = torch.div(cand_row[perm], W, rounding_mode="floor")
+        starts = torch.zeros(B + 1, dtype=torch.int64)
+        starts[1:] = torch.bincount(sample, minlength=B).cumsum(0)
+        chosen = perm[torch.arange(perm.shape[0]) - starts[sample] < W]                  # [B W]: every sample has >= W
+        parent, predicted = cand_row[chosen], cand_id[chosen]
+        was_done = ~live[parent]
+        ends = ~was_done & (predicted == end_id)
+        append = ~was_done & ~ends
+        new_tokens = tokens.reshape(R, -1)[parent].clone()
+        new_tokens[append, step] = predicted[append]
+        next_tokens = torch.where(was_done, torch.full_like(predicted, end_id),
+                                  torch.where(predicted < V, predicted, torch.full_like(predicted, self.__unk_id)))
+        state = (score[chosen].reshape(B, W), (was_done | ends).reshape(B, W),
+                 (lengths.reshape(-1)[parent] + append.long()).reshape(B, W), new_tokens.reshape(B, W, -1))
+        return state, next_tokens, parent
+
+    def beam_decode(self, *, input_memories, input_memories_origin_idx, initial_states, input_element_ids, start_id: int,
+                    end_id: int, max_seq_len: int, beam_width: int, top_k: int = 100):
+        """Beam search over the dictionary of `greedy_decode` (the reference has none: grucopydecoder.py:406-442 extended to
+        the W = beam_width best hypotheses of every sample); tensor arguments and the extended id space as there.
+
+        Each sample keeps W slots; before the first step slot 0 is (START, its initial state, score 0) and the others
+        are the same hypothesis at -inf.  At each of the `max_seq_len` steps every live slot takes a GRU step on its next
+        token and has the entries `greedy_decode` builds for a sample, from its own scores; entry e is the candidate
+        (parent, e, score[parent] + logprob(e)), a finished slot is its own single candidate.  The W candidates of a
+        sample that come first by: higher score; lower parent; inside a parent the ids of its W best vocabulary entries
+        before its other entries (of equal vocabulary scores the lower id is the larger); lower id -- are the new slots
+        0 .. W - 1, in that order.  END finishes a hypothesis (its log-probability included), anything else is appended;
+        no length normalisation, no early exit.  W = 1 is `greedy_decode`.
+
+        :return: token_ids int64 [num-targets, W, max_seq_len] (-1 after the tokens, END not included), lengths int64
+            [num-targets, W], logprobs float32 [num-targets, W], descending per sample.
+
+        On GPU tensors the W hypotheses of a sample ride through the fused attention pool and the copy-score kernel as
+        W heads of one launch, the step between them is csrc/beam_step.hip and the hidden states are reordered by the row
+        gather; nothing is read back inside the loop.  beam_width <= min(top_k, vocabulary size), and <= 8 (the head
+        limit of the fused pool) on GPU tensors; the CPU route takes any."""
+        x, index, h, ids = input_memories, input_memories_origin_idx, initial_states, input_element_ids
+        if self.training and self.__dropout.p > 0.0:
+            raise _lib.PtgnnAmdError("beam_decode: dropout is active (call eval() first)")
+        V = self.__vocab_bias.shape[0]
+        B, T, I, W = int(h.shape[0]), int(max_seq_len), int(x.shape[0]), int(beam_width)
+        if ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] != I or ids.device != x.device:
+            raise _lib.PtgnnAmdError("beam_decode: input_element_ids must be an int64 tensor with one entry per memory, on "
+                                     "the memories' device")
+        if top_k < 1 or T < 0 or not (0 <= start_id < V and 0 <= end_id < V):
+            raise _lib.PtgnnAmdError(f"beam_decode: needs top_k >= 1, max_seq_len >= 0 and start_id / end_id inside the "
+                                     f"vocabulary of {V} (got {top_k}, {T}, {start_id}, {end_id})")
+        if not 1 <= W <= min(top_k, V):
+            raise _lib.PtgnnAmdError(f"beam_decode: needs 1 <= beam_width <= min(top_k, vocabulary size) = "
+                                     f"{min(top_k, V)}, so that every step has beam_width finite candidates (got {W})")
+        if x.is_cuda and W > 8:
+            raise _lib.PtgnnAmdError(f"beam_decode: beam_width {W} > 8, the head limit of the fused attention pool that "
+                                     f"carries the hypotheses of a sample on the GPU")
+        dev = x.device
+        tokens = torch.full((B, W, T), -1, dtype=torch.int64, device=dev)
+        lengths = torch.zeros(B, W, dtype=torch.int64, device=dev)
+        beam = torch.full((B, W), -math.inf, dtype=torch.float32, device=dev)
+        beam[:, :1] = 0.0
+        if B == 0 or T == 0:
+            return tokens, lengths, beam
+        span = 1
+        if I:
+            low, high = (int(v) for v in torch.aminmax(ids))     # the one read-back of the call, before the loop
+            if low < 0 or high >= _MAX_ELEMENT_ID:
+                raise _lib.PtgnnAmdError(f"beam_decode: input_element_ids must lie in [0, {_MAX_ELEMENT_ID}) (got "
+                                         f"{low} .. {high})")
+            span = high + 1
+        next_tokens = torch.full((B * W,), int(start_id), dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            x, h = x.float(), h.float()                          # AMP: fp32 inside, as everywhere
+            h = h.unsqueeze(1).expand(B, W, h.shape[1]).reshape(B * W, -1).contiguous()    # row b W + j
+            if not x.is_cuda:    # device dispatch: CPU tensors take the same algorithm on torch operators
+                slot = torch.arange(W).repeat_interleave(I)      # the memories once per slot, slot-major
+                x_rows, row_of_memory, ids_rows = x.repeat(W, 1), index.repeat(W) * W + slot, ids.repeat(W)
+                state = (beam, torch.zeros(B, W, dtype=torch.bool), lengths, tokens)
+                for step in range(T):
+                    copy_logprobs, target_logprobs, new_h = self._compute_logprobs(h, x_rows, row_of_memory,
+                                                                                   next_tokens.unsqueeze(1))
+                    state, next_tokens, parent = self.__host_beam_step(
+                        copy_logprobs.squeeze(1), target_logprobs.squeeze(1), row_of_memory, ids_rows, top_k, W, end_id,
+                        step, state)
+                    h = new_h.squeeze(0)[parent]
+                return state[3], state[2], state[0]
+            self.__check_index(x, index)
+            x = x.contiguous()
+            gru, H = self.__output_gru, h.shape[1]
+            plan = _index_plan(index, B)
+            groups = ops.value_groups(index, ids, B, span)
+            state = (beam, torch.zeros(B, W, dtype=torch.int32, device=dev), lengths, tokens)
+            spare = tuple(torch.empty_like(t) for t in state)
+            parent_rows = torch.empty(B * W, dtype=torch.int64, device=dev)
+            for step in range(T):
+                embedded = _rows(self.__embedding_layer.weight, next_tokens)               # [B W, E]
+                new_h = dense.gru_cell_weights(embedded, h, gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0,
+                                               gru.bias_hh_l0)
+                attention_out, copy_scores, total_copy = self.__attend(new_h.reshape(B, W, H), x, index, plan)
+                raw_scores = self.__raw_vocabulary_scores(attention_out, new_h)            # [B W, V]
+                ops.beam_step(raw_scores, self.__vocab_bias, copy_scores, total_copy, groups, top_k, self.__unk_id, end_id,
+                              step, state, spare, next_tokens, parent_rows)
+                state, spare = spare, state
+                h = ops.gather_rows(new_h, parent_rows)
+            ops.post_index_check(dev)
+        return state[3], state[2], state[0]
 
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form (as for the attention reducers)."""
