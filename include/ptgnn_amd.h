@@ -182,6 +182,13 @@ enum {
   PTGNN_AMD_KERNEL_BEAM_STEP = PTGNN_AMD_KERNEL_BEAM_FIRST_, /* ptgnn_amd_beam_step_f32 */
   PTGNN_AMD_KERNEL_BEAM_END_
 };
+/* An eighth id range: the opt-in 16-bit-input dense blocks (csrc/half_gemm.hip). */
+enum {
+  PTGNN_AMD_KERNEL_HALF_FIRST_ = 448,
+  PTGNN_AMD_KERNEL_HALF_LINEAR = PTGNN_AMD_KERNEL_HALF_FIRST_, /* ptgnn_amd_half_linear */
+  PTGNN_AMD_KERNEL_HALF_GRU,                                   /* ptgnn_amd_half_gru_cell */
+  PTGNN_AMD_KERNEL_HALF_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1286,6 +1293,47 @@ int ptgnn_amd_beam_step_f32(const float *scores, int64_t ld, const float *bias /
                             int32_t *done_out, int64_t *lengths_out, int64_t *tokens_out, int64_t *next_tokens,
                             int64_t *parent_rows, int32_t *bad /* nullable */, void *workspace, size_t workspace_bytes,
                             void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks (csrc/half_gemm.hip).
+ *
+ * Replaces: what an `enable_amp` user of the reference trainer gets (ptgnn/baseneuralmodel/trainer.py:205,221: the
+ *   forward runs under torch.cuda.amp.autocast, so the message Linears and the GRU cell of gatedmessagepassing.py:57-69
+ *   take their operands in the autocast dtype; the reference up-casts only at the scatter,
+ *   abstractmessagepassing.py:43-50).  OFF by default: nothing in the library calls these entries unless the host's
+ *   ptgnn_amd.precision setting asks for it; this is not a GEMM mode (ptgnn_amd_set_gemm_mode is unchanged).
+ *
+ * States stay fp32 in memory.  The kernels round x / a / h to `dtype` (PTGNN_AMD_HALF_BF16 / _F16) in registers, to
+ * nearest even, exactly as tensor.to(dtype) does; the weights arrive ALREADY rounded as 16-bit arrays in the nn.Linear /
+ * nn.GRUCell layouts (the host makes them with tensor.to(dtype)).  Products run on v_mfma_f32_32x32x16_{bf16,f16};
+ * accumulation, bias, activation, gate math and the stores are fp32:
+ *   ptgnn_amd_half_linear  : y = act(rnd(x) rnd(W)^T + b); x [rows, k] (ld_x), w 16-bit [n_out, k], bias fp32 [n_out]
+ *     (nullable), y [rows, n_out] (ld_y), act = PTGNN_AMD_ACT_* as ptgnn_amd_linear_f32.
+ *   ptgnn_amd_half_gru_cell: gi = rnd(a) rnd(W_ih)^T + b_ih, gh = rnd(h) rnd(W_hh)^T + b_hh, r = sigmoid(gi_r + gh_r),
+ *     z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n), h' = (1 - z) n + z h with the UNROUNDED fp32 h in the blend.
+ *     Shapes as ptgnn_amd_gru_cell_f32, w_ih / w_hh 16-bit; `out` has its own ld_out (a column slice of a wider buffer is
+ *     fine); out != h.  Gate math: the streaming fp32 cell's expressions, so both cells meet the same bar against a
+ *     float64 reference on the rounded operands.
+ *   ptgnn_amd_half_supported(kind, k_or_m, n_out_or_hd, dtype): 1 when the kernels take the shape, else 0; needs no
+ *     device.  kind PTGNN_AMD_HALF_KIND_LINEAR: k % 32 == 0, k <= 1024, n_out % 32 == 0.  _GRU: m % 32 == 0,
+ *     hd % 32 == 0, both <= 1024.
+ * Any number of rows, 0 included (no launch).  x, a, h and the weights must be 16-byte aligned with ld % 4 == 0; y, out
+ * and the biases aligned to a float.  A bad dtype / act / size or a null pointer answers PTGNN_AMD_EINVAL, a shape or an
+ * alignment outside the above PTGNN_AMD_EUNSUPPORTED, both with a message and before anything touches the device.
+ * Row independence: the bits of output row r depend on row r of the inputs and on the weights only -- not on `rows`,
+ * the launch geometry or the row's position; a launch over [0, n) equals launches over any partition of it.
+ * Magnitudes below the 16-bit type's smallest normal (bf16: 2^-126, fp16: 2^-14) are outside the contract (whether
+ * they flush follows the hardware's denormal mode, not torch's); fp16 overflow becomes inf, as tensor.half() gives.
+ * No float atomics: two calls give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+enum { PTGNN_AMD_HALF_BF16 = 1, PTGNN_AMD_HALF_F16 = 2 };
+enum { PTGNN_AMD_HALF_KIND_LINEAR = 0, PTGNN_AMD_HALF_KIND_GRU = 1 };
+int ptgnn_amd_half_supported(int kind, int32_t k_or_m, int32_t n_out_or_hd, int dtype);
+int ptgnn_amd_half_linear(const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w, int32_t n_out,
+                          const float *bias /* nullable */, int act, int dtype, float *y, int64_t ld_y, void *stream);
+int ptgnn_amd_half_gru_cell(const float *a, int64_t ld_a, const float *h, int64_t ld_h, const void *w_ih,
+                            const void *w_hh, const float *b_ih, const float *b_hh, int64_t n, int32_t m, int32_t hd,
+                            int dtype, float *out, int64_t ld_out, void *stream);
 
 #pragma GCC visibility pop
 

@@ -27,6 +27,7 @@ static std::atomic<int64_t> g_head_launches[PTGNN_AMD_KERNEL_HEAD_END_ - PTGNN_A
 static std::atomic<int64_t> g_seq_launches[PTGNN_AMD_KERNEL_SEQ_END_ - PTGNN_AMD_KERNEL_SEQ_FIRST_];
 static std::atomic<int64_t> g_decode_launches[PTGNN_AMD_KERNEL_DECODE_END_ - PTGNN_AMD_KERNEL_DECODE_FIRST_];
 static std::atomic<int64_t> g_beam_launches[PTGNN_AMD_KERNEL_BEAM_END_ - PTGNN_AMD_KERNEL_BEAM_FIRST_];
+static std::atomic<int64_t> g_half_launches[PTGNN_AMD_KERNEL_HALF_END_ - PTGNN_AMD_KERNEL_HALF_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -41,6 +42,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_decode_launches[kernel_id - PTGNN_AMD_KERNEL_DECODE_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_BEAM_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_BEAM_END_)
     return &g_beam_launches[kernel_id - PTGNN_AMD_KERNEL_BEAM_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_HALF_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HALF_END_)
+    return &g_half_launches[kernel_id - PTGNN_AMD_KERNEL_HALF_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -102,6 +105,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
   static const char *const beam_names[PTGNN_AMD_KERNEL_BEAM_END_ - PTGNN_AMD_KERNEL_BEAM_FIRST_] = {"beam_step"};
   if (kernel_id >= PTGNN_AMD_KERNEL_BEAM_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_BEAM_END_)
     return beam_names[kernel_id - PTGNN_AMD_KERNEL_BEAM_FIRST_];
+  static const char *const half_names[PTGNN_AMD_KERNEL_HALF_END_ - PTGNN_AMD_KERNEL_HALF_FIRST_] = {"half_linear",
+                                                                                                    "half_gru"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_HALF_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HALF_END_)
+    return half_names[kernel_id - PTGNN_AMD_KERNEL_HALF_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

@@ -33,6 +33,11 @@ per-edge path: torch only gathers / concatenates rows, every Linear runs on the 
 and the aggregation on the HIP segment-reduce seam with its autograd rule.  fp16 / bf16 node states (AMP) are up-cast
 to fp32 on entry and the result is cast back.  No GPU path runs on a vendor BLAS or falls back to torch.
 
+Opt-in 16-bit matrix-core inputs (`ptgnn_amd/precision.py`, off by default): the GGNN layer's INFERENCE routes round the
+operands of the table-form message Linear and of the GRU cell to bf16 / fp16 and run them on csrc/half_gemm.hip.  The
+grouped per-edge GEMM of the edge form, every training route, `forward_sharded`, every other layer and the decoder stay
+fp32 under the setting (the follow-ups).
+
 Device dispatch (round 5): tensors on the CPU take `ptgnn_amd/torch_route.py` (plain torch operators, so that the
 reference's `predict.py` -- which restores and runs on "cpu" -- and a CPU `ModelTrainer` work with these layers);
 tensors on the GPU always take the HIP library and raise when it is missing.
@@ -53,7 +58,7 @@ from typing import Dict, List, Optional, Tuple, Union
 import torch
 from torch import nn
 
-from ptgnn_amd import _lib, dense, ops, torch_route
+from ptgnn_amd import _lib, dense, ops, precision, torch_route
 from ptgnn_amd.scatter import (block_attention as block_attention_autograd, edge_linear as edge_linear_autograd,
                                edge_linear_feat as edge_linear_feat_autograd,
                                gather_reduce as gather_reduce_autograd, graph_norm as graph_norm_autograd,
@@ -233,10 +238,21 @@ def _train_edge_messages(owner, x, plan, weights, use_dst: bool, p: float = 0.0,
 _AMP_DTYPES = (torch.float16, torch.bfloat16)
 
 
+def _half_weights(owner, name: str, dtype, kind: int, k_or_m: int, n_out_or_hd: int, make):
+    """The rounded copies of a layer's weights for a 16-bit matrix-input setting (ptgnn_amd/precision.py), made by torch
+    (`w.detach().to(dtype).contiguous()`) once per forward scope; None under float32 and for shapes the 16-bit kernels
+    do not take (the op then runs its fp32 kernel)."""
+    if dtype == torch.float32 or not ops.half_supported(kind, k_or_m, n_out_or_hd, dtype):
+        return None
+    return _scoped(owner, (name, dtype), make)
+
+
 def _amp_forward(layer, node_states, adjacency_lists, edge_features, cast_features: bool = True) -> torch.Tensor:
     """AMP (trainer.py:205,221): the reference computes messages in the autocast dtype and up-casts them to fp32 at the
     aggregation (abstractmessagepassing.py:43-50).  Here the whole layer runs in fp32 on the HIP kernels -- every
-    intermediate at least as precise as the reference's -- and only the returned states go back to the caller's dtype."""
+    intermediate at least as precise as the reference's -- and only the returned states go back to the caller's dtype.
+    Under a 16-bit matrix-input setting (ptgnn_amd/precision.py) the up-cast states take the GGNN layer's 16-bit routes
+    like any fp32 states: rounding an up-cast value is exact."""
     if cast_features:
         edge_features = [f.float() if f is not None and f.dtype in _AMP_DTYPES else f for f in edge_features]
     return layer.forward(node_states.float(), adjacency_lists, None, None, None, edge_features).to(node_states.dtype)
@@ -487,7 +503,8 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
         if _on_host(node_states):
             return torch_route.ggnn_layer(node_states, adjacency_lists, edge_features,
                                           list(self.__edge_message_transformation_layers), self.__dropout,
-                                          self.__state_update, self.__aggregation_fn)
+                                          self.__state_update, self.__aggregation_fn,
+                                          inputs=self._host_matrix_inputs(node_states, edge_features))
         if node_states.dtype in _AMP_DTYPES:
             return _amp_forward(self, node_states, adjacency_lists, edge_features)
         num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
@@ -520,11 +537,28 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             agg = segment_reduce(self._general_messages(node_states, adjacency_lists, edge_features), plan, agg_fn)
         return dense.gru_cell(self.__state_update, agg, node_states)
 
+    def _host_matrix_inputs(self, node_states, edge_features):
+        """The matrix-input setting as the CPU route applies it: fp32 states, inference only (as on the GPU)."""
+        if node_states.dtype != torch.float32 or (self.training and self.__dropout.p > 0):
+            return torch.float32
+        if torch.is_grad_enabled() and not _no_grad_needed(node_states, *self.parameters(),
+                                                           *[f for f in edge_features if f is not None]):
+            return torch.float32
+        return precision.resolve(node_states)
+
+    def _rounded_gru_weights(self, dtype):
+        gru = self.__state_update
+        return _half_weights(self, "gru_w16", dtype, ops.HALF_KIND_GRU, self._message_dimension, self.__state_dimension,
+                             lambda: (gru.weight_ih.detach().to(dtype).contiguous(),
+                                      gru.weight_hh.detach().to(dtype).contiguous()))
+
     def _forward_fused(self, node_states, adjacency_lists, plan) -> torch.Tensor:
         """Inference: message table (or edge form) -> aggregation -> GRU cell, pipelined over destination-row ranges on
-        large minibatches (ops.aggregate_gru)."""
+        large minibatches (ops.aggregate_gru).  Under a 16-bit matrix-input setting the table Linear and the GRU cell
+        take the 16-bit kernels; the grouped per-edge GEMM of the edge form stays fp32."""
         num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
         gru = self.__state_update
+        inputs = precision.resolve(node_states)
         if _prefer_edge_path(plan.num_edges, num_nodes, len(adjacency_lists), H, M):
             # many sparse edge types: one grouped per-edge GEMM.  The message W_t x[src] is the same row for
             # every edge of type t that leaves src: the GEMM produces one row per distinct (type, source) pair
@@ -534,19 +568,26 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights)
             tb = 0
         else:
-            msgs, col, tb = ops.linear(node_states, self._stacked_edge_weights()), None, None      # [N, T*M]
+            w = self._stacked_edge_weights()
+            w16 = _half_weights(self, "edge_w16", inputs, ops.HALF_KIND_LINEAR, H, w.shape[0],
+                                lambda: w.to(inputs).contiguous())
+            msgs, col, tb = ops.linear(node_states, w, inputs=inputs, rounded=w16), None, None      # [N, T*M]
         return ops.aggregate_gru(msgs, plan, M, self.__aggregation_fn, node_states, gru.weight_ih, gru.weight_hh,
                                  gru.bias_ih, gru.bias_hh, type_bits=tb, col=col,
-                                 out=_take_output_hint(num_nodes, H, node_states))
+                                 out=_take_output_hint(num_nodes, H, node_states), inputs=inputs,
+                                 rounded=self._rounded_gru_weights(inputs))
 
     def _forward_features_inference(self, node_states, adjacency_lists, plan, edge_features) -> torch.Tensor:
-        """Inference with edge features: fused gather of [x[src] | features] inside the grouped GEMM."""
+        """Inference with edge features: fused gather of [x[src] | features] inside the grouped GEMM (fp32 under every
+        matrix-input setting; the GRU cell follows the setting)."""
         gru = self.__state_update
+        inputs = precision.resolve(node_states)
         msgs = ops.edge_linear(node_states, adjacency_lists,
                                [l.weight for l in self.__edge_message_transformation_layers], False,
                                edge_feats=edge_features)
         agg = ops.gather_reduce(msgs, plan, self._message_dimension, self.__aggregation_fn, type_bits=0, col=plan.perm)
-        return ops.gru_cell(agg, node_states, gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh)
+        return ops.gru_cell(agg, node_states, gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh, inputs=inputs,
+                            rounded=self._rounded_gru_weights(inputs))
 
     def _general_messages(self, node_states, adjacency_lists, edge_features) -> torch.Tensor:
         """General per-edge path (per-edge dropout with edge features, odd widths): message order = type-major."""

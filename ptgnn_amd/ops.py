@@ -56,8 +56,11 @@ _DECODE_FAMILY_FIRST = 320  # PTGNN_AMD_KERNEL_DECODE_FIRST_: the copying decode
 _BEAM_FAMILY_FIRST = 384  # PTGNN_AMD_KERNEL_BEAM_FIRST_: the copying decoder's beam-search step
 
 
+_HALF_FAMILY_FIRST = 448  # PTGNN_AMD_KERNEL_HALF_FIRST_: the opt-in 16-bit-input dense blocks
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
-                  sequence: bool = False, decode: bool = False, beam: bool = False) -> dict:
+                  sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -66,12 +69,14 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `char_cnn=True` adds the char-CNN embedder's (char_embed, char_embed_backward, window_max, window_max_backward);
     `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward);
     `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish);
-    `decode=True` its greedy-decoding step (decode_step); `beam=True` its beam-search step (beam_step)."""
+    `decode=True` its greedy-decoding step (decode_step); `beam=True` its beam-search step (beam_step);
+    `half=True` the 16-bit-input dense blocks (half_linear, half_gru)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
             + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()) \
-            + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()):
+            + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()) \
+            + ((_HALF_FAMILY_FIRST,) if half else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -84,7 +89,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True)
+    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -1210,9 +1215,51 @@ def pna_aggregate_backward(messages: torch.Tensor, plan: GraphPlan, agg: torch.T
     return out
 
 
+# The opt-in 16-bit matrix-core inputs (include/ptgnn_amd.h: ptgnn_amd_half_*; ptgnn_amd/precision.py is the switch the
+# LAYERS read -- nothing here does: `inputs=` is explicit, because inside an autograd Function.forward grad mode is off
+# and an op cannot tell inference from training).
+HALF_IDS = {torch.bfloat16: 1, torch.float16: 2}     # PTGNN_AMD_HALF_BF16 / _F16
+HALF_KIND_LINEAR, HALF_KIND_GRU = 0, 1               # PTGNN_AMD_HALF_KIND_*
+
+
+def half_supported(kind: int, k_or_m: int, n_out_or_hd: int, dtype) -> bool:
+    """Whether the 16-bit-input kernels take the shape (ptgnn_amd_half_supported; needs no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_half_supported(kind, int(k_or_m), int(n_out_or_hd), HALF_IDS[dtype]))
+
+
+def _half_inputs(inputs) -> Optional[torch.dtype]:
+    """The `inputs=` keyword of linear / gru_cell / aggregate_gru: None and float32 mean the fp32 kernels."""
+    if inputs is None or inputs == torch.float32:
+        return None
+    if inputs not in HALF_IDS:
+        raise _lib.PtgnnAmdError(f"inputs must be None, torch.float32, torch.bfloat16 or torch.float16 (got {inputs!r})")
+    return inputs
+
+
+def _half_rows_ok(t: torch.Tensor) -> bool:
+    """An fp32 operand the 16-bit kernels' fragment loads can read: 16-byte aligned rows."""
+    return t.data_ptr() % 16 == 0 and _ld(t) % 4 == 0
+
+
+def _rounded_weight(w: torch.Tensor, dtype: torch.dtype, given: Optional[torch.Tensor]) -> torch.Tensor:
+    """`w` rounded to `dtype` by torch (round to nearest even), or the caller's cached copy of exactly that."""
+    if given is None:
+        return w.detach().to(dtype).contiguous()
+    if given.dtype != dtype or given.shape != w.shape or given.device != w.device:
+        raise _lib.PtgnnAmdError(f"rounded weight must be {dtype} {tuple(w.shape)} on {w.device} "
+                                 f"(got {given.dtype} {tuple(given.shape)} on {given.device})")
+    return given.contiguous()
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
-           act: Optional[str] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = act(x W^T + b) on fp32 MFMA.  weight is nn.Linear layout [n_out, k]."""
+           act: Optional[str] = None, out: Optional[torch.Tensor] = None, inputs=None,
+           rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = act(x W^T + b) on fp32 MFMA.  weight is nn.Linear layout [n_out, k].
+    `inputs` = torch.bfloat16 / torch.float16: x and the weight are rounded to that type and multiplied on the 16-bit
+    matrix cores (fp32 accumulation and output) where `half_supported` takes the shape and x has 16-byte aligned rows;
+    otherwise the fp32 kernel runs, silently.  `rounded`: the caller's `weight.to(inputs)`, to save the conversion."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
     _require_cuda_f32("weight", weight)
@@ -1225,6 +1272,15 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         out = torch.empty(rows, n_out, dtype=torch.float32, device=x.device)
     if bias is not None:
         bias = bias.contiguous()
+    half = _half_inputs(inputs)
+    if half is not None and half_supported(HALF_KIND_LINEAR, k, n_out, half) and _half_rows_ok(x):
+        w16 = _rounded_weight(weight, half, rounded)
+        with _timed("half_linear", flops=2.0 * rows * k * n_out, bytes=4.0 * rows * (k + n_out) + 2.0 * n_out * k):
+            rc = lib.ptgnn_amd_half_linear(x.data_ptr(), rows, k, _ld(x), w16.data_ptr(), n_out,
+                                           bias.data_ptr() if bias is not None else None, ACT_IDS[act],
+                                           HALF_IDS[half], out.data_ptr(), _ld(out), _stream(out))
+        _lib.check(rc, "ptgnn_amd_half_linear")
+        return out
     with _timed("linear", flops=2.0 * rows * k * n_out, bytes=4.0 * (rows * k + n_out * k + rows * n_out)):
         rc = lib.ptgnn_amd_linear_f32(x.data_ptr(), rows, k, _ld(x), weight.data_ptr(), n_out,
                                       bias.data_ptr() if bias is not None else None, ACT_IDS[act],
@@ -1577,9 +1633,14 @@ def act_dropout_backward(grad: torch.Tensor, y: torch.Tensor, keep: Optional[tor
     return out
 
 
-def gru_cell(a: torch.Tensor, h: torch.Tensor, w_ih, w_hh, b_ih, b_hh, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def gru_cell(a: torch.Tensor, h: torch.Tensor, w_ih, w_hh, b_ih, b_hh, out: Optional[torch.Tensor] = None,
+             inputs=None, rounded=None) -> torch.Tensor:
     """`out`: optional caller-owned [n, hd] fp32 destination with unit inner stride (e.g. the right half of the
-    buffer a concat residual returns)."""
+    buffer a concat residual returns).
+    `inputs` = torch.bfloat16 / torch.float16: a, h and both weights are rounded to that type in the gate GEMMs (16-bit
+    matrix cores; fp32 accumulation, gate math and blend with the unrounded h) where `half_supported` takes the widths
+    and a, h have 16-byte aligned rows; otherwise the fp32 cell runs, silently.  `rounded`: the caller's
+    (w_ih.to(inputs), w_hh.to(inputs))."""
     lib = _lib.load()
     _require_cuda_f32("a", a)
     _require_cuda_f32("h", h)
@@ -1590,6 +1651,16 @@ def gru_cell(a: torch.Tensor, h: torch.Tensor, w_ih, w_hh, b_ih, b_hh, out: Opti
         out = torch.empty(n, hd, dtype=torch.float32, device=a.device)
     elif tuple(out.shape) != (n, hd) or out.dtype != torch.float32 or out.stride(1) != 1 or not out.is_cuda:
         raise _lib.PtgnnAmdError(f"gru_cell: `out` must be a float32 CUDA [{n}, {hd}] view with unit inner stride")
+    half = _half_inputs(inputs)
+    if half is not None and half_supported(HALF_KIND_GRU, m, hd, half) and _half_rows_ok(a) and _half_rows_ok(h):
+        given = rounded if rounded is not None else (None, None)
+        wi16, wh16 = _rounded_weight(w_ih, half, given[0]), _rounded_weight(w_hh, half, given[1])
+        with _timed("half_gru_cell", flops=2.0 * n * 3 * hd * (m + hd), bytes=4.0 * n * (m + 2 * hd) + 6.0 * hd * (m + hd)):
+            rc = lib.ptgnn_amd_half_gru_cell(a.data_ptr(), _ld(a), h.data_ptr(), _ld(h), wi16.data_ptr(), wh16.data_ptr(),
+                                             b_ih.contiguous().data_ptr(), b_hh.contiguous().data_ptr(), n, m, hd,
+                                             HALF_IDS[half], out.data_ptr(), _ld(out), _stream(out))
+        _lib.check(rc, "ptgnn_amd_half_gru_cell")
+        return out
     with _timed("gru_cell", flops=2.0 * n * 3 * hd * (m + hd), bytes=4.0 * (n * (m + 2 * hd) + 3 * hd * (m + hd))):
         rc = lib.ptgnn_amd_gru_cell_f32(a.data_ptr(), _ld(a), h.data_ptr(), _ld(h),
                                         w_ih.contiguous().data_ptr(), w_hh.contiguous().data_ptr(),
@@ -1615,14 +1686,15 @@ AGG_PIPELINE_MIN_ROWS = int(os.environ.get("PTGNN_AMD_AGG_PIPELINE_MIN_ROWS", "6
 
 def aggregate_gru(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str, h: torch.Tensor, w_ih, w_hh, b_ih,
                   b_hh, type_bits: Optional[int] = None, col: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, inputs=None, rounded=None) -> torch.Tensor:
     """GRUCell(aggregate(ysrc over plan), h) -- `gather_reduce` followed by `gru_cell`, pipelined over row ranges on
-    large minibatches (see above)."""
+    large minibatches (see above).  `inputs` / `rounded`: as `gru_cell` (the 16-bit cell is row-independent, so the
+    row ranges give the bits of one launch there too)."""
     N = plan.num_nodes
     pieces = AGG_PIPELINE
     if (pieces < 2 or N < AGG_PIPELINE_MIN_ROWS or N < 64 * pieces or torch.cuda.is_current_stream_capturing()):
         agg = gather_reduce(ysrc, plan, msg_dim, reduce, type_bits=type_bits, col=col)
-        return gru_cell(agg, h, w_ih, w_hh, b_ih, b_hh, out=out)
+        return gru_cell(agg, h, w_ih, w_hh, b_ih, b_hh, out=out, inputs=inputs, rounded=rounded)
     dev = h.device
     hd = h.shape[1]
     agg = torch.empty(N, msg_dim, dtype=torch.float32, device=dev)
@@ -1648,7 +1720,7 @@ def aggregate_gru(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
             main.wait_event(ready[i - 1])
         lo, hi = bounds[i], bounds[i + 1]
         if hi > lo:
-            gru_cell(agg[lo:hi], h[lo:hi], w_ih, w_hh, b_ih, b_hh, out=out[lo:hi])
+            gru_cell(agg[lo:hi], h[lo:hi], w_ih, w_hh, b_ih, b_hh, out=out[lo:hi], inputs=inputs, rounded=rounded)
     return out
 
 

@@ -315,16 +315,37 @@ def _message_inputs(node_states, adjacency_lists, edge_features, with_target: bo
         yield parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
 
 
+def _rounded(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """`t` rounded to a 16-bit type and back: the value the 16-bit matrix cores multiply (ptgnn_amd/precision.py)."""
+    return t.to(dtype).float()
+
+
 def ggnn_layer(node_states, adjacency_lists, edge_features, edge_linears: Sequence[nn.Linear], dropout: nn.Module,
-               gru: nn.GRUCell, reduce: str) -> torch.Tensor:
+               gru: nn.GRUCell, reduce: str, inputs: torch.dtype = torch.float32) -> torch.Tensor:
     """gatedmessagepassing.py:46-69 on host tensors: per type W_t . Dropout([x_src ; f_e]), type-major messages,
-    segment reduce onto the targets, GRUCell(aggregate, state)."""
+    segment reduce onto the targets, GRUCell(aggregate, state).
+    `inputs` = torch.bfloat16 / torch.float16 (the caller's matrix-input setting, inference only): the operands the GPU
+    routes round are rounded here with torch and multiplied by the fp32 operators -- the message Linear's (without edge
+    features: the GPU's table form; with them the per-edge GEMM stays fp32 there and here) and the GRU gate GEMMs', with
+    the unrounded state in the blend."""
     _host_only(node_states)
-    msgs = [lin(dropout(inp)) for inp, lin in
-            zip(_message_inputs(node_states, adjacency_lists, edge_features, False), edge_linears)]
+    if inputs == torch.float32:
+        msgs = [lin(dropout(inp)) for inp, lin in
+                zip(_message_inputs(node_states, adjacency_lists, edge_features, False), edge_linears)]
+    else:
+        plain = all(f is None or f.shape[-1] == 0 for f in edge_features)
+        msgs = [nn.functional.linear(_rounded(inp, inputs), _rounded(lin.weight, inputs)) if plain else lin(inp)
+                for inp, lin in zip(_message_inputs(node_states, adjacency_lists, edge_features, False), edge_linears)]
     targets = torch.cat([d for _, d in adjacency_lists])
     agg = aggregate(torch.cat(msgs, dim=0), targets, node_states.shape[0], reduce)
-    return gru(agg, node_states)
+    if inputs == torch.float32:
+        return gru(agg, node_states)
+    gi = nn.functional.linear(_rounded(agg, inputs), _rounded(gru.weight_ih, inputs), gru.bias_ih)
+    gh = nn.functional.linear(_rounded(node_states, inputs), _rounded(gru.weight_hh, inputs), gru.bias_hh)
+    (i_r, i_z, i_n), (h_r, h_z, h_n) = gi.chunk(3, dim=1), gh.chunk(3, dim=1)
+    r, z = torch.sigmoid(i_r + h_r), torch.sigmoid(i_z + h_z)
+    n = torch.tanh(i_n + r * h_n)
+    return (1.0 - z) * n + z * node_states
 
 
 def mlp_layer(node_states, adjacency_lists, edge_features, edge_mlps: Sequence[nn.Module], with_target: bool,
