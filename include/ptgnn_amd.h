@@ -189,6 +189,13 @@ enum {
   PTGNN_AMD_KERNEL_HALF_GRU,                                   /* ptgnn_amd_half_gru_cell */
   PTGNN_AMD_KERNEL_HALF_END_
 };
+/* A ninth id range: the opt-in 16-bit-input grouped per-edge GEMM (csrc/edge_gemm16.hip). */
+enum {
+  PTGNN_AMD_KERNEL_EDGE16_FIRST_ = 512,
+  PTGNN_AMD_KERNEL_EDGE16 = PTGNN_AMD_KERNEL_EDGE16_FIRST_, /* ptgnn_amd_edge_linear16 */
+  PTGNN_AMD_KERNEL_EDGE16_SHARED,                           /* ptgnn_amd_edge_linear16_shared */
+  PTGNN_AMD_KERNEL_EDGE16_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1334,6 +1341,42 @@ int ptgnn_amd_half_linear(const float *x, int64_t rows, int32_t k, int64_t ld_x,
 int ptgnn_amd_half_gru_cell(const float *a, int64_t ld_a, const float *h, int64_t ld_h, const void *w_ih,
                             const void *w_hh, const float *b_ih, const float *b_hh, int64_t n, int32_t m, int32_t hd,
                             int dtype, float *out, int64_t ld_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the GGNN layer's grouped per-edge GEMM (csrc/edge_gemm16.hip).
+ *
+ * Replaces: the message Linears of gatedmessagepassing.py:50-61 under autocast, where the minibatch takes the edge form
+ *   (ptgnn_amd_edge_linear_f32 / ptgnn_amd_edge_linear_shared_f32 are the fp32 launches and stay as they are).  OFF by
+ *   default: the host's ptgnn_amd.precision setting asks for it with `edge_gemm=True`.
+ *
+ *   msg[r] = act(rnd(x[src[r]]) rnd(W_t)^T) for every message row r of edge type t; no bias.  x fp32 [num_rows, state_dim]
+ *   (ld_x), gathered ids clamped into [0, num_rows); w = ONE 16-bit [num_types, msg_dim, state_dim] stack ALREADY rounded
+ *   by the host (tensor.to(dtype)); the gathered rows are rounded to `dtype` (PTGNN_AMD_HALF_BF16 / _F16) in registers, to
+ *   nearest even; products on v_mfma_f32_32x32x16_{bf16,f16}, fp32 accumulation, fp32 msg [rows, msg_dim] (ld_msg).
+ *   ptgnn_amd_edge_linear16       : one row per edge in type-major order; src_per_type / edges_per_type are HOST arrays
+ *     (device id pointers, counts) as ptgnn_amd_edge_linear_f32 takes them without a target-state half.  No edges: no
+ *     launch, PTGNN_AMD_OK.
+ *   ptgnn_amd_edge_linear16_shared: one row per distinct (type, source) pair; `edge_table` is the device-resident table
+ *     ptgnn_amd_unique_sources wrote on the same stream, as ptgnn_amd_edge_linear_shared_f32 takes it: no host
+ *     synchronisation, no read-back (a table without rows launches workgroups that leave at once).
+ *   ptgnn_amd_edge_linear16_supported(state_dim, msg_dim, num_types, dtype): 1 when the kernels take the shape, else 0;
+ *     needs no device.  state_dim % 32 == 0, msg_dim % 32 == 0, both <= 1024, 2 <= num_types <= 64.
+ * x and w must be 16-byte aligned with ld_x % 4 == 0, msg aligned to a float.  A bad dtype / act / size or a null
+ * pointer answers PTGNN_AMD_EINVAL, a shape, an alignment or a row count beyond the int32 unit / key range
+ * PTGNN_AMD_EUNSUPPORTED, all with a message that starts "edge_linear16:" and before anything touches the device.
+ * Row independence: a row's K chain is k ascending in steps of 16 into one accumulator; the bits of message row r
+ * depend on x[src[r]] and W_t only -- not on the launch form, the row's position, the number of rows or the workgroup
+ * count -- so the aggregate of the shared form equals the aggregate of the per-edge form bit for bit.  Small magnitudes
+ * and fp16 overflow: as ptgnn_amd_half_linear.  No atomics: two calls give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_edge_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype);
+int ptgnn_amd_edge_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                            const int64_t *const *src_per_type, const int64_t *edges_per_type, const void *w,
+                            int32_t num_types, int32_t msg_dim, int act, int dtype, float *msg, int64_t ld_msg,
+                            void *stream);
+int ptgnn_amd_edge_linear16_shared(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                   const void *edge_table, const void *w, int32_t num_types, int32_t msg_dim, int act,
+                                   int dtype, float *msg, int64_t ld_msg, void *stream);
 
 #pragma GCC visibility pop
 

@@ -1,0 +1,359 @@
+// Opt-in 16-bit matrix-core inputs for the GGNN layer's grouped per-edge GEMM (the edge form's message Linear):
+//
+//     msg[r, :] = act( rnd(X[src[r], :]) . rnd(W_t)^T )          for every message row r of edge type t
+//
+// on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulation; no bias (the GGNN message Linear has none).  Two launch forms
+// over the same kernels:
+//   ptgnn_amd_edge_linear16_shared : one row per distinct (type, source) pair; the geometry is the device-resident
+//                                    StreamEdgeTable that ptgnn_amd_unique_sources wrote (no host synchronisation)
+//   ptgnn_amd_edge_linear16        : one row per edge in type-major order, from host arrays of per-type `src` pointers
+// Contracts: include/ptgnn_amd.h.  The fp32 pair is ptgnn_amd_edge_linear_shared_f32 / ptgnn_amd_edge_linear_f32
+// (edge_gemm.hip, stream_gemm.hip: untouched).
+//
+// States and messages stay fp32 in HBM.  The gathered x rows are rounded to nearest even in registers (fptrunc through
+// __builtin_convertvector, what tensor.to(dtype) does; never a truncating pack); the weights arrive already rounded by
+// the host as ONE 16-bit [T, M, H] stack.
+//
+// Work unit = 32 consecutive message rows of one type (the table's `unit_off` prefix; its `wg_off` apportioning belongs
+// to the fp32 kernel and is not read).  Two kernels, chosen by H and M alone:
+//   * k_edge16_ws (H in {64, 128, 256}, M <= 128: the GGNN widths), modelled on k_half_gru_ws: a workgroup of four waves walks
+//     a contiguous run of units; wave s keeps columns [32 s, 32 s + 32) of W_t in registers (H / 16 B fragments, reloaded
+//     only when the run crosses into the next type); a unit's 32 gathered rows are loaded once, coalesced (a row is one
+//     512-byte request of 32 lanes at H = 128), rounded and parked in LDS at a row stride of (H + 8) x 2 bytes -- an odd
+//     number of 16-byte units, so the ds_read_b128 fragment reads are conflict-free; the next unit's gather is issued
+//     before the current unit's MFMAs and lands in the other LDS buffer after them: one barrier per unit.
+//   * k_edge16 (every other supported shape), modelled on k_half_linear: a wave owns a unit x 128 output columns, its
+//     lanes read their row's fragment straight from the gathered row and the weights from L2; no LDS, no barrier.
+//
+// Row independence: in both kernels a row's K chain is one accumulator per 32-column tile, zeroed, k ascending in steps
+// of 16, on the same rounded operands -- the bits of message row r depend on x[src[r]] and W_t only, not on the launch
+// form, the kernel, the row's position in its unit, the number of rows or the workgroup count.  The aggregation that
+// follows gives the same bits whichever form ran, as the fp32 pair does.
+//
+// No atomics, no inline assembly; every store is a plain C++ assignment.
+#include <stdlib.h>
+
+#include "half16.h"
+#include "stream_gemm.h"
+
+namespace ptgnn_amd {
+namespace {
+
+using namespace half16;
+
+struct Edge16Args {
+  StreamEdgeTable tab;               // per-edge form: the table by value (src, edge_off, unit_off); shared form: unused
+  const StreamEdgeTable *tab_dev;    // shared form: the table in device memory
+  const float *x;
+  int64_t ld_x, num_rows;            // rows of x: gathered ids are clamped into [0, num_rows)
+  const uint16_t *w;                 // [T, M, H], rounded by the host
+  int H, M, act;
+  float *msg;
+  int64_t ld_msg;
+};
+
+// The id lists are global memory; read out of a table in device memory the pointers would be generic and their loads
+// flat (stream_gemm.hip k_stream_edge says what that does to the wait counts).
+using GlobalIds = const __attribute__((address_space(1))) int64_t *;
+
+// The 32-row unit `u` of the table: its edge type, its first id, the rows left in the type from there (>= 1) and its
+// first message row.  `v_unit` = unit_off[lane] (entries past the last type hold the total): one ballot finds the type.
+struct Unit {
+  int t;
+  GlobalIds ids;
+  int64_t left, out0;
+};
+__device__ __forceinline__ Unit locate(const StreamEdgeTable &tab, int v_unit, int u) {
+  Unit q;
+  q.t = __popcll(__ballot(v_unit <= u)) - 1;          // last type whose first unit is <= u: the one that owns u
+  const int64_t row0 = (int64_t)(u - __builtin_amdgcn_readlane(v_unit, q.t)) * 32;
+  const int64_t type_row0 = tab.edge_off[q.t];
+  q.left = tab.edge_off[q.t + 1] - type_row0 - row0;
+  q.ids = (GlobalIds)tab.src[q.t] + row0;
+  q.out0 = type_row0 + row0;
+  return q;
+}
+
+// ids were range-checked by the plan build; clamp anyway so a bad id can never fault
+__device__ __forceinline__ int64_t clamp_row(int64_t id, int64_t num_rows) {
+  return id < 0 ? 0 : (id < num_rows ? id : num_rows - 1);
+}
+
+constexpr int kTiles = 4;   // 32-column tiles per wave of k_edge16
+
+template <int DT, bool INDIRECT>
+__global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
+  using Hf = Half16<DT>;
+  const StreamEdgeTable *tabp;
+  if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
+  const StreamEdgeTable &tab = *tabp;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 31, hi = lane >> 5;
+  const int v_unit = tab.unit_off[lane];
+  const int col_groups = (p.M + 32 * kTiles - 1) / (32 * kTiles);
+  const int64_t items = (int64_t)tab.unit_off[kStreamMaxTypes] * col_groups;
+  // a wave's items are (unit, column group) pairs, wave-strided over the launch; no barrier in this kernel
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < items; i += (int64_t)gridDim.x * 4) {
+    const Unit q = locate(tab, v_unit, (int)(i / col_groups));
+    const int col0 = (int)(i % col_groups) * (32 * kTiles);
+    const int tiles = (p.M - col0) / 32 < kTiles ? (p.M - col0) / 32 : kTiles;   // >= 1
+
+    f32x16 acc[kTiles];
+#pragma unroll
+    for (int n = 0; n < kTiles; ++n) zero(acc[n]);
+    // rows past the type's end read its last row (never stored); column tiles past the end recompute the last valid one
+    const int64_t e = li < q.left ? li : q.left - 1;
+    const float *ap = p.x + clamp_row(q.ids[e], p.num_rows) * p.ld_x + 8 * hi;
+    const uint16_t *bp[kTiles];
+#pragma unroll
+    for (int n = 0; n < kTiles; ++n) {
+      const int tc = n < tiles ? n : tiles - 1;
+      bp[n] = p.w + ((int64_t)q.t * p.M + col0 + tc * 32 + li) * p.H + 8 * hi;
+    }
+    for (int kk = 0; kk < p.H; kk += 32) {         // H % 32 == 0: two MFMA k-steps per trip
+#pragma unroll
+      for (int k0 = kk; k0 < kk + 32; k0 += 16) {
+        const typename Hf::vec a = round8<DT>(ap + k0);
+#pragma unroll
+        for (int n = 0; n < kTiles; ++n) acc[n] = Hf::mfma(a, load8<DT>(bp[n] + k0), acc[n]);
+      }
+    }
+#pragma unroll
+    for (int n = 0; n < kTiles; ++n) {
+      if (n < tiles) {
+        const int col = col0 + n * 32 + li;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = frag_row(r, hi);
+          if (row < q.left) p.msg[(q.out0 + row) * p.ld_msg + col] = act_runtime(acc[n][r], p.act);
+        }
+      }
+    }
+  }
+}
+
+template <int DT, int KS, bool INDIRECT>
+__global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
+  using Hf = Half16<DT>;
+  using vec = typename Hf::vec;
+  using half4 = __attribute__((ext_vector_type(4))) typename Hf::elem;
+  using f32x4 = __attribute__((ext_vector_type(4))) float;
+  constexpr int H = 16 * KS;
+  constexpr int LD = H + 8;              // LDS row stride in 16-bit elements
+  constexpr int RV = H / 4;              // float4 per gathered row
+  constexpr int NV = 32 * RV / 256;      // float4 per thread and unit
+  static_assert(32 * RV % 256 == 0 && (LD / 8) % 2 == 1, "panel shape");
+  __shared__ __attribute__((aligned(16))) uint16_t panel[2][32 * LD];
+
+  const StreamEdgeTable *tabp;
+  if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
+  const StreamEdgeTable &tab = *tabp;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 31, hi = lane >> 5;
+  const int v_unit = tab.unit_off[lane];
+  const int64_t total = tab.unit_off[kStreamMaxTypes];
+  // a contiguous run of the type-major unit order per workgroup: few type changes, and no table of its own to balance
+  const int u_begin = (int)(blockIdx.x * total / gridDim.x), u_end = (int)((blockIdx.x + 1) * total / gridDim.x);
+  if (u_begin >= u_end) return;          // whole workgroup: before any barrier
+  const int j = wave * 32 + li;          // this lane's output column
+  const bool active = wave * 32 < p.M;   // M < 128: the waves past the last column slice only gather
+
+  float4 stage[NV];
+  auto fetch = [&](const Unit &q) {      // the unit's gathered rows -> registers (rows past the type's end: its last row)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      const int r = v / RV, c = (v % RV) * 4;
+      const int64_t e = r < q.left ? r : q.left - 1;
+      stage[i] = *reinterpret_cast<const float4 *>(p.x + clamp_row(q.ids[e], p.num_rows) * p.ld_x + c);
+    }
+  };
+  auto park = [&](int buf) {             // registers -> rounded 16-bit panel in LDS
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      const int r = v / RV, c = (v % RV) * 4;
+      const f32x4 f = {stage[i].x, stage[i].y, stage[i].z, stage[i].w};
+      *reinterpret_cast<half4 *>(&panel[buf][r * LD + c]) = __builtin_convertvector(f, half4);
+    }
+  };
+
+  vec bw[KS];                            // columns j of W_t, all of K
+  int t_loaded = -1;
+  Unit cur = locate(tab, v_unit, u_begin);
+  fetch(cur);
+  park(0);
+  __syncthreads();
+  int buf = 0;
+  for (int u = u_begin; u < u_end; ++u) {
+    const Unit nxt = locate(tab, v_unit, u + 1 < u_end ? u + 1 : u);   // no branch around the loads: the last trip
+    fetch(nxt);                                                         // re-reads its own unit
+    if (active) {
+      if (cur.t != t_loaded) {           // wave-uniform
+        t_loaded = cur.t;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) bw[ks] = load8<DT>(p.w + ((int64_t)cur.t * p.M + j) * H + ks * 16 + 8 * hi);
+      }
+      f32x16 acc;
+      zero(acc);
+      const uint16_t *ap = &panel[buf][li * LD + 8 * hi];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) acc = Hf::mfma(*reinterpret_cast<const vec *>(ap + ks * 16), bw[ks], acc);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = frag_row(r, hi);
+        if (row < cur.left) p.msg[(cur.out0 + row) * p.ld_msg + j] = act_runtime(acc[r], p.act);
+      }
+    }
+    park(buf ^ 1);
+    __syncthreads();                     // the other buffer is complete; everyone is done reading this one
+    buf ^= 1;
+    cur = nxt;
+  }
+}
+
+bool shape_ok(int32_t state_dim, int32_t msg_dim, int32_t num_types) {
+  return state_dim > 0 && state_dim % 32 == 0 && state_dim <= 1024 && msg_dim > 0 && msg_dim % 32 == 0 &&
+         msg_dim <= 1024 && num_types >= 2 && num_types <= kStreamMaxTypes;
+}
+
+int env_int(const char *name, int fallback, int lo, int hi) {   // developer A/B knobs
+  if (const char *e = getenv(name)) {
+    const int v = atoi(e);
+    if (v >= lo && v <= hi) return v;
+  }
+  return fallback;
+}
+
+// the argument checks the two entries share; everything here answers before anything touches the device
+int check_operands(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim, const void *w, int32_t msg_dim,
+                   const float *msg, int64_t ld_msg) {
+  PTGNN_REQUIRE(x && w && msg, PTGNN_AMD_EINVAL, "edge_linear16: null pointer");
+  PTGNN_REQUIRE(num_rows > 0 && ld_x >= state_dim && ld_msg >= msg_dim, PTGNN_AMD_EINVAL,
+                "edge_linear16: num_rows must be positive, ld_x >= state_dim and ld_msg >= msg_dim");
+  PTGNN_REQUIRE(aligned16(x) && ld_x % 4 == 0 && aligned16(w) && (reinterpret_cast<uintptr_t>(msg) & 3u) == 0,
+                PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: x and w must be 16-byte aligned with ld_x %% 4 == 0 (ld_x=%lld), msg float-aligned",
+                (long long)ld_x);
+  return PTGNN_AMD_OK;
+}
+
+int check_shape(int32_t state_dim, int32_t num_types, int32_t msg_dim, int act, int dtype) {
+  PTGNN_REQUIRE(num_types > 0 && state_dim > 0 && msg_dim > 0, PTGNN_AMD_EINVAL, "edge_linear16: bad sizes");
+  PTGNN_REQUIRE(act >= 0 && act <= PTGNN_AMD_ACT_RELU, PTGNN_AMD_EINVAL, "edge_linear16: bad act");
+  PTGNN_REQUIRE(dtype_ok(dtype), PTGNN_AMD_EINVAL, "edge_linear16: dtype %d is neither PTGNN_AMD_HALF_BF16 nor _F16",
+                dtype);
+  PTGNN_REQUIRE(shape_ok(state_dim, msg_dim, num_types), PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: state_dim=%d msg_dim=%d num_types=%d: needs both widths %% 32 == 0 and <= 1024, "
+                "2 <= num_types <= %d", state_dim, msg_dim, num_types, kStreamMaxTypes);
+  return PTGNN_AMD_OK;
+}
+
+// Workgroups of a weight-stationary instance that one CU holds at once (registers and LDS decide; asked once).  The
+// launch is ONE such round: measured at the cfg3 layer shapes, any grid that needs a partly filled second round loses
+// 15 - 20 % to it (profiles/edge_inputs_notes.md).
+template <int DT, int KS, bool INDIRECT>
+int ws_resident_per_cu() {
+  static const int per_cu = [] {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT>, 256, 0) != hipSuccess || n < 1) {
+      (void)hipGetLastError();
+      n = 2;
+    }
+    return n;
+  }();
+  return per_cu;
+}
+
+// `units` < 0: unknown on the host (shared form) -- the launch is sized for the device, workgroups without units leave
+template <bool INDIRECT>
+int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
+  const int64_t cus = num_compute_units();
+  const bool ws = (p.H == 64 || p.H == 128 || p.H == 256) && p.M <= 128 && env_int("PTGNN_AMD_EDGE16_WS", 1, 0, 1) == 1;
+  if (ws) {
+    const int knob = env_int("PTGNN_AMD_EDGE16_WGS", 0, 0, 16);   // workgroups per CU; 0: one resident round
+#define PTGNN_EDGE16_WS_KS(DT, KS)                                                                   \
+  do {                                                                                               \
+    int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT>());                     \
+    if (units >= 0 && units < grid) grid = units;                                                    \
+    k_edge16_ws<DT, KS, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);                                \
+  } while (0)
+#define PTGNN_EDGE16_WS(DT)                                   \
+  do {                                                        \
+    if (p.H == 64) PTGNN_EDGE16_WS_KS(DT, 4);                 \
+    else if (p.H == 128) PTGNN_EDGE16_WS_KS(DT, 8);           \
+    else PTGNN_EDGE16_WS_KS(DT, 16);                          \
+  } while (0)
+    if (dtype == PTGNN_AMD_HALF_BF16) PTGNN_EDGE16_WS(PTGNN_AMD_HALF_BF16);
+    else PTGNN_EDGE16_WS(PTGNN_AMD_HALF_F16);
+#undef PTGNN_EDGE16_WS
+#undef PTGNN_EDGE16_WS_KS
+  } else {
+    const int col_groups = (p.M + 32 * kTiles - 1) / (32 * kTiles);
+    int64_t grid = cus * 8;
+    if (units >= 0 && (units * col_groups + 3) / 4 < grid) grid = (units * col_groups + 3) / 4;
+    if (dtype == PTGNN_AMD_HALF_BF16) k_edge16<PTGNN_AMD_HALF_BF16, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);
+    else k_edge16<PTGNN_AMD_HALF_F16, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);
+  }
+  PTGNN_LAUNCH_CHECK();
+  count_launch(INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16);
+  return PTGNN_AMD_OK;
+}
+
+}  // namespace
+}  // namespace ptgnn_amd
+
+using namespace ptgnn_amd;
+
+extern "C" int ptgnn_amd_edge_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype) {
+  return dtype_ok(dtype) && shape_ok(state_dim, msg_dim, num_types) ? 1 : 0;
+}
+
+extern "C" int ptgnn_amd_edge_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                       const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                       const void *w, int32_t num_types, int32_t msg_dim, int act, int dtype,
+                                       float *msg, int64_t ld_msg, void *stream_) {
+  if (const int rc = check_shape(state_dim, num_types, msg_dim, act, dtype)) return rc;
+  PTGNN_REQUIRE(edges_per_type, PTGNN_AMD_EINVAL, "edge_linear16: null edge counts");
+  Edge16Args p{};
+  p.tab.num_types = num_types;
+  int64_t units = 0;
+  for (int t = 0; t < num_types; ++t) {
+    const int64_t n = edges_per_type[t];
+    PTGNN_REQUIRE(n >= 0, PTGNN_AMD_EINVAL, "edge_linear16: negative edge count of type %d", t);
+    PTGNN_REQUIRE(n == 0 || (src_per_type && src_per_type[t]), PTGNN_AMD_EINVAL,
+                  "edge_linear16: null source ids of type %d", t);
+    p.tab.src[t] = n ? src_per_type[t] : nullptr;
+    p.tab.edge_off[t + 1] = p.tab.edge_off[t] + n;
+    units += (n + 31) / 32;
+    PTGNN_REQUIRE(units < ((int64_t)1 << 30), PTGNN_AMD_EUNSUPPORTED, "edge_linear16: too many 32-row units");
+    p.tab.unit_off[t + 1] = (int32_t)units;
+  }
+  if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
+  if (const int rc = check_operands(x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
+  for (int t = num_types + 1; t <= kStreamMaxTypes; ++t) {   // the kernels fetch the prefix one entry per lane and search
+    p.tab.unit_off[t] = (int32_t)units;                      // it with a ballot: entries past the last type hold the total
+    p.tab.edge_off[t] = p.tab.edge_off[num_types];
+  }
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = act; p.msg = msg; p.ld_msg = ld_msg;
+  return launch<false>(p, dtype, units, (hipStream_t)stream_);
+}
+
+extern "C" int ptgnn_amd_edge_linear16_shared(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                              const void *edge_table, const void *w, int32_t num_types,
+                                              int32_t msg_dim, int act, int dtype, float *msg, int64_t ld_msg,
+                                              void *stream_) {
+  if (const int rc = check_shape(state_dim, num_types, msg_dim, act, dtype)) return rc;
+  PTGNN_REQUIRE(edge_table, PTGNN_AMD_EINVAL, "edge_linear16: shared: null edge table");
+  if (const int rc = check_operands(x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
+  // the table's (type, source) keys are int32 (ptgnn_amd_unique_sources): no table exists beyond that
+  PTGNN_REQUIRE(num_rows * num_types < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: shared: too many (type, source) pairs (%lld rows x %d types)", (long long)num_rows,
+                num_types);
+  Edge16Args p{};
+  p.tab_dev = static_cast<const StreamEdgeTable *>(edge_table);
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = act; p.msg = msg; p.ld_msg = ld_msg;
+  return launch<true>(p, dtype, -1, (hipStream_t)stream_);
+}

@@ -28,6 +28,7 @@ static std::atomic<int64_t> g_seq_launches[PTGNN_AMD_KERNEL_SEQ_END_ - PTGNN_AMD
 static std::atomic<int64_t> g_decode_launches[PTGNN_AMD_KERNEL_DECODE_END_ - PTGNN_AMD_KERNEL_DECODE_FIRST_];
 static std::atomic<int64_t> g_beam_launches[PTGNN_AMD_KERNEL_BEAM_END_ - PTGNN_AMD_KERNEL_BEAM_FIRST_];
 static std::atomic<int64_t> g_half_launches[PTGNN_AMD_KERNEL_HALF_END_ - PTGNN_AMD_KERNEL_HALF_FIRST_];
+static std::atomic<int64_t> g_edge16_launches[PTGNN_AMD_KERNEL_EDGE16_END_ - PTGNN_AMD_KERNEL_EDGE16_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -44,6 +45,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_beam_launches[kernel_id - PTGNN_AMD_KERNEL_BEAM_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_HALF_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HALF_END_)
     return &g_half_launches[kernel_id - PTGNN_AMD_KERNEL_HALF_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_END_)
+    return &g_edge16_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -109,6 +112,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
                                                                                                     "half_gru"};
   if (kernel_id >= PTGNN_AMD_KERNEL_HALF_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HALF_END_)
     return half_names[kernel_id - PTGNN_AMD_KERNEL_HALF_FIRST_];
+  static const char *const edge16_names[PTGNN_AMD_KERNEL_EDGE16_END_ - PTGNN_AMD_KERNEL_EDGE16_FIRST_] = {
+      "edge16", "edge16_shared"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_END_)
+    return edge16_names[kernel_id - PTGNN_AMD_KERNEL_EDGE16_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

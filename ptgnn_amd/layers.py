@@ -34,9 +34,9 @@ and the aggregation on the HIP segment-reduce seam with its autograd rule.  fp16
 to fp32 on entry and the result is cast back.  No GPU path runs on a vendor BLAS or falls back to torch.
 
 Opt-in 16-bit matrix-core inputs (`ptgnn_amd/precision.py`, off by default): the GGNN layer's INFERENCE routes round the
-operands of the table-form message Linear and of the GRU cell to bf16 / fp16 and run them on csrc/half_gemm.hip.  The
-grouped per-edge GEMM of the edge form, every training route, `forward_sharded`, every other layer and the decoder stay
-fp32 under the setting (the follow-ups).
+operands of the table-form message Linear and of the GRU cell to bf16 / fp16 and run them on csrc/half_gemm.hip; with
+`edge_gemm=True` the edge form's grouped per-edge GEMM does the same on csrc/edge_gemm16.hip.  The edge-feature route's
+grouped GEMM, every training route, `forward_sharded`, every other layer and the decoder stay fp32 under every setting.
 
 Device dispatch (round 5): tensors on the CPU take `ptgnn_amd/torch_route.py` (plain torch operators, so that the
 reference's `predict.py` -- which restores and runs on "cpu" -- and a CPU `ModelTrainer` work with these layers);
@@ -188,15 +188,16 @@ def _kernel_act(act: Optional[nn.Module]) -> Optional[str]:
     return "tanh" if isinstance(act, nn.Tanh) else ("relu" if isinstance(act, nn.ReLU) else None)
 
 
-def _edge_messages(table: torch.Tensor, adjacency_lists, plan, weights):
+def _edge_messages(table: torch.Tensor, adjacency_lists, plan, weights, inputs=None, rounded=None):
     """GGNN messages of the edge form (inference) and the `col` that maps CSR slots to their rows: one row per distinct
     (edge type, source) pair of the plan where the shared-row launch applies (GraphPlan.unique_messages), else one row
-    per edge in reference order (gatedmessagepassing.py:50-61).  The aggregate has the same bits either way."""
+    per edge in reference order (gatedmessagepassing.py:50-61).  The aggregate has the same bits either way -- also
+    under 16-bit `inputs` (with `rounded`, the [T, M, H] stack of the rounded weights), which both launches follow."""
     if UNIQUE_MESSAGES and ops.edge_linear_shared_supported(table.shape[1], weights[0].shape[0], len(weights)):
         uniq = plan.unique_messages()
         if uniq is not None:
-            return ops.edge_linear_shared(table, uniq, weights), uniq.slot_row
-    return ops.edge_linear(table, adjacency_lists, weights, False), plan.perm
+            return ops.edge_linear_shared(table, uniq, weights, inputs=inputs, rounded=rounded), uniq.slot_row
+    return ops.edge_linear(table, adjacency_lists, weights, False, inputs=inputs, rounded=rounded), plan.perm
 
 
 def _feat_gemm_ok(node_states, edge_features, state_dim: int, out_dim: int, *params, shapes_only: bool = False) -> bool:
@@ -555,7 +556,8 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
     def _forward_fused(self, node_states, adjacency_lists, plan) -> torch.Tensor:
         """Inference: message table (or edge form) -> aggregation -> GRU cell, pipelined over destination-row ranges on
         large minibatches (ops.aggregate_gru).  Under a 16-bit matrix-input setting the table Linear and the GRU cell
-        take the 16-bit kernels; the grouped per-edge GEMM of the edge form stays fp32."""
+        take the 16-bit kernels; the grouped per-edge GEMM of the edge form does when the setting was made with
+        `edge_gemm=True` (both of its launch forms, so the back-off between them never changes the numerics)."""
         num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
         gru = self.__state_update
         inputs = precision.resolve(node_states)
@@ -565,7 +567,12 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             # of the plan (GraphPlan.unique_messages, built once per minibatch on the device) and the
             # aggregation reads it per edge -- same bits, fewer rows.
             weights = [l.weight for l in self.__edge_message_transformation_layers]
-            msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights)
+            edge_inputs = precision.edge_gemm_inputs(node_states)
+            w16 = None
+            if edge_inputs != torch.float32 and ops.edge_linear16_supported(H, M, len(weights), edge_inputs):
+                w16 = _scoped(self, ("edge_stack16", edge_inputs),
+                              lambda: torch.stack([w.detach() for w in weights]).to(edge_inputs))
+            msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights, inputs=edge_inputs, rounded=w16)
             tb = 0
         else:
             w = self._stacked_edge_weights()

@@ -59,8 +59,12 @@ _BEAM_FAMILY_FIRST = 384  # PTGNN_AMD_KERNEL_BEAM_FIRST_: the copying decoder's 
 _HALF_FAMILY_FIRST = 448  # PTGNN_AMD_KERNEL_HALF_FIRST_: the opt-in 16-bit-input dense blocks
 
 
+_EDGE16_FAMILY_FIRST = 512  # PTGNN_AMD_KERNEL_EDGE16_FIRST_: the opt-in 16-bit-input grouped per-edge GEMM
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
-                  sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False) -> dict:
+                  sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
+                  edge16: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -70,13 +74,14 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `heads=True` the task heads' (logit_loss, logit_loss_backward, candidate_scores, candidate_scores_backward);
     `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish);
     `decode=True` its greedy-decoding step (decode_step); `beam=True` its beam-search step (beam_step);
-    `half=True` the 16-bit-input dense blocks (half_linear, half_gru)."""
+    `half=True` the 16-bit-input dense blocks (half_linear, half_gru); `edge16=True` the 16-bit-input grouped per-edge
+    GEMM's two launch forms (edge16, edge16_shared)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
             + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()) \
             + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()) \
-            + ((_HALF_FAMILY_FIRST,) if half else ()):
+            + ((_HALF_FAMILY_FIRST,) if half else ()) + ((_EDGE16_FAMILY_FIRST,) if edge16 else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -89,7 +94,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
-    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True)
+    now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
+                        edge16=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -485,11 +491,35 @@ def edge_linear_shared_supported(state_dim: int, msg_dim: int, num_types: int) -
     return bool(_lib.load().ptgnn_amd_edge_linear_shared_supported(state_dim, msg_dim, num_types))
 
 
+def edge_linear16_supported(state_dim: int, msg_dim: int, num_types: int, dtype) -> bool:
+    """Whether the 16-bit-input grouped per-edge GEMM takes the shape (ptgnn_amd_edge_linear16_supported; no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_edge_linear16_supported(int(state_dim), int(msg_dim), int(num_types),
+                                                             HALF_IDS[dtype]))
+
+
+def _edge16_stack(ws: Sequence[torch.Tensor], dtype: torch.dtype, given: Optional[torch.Tensor]) -> torch.Tensor:
+    """The [T, M, H] stack of the per-type weights rounded to `dtype` by torch (round to nearest even), or the caller's
+    cached copy of exactly that."""
+    shape = (len(ws),) + tuple(ws[0].shape)
+    if given is None:
+        return torch.stack(list(ws)).to(dtype)          # two launches, whatever T; the rounding of w.to(dtype)
+    if given.dtype != dtype or tuple(given.shape) != shape or given.device != ws[0].device:
+        raise _lib.PtgnnAmdError(f"rounded weights must be {dtype} {shape} on {ws[0].device} "
+                                 f"(got {given.dtype} {tuple(given.shape)} on {given.device})")
+    return given.contiguous()
+
+
 def edge_linear_shared(x: torch.Tensor, uniq: UniqueMessages, weights: Sequence[torch.Tensor],
-                       act: Optional[str] = None) -> torch.Tensor:
+                       act: Optional[str] = None, inputs=None, rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
     """msg[r] = act(W_t x[unique_src[r]]) over the message rows of `uniq` (GraphPlan.unique_messages): the grouped
     per-edge GEMM of `edge_linear` with one row per distinct (edge type, source) pair; rows beyond the table's count
-    are not written.  The launch geometry comes from the device-resident table: no host synchronisation."""
+    are not written.  The launch geometry comes from the device-resident table: no host synchronisation.
+    `inputs` = torch.bfloat16 / torch.float16: the gathered rows and the weights are rounded to that type and multiplied
+    on the 16-bit matrix cores (fp32 accumulation and output) where `edge_linear16_supported` takes the shape and x has
+    16-byte aligned rows; otherwise the fp32 kernel runs, silently.  `rounded`: the caller's [T, M, H] stack of
+    `weight.to(inputs)`, to save the conversion."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
     x = _rowmajor(x)
@@ -501,11 +531,21 @@ def edge_linear_shared(x: torch.Tensor, uniq: UniqueMessages, weights: Sequence[
         if tuple(w.shape) != (M, H) or not w.is_cuda or w.dtype != torch.float32:
             raise _lib.PtgnnAmdError(f"edge_linear_shared: weight shape {tuple(w.shape)} does not match [{M}, {H}]")
     msg = torch.empty(uniq.capacity, M, dtype=torch.float32, device=x.device)
-    wp = (ctypes.c_void_p * T)(*[w.data_ptr() for w in ws])
 
     def rows():                       # resolved when the timer is summarised: the count is back by then
         r = uniq.rows(wait=True)
         return float(r if r is not None else uniq.num_edges)
+    half = _half_inputs(inputs)
+    if half is not None and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
+        w16 = _edge16_stack(ws, half, rounded)
+        with _timed("edge_linear16_shared", flops=lambda: 2.0 * rows() * H * M,
+                    bytes=lambda: 4.0 * (rows() * H + rows() * M) + 2.0 * T * M * H + 8.0 * rows()):
+            rc = lib.ptgnn_amd_edge_linear16_shared(x.data_ptr(), _ld(x), x.shape[0], H, uniq.edge_table.data_ptr(),
+                                                    w16.data_ptr(), T, M, ACT_IDS[act], HALF_IDS[half],
+                                                    msg.data_ptr(), M, _stream(msg))
+        _lib.check(rc, "ptgnn_amd_edge_linear16_shared")
+        return msg
+    wp = (ctypes.c_void_p * T)(*[w.data_ptr() for w in ws])
     with _timed("edge_linear_shared", flops=lambda: 2.0 * rows() * H * M,
                 bytes=lambda: 4.0 * (rows() * H + rows() * M + T * M * H) + 8.0 * rows()):
         rc = lib.ptgnn_amd_edge_linear_shared_f32(x.data_ptr(), _ld(x), x.shape[0], H, uniq.edge_table.data_ptr(),
@@ -1342,14 +1382,21 @@ def edge_weight_grad_masked_supported(state_dim: int, msg_dim: int) -> bool:
 def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor], use_dst: bool,
                 act: Optional[str] = None, dropout: Optional[Tuple[int, float, int]] = None,
                 mask_bits: Optional[torch.Tensor] = None,
-                edge_feats: Optional[Sequence[Optional[torch.Tensor]]] = None) -> torch.Tensor:
+                edge_feats: Optional[Sequence[Optional[torch.Tensor]]] = None, inputs=None,
+                rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
     """msg[off_t + e] = act([x[src_t[e]] ; x[dst_t[e]] (if use_dst)] W_t^T) for every edge type in one
     launch; rows in type-major message order.  weights[t] is the type's nn.Linear weight.
     `edge_feats[t]` = [E_t, F] per-edge feature rows appended to the message input (weights [M, H (+H) + F];
     gatedmessagepassing.py:57-61, mlpmessagepassing.py:96-98) -- see `_edge_linear_feat`.
     dropout = (mode, p, seed): nn.Dropout(p) on the gathered input rows (mode 1) or on the output rows
     (mode 2, the input-gradient form) with the hash mask of ptgnn_amd_edge_linear_dropout_f32; with
-    `mask_bits` (`dropout_bitmask` of the same p and seed) the streaming kernel applies the mask from its bits."""
+    `mask_bits` (`dropout_bitmask` of the same p and seed) the streaming kernel applies the mask from its bits.
+    `inputs` / `rounded`: the 16-bit matrix-core form, as `edge_linear_shared` takes them -- the plain GGNN form only:
+    with dropout, edge features or `use_dst` a 16-bit `inputs` raises."""
+    half = _half_inputs(inputs)
+    if half is not None and (use_dst or (dropout is not None and dropout[0] != 0 and dropout[1] > 0.0)
+                             or (edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats))):
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout, edge features nor a target-state half")
     if edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats):
         if dropout is not None and dropout[0] != 0 and dropout[1] > 0.0:
             raise _lib.PtgnnAmdError("edge_linear: the dropout forms take no edge features")
@@ -1372,9 +1419,17 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     dsts = [a[1].contiguous() for a in adjacency_lists]
     PtrArr, CntArr = ctypes.c_void_p * T, ctypes.c_int64 * T
     sp = PtrArr(*[s.data_ptr() if s.numel() else None for s in srcs])
+    cn = CntArr(*counts)
+    if half is not None and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
+        w16 = _edge16_stack(ws, half, rounded)
+        with _timed("edge_linear16", flops=2.0 * E * H * M, bytes=4.0 * (E * H + E * M) + 2.0 * T * M * H + 8.0 * E):
+            rc = lib.ptgnn_amd_edge_linear16(x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),
+                                             ctypes.cast(cn, ctypes.c_void_p), w16.data_ptr(), T, M, ACT_IDS[act],
+                                             HALF_IDS[half], msg.data_ptr(), M, _stream(msg))
+        _lib.check(rc, "ptgnn_amd_edge_linear16")
+        return msg[:E] if E > 0 else msg[:0]
     dp = PtrArr(*[d.data_ptr() if d.numel() else None for d in dsts])
     wp = PtrArr(*[w.data_ptr() for w in ws])
-    cn = CntArr(*counts)
     K = H * (2 if use_dst else 1)
     if dropout is not None and dropout[0] != 0 and dropout[1] > 0.0:
         if use_dst or act is not None:

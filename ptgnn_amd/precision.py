@@ -11,10 +11,25 @@ the stored states stay fp32.  That is what an `enable_amp` user of the reference
     with ptgnn_amd.matrix_inputs(torch.bfloat16): # or explicitly, for a block
         out = model(batch)
 
-What stays fp32 under the setting: every training route (anything that needs a gradient), `forward_sharded`, the
-grouped per-edge GEMM of the edge form, every other layer and the decoder.  Shapes the 16-bit kernels do not take
-(widths that are not multiples of 32) run the fp32 kernels, silently.  CPU tensors (ptgnn_amd/torch_route.py) round the
-same operands with torch, so a checkpoint behaves alike on both devices; "autocast" never touches CPU tensors.
+The grouped per-edge GEMM of the edge form (many sparse edge types: the Graph2Class batches) has a switch of its own,
+because it is the one GPU route that stayed fp32 when the setting first shipped and existing users keep their bits:
+
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, edge_gemm=True):   # also set_matrix_inputs(v, edge_gemm=True)
+        out = model(batch)
+
+With the flag the inference edge form (`GatedMessagePassingLayer._forward_fused`) rounds the gathered source states and
+the per-type weights like the table form does and runs csrc/edge_gemm16.hip, in both of its launch forms (one row per
+distinct (type, source) pair, or one per edge when the unique-row back-off fires) -- same bits either way.  Every call
+without the keyword means `edge_gemm=False`; `set_matrix_inputs(torch.float32)` resets everything, and `edge_gemm=True`
+with float32 is accepted and means fp32.
+
+What stays fp32 under every setting: every training route (anything that needs a gradient), `forward_sharded`, the
+edge-feature route's grouped GEMM, every other layer and the decoder; without `edge_gemm=True` also the grouped per-edge
+GEMM of the edge form.  Shapes the 16-bit kernels do not take (widths that are not multiples of 32; for the per-edge
+GEMM also fewer than 2 or more than 64 edge types) run the fp32 kernels, silently.  CPU tensors
+(ptgnn_amd/torch_route.py) round the same operands with torch under the dtype setting alone -- message operands
+included, so the flag changes nothing there -- and a checkpoint behaves alike on both devices; "autocast" never touches
+CPU tensors.
 
 The setting is process-wide (like `ops.set_gemm_mode`); the layers read it, `ptgnn_amd.ops` never does -- its
 `inputs=` keyword is explicit, because inside an autograd `Function.forward` grad mode is off and an op could not tell
@@ -30,6 +45,7 @@ HALF_DTYPES = (torch.bfloat16, torch.float16)
 _CHOICES = (torch.float32,) + HALF_DTYPES + ("autocast",)
 
 _setting = torch.float32
+_edge_gemm = False
 
 
 def _checked(v):
@@ -38,11 +54,17 @@ def _checked(v):
     return v
 
 
-def set_matrix_inputs(v):
-    """Set the operand type of the GGNN inference GEMMs; returns the previous setting."""
-    global _setting
-    prev, _setting = _setting, _checked(v)
+def _set(v, edge_gemm):
+    global _setting, _edge_gemm
+    prev = (_setting, _edge_gemm)
+    _setting, _edge_gemm = _checked(v), bool(edge_gemm)
     return prev
+
+
+def set_matrix_inputs(v, *, edge_gemm=False):
+    """Set the operand type of the GGNN inference GEMMs, and whether the edge form's grouped per-edge GEMM follows it;
+    returns the previous dtype setting."""
+    return _set(v, edge_gemm)[0]
 
 
 def get_matrix_inputs():
@@ -50,12 +72,12 @@ def get_matrix_inputs():
 
 
 @contextlib.contextmanager
-def matrix_inputs(v):
-    prev = set_matrix_inputs(v)
+def matrix_inputs(v, *, edge_gemm=False):
+    prev = _set(v, edge_gemm)
     try:
         yield
     finally:
-        set_matrix_inputs(prev)
+        _set(*prev)
 
 
 def resolve(tensor: torch.Tensor) -> torch.dtype:
@@ -68,3 +90,9 @@ def resolve(tensor: torch.Tensor) -> torch.dtype:
             return dt if dt in HALF_DTYPES else torch.float32
         return torch.float32
     return v
+
+
+def edge_gemm_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the edge form's grouped per-edge GEMM for a layer call on `tensor`: `resolve(tensor)` when the
+    setting was made with `edge_gemm=True`, else float32."""
+    return resolve(tensor) if _edge_gemm else torch.float32
