@@ -10,20 +10,17 @@
 // Contracts: include/ptgnn_amd.h.  The fp32 pair is ptgnn_amd_edge_linear_shared_f32 / ptgnn_amd_edge_linear_f32
 // (edge_gemm.hip, stream_gemm.hip: untouched).
 //
-// States and messages stay fp32 in HBM.  The gathered x rows are rounded to nearest even in registers (fptrunc through
-// __builtin_convertvector, what tensor.to(dtype) does; never a truncating pack); the weights arrive already rounded by
-// the host as ONE 16-bit [T, M, H] stack.
+// States and messages stay fp32 in HBM; the weights arrive already rounded by the host as ONE 16-bit [T, M, H] stack.
+// Operands, the chain, the per-wave tile and the rounded LDS panel: half16.h.
 //
 // Work unit = 32 consecutive message rows of one type (the table's `unit_off` prefix; its `wg_off` apportioning belongs
 // to the fp32 kernel and is not read).  Two kernels, chosen by H and M alone:
-//   * k_edge16_ws (H in {64, 128, 256}, M <= 128: the GGNN widths), modelled on k_half_gru_ws: a workgroup of four waves walks
-//     a contiguous run of units; wave s keeps columns [32 s, 32 s + 32) of W_t in registers (H / 16 B fragments, reloaded
-//     only when the run crosses into the next type); a unit's 32 gathered rows are loaded once, coalesced (a row is one
-//     512-byte request of 32 lanes at H = 128), rounded and parked in LDS at a row stride of (H + 8) x 2 bytes -- an odd
-//     number of 16-byte units, so the ds_read_b128 fragment reads are conflict-free; the next unit's gather is issued
-//     before the current unit's MFMAs and lands in the other LDS buffer after them: one barrier per unit.
-//   * k_edge16 (every other supported shape), modelled on k_half_linear: a wave owns a unit x 128 output columns, its
-//     lanes read their row's fragment straight from the gathered row and the weights from L2; no LDS, no barrier.
+//   * k_edge16_ws (H in {64, 128, 256}, M <= 128: the GGNN widths): a workgroup of four waves walks a contiguous run of
+//     units; wave s keeps columns [32 s, 32 s + 32) of W_t in registers (H / 16 B fragments, reloaded only when the run
+//     crosses into the next type); a unit's 32 gathered rows (a row is one 512-byte request of 32 lanes at H = 128) go
+//     through a RoundedPanel.
+//   * k_edge16 (every other supported shape): a wave owns a unit x 128 output columns as one wave_tile over the gathered
+//     rows, wave-strided over the launch.
 //
 // Row independence: in both kernels a row's K chain is one accumulator per 32-column tile, zeroed, k ascending in steps
 // of 16, on the same rounded operands -- the bits of message row r depend on x[src[r]] and W_t only, not on the launch
@@ -62,6 +59,12 @@ struct Unit {
   int t;
   GlobalIds ids;
   int64_t left, out0;
+  // The row of x that message row r of the unit gathers.  Rows past the type's end read its last row (never stored);
+  // the ids were range-checked by the plan build and are clamped anyway, so a bad id can never fault.
+  __device__ __forceinline__ const float *row(const float *x, int64_t ld_x, int64_t num_rows, int r) const {
+    const int64_t id = ids[r < left ? r : left - 1];
+    return x + (id < 0 ? 0 : (id < num_rows ? id : num_rows - 1)) * ld_x;
+  }
 };
 __device__ __forceinline__ Unit locate(const StreamEdgeTable &tab, int v_unit, int u) {
   Unit q;
@@ -74,21 +77,14 @@ __device__ __forceinline__ Unit locate(const StreamEdgeTable &tab, int v_unit, i
   return q;
 }
 
-// ids were range-checked by the plan build; clamp anyway so a bad id can never fault
-__device__ __forceinline__ int64_t clamp_row(int64_t id, int64_t num_rows) {
-  return id < 0 ? 0 : (id < num_rows ? id : num_rows - 1);
-}
-
 constexpr int kTiles = 4;   // 32-column tiles per wave of k_edge16
 
 template <int DT, bool INDIRECT>
 __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
-  using Hf = Half16<DT>;
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
   const StreamEdgeTable &tab = *tabp;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, hi = lane >> 5;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = frag_li();
   const int v_unit = tab.unit_off[lane];
   const int col_groups = (p.M + 32 * kTiles - 1) / (32 * kTiles);
   const int64_t items = (int64_t)tab.unit_off[kStreamMaxTypes] * col_groups;
@@ -99,34 +95,14 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
     const int tiles = (p.M - col0) / 32 < kTiles ? (p.M - col0) / 32 : kTiles;   // >= 1
 
     f32x16 acc[kTiles];
-#pragma unroll
-    for (int n = 0; n < kTiles; ++n) zero(acc[n]);
-    // rows past the type's end read its last row (never stored); column tiles past the end recompute the last valid one
-    const int64_t e = li < q.left ? li : q.left - 1;
-    const float *ap = p.x + clamp_row(q.ids[e], p.num_rows) * p.ld_x + 8 * hi;
-    const uint16_t *bp[kTiles];
-#pragma unroll
-    for (int n = 0; n < kTiles; ++n) {
-      const int tc = n < tiles ? n : tiles - 1;
-      bp[n] = p.w + ((int64_t)q.t * p.M + col0 + tc * 32 + li) * p.H + 8 * hi;
-    }
-    for (int kk = 0; kk < p.H; kk += 32) {         // H % 32 == 0: two MFMA k-steps per trip
-#pragma unroll
-      for (int k0 = kk; k0 < kk + 32; k0 += 16) {
-        const typename Hf::vec a = round8<DT>(ap + k0);
-#pragma unroll
-        for (int n = 0; n < kTiles; ++n) acc[n] = Hf::mfma(a, load8<DT>(bp[n] + k0), acc[n]);
-      }
-    }
+    wave_tile<DT>(q.row(p.x, p.ld_x, p.num_rows, li), p.w + (int64_t)q.t * p.M * p.H, p.H, col0, tiles, acc);
 #pragma unroll
     for (int n = 0; n < kTiles; ++n) {
       if (n < tiles) {
         const int col = col0 + n * 32 + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = frag_row(r, hi);
-          if (row < q.left) p.msg[(q.out0 + row) * p.ld_msg + col] = act_runtime(acc[n][r], p.act);
-        }
+        for_frag_rows(q.out0, q.out0 + q.left, [&](int r, int64_t row) {
+          p.msg[row * p.ld_msg + col] = act_runtime(acc[n][r], p.act);
+        });
       }
     }
   }
@@ -136,20 +112,13 @@ template <int DT, int KS, bool INDIRECT>
 __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   using Hf = Half16<DT>;
   using vec = typename Hf::vec;
-  using half4 = __attribute__((ext_vector_type(4))) typename Hf::elem;
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
   constexpr int H = 16 * KS;
-  constexpr int LD = H + 8;              // LDS row stride in 16-bit elements
-  constexpr int RV = H / 4;              // float4 per gathered row
-  constexpr int NV = 32 * RV / 256;      // float4 per thread and unit
-  static_assert(32 * RV % 256 == 0 && (LD / 8) % 2 == 1, "panel shape");
-  __shared__ __attribute__((aligned(16))) uint16_t panel[2][32 * LD];
+  RoundedPanel<DT, 32, H> panel;
 
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
   const StreamEdgeTable &tab = *tabp;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, hi = lane >> 5;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = frag_li(), hi = frag_hi();
   const int v_unit = tab.unit_off[lane];
   const int64_t total = tab.unit_off[kStreamMaxTypes];
   // a contiguous run of the type-major unit order per workgroup: few type changes, and no table of its own to balance
@@ -158,36 +127,21 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   const int j = wave * 32 + li;          // this lane's output column
   const bool active = wave * 32 < p.M;   // M < 128: the waves past the last column slice only gather
 
-  float4 stage[NV];
-  auto fetch = [&](const Unit &q) {      // the unit's gathered rows -> registers (rows past the type's end: its last row)
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = threadIdx.x + i * 256;
-      const int r = v / RV, c = (v % RV) * 4;
-      const int64_t e = r < q.left ? r : q.left - 1;
-      stage[i] = *reinterpret_cast<const float4 *>(p.x + clamp_row(q.ids[e], p.num_rows) * p.ld_x + c);
-    }
-  };
-  auto park = [&](int buf) {             // registers -> rounded 16-bit panel in LDS
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = threadIdx.x + i * 256;
-      const int r = v / RV, c = (v % RV) * 4;
-      const f32x4 f = {stage[i].x, stage[i].y, stage[i].z, stage[i].w};
-      *reinterpret_cast<half4 *>(&panel[buf][r * LD + c]) = __builtin_convertvector(f, half4);
-    }
+  // The unit's gathered rows.  Operands by value: read through a reference to `p` inside the closure, the clamp of the
+  // first gather compiles to a branch per id and the four id -> row chains of the prologue run one after the other.
+  const float *const x = p.x;
+  const int64_t ld_x = p.ld_x, num_rows = p.num_rows;
+  auto rows_of = [=](const Unit &q) {
+    return [=](int r, int c) { return q.row(x, ld_x, num_rows, r) + c; };
   };
 
   vec bw[KS];                            // columns j of W_t, all of K
   int t_loaded = -1;
   Unit cur = locate(tab, v_unit, u_begin);
-  fetch(cur);
-  park(0);
-  __syncthreads();
-  int buf = 0;
+  panel.prime(rows_of(cur));
   for (int u = u_begin; u < u_end; ++u) {
     const Unit nxt = locate(tab, v_unit, u + 1 < u_end ? u + 1 : u);   // no branch around the loads: the last trip
-    fetch(nxt);                                                         // re-reads its own unit
+    panel.fetch(rows_of(nxt));                                          // re-reads its own unit
     if (active) {
       if (cur.t != t_loaded) {           // wave-uniform
         t_loaded = cur.t;
@@ -196,18 +150,13 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
       }
       f32x16 acc;
       zero(acc);
-      const uint16_t *ap = &panel[buf][li * LD + 8 * hi];
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) acc = Hf::mfma(*reinterpret_cast<const vec *>(ap + ks * 16), bw[ks], acc);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = frag_row(r, hi);
-        if (row < cur.left) p.msg[(cur.out0 + row) * p.ld_msg + j] = act_runtime(acc[r], p.act);
-      }
+      for (int ks = 0; ks < KS; ++ks) acc = Hf::mfma(panel.frag(li, ks), bw[ks], acc);
+      for_frag_rows(cur.out0, cur.out0 + cur.left, [&](int r, int64_t row) {
+        p.msg[row * p.ld_msg + j] = act_runtime(acc[r], p.act);
+      });
     }
-    park(buf ^ 1);
-    __syncthreads();                     // the other buffer is complete; everyone is done reading this one
-    buf ^= 1;
+    panel.flip();
     cur = nxt;
   }
 }
@@ -231,8 +180,7 @@ int check_operands(const float *x, int64_t ld_x, int64_t num_rows, int32_t state
   PTGNN_REQUIRE(x && w && msg, PTGNN_AMD_EINVAL, "edge_linear16: null pointer");
   PTGNN_REQUIRE(num_rows > 0 && ld_x >= state_dim && ld_msg >= msg_dim, PTGNN_AMD_EINVAL,
                 "edge_linear16: num_rows must be positive, ld_x >= state_dim and ld_msg >= msg_dim");
-  PTGNN_REQUIRE(aligned16(x) && ld_x % 4 == 0 && aligned16(w) && (reinterpret_cast<uintptr_t>(msg) & 3u) == 0,
-                PTGNN_AMD_EUNSUPPORTED,
+  PTGNN_REQUIRE(rows16(x, ld_x) && aligned16(w) && aligned4(msg), PTGNN_AMD_EUNSUPPORTED,
                 "edge_linear16: x and w must be 16-byte aligned with ld_x %% 4 == 0 (ld_x=%lld), msg float-aligned",
                 (long long)ld_x);
   return PTGNN_AMD_OK;
@@ -272,28 +220,19 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
   const bool ws = (p.H == 64 || p.H == 128 || p.H == 256) && p.M <= 128 && env_int("PTGNN_AMD_EDGE16_WS", 1, 0, 1) == 1;
   if (ws) {
     const int knob = env_int("PTGNN_AMD_EDGE16_WGS", 0, 0, 16);   // workgroups per CU; 0: one resident round
-#define PTGNN_EDGE16_WS_KS(DT, KS)                                                                   \
-  do {                                                                                               \
-    int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT>());                     \
-    if (units >= 0 && units < grid) grid = units;                                                    \
-    k_edge16_ws<DT, KS, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);                                \
-  } while (0)
-#define PTGNN_EDGE16_WS(DT)                                   \
-  do {                                                        \
-    if (p.H == 64) PTGNN_EDGE16_WS_KS(DT, 4);                 \
-    else if (p.H == 128) PTGNN_EDGE16_WS_KS(DT, 8);           \
-    else PTGNN_EDGE16_WS_KS(DT, 16);                          \
-  } while (0)
-    if (dtype == PTGNN_AMD_HALF_BF16) PTGNN_EDGE16_WS(PTGNN_AMD_HALF_BF16);
-    else PTGNN_EDGE16_WS(PTGNN_AMD_HALF_F16);
-#undef PTGNN_EDGE16_WS
-#undef PTGNN_EDGE16_WS_KS
+    with_dtype(dtype, [&](auto dt) {
+      with_case<4, 8, 16>(p.H / 16, [&](auto ks) {
+        constexpr int DT = decltype(dt)::value, KS = decltype(ks)::value;
+        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT>());
+        if (units >= 0 && units < grid) grid = units;
+        k_edge16_ws<DT, KS, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);
+      });
+    });
   } else {
     const int col_groups = (p.M + 32 * kTiles - 1) / (32 * kTiles);
     int64_t grid = cus * 8;
     if (units >= 0 && (units * col_groups + 3) / 4 < grid) grid = (units * col_groups + 3) / 4;
-    if (dtype == PTGNN_AMD_HALF_BF16) k_edge16<PTGNN_AMD_HALF_BF16, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);
-    else k_edge16<PTGNN_AMD_HALF_F16, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);
+    with_dtype(dtype, [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p); });
   }
   PTGNN_LAUNCH_CHECK();
   count_launch(INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16);

@@ -1,11 +1,33 @@
-// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip): the MFMA of each 16-bit type, the rounding
-// fragment load, the pre-rounded weight load and the C-fragment row map (cdna_hip_programming.md section 3).
+// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip): the MFMA of each 16-bit type and its fragment
+// maps, the per-wave tile, the rounded LDS panel, the fragment epilogue, and the host's dispatch and alignment checks.
+//
+// Operands.  fp32 rows stay fp32 in HBM.  A lane's MFMA A fragment (v_mfma_f32_32x32x16_{bf16,f16}: lane l = row l & 31,
+// k = 8 (l >> 5) + j: cdna_hip_programming.md section 3) is 8 consecutive values of its row, rounded to the 16-bit type
+// in registers (fptrunc through __builtin_convertvector: round to nearest even, what tensor.to(dtype) does; never a
+// truncating pack).  The weights arrive already rounded by the host as 16-bit arrays, so a lane's B fragment (column
+// l & 31 of W^T = row l & 31 of W, the same 8 k) is one dwordx4.  Products of two 16-bit values are exact in fp32;
+// accumulation and everything after it is fp32.
+//
+// The chain.  Every kernel here computes an output element as ONE accumulator, zeroed, k ascending in steps of 16 on
+// those rounded operands; the two schemes below differ only in where the fragments come from.
+//   * wave_tile: a wave owns 32 rows x up to TILES x 32 output columns; a lane rounds its row's fragment straight from
+//     the fp32 row (two dwordx4) and reads the weights from L2.  The fragment IS the memory order: no LDS, no barrier.
+//   * RoundedPanel: a workgroup loads ROWS x KT floats ONCE, coalesced (a thread's float4s are consecutive in a row),
+//     rounds them and parks them in LDS at a row stride of (KT + 8) x 2 bytes -- an odd number of 16-byte units, so the
+//     ds_read_b128 fragment reads of 16 consecutive rows hit 64 distinct banks.  Its waves keep their weights in registers.
+//     Two buffers: the next panel's loads are issued before the current panel's MFMAs and land in the other buffer after
+//     them, one barrier per panel.
+//
+// No atomics, no inline assembly; every store is a plain C++ assignment.
 #pragma once
+#include <type_traits>
+
 #include "dense_common.h"
 
 namespace ptgnn_amd {
 namespace half16 {
 
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x8 = __attribute__((ext_vector_type(8))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
@@ -48,8 +70,24 @@ __device__ __forceinline__ void zero(f32x16 &acc) {
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 }
 
+// this lane in its wave's fragments: row (A), column (B, C) li; k offset 8 hi (A, B), row offset 4 hi (C)
+__device__ __forceinline__ int frag_li() { return threadIdx.x & 31; }
+__device__ __forceinline__ int frag_hi() { return (threadIdx.x >> 5) & 1; }
+
 // row of C-fragment register r for lane half hi (cdna_hip_programming.md section 3; dtype-independent)
 __device__ __forceinline__ int frag_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// The fragment epilogue of a tile whose first row is `row0`: fn(r, row) for each of this lane's 16 C-fragment registers
+// r whose row is below `end`.
+template <class F>
+__device__ __forceinline__ void for_frag_rows(int64_t row0, int64_t end, F &&fn) {
+  const int hi = frag_hi();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t row = row0 + frag_row(r, hi);
+    if (row < end) fn(r, row);
+  }
+}
 
 __device__ __forceinline__ float act_runtime(float v, int act) {
   if (act == PTGNN_AMD_ACT_TANH) return fast_tanh(v);
@@ -57,7 +95,105 @@ __device__ __forceinline__ float act_runtime(float v, int act) {
   return v;
 }
 
+// The per-wave tile: acc[t] = rnd(arow) . rnd(W)[col0 + 32 t + li, :]^T over all of K (K % 32 == 0: two MFMA k-steps
+// per trip).  `arow`: the fp32 row of this lane (callers clamp rows past the end onto a valid one; never stored);
+// `w`: [*, K] rounded weights; column tiles past `tiles` (>= 1) recompute the last live one.
+template <int DT, int TILES>
+__device__ __forceinline__ void wave_tile(const float *__restrict__ arow, const uint16_t *__restrict__ w, int K,
+                                          int col0, int tiles, f32x16 (&acc)[TILES]) {
+  using H = Half16<DT>;
+  const int li = frag_li(), hi = frag_hi();
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) zero(acc[t]);
+  const float *ap = arow + 8 * hi;
+  const uint16_t *bp[TILES];
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) {
+    const int tc = t < tiles ? t : tiles - 1;
+    bp[t] = w + (int64_t)(col0 + tc * 32 + li) * K + 8 * hi;
+  }
+  for (int kk = 0; kk < K; kk += 32) {
+#pragma unroll
+    for (int k0 = kk; k0 < kk + 32; k0 += 16) {
+      const typename H::vec a = round8<DT>(ap + k0);
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) acc[t] = H::mfma(a, load8<DT>(bp[t] + k0), acc[t]);
+    }
+  }
+}
+
+// The rounded panel of a 256-thread workgroup: ROWS x KT values in each of two LDS buffers.  A walk is
+//     prime(src of the first panel);
+//     per panel: fetch(src of the next panel -- on the last trip its own: no branch around the loads);
+//                MFMAs on frag(row, ks); stores; flip();
+// where src(r, c) is the address of the 4 floats at row r, columns c .. c + 3 of a panel.
+template <int DT, int ROWS, int KT>
+struct RoundedPanel {
+  using vec = typename Half16<DT>::vec;
+  using half4 = __attribute__((ext_vector_type(4))) typename Half16<DT>::elem;
+  static constexpr int LD = KT + 8;             // LDS row stride in 16-bit elements
+  static constexpr int RV = KT / 4;             // float4 per panel row
+  static constexpr int NV = ROWS * RV / 256;    // float4 per thread and panel
+  static_assert(ROWS * RV % 256 == 0 && (LD / 8) % 2 == 1, "panel shape");
+
+  float4 stage[NV];
+  int cur;
+
+  // the LDS array: static to this instantiation, allocated in every kernel that uses it
+  static __device__ __forceinline__ uint16_t *buffer(int buf) {
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2][ROWS * LD];
+    return lds[buf];
+  }
+  template <class Src>
+  __device__ __forceinline__ void fetch(Src &&src) {   // a panel's rows -> registers
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      stage[i] = *reinterpret_cast<const float4 *>(src(v / RV, (v % RV) * 4));
+    }
+  }
+  __device__ __forceinline__ void park(int buf) {      // registers -> rounded 16-bit panel in LDS
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      const f32x4 f = {stage[i].x, stage[i].y, stage[i].z, stage[i].w};
+      *reinterpret_cast<half4 *>(buffer(buf) + (v / RV) * LD + (v % RV) * 4) = __builtin_convertvector(f, half4);
+    }
+  }
+  template <class Src>
+  __device__ __forceinline__ void prime(Src &&src) {
+    fetch(src);
+    park(0);
+    __syncthreads();
+    cur = 0;
+  }
+  // this lane's A fragment of k-step ks in row `row` of the current panel
+  __device__ __forceinline__ vec frag(int row, int ks) const {
+    return *reinterpret_cast<const vec *>(buffer(cur) + row * LD + ks * 16 + 8 * frag_hi());
+  }
+  __device__ __forceinline__ void flip() {
+    park(cur ^ 1);
+    __syncthreads();                     // the other buffer is complete; everyone is done reading this one
+    cur ^= 1;
+  }
+};
+
 inline bool dtype_ok(int dtype) { return dtype == PTGNN_AMD_HALF_BF16 || dtype == PTGNN_AMD_HALF_F16; }
+
+// a float matrix the fragment loads can read: 16-byte aligned base, rows a multiple of 16 bytes apart
+inline bool rows16(const void *p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// Host dispatch of a runtime value onto template arguments: calls fn(std::integral_constant<int, V>) for the V among
+// Vs that equals v.  False: none does.
+template <int... Vs, class F>
+bool with_case(int v, F &&fn) {
+  return ((v == Vs ? (fn(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <class F>
+bool with_dtype(int dtype, F &&fn) {
+  return with_case<PTGNN_AMD_HALF_BF16, PTGNN_AMD_HALF_F16>(dtype, fn);
+}
 
 }  // namespace half16
 }  // namespace ptgnn_amd

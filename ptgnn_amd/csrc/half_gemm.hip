@@ -3,20 +3,14 @@
 //   ptgnn_amd_half_linear   : y = act(rnd(x) rnd(W)^T + b)
 //   ptgnn_amd_half_gru_cell : h' = GRUCell(a, h) with rnd(a), rnd(h), rnd(W_ih), rnd(W_hh) in the gate GEMMs
 //   ptgnn_amd_half_supported: the shape check of the two, no device needed
-// Contracts + reference lines: include/ptgnn_amd.h.
+// Contracts + reference lines: include/ptgnn_amd.h.  Operands, the chain, the per-wave tile and the rounded LDS panel:
+// half16.h.  Bias, activation, gate math and the stores are fp32.
 //
-// States stay fp32 in HBM.  A lane loads the 8 consecutive floats of its MFMA A fragment (lane l = row l & 31,
-// k = 8 (l >> 5) + j: cdna_hip_programming.md section 3) as two dwordx4 and rounds them to the 16-bit type in registers
-// (fptrunc: round to nearest even, what tensor.to(dtype) does; never a truncating pack); the weights arrive already
-// rounded by the host as 16-bit arrays, so a lane's B fragment (column l & 31 of W^T = row l & 31 of W, the same 8 k) is
-// one dwordx4.  In k_half_linear and k_half_gru neither operand goes through LDS: the fragment IS the memory order.
-// Products of two 16-bit values are exact in fp32; accumulation, bias, activation, gate math and the stores are fp32.
-//
-// One wave owns 32 rows: 32 x 128 output columns of the Linear (4 accumulators), 32 x 32 or 32 x 64 state features of the
-// GRU (4 accumulators -- r, z, i_n, h_n -- per 32 features; r and z are ONE chain over K = M + H).  A workgroup is four
-// such waves over consecutive 32-row units and the same columns, so their weight reads hit the same cache lines.
-// The GGNN widths of the GRU (M, H in {64, 128}) take k_half_gru_ws further down: weights stationary in registers, row
-// panels rounded once into LDS.  Measured: profiles/half_inputs_notes.md.
+// One wave owns 32 rows: 32 x 128 output columns of the Linear (one wave_tile of 4 accumulators), 32 x 32 or 32 x 64
+// state features of the GRU (4 accumulators -- r, z, i_n, h_n -- per 32 features; r and z are ONE chain over K = M + H).
+// A workgroup is four such waves over consecutive 32-row units and the same columns, so their weight reads hit the same
+// cache lines.  The GGNN widths of the GRU (M, H in {64, 128}) take k_half_gru_ws further down: weights stationary in
+// registers, row panels rounded once into LDS.  Measured: profiles/half_inputs_notes.md.
 //
 // Row independence: the K order of a row's chains is fixed (k ascending in steps of 16, the a phase before the h
 // phase), every lane of a row runs the same instruction stream, and the gate math is individually rounded per element
@@ -39,42 +33,24 @@ __global__ __launch_bounds__(256) void k_half_linear(const float *__restrict__ x
                                                      const uint16_t *__restrict__ w, int n_out,
                                                      const float *__restrict__ bias, int act, float *__restrict__ y,
                                                      int64_t ld_y, int col_groups) {
-  using H = Half16<DT>;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, hi = lane >> 5;
+  const int wave = threadIdx.x >> 6, li = frag_li(), hi = frag_hi();
   const int64_t row0 = ((int64_t)(blockIdx.x / col_groups) * 4 + wave) * 32;
   if (row0 >= rows) return;                       // no barrier in this kernel
   const int col0 = (int)(blockIdx.x % col_groups) * (32 * kLinTiles);
   const int tiles = (n_out - col0) / 32 < kLinTiles ? (n_out - col0) / 32 : kLinTiles;   // >= 1
 
-  f32x16 acc[kLinTiles];
-#pragma unroll
-  for (int t = 0; t < kLinTiles; ++t) zero(acc[t]);
-
-  // rows past the end read the last valid row (never stored); column tiles past the end recompute the last valid one
   int64_t arow = row0 + li;
-  arow = arow < rows ? arow : rows - 1;
-  const float *ap = x + arow * ld_x + 8 * hi;
-  const uint16_t *bp[kLinTiles];
-#pragma unroll
-  for (int t = 0; t < kLinTiles; ++t) {
-    const int tc = t < tiles ? t : tiles - 1;
-    bp[t] = w + (int64_t)(col0 + tc * 32 + li) * K + 8 * hi;
-  }
-  for (int kk = 0; kk < K; kk += 32) {           // K % 32 == 0: two MFMA k-steps per trip
-#pragma unroll
-    for (int k0 = kk; k0 < kk + 32; k0 += 16) {
-      const typename H::vec a = round8<DT>(ap + k0);
-#pragma unroll
-      for (int t = 0; t < kLinTiles; ++t) acc[t] = H::mfma(a, load8<DT>(bp[t] + k0), acc[t]);
-    }
-  }
+  arow = arow < rows ? arow : rows - 1;           // rows past the end read the last valid row, never stored
+  f32x16 acc[kLinTiles];
+  wave_tile<DT>(x + arow * ld_x, w, K, col0, tiles, acc);
 
 #pragma unroll
   for (int t = 0; t < kLinTiles; ++t) {
     if (t < tiles) {
       const int col = col0 + t * 32 + li;
       const float bv = bias ? bias[col] : 0.f;
+      // not for_frag_rows: under it the 16 row addresses are hoisted out of the tile loop (76 -> 102 VGPRs), measured
+      // 0.7 % slower at the cfg3 shape (profiles/half16_refactor_notes.md)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t row = row0 + frag_row(r, hi);
@@ -105,10 +81,9 @@ __global__ __launch_bounds__(256) void k_half_gru(const float *__restrict__ a, i
                                                   int64_t n, int M, int Hd, float *__restrict__ out, int64_t ld_out,
                                                   int col_groups) {
   using H = Half16<DT>;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, hi = lane >> 5;
+  const int wave = threadIdx.x >> 6, li = frag_li(), hi = frag_hi();
   const int64_t row0 = ((int64_t)(blockIdx.x / col_groups) * 4 + wave) * 32;
-  if (row0 >= n) return;                          // no barrier in this kernel
+  if (row0 >= n) return;                         // no barrier in this kernel
   const int j0 = (int)(blockIdx.x % col_groups) * (32 * NF);   // Hd % (32 NF) == 0: every tile is whole
 
   f32x16 acc[NF][4];   // r, z, i_n, h_n
@@ -157,6 +132,7 @@ __global__ __launch_bounds__(256) void k_half_gru(const float *__restrict__ a, i
     const int j = j0 + f * 32 + li;
     const float bir = b_ih[j], biz = b_ih[Hd + j], bin = b_ih[2 * Hd + j];
     const float bhr = b_hh[j], bhz = b_hh[Hd + j], bhn = b_hh[2 * Hd + j];
+    // not for_frag_rows: at NF = 2 this kernel sits at 160 + 96 registers, and the helper's 2 more halve its occupancy
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t row = row0 + frag_row(r, hi);
@@ -175,13 +151,10 @@ __global__ __launch_bounds__(256) void k_half_gru(const float *__restrict__ a, i
 //   * a wave keeps the weights of its 32 state features in registers for the whole launch: 3 gates x (KA + KH) fragments
 //     (192 VGPRs at M = H = 128; one wave per SIMD), loaded once;
 //   * a workgroup's four waves are the H / 32 feature slices of 32 (H = 128) or 64 (H = 64) rows, and walk the row panels
-//     of the launch workgroup-strided; a panel's [a | h] rows are loaded ONCE, coalesced (a thread's float4s are
-//     consecutive in a row), rounded to the 16-bit type and parked in LDS (row stride (M + H + 8) x 2 bytes: an odd
-//     number of 16-byte units, so the ds_read_b128 fragment reads of 16 consecutive rows hit 64 distinct banks);
-//   * the next panel's loads are issued before the current panel's MFMAs and land in the other LDS buffer after them:
-//     one barrier per panel.
+//     of the launch workgroup-strided, each panel's [a | h] rows through a RoundedPanel (half16.h).
 // Same chains as k_half_gru (k ascending, the a phase before the h phase, one accumulator per gate) and the same gate
-// math: the two kernels give the same bits, so which one runs (a function of M and H alone) is not observable.
+// math: the two kernels give the same bits, so which one runs (a function of M and H alone) is not observable
+// (tests/test_gpu_half_inputs.py holds one against the other).
 // ---------------------------------------------------------------------------------------------
 template <int DT, int KA, int KH>
 __global__ __launch_bounds__(256) void k_half_gru_ws(const float *__restrict__ a, int64_t ld_a,
@@ -193,19 +166,12 @@ __global__ __launch_bounds__(256) void k_half_gru_ws(const float *__restrict__ a
                                                      int64_t num_panels) {
   using H = Half16<DT>;
   using vec = typename H::vec;
-  using half4 = __attribute__((ext_vector_type(4))) typename H::elem;
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
-  constexpr int M = 16 * KA, Hd = 16 * KH, KS = KA + KH, KT = M + Hd;
+  constexpr int M = 16 * KA, Hd = 16 * KH, KS = KA + KH;
   constexpr int S = Hd / 32;             // feature slices = waves per row unit (2 or 4)
   constexpr int PR = 32 * (4 / S);       // rows per panel (64 or 32)
-  constexpr int LD = KT + 8;             // LDS row stride in 16-bit elements
-  constexpr int RV = KT / 4;             // float4 per panel row
-  constexpr int NV = PR * RV / 256;      // float4 per thread and panel
-  static_assert(PR * RV % 256 == 0 && (LD / 8) % 2 == 1, "panel shape");
-  __shared__ __attribute__((aligned(16))) uint16_t panel[2][PR * LD];
+  RoundedPanel<DT, PR, M + Hd> panel;
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, hi = lane >> 5;
+  const int wave = threadIdx.x >> 6, li = frag_li(), hi = frag_hi();
   const int slice = wave % S, ru = wave / S;
   const int j = slice * 32 + li;
 
@@ -221,62 +187,37 @@ __global__ __launch_bounds__(256) void k_half_gru_ws(const float *__restrict__ a
   const float bir = b_ih[j], biz = b_ih[Hd + j], bin = b_ih[2 * Hd + j];
   const float bhr = b_hh[j], bhz = b_hh[Hd + j], bhn = b_hh[2 * Hd + j];
 
-  float4 stage[NV];
-  auto fetch = [&](int64_t p) {          // panel p's [a | h] rows -> registers (rows past n: the last valid row)
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = threadIdx.x + i * 256;
-      const int r = v / RV, c = (v % RV) * 4;
+  auto rows_of = [&](int64_t p) {        // panel p's [a | h] rows (rows past n: the last valid row)
+    return [=](int r, int c) {
       int64_t row = p * PR + r;
       row = row < n ? row : n - 1;
-      const float *src = c < M ? a + row * ld_a + c : h + row * ld_h + (c - M);
-      stage[i] = *reinterpret_cast<const float4 *>(src);
-    }
-  };
-  auto park = [&](int buf) {             // registers -> rounded 16-bit panel in LDS
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = threadIdx.x + i * 256;
-      const int r = v / RV, c = (v % RV) * 4;
-      const f32x4 f = {stage[i].x, stage[i].y, stage[i].z, stage[i].w};
-      *reinterpret_cast<half4 *>(&panel[buf][r * LD + c]) = __builtin_convertvector(f, half4);
-    }
+      return c < M ? a + row * ld_a + c : h + row * ld_h + (c - M);
+    };
   };
 
   int64_t p = blockIdx.x;
   if (p >= num_panels) return;           // whole workgroup: before any barrier
-  fetch(p);
-  park(0);
-  __syncthreads();
-  int cur = 0;
+  panel.prime(rows_of(p));
   for (; p < num_panels; p += gridDim.x) {
     const int64_t next = p + gridDim.x;
-    fetch(next < num_panels ? next : p);   // no branch around the loads; the last trip re-reads its own panel
+    panel.fetch(rows_of(next < num_panels ? next : p));
 
     f32x16 acc[4];   // r, z, i_n, h_n
 #pragma unroll
     for (int g = 0; g < 4; ++g) zero(acc[g]);
-    const uint16_t *ap = &panel[cur][(ru * 32 + li) * LD + 8 * hi];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const vec av = *reinterpret_cast<const vec *>(ap + ks * 16);
+      const vec av = panel.frag(ru * 32 + li, ks);
       acc[0] = H::mfma(av, bw[0][ks], acc[0]);
       acc[1] = H::mfma(av, bw[1][ks], acc[1]);
       if (ks < KA) acc[2] = H::mfma(av, bw[2][ks], acc[2]);
       else         acc[3] = H::mfma(av, bw[2][ks], acc[3]);
     }
-    const int64_t row0 = p * PR + ru * 32;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t row = row0 + frag_row(r, hi);
-      if (row < n) {
-        const float hprev = h[row * ld_h + j];    // the UNROUNDED state
-        out[row * ld_out + j] = gru_gate(acc[0][r], acc[1][r], acc[2][r], acc[3][r], hprev, bir, biz, bin, bhr, bhz, bhn);
-      }
-    }
-    park(cur ^ 1);
-    __syncthreads();                     // the other buffer is complete; everyone is done reading this one
-    cur ^= 1;
+    for_frag_rows(p * PR + ru * 32, n, [&](int r, int64_t row) {
+      const float hprev = h[row * ld_h + j];    // the UNROUNDED state
+      out[row * ld_out + j] = gru_gate(acc[0][r], acc[1][r], acc[2][r], acc[3][r], hprev, bir, biz, bin, bhr, bhz, bhn);
+    });
+    panel.flip();
   }
 }
 
@@ -288,10 +229,6 @@ bool shape_ok(int kind, int32_t k_or_m, int32_t n_out_or_hd) {
            n_out_or_hd <= 1024;
   return false;
 }
-
-// a float matrix the fragment loads can read: 16-byte aligned base, rows a multiple of 16 bytes apart
-bool rows16(const void *p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 }  // namespace
 }  // namespace ptgnn_amd
@@ -320,12 +257,10 @@ extern "C" int ptgnn_amd_half_linear(const float *x, int64_t rows, int32_t k, in
   PTGNN_REQUIRE(blocks < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED, "half_linear: too many tiles");
   hipStream_t st = (hipStream_t)stream_;
   const uint16_t *w16 = static_cast<const uint16_t *>(w);
-  if (dtype == PTGNN_AMD_HALF_BF16)
-    k_half_linear<PTGNN_AMD_HALF_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, rows, k, ld_x, w16, n_out, bias, act, y,
-                                                                         ld_y, col_groups);
-  else
-    k_half_linear<PTGNN_AMD_HALF_F16><<<(unsigned)blocks, 256, 0, st>>>(x, rows, k, ld_x, w16, n_out, bias, act, y,
-                                                                        ld_y, col_groups);
+  with_dtype(dtype, [&](auto dt) {
+    k_half_linear<decltype(dt)::value><<<(unsigned)blocks, 256, 0, st>>>(x, rows, k, ld_x, w16, n_out, bias, act, y, ld_y,
+                                                                         col_groups);
+  });
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_HALF_LINEAR);
   return PTGNN_AMD_OK;
@@ -354,33 +289,25 @@ extern "C" int ptgnn_amd_half_gru_cell(const float *a, int64_t ld_a, const float
   PTGNN_REQUIRE(blocks < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED, "half_gru_cell: too many tiles");
   hipStream_t st = (hipStream_t)stream_;
   const uint16_t *wi = static_cast<const uint16_t *>(w_ih), *wh = static_cast<const uint16_t *>(w_hh);
-  if ((m == 64 || m == 128) && (hd == 64 || hd == 128)) {   // the GGNN widths: weight-stationary (same bits)
-    const int64_t num_panels = (n + (hd == 128 ? 31 : 63)) / (hd == 128 ? 32 : 64);
-    const int64_t cus = num_compute_units();
-    const unsigned grid = (unsigned)(num_panels < cus ? num_panels : cus);
-#define PTGNN_HALF_GRU_WS(DT, KA, KH) \
-  k_half_gru_ws<DT, KA, KH><<<grid, 256, 0, st>>>(a, ld_a, h, ld_h, wi, wh, b_ih, b_hh, n, out, ld_out, num_panels)
-#define PTGNN_HALF_GRU_WS_DT(DT)                                        \
-  do {                                                                  \
-    if (m == 64 && hd == 64) PTGNN_HALF_GRU_WS(DT, 4, 4);               \
-    else if (m == 128 && hd == 64) PTGNN_HALF_GRU_WS(DT, 8, 4);         \
-    else if (m == 64 && hd == 128) PTGNN_HALF_GRU_WS(DT, 4, 8);         \
-    else PTGNN_HALF_GRU_WS(DT, 8, 8);                                   \
-  } while (0)
-    if (dtype == PTGNN_AMD_HALF_BF16) PTGNN_HALF_GRU_WS_DT(PTGNN_AMD_HALF_BF16);
-    else PTGNN_HALF_GRU_WS_DT(PTGNN_AMD_HALF_F16);
-#undef PTGNN_HALF_GRU_WS_DT
-#undef PTGNN_HALF_GRU_WS
-    PTGNN_LAUNCH_CHECK();
-    count_launch(PTGNN_AMD_KERNEL_HALF_GRU);
-    return PTGNN_AMD_OK;
-  }
-#define PTGNN_HALF_GRU(DT, NF)                                                                                     \
-  k_half_gru<DT, NF><<<(unsigned)blocks, 256, 0, st>>>(a, ld_a, h, ld_h, wi, wh, b_ih, b_hh, n, m, hd, out, ld_out, \
-                                                       col_groups)
-  if (dtype == PTGNN_AMD_HALF_BF16) { if (nf == 2) PTGNN_HALF_GRU(PTGNN_AMD_HALF_BF16, 2); else PTGNN_HALF_GRU(PTGNN_AMD_HALF_BF16, 1); }
-  else                              { if (nf == 2) PTGNN_HALF_GRU(PTGNN_AMD_HALF_F16, 2); else PTGNN_HALF_GRU(PTGNN_AMD_HALF_F16, 1); }
-#undef PTGNN_HALF_GRU
+  const bool ws = (m == 64 || m == 128) && (hd == 64 || hd == 128);   // the GGNN widths: weight-stationary (same bits)
+  const int64_t num_panels = (n + (hd == 128 ? 31 : 63)) / (hd == 128 ? 32 : 64);
+  const int64_t cus = ws ? num_compute_units() : 0;
+  const unsigned grid = (unsigned)(num_panels < cus ? num_panels : cus);
+  with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (ws)
+      with_case<4, 8>(m / 16, [&](auto ka) {
+        with_case<4, 8>(hd / 16, [&](auto kh) {
+          k_half_gru_ws<DT, decltype(ka)::value, decltype(kh)::value><<<grid, 256, 0, st>>>(
+              a, ld_a, h, ld_h, wi, wh, b_ih, b_hh, n, out, ld_out, num_panels);
+        });
+      });
+    else
+      with_case<1, 2>(nf, [&](auto f) {
+        k_half_gru<DT, decltype(f)::value><<<(unsigned)blocks, 256, 0, st>>>(a, ld_a, h, ld_h, wi, wh, b_ih, b_hh, n, m, hd,
+                                                                             out, ld_out, col_groups);
+      });
+  });
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_HALF_GRU);
   return PTGNN_AMD_OK;

@@ -104,12 +104,12 @@ def gru_cases():
     """(m, hd) -> 300-row case; the row counts of the tests are prefixes of it.  The seeds are ones at which the two
     float64 references are at least 24 bars apart for fp16 at every row count, the single first row included (with
     other seeds a lone row sits at 17 - 21 bars, around the precondition's 20); bf16 is above 100 everywhere."""
-    seeds = {(64, 64): 9316, (128, 64): 9300, (64, 128): 9381}
+    seeds = {(64, 64): 9316, (128, 64): 9300, (64, 128): 9381, (128, 128): 9505}
     return {key: C.gru_case(300, *key, seed) for key, seed in seeds.items()}
 
 
 @DTYPES
-@pytest.mark.parametrize("m,hd", [(64, 64), (128, 64), (64, 128)])
+@pytest.mark.parametrize("m,hd", [(64, 64), (128, 64), (64, 128), (128, 128)])
 @pytest.mark.parametrize("rows", [1, 33, 300])
 def test_gru_cell_matches_float64_on_the_rounded_operands(gru_cases, dt, m, hd, rows):
     from ptgnn_amd import ops
@@ -130,6 +130,24 @@ def test_gru_cell_at_widths_outside_the_weight_stationary_kernel(dt, m, hd, rows
     got, since = _launches(lambda: ops.gru_cell(*_cuda(a, h, *params), inputs=dt))
     assert since == {"half_gru": 1}, since
     _check(got, C.gru64(a, h, *params, dt=dt), C.gru64(a, h, *params), f"gru {C.IDS[dt]} rows={rows} m={m} hd={hd}")
+
+
+@DTYPES
+@pytest.mark.parametrize("hd", [64, 128])
+def test_the_two_gru_kernels_give_the_same_bits(dt, hd):
+    """M = 64 runs the weight-stationary kernel; the same case with M padded to 96 by zero columns of `a` and W_ih runs
+    the per-wave one (96 is outside {64, 128}).  The pad's k-steps add exact zeros to the r, z and i_n accumulators after
+    the real `a` steps and before the h phase, so the chains -- and with the shared gate math the results -- are equal."""
+    from ptgnn_amd import ops
+    rows, m = 65, 64
+    a, h, w_ih, w_hh, b_ih, b_hh = _cuda(*C.gru_case(rows, m, hd, 9950 + hd))
+    a_pad = torch.cat([a, torch.zeros(rows, 32, device="cuda")], 1)
+    w_ih_pad = torch.cat([w_ih, torch.zeros(3 * hd, 32, device="cuda")], 1)
+    stationary, since = _launches(lambda: ops.gru_cell(a, h, w_ih, w_hh, b_ih, b_hh, inputs=dt))
+    assert since == {"half_gru": 1}, since
+    per_wave, since = _launches(lambda: ops.gru_cell(a_pad, h, w_ih_pad, w_hh, b_ih, b_hh, inputs=dt))
+    assert since == {"half_gru": 1}, since
+    assert torch.equal(per_wave, stationary), (C.IDS[dt], hd)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
