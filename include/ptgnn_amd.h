@@ -196,6 +196,15 @@ enum {
   PTGNN_AMD_KERNEL_EDGE16_SHARED,                           /* ptgnn_amd_edge_linear16_shared */
   PTGNN_AMD_KERNEL_EDGE16_END_
 };
+/* A tenth id range: the opt-in 16-bit-input TRAINING launches (csrc/wgrad16.hip, csrc/half_gemm.hip).  A range of its
+ * own, so the eighth range ends where it did. */
+enum {
+  PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_ = 576,
+  PTGNN_AMD_KERNEL_HALF_WGRAD = PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_, /* ptgnn_amd_linear_weight_grad16 */
+  PTGNN_AMD_KERNEL_HALF_GRU_TRAIN,                                  /* ptgnn_amd_gru_cell_train16 */
+  PTGNN_AMD_KERNEL_HALF_LINEAR_ADD,                                 /* ptgnn_amd_linear_add16 */
+  PTGNN_AMD_KERNEL_HALF_TRAIN_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1341,6 +1350,57 @@ int ptgnn_amd_half_linear(const float *x, int64_t rows, int32_t k, int64_t ld_x,
 int ptgnn_amd_half_gru_cell(const float *a, int64_t ld_a, const float *h, int64_t ld_h, const void *w_ih,
                             const void *w_hh, const float *b_ih, const float *b_hh, int64_t n, int32_t m, int32_t hd,
                             int dtype, float *out, int64_t ld_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the GGNN TRAINING step (csrc/wgrad16.hip, csrc/half_gemm.hip).
+ *
+ * Replaces: the backward of the message Linears and of the GRU cell of gatedmessagepassing.py:57-69 under the
+ *   reference trainer's `enable_amp` (trainer.py:205,221: autocast runs them in the 16-bit type forward AND backward).
+ *   OFF by default: the host's ptgnn_amd.precision setting asks for it with `training=True`.
+ *
+ * Semantics.  States, saved tensors, gradients, accumulation, bias, gate math and gate-math backward stay fp32; only
+ * GEMM operands are rounded, to nearest even as tensor.to(dtype) does -- in registers, or by torch for the weights:
+ *   Linear y = x W^T + b: forward rnd(x) rnd(W)^T + b (ptgnn_amd_half_linear); d_x = rnd(g) rnd(W)
+ *     (ptgnn_amd_half_linear on the rounded TRANSPOSED weights); d_W = rnd(g)^T rnd(x) (ptgnn_amd_linear_weight_grad16);
+ *     d_b = column sums of the UNROUNDED fp32 g.
+ *   GRU cell: forward ptgnn_amd_gru_cell_train16 = ptgnn_amd_half_gru_cell (bit-equal `out`) that also writes
+ *     gates [n, 4 hd] = r | z | n | gh_n, the fp32 values its gate math used; d_gi, d_gh, d_h from the fp32
+ *     ptgnn_amd_gru_cell_backward_gates_f32; d_a = rnd(d_gi) rnd(W_ih); d_h + rnd(d_gh) rnd(W_hh) in one launch
+ *     (ptgnn_amd_linear_add16); d_W_ih = rnd(d_gi)^T rnd(a), d_W_hh = rnd(d_gh)^T rnd(h); the bias gradients are
+ *     column sums of the fp32 d_gi, d_gh.
+ *   fp16 overflow of a rounded gradient becomes inf, as tensor.half() gives (GradScaler expects it).
+ *
+ *   ptgnn_amd_linear_weight_grad16: grad_w [n_out, k] = rnd(grad_y)^T rnd(x), x [rows, k] (ld_x), grad_y [rows, n_out]
+ *     (ld_grad_y), both fp32 and rounded in the kernel; grad_b [n_out] (nullable) = column sums of the fp32 grad_y from
+ *     the same pass.  Every workgroup writes one fp32 partial tile to `workspace`
+ *     (ptgnn_amd_wgrad16_workspace_bytes(rows, n_out, k) bytes, 16-byte aligned); a second launch adds the partials in
+ *     a fixed order.  Any row count; rows == 0 gives zeros and launches no kernel.
+ *   ptgnn_amd_wgrad16_chunk_rows(rows, n_out, k): the rows one workgroup partial covers (ceil(rows / it) partials);
+ *     needs no device; 0 for a shape the kernel does not take.
+ *   ptgnn_amd_half_supported(PTGNN_AMD_HALF_KIND_WGRAD, k, n_out, dtype): k % 32 == 0, n_out % 32 == 0, both <= 1024.
+ *     (The kind's id is 3: id 2 stays an unknown kind, as it has always answered.)
+ *   ptgnn_amd_gru_cell_train16: arguments of ptgnn_amd_half_gru_cell plus `gates` (contiguous [n, 4 hd]).  Row
+ *     independence as documented for ptgnn_amd_half_gru_cell.
+ *   ptgnn_amd_linear_add16: ptgnn_amd_half_linear plus an fp32 `addend` [rows, n_out] (ld_add) added after the
+ *     activation in the store epilogue: y = act(rnd(x) rnd(W)^T + b) + addend.
+ * x, grad_y, a, h, the weights, grad_w, grad_b and the workspace must be 16-byte aligned with ld % 4 == 0; the other
+ * outputs, the addend and the biases aligned to a float.  Error codes as ptgnn_amd_half_linear, messages starting with
+ * "linear_weight_grad16:", "gru_cell_train16:", "linear_add16:", before anything touches the device.
+ * No float atomics anywhere: two calls give the same bits.
+ * (The entries carry a "16" suffix like ptgnn_amd_edge_linear16: the ptgnn_amd_half_* prefix is a closed set of three.)
+ * ---------------------------------------------------------------------------------------- */
+enum { PTGNN_AMD_HALF_KIND_WGRAD = 3 };
+int ptgnn_amd_linear_weight_grad16(const float *x, int64_t ld_x, int32_t k, const float *grad_y, int64_t ld_grad_y,
+                                   int64_t rows, int32_t n_out, int dtype, float *grad_w,
+                                   float *grad_b /* nullable */, void *workspace, size_t workspace_bytes, void *stream);
+size_t ptgnn_amd_wgrad16_workspace_bytes(int64_t rows, int32_t n_out, int32_t k);
+int64_t ptgnn_amd_wgrad16_chunk_rows(int64_t rows, int32_t n_out, int32_t k);
+int ptgnn_amd_gru_cell_train16(const float *a, int64_t ld_a, const float *h, int64_t ld_h, const void *w_ih,
+                               const void *w_hh, const float *b_ih, const float *b_hh, int64_t n, int32_t m, int32_t hd,
+                               int dtype, float *out, int64_t ld_out, float *gates, void *stream);
+int ptgnn_amd_linear_add16(const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w, int32_t n_out,
+                           const float *bias /* nullable */, int act, int dtype, const float *addend, int64_t ld_add,
+                           float *y, int64_t ld_y, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Opt-in 16-bit matrix-core inputs for the GGNN layer's grouped per-edge GEMM (csrc/edge_gemm16.hip).

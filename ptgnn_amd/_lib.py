@@ -194,6 +194,14 @@ SIGNATURES = {
     "ptgnn_amd_half_linear": (_c.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _c.c_int, _c.c_int, _vp, _i64, _vp]),
     "ptgnn_amd_half_gru_cell": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _c.c_int, _vp,
                                            _i64, _vp]),
+    "ptgnn_amd_linear_weight_grad16": (_c.c_int, [_vp, _i64, _i32, _vp, _i64, _i64, _i32, _c.c_int, _vp, _vp, _vp,
+                                                  _c.c_size_t, _vp]),
+    "ptgnn_amd_wgrad16_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
+    "ptgnn_amd_wgrad16_chunk_rows": (_i64, [_i64, _i32, _i32]),
+    "ptgnn_amd_gru_cell_train16": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _c.c_int, _vp,
+                                              _i64, _vp, _vp]),
+    "ptgnn_amd_linear_add16": (_c.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _c.c_int, _c.c_int, _vp, _i64, _vp, _i64,
+                                          _vp]),
     "ptgnn_amd_edge_linear16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int]),
     "ptgnn_amd_edge_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int, _vp,
                                            _i64, _vp]),

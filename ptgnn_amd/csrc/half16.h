@@ -1,5 +1,6 @@
-// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip): the MFMA of each 16-bit type and its fragment
-// maps, the per-wave tile, the rounded LDS panel, the fragment epilogue, and the host's dispatch and alignment checks.
+// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip, wgrad16.hip): the MFMA of each 16-bit type and
+// its fragment maps, the per-wave tile, the rounded LDS panel (row and transposed fragments), the fragment epilogue, and
+// the host's dispatch and alignment checks.
 //
 // Operands.  fp32 rows stay fp32 in HBM.  A lane's MFMA A fragment (v_mfma_f32_32x32x16_{bf16,f16}: lane l = row l & 31,
 // k = 8 (l >> 5) + j: cdna_hip_programming.md section 3) is 8 consecutive values of its row, rounded to the 16-bit type
@@ -127,14 +128,26 @@ __device__ __forceinline__ void wave_tile(const float *__restrict__ arow, const 
 //     per panel: fetch(src of the next panel -- on the last trip its own: no branch around the loads);
 //                MFMAs on frag(row, ks); stores; flip();
 // where src(r, c) is the address of the 4 floats at row r, columns c .. c + 3 of a panel.
-template <int DT, int ROWS, int KT>
+//
+// The transposed image (wgrad16.hip: the reduction index of a weight gradient is the panel's ROW index, so a lane's
+// fragment is 8 consecutive rows of one column).  Same panel, same park; the row stride LD_ is chosen as 32 x odd
+// elements (64 bytes x odd) and the fragments come from frag_tr: two ds_read_b64_tr_b16 (cdna_hip_programming.md T10),
+// through the v4i16 builtin -- bits are bits for both 16-bit types, and the file stays free of inline assembly.  Banks
+// (section 2 rule: (a / 4) % 64, counted per 32-lane half): a half reads rows q = 0 .. 3 of one 8-row group, 64
+// contiguous bytes = 16 banks of each; with a stride of 64 x odd bytes the four rows start at banks {0, 16, 32, 48}
+// in some order: 64 distinct banks, no conflict.  (At the row image's stride, KT + 8, the same read would be 4-way.)
+// The instruction needs EXEC all ones: rows past the end of the data are ZEROS in the image (`fetch` with `live`),
+// never masked lanes, and no caller may `return` or diverge before frag_tr.
+template <int DT, int ROWS, int KT, int LD_ = KT + 8>
 struct RoundedPanel {
   using vec = typename Half16<DT>::vec;
   using half4 = __attribute__((ext_vector_type(4))) typename Half16<DT>::elem;
-  static constexpr int LD = KT + 8;             // LDS row stride in 16-bit elements
+  using i16x4 = __attribute__((ext_vector_type(4))) short;
+  using i16x8 = __attribute__((ext_vector_type(8))) short;
+  static constexpr int LD = LD_;                // LDS row stride in 16-bit elements
   static constexpr int RV = KT / 4;             // float4 per panel row
   static constexpr int NV = ROWS * RV / 256;    // float4 per thread and panel
-  static_assert(ROWS * RV % 256 == 0 && (LD / 8) % 2 == 1, "panel shape");
+  static_assert(ROWS * RV % 256 == 0 && LD >= KT && ((LD / 8) % 2 == 1 || LD % 64 == 32), "panel shape");
 
   float4 stage[NV];
   int cur;
@@ -150,6 +163,15 @@ struct RoundedPanel {
     for (int i = 0; i < NV; ++i) {
       const int v = threadIdx.x + i * 256;
       stage[i] = *reinterpret_cast<const float4 *>(src(v / RV, (v % RV) * 4));
+    }
+  }
+  template <class Src>
+  __device__ __forceinline__ void fetch(Src &&src, int live) {   // rows >= live: zeros, nothing loaded
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      stage[i] = v / RV < live ? *reinterpret_cast<const float4 *>(src(v / RV, (v % RV) * 4))
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   __device__ __forceinline__ void park(int buf) {      // registers -> rounded 16-bit panel in LDS
@@ -170,6 +192,25 @@ struct RoundedPanel {
   // this lane's A fragment of k-step ks in row `row` of the current panel
   __device__ __forceinline__ vec frag(int row, int ks) const {
     return *reinterpret_cast<const vec *>(buffer(cur) + row * LD + ks * 16 + 8 * frag_hi());
+  }
+  template <class Src>
+  __device__ __forceinline__ void prime(Src &&src, int live) {
+    fetch(src, live);
+    park(0);
+    __syncthreads();
+    cur = 0;
+  }
+  // The transposed fragment: rows row0 + 8 hi .. + 7 (row0 % 8 == 0) of column col0 + li (col0 % 32 == 0) of the
+  // current panel, rows ascending in the vector.  Per 16-lane group the instruction gathers a 4-row x 16-column block:
+  // lane 4 q + p of the group supplies the address of the block's row q, columns 4 p .. 4 p + 3, and lane i receives
+  // column i.  Groups 0, 1 are the two column halves of the rows 8 hi .. (lane half hi = 0), groups 2, 3 of hi = 1.
+  __device__ __forceinline__ vec frag_tr(int row0, int col0) const {
+    using lds_i16x4 = __attribute__((address_space(3))) i16x4;
+    const int l = threadIdx.x & 63, q = (l >> 2) & 3, p = l & 3, g = (l >> 4) & 1;
+    const uint16_t *at = buffer(cur) + (row0 + 8 * (l >> 5) + q) * LD + col0 + 16 * g + 4 * p;
+    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)at);
+    const i16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)(at + 4 * LD));
+    return __builtin_bit_cast(vec, (i16x8)__builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7));
   }
   __device__ __forceinline__ void flip() {
     park(cur ^ 1);

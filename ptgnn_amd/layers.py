@@ -36,7 +36,11 @@ to fp32 on entry and the result is cast back.  No GPU path runs on a vendor BLAS
 Opt-in 16-bit matrix-core inputs (`ptgnn_amd/precision.py`, off by default): the GGNN layer's INFERENCE routes round the
 operands of the table-form message Linear and of the GRU cell to bf16 / fp16 and run them on csrc/half_gemm.hip; with
 `edge_gemm=True` the edge form's grouped per-edge GEMM does the same on csrc/edge_gemm16.hip.  The edge-feature route's
-grouped GEMM, every training route, `forward_sharded`, every other layer and the decoder stay fp32 under every setting.
+grouped GEMM, `forward_sharded`, every other layer and the decoder stay fp32 under every setting, and so does every
+training route unless the setting was made with `training=True`: then the GRU cell at the end of every GGNN training
+route and the table-form training Linear are 16-bit autograd nodes (`dense._GruCell`, `dense._Linear` with `inputs=`:
+forward, input gradients and weight gradients on csrc/half_gemm.hip and csrc/wgrad16.hip); `_EdgeLinear`,
+`_EdgeLinearFeat` and `_general_messages` stay fp32.
 
 Device dispatch (round 5): tensors on the CPU take `ptgnn_amd/torch_route.py` (plain torch operators, so that the
 reference's `predict.py` -- which restores and runs on "cpu" -- and a CPU `ModelTrainer` work with these layers);
@@ -517,6 +521,7 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
         has_feats = _has_edge_features(self._edge_feature_dimension, edge_features)
         p = self.__dropout.p if self.training else 0.0
         ws = [l.weight for l in self.__edge_message_transformation_layers]
+        train_inputs = precision.training_inputs(node_states)   # float32 unless the setting was made with training=True
         if (not has_feats and node_states.dtype == torch.float32 and _edge_training_ok(H, M)
                 and (p > 0 or _prefer_edge_path(plan.num_edges, num_nodes, len(ws), H, M))):
             # training, edge form: grouped per-edge GEMM with the reference's per-edge input dropout
@@ -525,7 +530,8 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
         elif self._table_ok(node_states, edge_features):
             # training without per-edge dropout, few edge types: differentiable HIP GEMM nodes (ptgnn_amd/dense.py)
             # for the dense blocks, the HIP kernel (forward + backward) for the aggregation
-            agg = gather_reduce_autograd(dense.linear(node_states, torch.cat(ws, dim=0)), None, plan, M, agg_fn)
+            agg = gather_reduce_autograd(dense.linear(node_states, torch.cat(ws, dim=0), inputs=train_inputs), None, plan,
+                                         M, agg_fn)
         elif (has_feats and p == 0.0 and agg_fn in ops.REDUCE_IDS
                 and _feat_gemm_ok(node_states, edge_features, H, M, *self.parameters())):
             return self._forward_features_inference(node_states, adjacency_lists, plan, edge_features)
@@ -536,7 +542,7 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             agg = segment_reduce(edge_linear_feat_autograd(node_states, plan, ws, False, edge_features), plan, agg_fn)
         else:
             agg = segment_reduce(self._general_messages(node_states, adjacency_lists, edge_features), plan, agg_fn)
-        return dense.gru_cell(self.__state_update, agg, node_states)
+        return dense.gru_cell(self.__state_update, agg, node_states, inputs=train_inputs)
 
     def _host_matrix_inputs(self, node_states, edge_features):
         """The matrix-input setting as the CPU route applies it: fp32 states, inference only (as on the GPU)."""

@@ -62,9 +62,12 @@ _HALF_FAMILY_FIRST = 448  # PTGNN_AMD_KERNEL_HALF_FIRST_: the opt-in 16-bit-inpu
 _EDGE16_FAMILY_FIRST = 512  # PTGNN_AMD_KERNEL_EDGE16_FIRST_: the opt-in 16-bit-input grouped per-edge GEMM
 
 
+_HALF_TRAIN_FAMILY_FIRST = 576  # PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_: the opt-in 16-bit-input training launches
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
-                  edge16: bool = False) -> dict:
+                  edge16: bool = False, half_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -75,13 +78,15 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `sequence=True` the copying decoder's loss kernels (vocab_loss, vocab_loss_backward, copy_loss_finish);
     `decode=True` its greedy-decoding step (decode_step); `beam=True` its beam-search step (beam_step);
     `half=True` the 16-bit-input dense blocks (half_linear, half_gru); `edge16=True` the 16-bit-input grouped per-edge
-    GEMM's two launch forms (edge16, edge16_shared)."""
+    GEMM's two launch forms (edge16, edge16_shared); `half_training=True` the 16-bit-input training launches
+    (half_wgrad, half_gru_train, half_linear_add)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
             + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()) \
             + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()) \
-            + ((_HALF_FAMILY_FIRST,) if half else ()) + ((_EDGE16_FAMILY_FIRST,) if edge16 else ()):
+            + ((_HALF_FAMILY_FIRST,) if half else ()) + ((_EDGE16_FAMILY_FIRST,) if edge16 else ()) \
+            + ((_HALF_TRAIN_FAMILY_FIRST,) if half_training else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -95,7 +100,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
-                        edge16=True)
+                        edge16=True, half_training=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -1260,6 +1265,7 @@ def pna_aggregate_backward(messages: torch.Tensor, plan: GraphPlan, agg: torch.T
 # and an op cannot tell inference from training).
 HALF_IDS = {torch.bfloat16: 1, torch.float16: 2}     # PTGNN_AMD_HALF_BF16 / _F16
 HALF_KIND_LINEAR, HALF_KIND_GRU = 0, 1               # PTGNN_AMD_HALF_KIND_*
+HALF_KIND_WGRAD = 3                                  # PTGNN_AMD_HALF_KIND_WGRAD (id 2 stays an unknown kind)
 
 
 def half_supported(kind: int, k_or_m: int, n_out_or_hd: int, dtype) -> bool:
@@ -1330,9 +1336,12 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
 
 def linear_add(x: torch.Tensor, weight: torch.Tensor, addend: torch.Tensor, bias: Optional[torch.Tensor] = None,
-               act: Optional[str] = None) -> torch.Tensor:
+               act: Optional[str] = None, inputs=None, rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(x W^T + b) + addend.  One launch where the streaming GEMM takes the shape (the add rides its store epilogue:
-    ptgnn_amd_linear_add_f32), else the GEMM followed by torch's add -- the same sum either way."""
+    ptgnn_amd_linear_add_f32), else the GEMM followed by torch's add -- the same sum either way.
+    `inputs` / `rounded`: as `linear` -- one launch of the 16-bit Linear with the fp32 addend in its store epilogue
+    (ptgnn_amd_linear_add16) where `half_supported` takes the shape and x has 16-byte aligned rows; otherwise the fp32
+    route, silently."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
     _require_cuda_f32("weight", weight)
@@ -1346,6 +1355,17 @@ def linear_add(x: torch.Tensor, weight: torch.Tensor, addend: torch.Tensor, bias
     out = torch.empty(rows, n_out, dtype=torch.float32, device=x.device)
     if bias is not None:
         bias = bias.contiguous()
+    half = _half_inputs(inputs)
+    if half is not None and half_supported(HALF_KIND_LINEAR, k, n_out, half) and _half_rows_ok(x):
+        w16 = _rounded_weight(weight, half, rounded)
+        with _timed("half_linear_add", flops=2.0 * rows * k * n_out,
+                    bytes=4.0 * rows * (k + 2 * n_out) + 2.0 * n_out * k):
+            rc = lib.ptgnn_amd_linear_add16(x.data_ptr(), rows, k, _ld(x), w16.data_ptr(), n_out,
+                                            bias.data_ptr() if bias is not None else None, ACT_IDS[act],
+                                            HALF_IDS[half], addend.data_ptr(), _ld(addend), out.data_ptr(), _ld(out),
+                                            _stream(out))
+        _lib.check(rc, "ptgnn_amd_linear_add16")
+        return out
     with _timed("linear", flops=2.0 * rows * k * n_out, bytes=4.0 * (rows * k + n_out * k + 2 * rows * n_out)):
         rc = lib.ptgnn_amd_linear_add_f32(x.data_ptr(), rows, k, _ld(x), weight.data_ptr(), n_out,
                                           bias.data_ptr() if bias is not None else None, ACT_IDS[act],
@@ -1593,6 +1613,48 @@ def linear_weight_grad(x: torch.Tensor, grad_y: torch.Tensor, want_bias: bool = 
     return (grad_w, grad_b) if want_bias else grad_w
 
 
+def half_wgrad_chunk_rows(rows: int, n_out: int, k: int) -> int:
+    """Rows one workgroup partial of `half_linear_weight_grad` covers (ptgnn_amd_wgrad16_chunk_rows; needs no device);
+    0 for a shape the 16-bit kernel does not take."""
+    return int(_lib.load().ptgnn_amd_wgrad16_chunk_rows(int(rows), int(n_out), int(k)))
+
+
+def half_linear_weight_grad(x: torch.Tensor, grad_y: torch.Tensor, dtype, want_bias: bool = False):
+    """grad_w [n_out, k] = rnd(grad_y)^T . rnd(x) with both fp32 operands rounded to `dtype` (torch.bfloat16 /
+    torch.float16) in the kernel, on the 16-bit matrix cores with fp32 accumulation (csrc/wgrad16.hip: deterministic
+    two-stage reduction); with `want_bias` also grad_b [n_out] = column sums of the UNROUNDED fp32 grad_y from the same
+    pass -> (grad_w, grad_b).  Where `half_supported(HALF_KIND_WGRAD, ...)` refuses the widths, or a row is not 16-byte
+    aligned, or `dtype` is None / float32: `linear_weight_grad` on the unrounded operands, silently."""
+    lib = _lib.load()
+    _require_cuda_f32("x", x)
+    _require_cuda_f32("grad_y", grad_y)
+    x, grad_y = _rowmajor(x), _rowmajor(grad_y)
+    rows, k = x.shape
+    n_out = grad_y.shape[1]
+    if grad_y.shape[0] != rows:
+        raise _lib.PtgnnAmdError("half_linear_weight_grad: x and grad_y row counts differ")
+    half = _half_inputs(dtype)
+    if half is None or not half_supported(HALF_KIND_WGRAD, k, n_out, half) or not (_half_rows_ok(x)
+                                                                                   and _half_rows_ok(grad_y)):
+        return linear_weight_grad(x, grad_y, want_bias=want_bias)
+    if rows == 0:
+        gw = torch.zeros(n_out, k, dtype=torch.float32, device=x.device)
+        return (gw, torch.zeros(n_out, dtype=torch.float32, device=x.device)) if want_bias else gw
+    grad_w = torch.empty(n_out, k, dtype=torch.float32, device=x.device)
+    grad_b = torch.empty(n_out, dtype=torch.float32, device=x.device) if want_bias else None
+    ws_bytes = lib.ptgnn_amd_wgrad16_workspace_bytes(rows, n_out, k)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    # roofline bytes: the fp32 operand rows once, the result, and the partial tiles written and read once
+    with _timed("half_linear_weight_grad", flops=2.0 * rows * k * n_out,
+                bytes=4.0 * (rows * k + rows * n_out + n_out * k) + 2.0 * ws_bytes):
+        rc = lib.ptgnn_amd_linear_weight_grad16(x.data_ptr(), _ld(x), k, grad_y.data_ptr(), _ld(grad_y), rows, n_out,
+                                                HALF_IDS[half], grad_w.data_ptr(),
+                                                grad_b.data_ptr() if want_bias else None, ws.data_ptr(), ws_bytes,
+                                                _stream(grad_w))
+    _lib.check(rc, "ptgnn_amd_linear_weight_grad16")
+    return (grad_w, grad_b) if want_bias else grad_w
+
+
 def segment_spread(grad: torch.Tensor, arg: Optional[torch.Tensor], plan: GraphPlan) -> torch.Tensor:
     """Backward of `segment_reduce` w.r.t. the messages: [N, D] row gradients -> [E, D] in message order
     (max/min: only the recorded winner slot of each (row, column) receives the gradient)."""
@@ -1779,8 +1841,10 @@ def aggregate_gru(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
     return out
 
 
-def gru_cell_train(a: torch.Tensor, h: torch.Tensor, w_ih, w_hh, b_ih, b_hh):
-    """Fused GRU cell that also returns the gates the backward needs: (h', gates [n, 4*hd] = r|z|n|gh_n)."""
+def gru_cell_train(a: torch.Tensor, h: torch.Tensor, w_ih, w_hh, b_ih, b_hh, inputs=None, rounded=None):
+    """Fused GRU cell that also returns the gates the backward needs: (h', gates [n, 4*hd] = r|z|n|gh_n).
+    `inputs` / `rounded`: as `gru_cell` -- the 16-bit cell in its training form (ptgnn_amd_gru_cell_train16): h' has
+    the bits of `gru_cell(..., inputs=inputs)`, gates holds the fp32 values its gate math used."""
     lib = _lib.load()
     _require_cuda_f32("a", a)
     _require_cuda_f32("h", h)
@@ -1789,6 +1853,18 @@ def gru_cell_train(a: torch.Tensor, h: torch.Tensor, w_ih, w_hh, b_ih, b_hh):
     hd = h.shape[1]
     out = torch.empty(n, hd, dtype=torch.float32, device=a.device)
     gates = torch.empty(n, 4 * hd, dtype=torch.float32, device=a.device)
+    half = _half_inputs(inputs)
+    if half is not None and half_supported(HALF_KIND_GRU, m, hd, half) and _half_rows_ok(a) and _half_rows_ok(h):
+        given = rounded if rounded is not None else (None, None)
+        wi16, wh16 = _rounded_weight(w_ih, half, given[0]), _rounded_weight(w_hh, half, given[1])
+        with _timed("half_gru_cell_train", flops=2.0 * n * 3 * hd * (m + hd),
+                    bytes=4.0 * n * (m + 2 * hd + 4 * hd) + 6.0 * hd * (m + hd)):
+            rc = lib.ptgnn_amd_gru_cell_train16(a.data_ptr(), _ld(a), h.data_ptr(), _ld(h), wi16.data_ptr(),
+                                                wh16.data_ptr(), b_ih.contiguous().data_ptr(),
+                                                b_hh.contiguous().data_ptr(), n, m, hd, HALF_IDS[half], out.data_ptr(),
+                                                _ld(out), gates.data_ptr(), _stream(out))
+        _lib.check(rc, "ptgnn_amd_gru_cell_train16")
+        return out, gates
     with _timed("gru_cell", flops=2.0 * n * 3 * hd * (m + hd),
                 bytes=4.0 * (n * (m + 2 * hd + 4 * hd) + 3 * hd * (m + hd))):
         rc = lib.ptgnn_amd_gru_cell_train_f32(a.data_ptr(), _ld(a), h.data_ptr(), _ld(h),

@@ -1,7 +1,8 @@
 """Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks.
 
 The default is `torch.float32`: every dense block runs the exact-fp32 MFMA kernels, bit for bit as without this module.
-With `torch.bfloat16` / `torch.float16` the INFERENCE routes of `GatedMessagePassingLayer` round the operands of the
+With `torch.bfloat16` / `torch.float16` the INFERENCE routes of `GatedMessagePassingLayer` (and, with `training=True`,
+its TRAINING routes: below) round the operands of the
 table-form message Linear and of the GRU cell's gate GEMMs to that type (round to nearest even, like `tensor.to(dtype)`)
 and multiply them on the 16-bit matrix cores (csrc/half_gemm.hip); accumulation, bias, gate math, the aggregation and
 the stored states stay fp32.  That is what an `enable_amp` user of the reference trainer gets from autocast
@@ -23,9 +24,27 @@ distinct (type, source) pair, or one per edge when the unique-row back-off fires
 without the keyword means `edge_gemm=False`; `set_matrix_inputs(torch.float32)` resets everything, and `edge_gemm=True`
 with float32 is accepted and means fp32.
 
-What stays fp32 under every setting: every training route (anything that needs a gradient), `forward_sharded`, the
-edge-feature route's grouped GEMM, every other layer and the decoder; without `edge_gemm=True` also the grouped per-edge
-GEMM of the edge form.  Shapes the 16-bit kernels do not take (widths that are not multiples of 32; for the per-edge
+Training has a switch of its own too, for the same reason (`matrix_inputs(torch.bfloat16)` while training is pinned to
+fp32 bits):
+
+    ptgnn_amd.set_matrix_inputs("autocast", training=True)          # next to enable_amp: the training loop follows too
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, training=True):
+        loss = model(batch); loss.backward()
+
+With the flag the GRU cell at the end of every GGNN training route and the message Linear of the table-form training
+route become 16-bit autograd nodes (ptgnn_amd/dense.py): the forward GEMMs, the input-gradient GEMMs and the
+weight-gradient GEMMs (csrc/wgrad16.hip) round their operands -- activations and incoming gradients in registers, the
+weights by torch -- while states, saved tensors, gradients, accumulation, bias, bias gradients (column sums of the
+unrounded fp32 gradient), gate math and gate-math backward stay fp32.  fp16 overflow of a rounded gradient becomes inf,
+as `tensor.half()` gives and `GradScaler` expects.  Every call without the keyword means `training=False`;
+`set_matrix_inputs(torch.float32)` resets it, and `training=True` with float32 is accepted and means fp32.  The forward
+of a training call under the flag has the bits of the inference route under the same setting.
+
+What stays fp32 under every setting: without `training=True` every training route (anything that needs a gradient);
+with it still the edge-form and edge-feature training GEMMs (`_EdgeLinear`, `_EdgeLinearFeat`), `_general_messages`
+and `forward_sharded`, MLP-MP, EGC and the attention layers, the reducers, the heads and the decoder; CPU tensors in
+training (the torch route rounds nothing where a gradient is needed); the edge-feature route's grouped GEMM; without
+`edge_gemm=True` also the grouped per-edge GEMM of the edge form.  Shapes the 16-bit kernels do not take (widths that are not multiples of 32; for the per-edge
 GEMM also fewer than 2 or more than 64 edge types) run the fp32 kernels, silently.  CPU tensors
 (ptgnn_amd/torch_route.py) round the same operands with torch under the dtype setting alone -- message operands
 included, so the flag changes nothing there -- and a checkpoint behaves alike on both devices; "autocast" never touches
@@ -46,6 +65,7 @@ _CHOICES = (torch.float32,) + HALF_DTYPES + ("autocast",)
 
 _setting = torch.float32
 _edge_gemm = False
+_training = False
 
 
 def _checked(v):
@@ -54,17 +74,17 @@ def _checked(v):
     return v
 
 
-def _set(v, edge_gemm):
-    global _setting, _edge_gemm
-    prev = (_setting, _edge_gemm)
-    _setting, _edge_gemm = _checked(v), bool(edge_gemm)
+def _set(v, edge_gemm, training=False):
+    global _setting, _edge_gemm, _training
+    prev = (_setting, _edge_gemm, _training)
+    _setting, _edge_gemm, _training = _checked(v), bool(edge_gemm), bool(training)
     return prev
 
 
-def set_matrix_inputs(v, *, edge_gemm=False):
-    """Set the operand type of the GGNN inference GEMMs, and whether the edge form's grouped per-edge GEMM follows it;
-    returns the previous dtype setting."""
-    return _set(v, edge_gemm)[0]
+def set_matrix_inputs(v, *, edge_gemm=False, training=False):
+    """Set the operand type of the GGNN inference GEMMs, whether the edge form's grouped per-edge GEMM follows it, and
+    whether the GGNN training routes do; returns the previous dtype setting."""
+    return _set(v, edge_gemm, training)[0]
 
 
 def get_matrix_inputs():
@@ -72,8 +92,8 @@ def get_matrix_inputs():
 
 
 @contextlib.contextmanager
-def matrix_inputs(v, *, edge_gemm=False):
-    prev = _set(v, edge_gemm)
+def matrix_inputs(v, *, edge_gemm=False, training=False):
+    prev = _set(v, edge_gemm, training)
     try:
         yield
     finally:
@@ -96,3 +116,9 @@ def edge_gemm_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the edge form's grouped per-edge GEMM for a layer call on `tensor`: `resolve(tensor)` when the
     setting was made with `edge_gemm=True`, else float32."""
     return resolve(tensor) if _edge_gemm else torch.float32
+
+
+def training_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the GGNN training routes' 16-bit autograd nodes for a layer call on `tensor`: `resolve(tensor)` when
+    the setting was made with `training=True` and the tensor is on a GPU, else float32."""
+    return resolve(tensor) if _training and tensor.is_cuda else torch.float32
