@@ -205,6 +205,13 @@ enum {
   PTGNN_AMD_KERNEL_HALF_LINEAR_ADD,                                 /* ptgnn_amd_linear_add16 */
   PTGNN_AMD_KERNEL_HALF_TRAIN_END_
 };
+/* An eleventh id range: the 16-bit-input grouped per-edge GEMM WITH a target-state half (csrc/edge_gemm16.hip: the MLP-MP
+ * message Linear).  A range of its own, so the ninth range ends where it did. */
+enum {
+  PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_ = 640,
+  PTGNN_AMD_KERNEL_EDGE16_DST = PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_, /* ptgnn_amd_edge_dst_linear16 */
+  PTGNN_AMD_KERNEL_EDGE16_DST_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1437,6 +1444,39 @@ int ptgnn_amd_edge_linear16(const float *x, int64_t ld_x, int64_t num_rows, int3
 int ptgnn_amd_edge_linear16_shared(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
                                    const void *edge_table, const void *w, int32_t num_types, int32_t msg_dim, int act,
                                    int dtype, float *msg, int64_t ld_msg, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the MLP-MP layer's grouped per-edge GEMM: the form WITH a target-state half
+ * (csrc/edge_gemm16.hip; the same two kernels as ptgnn_amd_edge_linear16, with a second id list per unit).
+ *
+ * Replaces: the single-Linear, bias-free edge transforms of mlpmessagepassing.py:88-98 under autocast
+ *   (`use_target_state_as_message_input=True`, no edge features), where the minibatch takes the edge form
+ *   (ptgnn_amd_edge_linear_f32 with dst_per_type is the fp32 launch and stays as it is).  OFF by default: the host's
+ *   ptgnn_amd.precision setting asks for it with `mlp=True`.  Without a target-state half the layer calls
+ *   ptgnn_amd_edge_linear16.
+ *
+ *   msg[r] = act( rnd(x[src[r]]) rnd(W_t[:, :H])^T + rnd(x[dst[r]]) rnd(W_t[:, H:2H])^T )      (H = state_dim)
+ *   for every message row r of edge type t, one row per edge in type-major order; no bias.  x, the ids, the counts, msg,
+ *   act and dtype as ptgnn_amd_edge_linear16 takes them, plus dst_per_type (a HOST array of device id pointers like
+ *   src_per_type); both id lists are clamped into [0, num_rows).  w = ONE 16-bit [num_types, msg_dim, 2 state_dim] stack
+ *   ALREADY rounded by the host.  No edges: no launch, PTGNN_AMD_OK.  There is no shared-row form: with a target half a
+ *   message row belongs to one edge.
+ *   ptgnn_amd_edge_dst_linear16_supported(state_dim, msg_dim, num_types, dtype): 1 when the kernels take the shape, else
+ *     0; needs no device.  state_dim % 32 == 0, msg_dim % 32 == 0, both <= 1024, 2 <= num_types <= 64.
+ * Alignment and error codes as ptgnn_amd_edge_linear16; every message starts "edge_linear16: dst:" and answers before
+ * anything touches the device.
+ * Row independence: a row's K chain is one accumulator per 32-column tile, zeroed, k ascending in steps of 16 over the
+ * source half and then over the target half; the bits of message row r depend on x[src[r]], x[dst[r]] and W_t only --
+ * not on the kernel, the row's position in its 32-row unit, the number of rows or the workgroup count.  Small magnitudes
+ * and fp16 overflow: as ptgnn_amd_half_linear.  No atomics: two calls give the same bits.
+ * (The names put "dst" before "linear16": the ptgnn_amd_edge_linear16* prefix is a closed set of three, and the ABI
+ * version stays -- the entries are additive, like every 16-bit entry before them.)
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_edge_dst_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype);
+int ptgnn_amd_edge_dst_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
+                                const int64_t *edges_per_type, const void *w, int32_t num_types, int32_t msg_dim,
+                                int act, int dtype, float *msg, int64_t ld_msg, void *stream);
 
 #pragma GCC visibility pop
 

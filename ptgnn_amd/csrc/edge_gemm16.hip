@@ -7,6 +7,12 @@
 //   ptgnn_amd_edge_linear16_shared : one row per distinct (type, source) pair; the geometry is the device-resident
 //                                    StreamEdgeTable that ptgnn_amd_unique_sources wrote (no host synchronisation)
 //   ptgnn_amd_edge_linear16        : one row per edge in type-major order, from host arrays of per-type `src` pointers
+// and, for the MLP-MP layer's message Linear (mlpmessagepassing.py:88-98), the per-edge form WITH a target-state half,
+//   ptgnn_amd_edge_dst_linear16    : msg[r, :] = act( rnd(X[src[r]]) . rnd(W_t[:, :H])^T + rnd(X[dst[r]]) . rnd(W_t[:, H:])^T )
+// over the same two kernels (template flag DST): the unit carries a second id list, W_t is [M, 2 H], and the chain runs
+// over the source half and then over the target half into the same accumulators.  k_edge16_ws takes it at 2 H in
+// {128, 256} (its KS = 8 and 16 register budgets; the panel row is [x[src] | x[dst]]), k_edge16 everywhere else.  There
+// is no shared-row form: with a target half a message row belongs to one edge.
 // Contracts: include/ptgnn_amd.h.  The fp32 pair is ptgnn_amd_edge_linear_shared_f32 / ptgnn_amd_edge_linear_f32
 // (edge_gemm.hip, stream_gemm.hip: untouched).
 //
@@ -57,15 +63,23 @@ using GlobalIds = const __attribute__((address_space(1))) int64_t *;
 // first message row.  `v_unit` = unit_off[lane] (entries past the last type hold the total): one ballot finds the type.
 struct Unit {
   int t;
-  GlobalIds ids;
+  GlobalIds ids, dst_ids;            // dst_ids: the target ids of the same rows (the forms with a target-state half only)
   int64_t left, out0;
   // The row of x that message row r of the unit gathers.  Rows past the type's end read its last row (never stored);
   // the ids were range-checked by the plan build and are clamped anyway, so a bad id can never fault.
-  __device__ __forceinline__ const float *row(const float *x, int64_t ld_x, int64_t num_rows, int r) const {
-    const int64_t id = ids[r < left ? r : left - 1];
+  __device__ __forceinline__ const float *row_of(GlobalIds list, const float *x, int64_t ld_x, int64_t num_rows,
+                                                 int r) const {
+    const int64_t id = list[r < left ? r : left - 1];
     return x + (id < 0 ? 0 : (id < num_rows ? id : num_rows - 1)) * ld_x;
   }
+  __device__ __forceinline__ const float *row(const float *x, int64_t ld_x, int64_t num_rows, int r) const {
+    return row_of(ids, x, ld_x, num_rows, r);
+  }
+  __device__ __forceinline__ const float *dst_row(const float *x, int64_t ld_x, int64_t num_rows, int r) const {
+    return row_of(dst_ids, x, ld_x, num_rows, r);
+  }
 };
+template <bool DST = false>
 __device__ __forceinline__ Unit locate(const StreamEdgeTable &tab, int v_unit, int u) {
   Unit q;
   q.t = __popcll(__ballot(v_unit <= u)) - 1;          // last type whose first unit is <= u: the one that owns u
@@ -73,13 +87,16 @@ __device__ __forceinline__ Unit locate(const StreamEdgeTable &tab, int v_unit, i
   const int64_t type_row0 = tab.edge_off[q.t];
   q.left = tab.edge_off[q.t + 1] - type_row0 - row0;
   q.ids = (GlobalIds)tab.src[q.t] + row0;
+  if constexpr (DST) q.dst_ids = (GlobalIds)tab.dst[q.t] + row0;
   q.out0 = type_row0 + row0;
   return q;
 }
 
 constexpr int kTiles = 4;   // 32-column tiles per wave of k_edge16
 
-template <int DT, bool INDIRECT>
+// DST (both kernels): the message input is [x[src] | x[dst]] and W_t is [M, 2 H] -- one chain over the source half, then
+// over the target half, into the same accumulators.
+template <int DT, bool INDIRECT, bool DST = false>
 __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
@@ -90,12 +107,20 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   const int64_t items = (int64_t)tab.unit_off[kStreamMaxTypes] * col_groups;
   // a wave's items are (unit, column group) pairs, wave-strided over the launch; no barrier in this kernel
   for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < items; i += (int64_t)gridDim.x * 4) {
-    const Unit q = locate(tab, v_unit, (int)(i / col_groups));
+    const Unit q = locate<DST>(tab, v_unit, (int)(i / col_groups));
     const int col0 = (int)(i % col_groups) * (32 * kTiles);
     const int tiles = (p.M - col0) / 32 < kTiles ? (p.M - col0) / 32 : kTiles;   // >= 1
 
     f32x16 acc[kTiles];
-    wave_tile<DT>(q.row(p.x, p.ld_x, p.num_rows, li), p.w + (int64_t)q.t * p.M * p.H, p.H, col0, tiles, acc);
+    if constexpr (DST) {
+      const uint16_t *w = p.w + (int64_t)q.t * p.M * (2 * p.H);
+#pragma unroll
+      for (int n = 0; n < kTiles; ++n) zero(acc[n]);
+      wave_tile_more<DT>(q.row(p.x, p.ld_x, p.num_rows, li), w, 2 * p.H, p.H, col0, tiles, acc);
+      wave_tile_more<DT>(q.dst_row(p.x, p.ld_x, p.num_rows, li), w + p.H, 2 * p.H, p.H, col0, tiles, acc);
+    } else {
+      wave_tile<DT>(q.row(p.x, p.ld_x, p.num_rows, li), p.w + (int64_t)q.t * p.M * p.H, p.H, col0, tiles, acc);
+    }
 #pragma unroll
     for (int n = 0; n < kTiles; ++n) {
       if (n < tiles) {
@@ -108,11 +133,11 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   }
 }
 
-template <int DT, int KS, bool INDIRECT>
+template <int DT, int KS, bool INDIRECT, bool DST = false>
 __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   using Hf = Half16<DT>;
   using vec = typename Hf::vec;
-  constexpr int H = 16 * KS;
+  constexpr int H = 16 * KS;             // the K of the chain = the panel's width; DST: 2 x state_dim
   RoundedPanel<DT, 32, H> panel;
 
   const StreamEdgeTable *tabp;
@@ -132,15 +157,20 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   const float *const x = p.x;
   const int64_t ld_x = p.ld_x, num_rows = p.num_rows;
   auto rows_of = [=](const Unit &q) {
-    return [=](int r, int c) { return q.row(x, ld_x, num_rows, r) + c; };
+    return [=](int r, int c) {
+      if constexpr (DST)                 // a panel row is [x[src] | x[dst]]; a float4 never straddles (H / 2 % 4 == 0)
+        return c < H / 2 ? q.row(x, ld_x, num_rows, r) + c : q.dst_row(x, ld_x, num_rows, r) + (c - H / 2);
+      else
+        return q.row(x, ld_x, num_rows, r) + c;
+    };
   };
 
   vec bw[KS];                            // columns j of W_t, all of K
   int t_loaded = -1;
-  Unit cur = locate(tab, v_unit, u_begin);
+  Unit cur = locate<DST>(tab, v_unit, u_begin);
   panel.prime(rows_of(cur));
   for (int u = u_begin; u < u_end; ++u) {
-    const Unit nxt = locate(tab, v_unit, u + 1 < u_end ? u + 1 : u);   // no branch around the loads: the last trip
+    const Unit nxt = locate<DST>(tab, v_unit, u + 1 < u_end ? u + 1 : u);   // no branch around the loads: the last trip
     panel.fetch(rows_of(nxt));                                          // re-reads its own unit
     if (active) {
       if (cur.t != t_loaded) {           // wave-uniform
@@ -174,37 +204,67 @@ int env_int(const char *name, int fallback, int lo, int hi) {   // developer A/B
   return fallback;
 }
 
-// the argument checks the two entries share; everything here answers before anything touches the device
-int check_operands(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim, const void *w, int32_t msg_dim,
-                   const float *msg, int64_t ld_msg) {
-  PTGNN_REQUIRE(x && w && msg, PTGNN_AMD_EINVAL, "edge_linear16: null pointer");
+// the argument checks the entries share; everything here answers before anything touches the device.  `who`: "" or
+// " dst:" -- the messages of the entry with a target-state half start "edge_linear16: dst:"
+int check_operands(const char *who, const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim, const void *w,
+                   int32_t msg_dim, const float *msg, int64_t ld_msg) {
+  PTGNN_REQUIRE(x && w && msg, PTGNN_AMD_EINVAL, "edge_linear16:%s null pointer", who);
   PTGNN_REQUIRE(num_rows > 0 && ld_x >= state_dim && ld_msg >= msg_dim, PTGNN_AMD_EINVAL,
-                "edge_linear16: num_rows must be positive, ld_x >= state_dim and ld_msg >= msg_dim");
+                "edge_linear16:%s num_rows must be positive, ld_x >= state_dim and ld_msg >= msg_dim", who);
   PTGNN_REQUIRE(rows16(x, ld_x) && aligned16(w) && aligned4(msg), PTGNN_AMD_EUNSUPPORTED,
-                "edge_linear16: x and w must be 16-byte aligned with ld_x %% 4 == 0 (ld_x=%lld), msg float-aligned",
-                (long long)ld_x);
+                "edge_linear16:%s x and w must be 16-byte aligned with ld_x %% 4 == 0 (ld_x=%lld), msg float-aligned",
+                who, (long long)ld_x);
   return PTGNN_AMD_OK;
 }
 
-int check_shape(int32_t state_dim, int32_t num_types, int32_t msg_dim, int act, int dtype) {
-  PTGNN_REQUIRE(num_types > 0 && state_dim > 0 && msg_dim > 0, PTGNN_AMD_EINVAL, "edge_linear16: bad sizes");
-  PTGNN_REQUIRE(act >= 0 && act <= PTGNN_AMD_ACT_RELU, PTGNN_AMD_EINVAL, "edge_linear16: bad act");
-  PTGNN_REQUIRE(dtype_ok(dtype), PTGNN_AMD_EINVAL, "edge_linear16: dtype %d is neither PTGNN_AMD_HALF_BF16 nor _F16",
-                dtype);
+int check_shape(const char *who, int32_t state_dim, int32_t num_types, int32_t msg_dim, int act, int dtype) {
+  PTGNN_REQUIRE(num_types > 0 && state_dim > 0 && msg_dim > 0, PTGNN_AMD_EINVAL, "edge_linear16:%s bad sizes", who);
+  PTGNN_REQUIRE(act >= 0 && act <= PTGNN_AMD_ACT_RELU, PTGNN_AMD_EINVAL, "edge_linear16:%s bad act", who);
+  PTGNN_REQUIRE(dtype_ok(dtype), PTGNN_AMD_EINVAL, "edge_linear16:%s dtype %d is neither PTGNN_AMD_HALF_BF16 nor _F16",
+                who, dtype);
   PTGNN_REQUIRE(shape_ok(state_dim, msg_dim, num_types), PTGNN_AMD_EUNSUPPORTED,
-                "edge_linear16: state_dim=%d msg_dim=%d num_types=%d: needs both widths %% 32 == 0 and <= 1024, "
-                "2 <= num_types <= %d", state_dim, msg_dim, num_types, kStreamMaxTypes);
+                "edge_linear16:%s state_dim=%d msg_dim=%d num_types=%d: needs both widths %% 32 == 0 and <= 1024, "
+                "2 <= num_types <= %d", who, state_dim, msg_dim, num_types, kStreamMaxTypes);
+  return PTGNN_AMD_OK;
+}
+
+// The per-edge entries' table from HOST arrays of per-type id pointers and counts; `dst_per_type` null: no target half.
+// `units`: the 32-row units of the launch (0: nothing to launch).
+int host_table(const char *who, const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
+               const int64_t *edges_per_type, int32_t num_types, bool with_dst, StreamEdgeTable &tab, int64_t &units) {
+  PTGNN_REQUIRE(edges_per_type, PTGNN_AMD_EINVAL, "edge_linear16:%s null edge counts", who);
+  tab.num_types = num_types;
+  units = 0;
+  for (int t = 0; t < num_types; ++t) {
+    const int64_t n = edges_per_type[t];
+    PTGNN_REQUIRE(n >= 0, PTGNN_AMD_EINVAL, "edge_linear16:%s negative edge count of type %d", who, t);
+    PTGNN_REQUIRE(n == 0 || (src_per_type && src_per_type[t]), PTGNN_AMD_EINVAL,
+                  "edge_linear16:%s null source ids of type %d", who, t);
+    PTGNN_REQUIRE(!with_dst || n == 0 || (dst_per_type && dst_per_type[t]), PTGNN_AMD_EINVAL,
+                  "edge_linear16:%s null target ids of type %d", who, t);
+    tab.src[t] = n ? src_per_type[t] : nullptr;
+    tab.dst[t] = n && with_dst ? dst_per_type[t] : nullptr;
+    tab.edge_off[t + 1] = tab.edge_off[t] + n;
+    units += (n + 31) / 32;
+    PTGNN_REQUIRE(units < ((int64_t)1 << 30), PTGNN_AMD_EUNSUPPORTED, "edge_linear16:%s too many 32-row units", who);
+    tab.unit_off[t + 1] = (int32_t)units;
+  }
+  for (int t = num_types + 1; t <= kStreamMaxTypes; ++t) {   // the kernels fetch the prefix one entry per lane and search
+    tab.unit_off[t] = (int32_t)units;                        // it with a ballot: entries past the last type hold the total
+    tab.edge_off[t] = tab.edge_off[num_types];
+  }
   return PTGNN_AMD_OK;
 }
 
 // Workgroups of a weight-stationary instance that one CU holds at once (registers and LDS decide; asked once).  The
 // launch is ONE such round: measured at the cfg3 layer shapes, any grid that needs a partly filled second round loses
 // 15 - 20 % to it (profiles/edge_inputs_notes.md).
-template <int DT, int KS, bool INDIRECT>
+template <int DT, int KS, bool INDIRECT, bool DST>
 int ws_resident_per_cu() {
   static const int per_cu = [] {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT>, 256, 0) != hipSuccess || n < 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST>, 256, 0) != hipSuccess ||
+        n < 1) {
       (void)hipGetLastError();
       n = 2;
     }
@@ -214,28 +274,34 @@ int ws_resident_per_cu() {
 }
 
 // `units` < 0: unknown on the host (shared form) -- the launch is sized for the device, workgroups without units leave
-template <bool INDIRECT>
+// DST: the chain is 2 H long, so the weight-stationary register budgets (KS = 8, 16) hold H in {64, 128}
+template <bool INDIRECT, bool DST = false>
 int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
   const int64_t cus = num_compute_units();
-  const bool ws = (p.H == 64 || p.H == 128 || p.H == 256) && p.M <= 128 && env_int("PTGNN_AMD_EDGE16_WS", 1, 0, 1) == 1;
+  const int k = DST ? 2 * p.H : p.H;
+  const bool ws = (k == 128 || k == 256 || (!DST && k == 64)) && p.M <= 128 &&
+                  env_int("PTGNN_AMD_EDGE16_WS", 1, 0, 1) == 1;
   if (ws) {
     const int knob = env_int("PTGNN_AMD_EDGE16_WGS", 0, 0, 16);   // workgroups per CU; 0: one resident round
     with_dtype(dtype, [&](auto dt) {
-      with_case<4, 8, 16>(p.H / 16, [&](auto ks) {
+      auto run = [&](auto ks) {
         constexpr int DT = decltype(dt)::value, KS = decltype(ks)::value;
-        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT>());
+        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST>());
         if (units >= 0 && units < grid) grid = units;
-        k_edge16_ws<DT, KS, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p);
-      });
+        k_edge16_ws<DT, KS, INDIRECT, DST><<<(unsigned)grid, 256, 0, st>>>(p);
+      };
+      if constexpr (DST) with_case<8, 16>(k / 16, run); else with_case<4, 8, 16>(k / 16, run);
     });
   } else {
     const int col_groups = (p.M + 32 * kTiles - 1) / (32 * kTiles);
     int64_t grid = cus * 8;
     if (units >= 0 && (units * col_groups + 3) / 4 < grid) grid = (units * col_groups + 3) / 4;
-    with_dtype(dtype, [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT><<<(unsigned)grid, 256, 0, st>>>(p); });
+    with_dtype(dtype,
+               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST><<<(unsigned)grid, 256, 0, st>>>(p); });
   }
   PTGNN_LAUNCH_CHECK();
-  count_launch(INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16);
+  count_launch(DST ? PTGNN_AMD_KERNEL_EDGE16_DST
+                   : (INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16));
   return PTGNN_AMD_OK;
 }
 
@@ -252,40 +318,45 @@ extern "C" int ptgnn_amd_edge_linear16(const float *x, int64_t ld_x, int64_t num
                                        const int64_t *const *src_per_type, const int64_t *edges_per_type,
                                        const void *w, int32_t num_types, int32_t msg_dim, int act, int dtype,
                                        float *msg, int64_t ld_msg, void *stream_) {
-  if (const int rc = check_shape(state_dim, num_types, msg_dim, act, dtype)) return rc;
-  PTGNN_REQUIRE(edges_per_type, PTGNN_AMD_EINVAL, "edge_linear16: null edge counts");
+  if (const int rc = check_shape("", state_dim, num_types, msg_dim, act, dtype)) return rc;
   Edge16Args p{};
-  p.tab.num_types = num_types;
   int64_t units = 0;
-  for (int t = 0; t < num_types; ++t) {
-    const int64_t n = edges_per_type[t];
-    PTGNN_REQUIRE(n >= 0, PTGNN_AMD_EINVAL, "edge_linear16: negative edge count of type %d", t);
-    PTGNN_REQUIRE(n == 0 || (src_per_type && src_per_type[t]), PTGNN_AMD_EINVAL,
-                  "edge_linear16: null source ids of type %d", t);
-    p.tab.src[t] = n ? src_per_type[t] : nullptr;
-    p.tab.edge_off[t + 1] = p.tab.edge_off[t] + n;
-    units += (n + 31) / 32;
-    PTGNN_REQUIRE(units < ((int64_t)1 << 30), PTGNN_AMD_EUNSUPPORTED, "edge_linear16: too many 32-row units");
-    p.tab.unit_off[t + 1] = (int32_t)units;
-  }
+  if (const int rc = host_table("", src_per_type, nullptr, edges_per_type, num_types, false, p.tab, units)) return rc;
   if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
-  if (const int rc = check_operands(x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
-  for (int t = num_types + 1; t <= kStreamMaxTypes; ++t) {   // the kernels fetch the prefix one entry per lane and search
-    p.tab.unit_off[t] = (int32_t)units;                      // it with a ballot: entries past the last type hold the total
-    p.tab.edge_off[t] = p.tab.edge_off[num_types];
-  }
+  if (const int rc = check_operands("", x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
   p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
   p.H = state_dim; p.M = msg_dim; p.act = act; p.msg = msg; p.ld_msg = ld_msg;
   return launch<false>(p, dtype, units, (hipStream_t)stream_);
+}
+
+extern "C" int ptgnn_amd_edge_dst_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype) {
+  return dtype_ok(dtype) && shape_ok(state_dim, msg_dim, num_types) ? 1 : 0;
+}
+
+extern "C" int ptgnn_amd_edge_dst_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                           const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
+                                           const int64_t *edges_per_type, const void *w, int32_t num_types,
+                                           int32_t msg_dim, int act, int dtype, float *msg, int64_t ld_msg,
+                                           void *stream_) {
+  if (const int rc = check_shape(" dst:", state_dim, num_types, msg_dim, act, dtype)) return rc;
+  Edge16Args p{};
+  int64_t units = 0;
+  if (const int rc = host_table(" dst:", src_per_type, dst_per_type, edges_per_type, num_types, true, p.tab, units))
+    return rc;
+  if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
+  if (const int rc = check_operands(" dst:", x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = act; p.msg = msg; p.ld_msg = ld_msg;
+  return launch<false, true>(p, dtype, units, (hipStream_t)stream_);
 }
 
 extern "C" int ptgnn_amd_edge_linear16_shared(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
                                               const void *edge_table, const void *w, int32_t num_types,
                                               int32_t msg_dim, int act, int dtype, float *msg, int64_t ld_msg,
                                               void *stream_) {
-  if (const int rc = check_shape(state_dim, num_types, msg_dim, act, dtype)) return rc;
+  if (const int rc = check_shape("", state_dim, num_types, msg_dim, act, dtype)) return rc;
   PTGNN_REQUIRE(edge_table, PTGNN_AMD_EINVAL, "edge_linear16: shared: null edge table");
-  if (const int rc = check_operands(x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
+  if (const int rc = check_operands("", x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
   // the table's (type, source) keys are int32 (ptgnn_amd_unique_sources): no table exists beyond that
   PTGNN_REQUIRE(num_rows * num_types < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED,
                 "edge_linear16: shared: too many (type, source) pairs (%lld rows x %d types)", (long long)num_rows,

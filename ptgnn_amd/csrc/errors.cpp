@@ -30,6 +30,7 @@ static std::atomic<int64_t> g_beam_launches[PTGNN_AMD_KERNEL_BEAM_END_ - PTGNN_A
 static std::atomic<int64_t> g_half_launches[PTGNN_AMD_KERNEL_HALF_END_ - PTGNN_AMD_KERNEL_HALF_FIRST_];
 static std::atomic<int64_t> g_edge16_launches[PTGNN_AMD_KERNEL_EDGE16_END_ - PTGNN_AMD_KERNEL_EDGE16_FIRST_];
 static std::atomic<int64_t> g_half_train_launches[PTGNN_AMD_KERNEL_HALF_TRAIN_END_ - PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_];
+static std::atomic<int64_t> g_edge16_dst_launches[PTGNN_AMD_KERNEL_EDGE16_DST_END_ - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -50,6 +51,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_edge16_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HALF_TRAIN_END_)
     return &g_half_train_launches[kernel_id - PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_DST_END_)
+    return &g_edge16_dst_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -123,6 +126,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "half_wgrad", "half_gru_train", "half_linear_add"};
   if (kernel_id >= PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_HALF_TRAIN_END_)
     return half_train_names[kernel_id - PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_];
+  static const char *const edge16_dst_names[PTGNN_AMD_KERNEL_EDGE16_DST_END_ - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_] = {
+      "edge16_dst"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_DST_END_)
+    return edge16_dst_names[kernel_id - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

@@ -13,6 +13,7 @@
 // those rounded operands; the two schemes below differ only in where the fragments come from.
 //   * wave_tile: a wave owns 32 rows x up to TILES x 32 output columns; a lane rounds its row's fragment straight from
 //     the fp32 row (two dwordx4) and reads the weights from L2.  The fragment IS the memory order: no LDS, no barrier.
+//     (wave_tile_more continues the same accumulators over a second row: the [x[src] | x[dst]] chain of edge_gemm16.hip.)
 //   * RoundedPanel: a workgroup loads ROWS x KT floats ONCE, coalesced (a thread's float4s are consecutive in a row),
 //     rounds them and parks them in LDS at a row stride of (KT + 8) x 2 bytes -- an odd number of 16-byte units, so the
 //     ds_read_b128 fragment reads of 16 consecutive rows hit 64 distinct banks.  Its waves keep their weights in registers.
@@ -99,19 +100,19 @@ __device__ __forceinline__ float act_runtime(float v, int act) {
 // The per-wave tile: acc[t] = rnd(arow) . rnd(W)[col0 + 32 t + li, :]^T over all of K (K % 32 == 0: two MFMA k-steps
 // per trip).  `arow`: the fp32 row of this lane (callers clamp rows past the end onto a valid one; never stored);
 // `w`: [*, K] rounded weights; column tiles past `tiles` (>= 1) recompute the last live one.
+// wave_tile_more CONTINUES the accumulators over K further columns: `w` then points at those columns of the first weight
+// row and `ldw` is the weight rows' stride -- a chain over [a1 | a2] . [W1 | W2]^T is zero, more(a1, W1), more(a2, W2).
 template <int DT, int TILES>
-__device__ __forceinline__ void wave_tile(const float *__restrict__ arow, const uint16_t *__restrict__ w, int K,
-                                          int col0, int tiles, f32x16 (&acc)[TILES]) {
+__device__ __forceinline__ void wave_tile_more(const float *__restrict__ arow, const uint16_t *__restrict__ w, int ldw,
+                                               int K, int col0, int tiles, f32x16 (&acc)[TILES]) {
   using H = Half16<DT>;
   const int li = frag_li(), hi = frag_hi();
-#pragma unroll
-  for (int t = 0; t < TILES; ++t) zero(acc[t]);
   const float *ap = arow + 8 * hi;
   const uint16_t *bp[TILES];
 #pragma unroll
   for (int t = 0; t < TILES; ++t) {
     const int tc = t < tiles ? t : tiles - 1;
-    bp[t] = w + (int64_t)(col0 + tc * 32 + li) * K + 8 * hi;
+    bp[t] = w + (int64_t)(col0 + tc * 32 + li) * ldw + 8 * hi;
   }
   for (int kk = 0; kk < K; kk += 32) {
 #pragma unroll
@@ -121,6 +122,13 @@ __device__ __forceinline__ void wave_tile(const float *__restrict__ arow, const 
       for (int t = 0; t < TILES; ++t) acc[t] = H::mfma(a, load8<DT>(bp[t] + k0), acc[t]);
     }
   }
+}
+template <int DT, int TILES>
+__device__ __forceinline__ void wave_tile(const float *__restrict__ arow, const uint16_t *__restrict__ w, int K,
+                                          int col0, int tiles, f32x16 (&acc)[TILES]) {
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) zero(acc[t]);
+  wave_tile_more<DT>(arow, w, K, K, col0, tiles, acc);
 }
 
 // The rounded panel of a 256-thread workgroup: ROWS x KT values in each of two LDS buffers.  A walk is

@@ -1197,10 +1197,10 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         if _no_grad_needed(node_states, *self.parameters()):
             epi = self._epilogue(M, 256)
             if edge_form:
-                msgs = ops.edge_linear(node_states, adjacency_lists, ws, use_dst)
+                msgs = self._edge_form_messages(node_states, adjacency_lists)
                 agg = ops.pna_aggregate(msgs, plan, M, delta, type_bits=0, col=plan.perm, **epi)
             else:
-                ysrc, ydst = self._table_halves(ops.linear(node_states, self._stacked_edge_weights()), T)
+                ysrc, ydst = self._table_halves(self._message_table(node_states), T)
                 agg = ops.pna_aggregate(ysrc, plan, M, delta, ydst=ydst, **epi)
             return self._update(agg, bool(epi))
         if not _edge_training_ok(H, M):
@@ -1259,7 +1259,8 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
             return torch_route.mlp_layer(node_states, adjacency_lists, edge_features,
                                          list(self.__edge_message_transformation_layers),
                                          self.__use_target_state_as_message_input, self.__aggregation_fn,
-                                         self.__message_activation, self.__state_update)
+                                         self.__message_activation, self.__state_update,
+                                         inputs=self._host_matrix_inputs(node_states, edge_features))
         if node_states.dtype in _AMP_DTYPES:
             return _amp_forward(self, node_states, adjacency_lists, edge_features)
 
@@ -1294,11 +1295,49 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         N, T = node_states.shape[0], len(adjacency_lists)
         plan = ops.plan_for(adjacency_lists, N)
         if _prefer_edge_path(plan.num_edges, N, T, self.__input_state_dim, self._message_dimension):
-            msgs = ops.edge_linear(node_states, adjacency_lists, self._first_weights(),
-                                   self.__use_target_state_as_message_input)
+            msgs = self._edge_form_messages(node_states, adjacency_lists)
             return self._aggregate_and_update(msgs, None, plan, col=plan.perm, type_bits=0)
-        ysrc, ydst = self._table_halves(ops.linear(node_states, self._stacked_edge_weights()), T)
+        ysrc, ydst = self._table_halves(self._message_table(node_states), T)
         return self._aggregate_and_update(ysrc, ydst, plan)
+
+    def _message_table(self, node_states) -> torch.Tensor:
+        """Inference, table form: [N, (1|2) T M] = X [W^s_0; ...; W^d_0; ...]^T.  Under a 16-bit matrix-input setting made
+        with `mlp=True` (ptgnn_amd/precision.py) the states and the stacked weights are rounded and multiplied on the
+        16-bit matrix cores, as the GGNN table form does; widths the kernel declines run fp32."""
+        w = self._stacked_edge_weights()
+        inputs = precision.mlp_inputs(node_states)
+        w16 = _half_weights(self, "mlp_table_w16", inputs, ops.HALF_KIND_LINEAR, self.__input_state_dim, w.shape[0],
+                            lambda: w.to(inputs).contiguous())
+        return ops.linear(node_states, w, inputs=inputs, rounded=w16)
+
+    def _edge_form_messages(self, node_states, adjacency_lists) -> torch.Tensor:
+        """Inference, edge form: the grouped per-edge GEMM over [x[src] | x[dst]] (or x[src] alone), one row per edge in
+        type-major order.  Under `mlp=True` it takes the 16-bit launch (ptgnn_amd_edge_dst_linear16, or
+        ptgnn_amd_edge_linear16 without a target-state half) on a [T, M, (1|2) H] stack rounded once per forward scope;
+        shapes the launch declines run fp32."""
+        ws = self._first_weights()
+        use_dst = self.__use_target_state_as_message_input
+        H, M, T = self.__input_state_dim, self._message_dimension, len(ws)
+        inputs = precision.mlp_inputs(node_states)
+        w16 = None
+        if inputs != torch.float32 and (ops.edge_linear16_dst_supported if use_dst
+                                        else ops.edge_linear16_supported)(H, M, T, inputs):
+            w16 = _scoped(self, ("mlp_edge_stack16", inputs), lambda: torch.stack([w.detach() for w in ws]).to(inputs))
+        return ops.edge_linear(node_states, adjacency_lists, ws, use_dst, inputs=inputs, rounded=w16)
+
+    def _host_matrix_inputs(self, node_states, edge_features):
+        """The `mlp=True` matrix-input setting as the CPU route applies it: fp32 states, inference only (as on the GPU),
+        and only for the edge transforms the GPU routes round -- single bias-free Linears without edge features."""
+        if node_states.dtype != torch.float32 or _has_edge_features(self._features_dimension, edge_features):
+            return torch.float32
+        if not all(m.is_single_linear for m in self.__edge_message_transformation_layers):
+            return torch.float32
+        agg = self.__aggregation_fn
+        if not (agg in ops.REDUCE_IDS if isinstance(agg, str) else type(agg) is PnaMessageAggregation):
+            return torch.float32
+        if torch.is_grad_enabled() and not _no_grad_needed(node_states, *self.parameters()):
+            return torch.float32
+        return precision.mlp_inputs(node_states)
 
     def _forward_training(self, node_states, adjacency_lists) -> torch.Tensor:
         """Training, single-Linear edge transforms."""

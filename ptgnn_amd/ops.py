@@ -65,9 +65,12 @@ _EDGE16_FAMILY_FIRST = 512  # PTGNN_AMD_KERNEL_EDGE16_FIRST_: the opt-in 16-bit-
 _HALF_TRAIN_FAMILY_FIRST = 576  # PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_: the opt-in 16-bit-input training launches
 
 
+_EDGE16_DST_FAMILY_FIRST = 640  # PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_: the 16-bit per-edge GEMM with a target-state half
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
-                  edge16: bool = False, half_training: bool = False) -> dict:
+                  edge16: bool = False, half_training: bool = False, edge16_dst: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -79,14 +82,16 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `decode=True` its greedy-decoding step (decode_step); `beam=True` its beam-search step (beam_step);
     `half=True` the 16-bit-input dense blocks (half_linear, half_gru); `edge16=True` the 16-bit-input grouped per-edge
     GEMM's two launch forms (edge16, edge16_shared); `half_training=True` the 16-bit-input training launches
-    (half_wgrad, half_gru_train, half_linear_add)."""
+    (half_wgrad, half_gru_train, half_linear_add); `edge16_dst=True` the 16-bit-input per-edge GEMM with a target-state
+    half (edge16_dst: the MLP-MP message Linear)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
             + ((_HEAD_FAMILY_FIRST,) if heads else ()) + ((_SEQ_FAMILY_FIRST,) if sequence else ()) \
             + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()) \
             + ((_HALF_FAMILY_FIRST,) if half else ()) + ((_EDGE16_FAMILY_FIRST,) if edge16 else ()) \
-            + ((_HALF_TRAIN_FAMILY_FIRST,) if half_training else ()):
+            + ((_HALF_TRAIN_FAMILY_FIRST,) if half_training else ()) \
+            + ((_EDGE16_DST_FAMILY_FIRST,) if edge16_dst else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -100,7 +105,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
-                        edge16=True, half_training=True)
+                        edge16=True, half_training=True, edge16_dst=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -504,9 +509,18 @@ def edge_linear16_supported(state_dim: int, msg_dim: int, num_types: int, dtype)
                                                              HALF_IDS[dtype]))
 
 
+def edge_linear16_dst_supported(state_dim: int, msg_dim: int, num_types: int, dtype) -> bool:
+    """Whether the 16-bit-input grouped per-edge GEMM with a target-state half takes the shape
+    (ptgnn_amd_edge_dst_linear16_supported; no device).  `state_dim` is H: the weights are [msg_dim, 2 H]."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_edge_dst_linear16_supported(int(state_dim), int(msg_dim), int(num_types),
+                                                                 HALF_IDS[dtype]))
+
+
 def _edge16_stack(ws: Sequence[torch.Tensor], dtype: torch.dtype, given: Optional[torch.Tensor]) -> torch.Tensor:
-    """The [T, M, H] stack of the per-type weights rounded to `dtype` by torch (round to nearest even), or the caller's
-    cached copy of exactly that."""
+    """The [T, M, H] stack ([T, M, 2 H] with a target-state half) of the per-type weights rounded to `dtype` by torch
+    (round to nearest even), or the caller's cached copy of exactly that."""
     shape = (len(ws),) + tuple(ws[0].shape)
     if given is None:
         return torch.stack(list(ws)).to(dtype)          # two launches, whatever T; the rounding of w.to(dtype)
@@ -1411,12 +1425,16 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     dropout = (mode, p, seed): nn.Dropout(p) on the gathered input rows (mode 1) or on the output rows
     (mode 2, the input-gradient form) with the hash mask of ptgnn_amd_edge_linear_dropout_f32; with
     `mask_bits` (`dropout_bitmask` of the same p and seed) the streaming kernel applies the mask from its bits.
-    `inputs` / `rounded`: the 16-bit matrix-core form, as `edge_linear_shared` takes them -- the plain GGNN form only:
-    with dropout, edge features or `use_dst` a 16-bit `inputs` raises."""
+    `inputs` / `rounded`: the 16-bit matrix-core form, as `edge_linear_shared` takes them; with `use_dst` the launch is
+    ptgnn_amd_edge_dst_linear16 (`edge_linear16_dst_supported`; `rounded` is then the [T, M, 2 H] stack).  With dropout
+    or edge features a 16-bit `inputs` raises, and with `use_dst` it wants GPU states."""
     half = _half_inputs(inputs)
-    if half is not None and (use_dst or (dropout is not None and dropout[0] != 0 and dropout[1] > 0.0)
+    if half is not None and ((dropout is not None and dropout[0] != 0 and dropout[1] > 0.0)
                              or (edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats))):
-        raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout, edge features nor a target-state half")
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout nor edge features")
+    if half is not None and use_dst and not x.is_cuda:
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs with a target-state half run on the GPU kernel only "
+                                 f"(got states on {x.device})")
     if edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats):
         if dropout is not None and dropout[0] != 0 and dropout[1] > 0.0:
             raise _lib.PtgnnAmdError("edge_linear: the dropout forms take no edge features")
@@ -1440,7 +1458,20 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     PtrArr, CntArr = ctypes.c_void_p * T, ctypes.c_int64 * T
     sp = PtrArr(*[s.data_ptr() if s.numel() else None for s in srcs])
     cn = CntArr(*counts)
-    if half is not None and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
+    if half is not None and use_dst and edge_linear16_dst_supported(H, M, T, half) and _half_rows_ok(x):
+        w16 = _edge16_stack(ws, half, rounded)
+        if any(d.numel() != c for d, c in zip(dsts, counts)):
+            raise _lib.PtgnnAmdError("edge_linear: source and target id lists differ in length")
+        dp = PtrArr(*[d.data_ptr() if d.numel() else None for d in dsts])
+        with _timed("edge_linear16_dst", flops=4.0 * E * H * M,
+                    bytes=4.0 * (2 * E * H + E * M) + 4.0 * T * M * H + 16.0 * E):
+            rc = lib.ptgnn_amd_edge_dst_linear16(x.data_ptr(), _ld(x), x.shape[0], H,
+                                                 ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(dp, ctypes.c_void_p),
+                                                 ctypes.cast(cn, ctypes.c_void_p), w16.data_ptr(), T, M,
+                                                 ACT_IDS[act], HALF_IDS[half], msg.data_ptr(), M, _stream(msg))
+        _lib.check(rc, "ptgnn_amd_edge_dst_linear16")
+        return msg[:E] if E > 0 else msg[:0]
+    if half is not None and not use_dst and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
         w16 = _edge16_stack(ws, half, rounded)
         with _timed("edge_linear16", flops=2.0 * E * H * M, bytes=4.0 * (E * H + E * M) + 2.0 * T * M * H + 8.0 * E):
             rc = lib.ptgnn_amd_edge_linear16(x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),

@@ -1,4 +1,4 @@
-"""Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks.
+"""Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks and the MLP-MP layer's message GEMMs.
 
 The default is `torch.float32`: every dense block runs the exact-fp32 MFMA kernels, bit for bit as without this module.
 With `torch.bfloat16` / `torch.float16` the INFERENCE routes of `GatedMessagePassingLayer` (and, with `training=True`,
@@ -40,15 +40,39 @@ as `tensor.half()` gives and `GradScaler` expects.  Every call without the keywo
 `set_matrix_inputs(torch.float32)` resets it, and `training=True` with float32 is accepted and means fp32.  The forward
 of a training call under the flag has the bits of the inference route under the same setting.
 
+The MLP-MP layer (`MlpMessagePassingLayer`, the layer of the published Typilus Graph2Class architecture) has a switch of
+its own as well -- it stayed fp32 under every setting above, and existing users keep their bits:
+
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, mlp=True):         # also set_matrix_inputs(v, mlp=True)
+        out = model(batch)
+
+With the flag the layer's INFERENCE routes with single-Linear, bias-free edge transforms and no edge features (the routes
+behind `_fused_ok`, and the inference branch of `_forward_pna`) round the operands of the message transformation -- the
+node states and the first-Linear weights -- and multiply them on the 16-bit matrix cores: the [N, (1|2) T M] table Linear
+of the table form (ptgnn_amd_half_linear on the stacked source and target halves), and the grouped per-edge GEMM of the
+edge form (csrc/edge_gemm16.hip: ptgnn_amd_edge_dst_linear16 over [x[src] | x[dst]], or ptgnn_amd_edge_linear16 with
+`use_target_state_as_message_input=False`).  States, messages, the aggregation, GELU, LayerNorm, the dense update and
+every store stay fp32.  Every call without the keyword means `mlp=False`; `set_matrix_inputs(torch.float32)` resets it,
+and `mlp=True` with float32 is accepted and means fp32.  The flag is independent of the GGNN flags: a GGNN layer under
+`mlp=True` alone behaves as under the plain dtype setting.
+
+What deliberately stays fp32 in the MLP-MP layer under `mlp=True`: the dense update Linear + Tanh (1 / (2 T) of the
+table's FLOPs; in the hidden-64 edge form it has no launch of its own -- `ops.gather_update` aggregates, normalises and
+updates in ONE launch, and that launch is still taken); deeper or biased edge MLPs (`_forward_deep_mlps`); edge features;
+aggregation modules other than exactly `PnaMessageAggregation`; `_forward_general`; `forward_sharded`; every training
+route.
+
 What stays fp32 under every setting: without `training=True` every training route (anything that needs a gradient);
 with it still the edge-form and edge-feature training GEMMs (`_EdgeLinear`, `_EdgeLinearFeat`), `_general_messages`
-and `forward_sharded`, MLP-MP, EGC and the attention layers, the reducers, the heads and the decoder; CPU tensors in
+and `forward_sharded`, every MLP-MP training route, EGC and the attention layers, the reducers, the heads and the
+decoder; without `mlp=True` all of MLP-MP; CPU tensors in
 training (the torch route rounds nothing where a gradient is needed); the edge-feature route's grouped GEMM; without
 `edge_gemm=True` also the grouped per-edge GEMM of the edge form.  Shapes the 16-bit kernels do not take (widths that are not multiples of 32; for the per-edge
 GEMM also fewer than 2 or more than 64 edge types) run the fp32 kernels, silently.  CPU tensors
 (ptgnn_amd/torch_route.py) round the same operands with torch under the dtype setting alone -- message operands
-included, so the flag changes nothing there -- and a checkpoint behaves alike on both devices; "autocast" never touches
-CPU tensors.
+included, so the flag changes nothing there -- and a checkpoint behaves alike on both devices; the MLP-MP layer's CPU
+route rounds the node states and the message Linears' weights under `mlp=True` under the same conditions as the GPU
+routes (fp32 states, nothing needs a gradient); "autocast" never touches CPU tensors.
 
 The setting is process-wide (like `ops.set_gemm_mode`); the layers read it, `ptgnn_amd.ops` never does -- its
 `inputs=` keyword is explicit, because inside an autograd `Function.forward` grad mode is off and an op could not tell
@@ -66,6 +90,7 @@ _CHOICES = (torch.float32,) + HALF_DTYPES + ("autocast",)
 _setting = torch.float32
 _edge_gemm = False
 _training = False
+_mlp = False
 
 
 def _checked(v):
@@ -74,17 +99,18 @@ def _checked(v):
     return v
 
 
-def _set(v, edge_gemm, training=False):
-    global _setting, _edge_gemm, _training
-    prev = (_setting, _edge_gemm, _training)
-    _setting, _edge_gemm, _training = _checked(v), bool(edge_gemm), bool(training)
+def _set(v, edge_gemm, training=False, mlp=False):
+    global _setting, _edge_gemm, _training, _mlp
+    prev = (_setting, _edge_gemm, _training, _mlp)
+    _setting, _edge_gemm, _training, _mlp = _checked(v), bool(edge_gemm), bool(training), bool(mlp)
     return prev
 
 
-def set_matrix_inputs(v, *, edge_gemm=False, training=False):
-    """Set the operand type of the GGNN inference GEMMs, whether the edge form's grouped per-edge GEMM follows it, and
-    whether the GGNN training routes do; returns the previous dtype setting."""
-    return _set(v, edge_gemm, training)[0]
+def set_matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False):
+    """Set the operand type of the GGNN inference GEMMs, whether the edge form's grouped per-edge GEMM follows it,
+    whether the GGNN training routes do, and whether the MLP-MP layer's inference message GEMMs do; returns the previous
+    dtype setting."""
+    return _set(v, edge_gemm, training, mlp)[0]
 
 
 def get_matrix_inputs():
@@ -92,8 +118,8 @@ def get_matrix_inputs():
 
 
 @contextlib.contextmanager
-def matrix_inputs(v, *, edge_gemm=False, training=False):
-    prev = _set(v, edge_gemm, training)
+def matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False):
+    prev = _set(v, edge_gemm, training, mlp)
     try:
         yield
     finally:
@@ -122,3 +148,9 @@ def training_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the GGNN training routes' 16-bit autograd nodes for a layer call on `tensor`: `resolve(tensor)` when
     the setting was made with `training=True` and the tensor is on a GPU, else float32."""
     return resolve(tensor) if _training and tensor.is_cuda else torch.float32
+
+
+def mlp_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the MLP-MP layer's inference message GEMMs for a layer call on `tensor`: `resolve(tensor)` when the
+    setting was made with `mlp=True`, else float32."""
+    return resolve(tensor) if _mlp else torch.float32

@@ -349,11 +349,21 @@ def ggnn_layer(node_states, adjacency_lists, edge_features, edge_linears: Sequen
 
 
 def mlp_layer(node_states, adjacency_lists, edge_features, edge_mlps: Sequence[nn.Module], with_target: bool,
-              aggregation, activation: Optional[nn.Module], state_update: nn.Module) -> torch.Tensor:
-    """mlpmessagepassing.py:80-117 on host tensors."""
+              aggregation, activation: Optional[nn.Module], state_update: nn.Module,
+              inputs: torch.dtype = torch.float32) -> torch.Tensor:
+    """mlpmessagepassing.py:80-117 on host tensors.
+    `inputs` = torch.bfloat16 / torch.float16 (the caller's `mlp=True` matrix-input setting; inference with single
+    bias-free Linear edge transforms and no edge features only): the operands the GPU routes round -- the node states and
+    the message Linears' weights -- are rounded here with torch and multiplied by the fp32 operator; everything after the
+    messages stays as it is."""
     _host_only(node_states)
-    msgs = [mlp(inp) for inp, mlp in
-            zip(_message_inputs(node_states, adjacency_lists, edge_features, with_target), edge_mlps)]
+    if inputs == torch.float32:
+        msgs = [mlp(inp) for inp, mlp in
+                zip(_message_inputs(node_states, adjacency_lists, edge_features, with_target), edge_mlps)]
+    else:
+        msgs = [nn.functional.linear(inp, _rounded(mlp.linears[0].weight, inputs)) for inp, mlp in
+                zip(_message_inputs(_rounded(node_states, inputs), adjacency_lists, edge_features, with_target),
+                    edge_mlps)]
     messages = torch.cat(msgs, dim=0)
     targets = torch.cat([d for _, d in adjacency_lists], dim=0)
     if isinstance(aggregation, str):
