@@ -29,7 +29,12 @@
 //   * work = balanced runs of units in group-major order (group = column slab / GRU feature tile / edge type;
 //     the edge kernel apportions its workgroups to the types), units claimed dynamically from an LDS
 //     counter inside a run; the dense kernels map runs so that the column slabs of one row range share an
-//     XCD (L2 reuse of A).
+//     XCD (L2 reuse of A);
+//   * the GRU claims only the first 8 floor(count / 8) units of a run whole: the last count % 8 (up to 6) are shared
+//     between the waves as accumulator groups {r}, {z}, {n_i, h_n} that meet in LDS before the unit's epilogue, so
+//     that a run ends after ~count / 8 rounds instead of leaving SIMDs idle behind one to four last units (`Tail
+//     split` below).  Only where the slab leaves 48 KB of LDS for the exchange: H = 128 at K = 256 does; at K = 384
+//     (the last GGNN layer, 146 KB slab) and in training launches (gate outputs) units stay whole.
 // The accumulation order over K inside a row is ONE fixed permutation shared with the tile kernels, so a
 // result does not depend on the kernel, the tile position, the shard or the layer form that produced it.
 //
@@ -86,7 +91,8 @@ __device__ __forceinline__ float4 load_piece(const ARows &r, int cc, int ch0, in
 __device__ __forceinline__ int lane_piece_offset(int hi) { return hi * 4; }
 
 // ---- one K chunk (32 columns) of one unit ---------------------------------------------------------
-// NBLK column blocks of the slab per step; GRU maps block 2 to accumulator 3 in phase 1 (h_n).
+// NBLK column blocks of the slab per step; GRU sends its last block to the last accumulator in phase 1 (h_n): block 2
+// to accumulator 3 in a whole unit, block 0 to accumulator 1 in the {n_i, h_n} group of a split unit.
 template <int NBLK, int NACC, int PH, bool GRU>
 __device__ __forceinline__ void chunk_f32(f32x16 (&acc)[NACC], float4 (&buf)[4], float4 (&bcur)[NBLK],
                                           const float *bl, int cbs, int kofs, int kofs_next, const ARows &rows,
@@ -107,7 +113,7 @@ __device__ __forceinline__ void chunk_f32(f32x16 (&acc)[NACC], float4 (&buf)[4],
     const float4 a = buf[g];
 #define PTGNN_STEP(C)                                                                     \
     _Pragma("unroll") for (int n = 0; n < NBLK; ++n) {                                    \
-      const int t = (GRU && PH == 1 && n == 2) ? 3 : n;                                   \
+      const int t = (GRU && PH == 1 && n == NBLK - 1) ? NACC - 1 : n;                     \
       acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.C, bcur[n].C, acc[t], 0, 0, 0);     \
     }
     PTGNN_STEP(x) PTGNN_STEP(y) PTGNN_STEP(z) PTGNN_STEP(w)
@@ -223,6 +229,24 @@ __device__ __forceinline__ int claim_unit(int *counter) {
   if ((threadIdx.x & 63) == 0) v = atomicAdd(counter, 1);
   return __builtin_amdgcn_readfirstlane(v);
 }
+
+// Tail split (k_stream_gru).  Claimed whole, the last `count % 8` units of a run leave most of the workgroup idle: a unit
+// alone on its SIMD takes half a round, five to seven units a whole one, where `count / 8` rounds would do
+// (profiles/r04_notes.md 1, profiles/tail_split_notes.md).  So the whole-unit loop stops at the last multiple of 8 and the
+// waves share the rest in SUB-UNITS, one accumulator group {r}, {z} or {n_i, h_n} of a unit each.  A sub-unit runs its
+// accumulators through the unit's own K loop -- same chunk order, same `kcol()` permutation, same MFMA sequence per
+// accumulator -- so the bits are those of the whole unit.  A wave draws ONE arrival ticket `a` from a second LDS counter
+// and takes sub-units a, a + 8, a + 16, ...: the early waves get the larger share, and the next sub-unit is known in
+// advance, so its rows are prefetched under the current one like a next unit's (claiming ahead from a counter instead
+// would hand the first wave two or three of a handful of sub-units).
+// The same split by 32 x 32 output blocks was built for k_stream_edge / k_stream_linear and measured 3 % SLOWER on the edge
+// GEMM (its tail starts with two dependent round trips, ids then gathered rows, that the whole-unit loop had hidden under
+// earlier units): they keep whole units.
+// PTGNN_TAIL_SPLIT=0 (A/B, scripts/build_variant.sh ... -DPTGNN_TAIL_SPLIT=0) is the whole-unit form.
+#ifndef PTGNN_TAIL_SPLIT
+#define PTGNN_TAIL_SPLIT 1
+#endif
+constexpr bool kSplitGru = PTGNN_TAIL_SPLIT != 0;
 
 // ---------------------------------------------------------------------------------------------------
 // linear: y = act(x W^T + b)
@@ -457,7 +481,14 @@ struct GruArgs {
   float *out; int64_t ld_out; float *gates;
   int nrb, ncs, rps, run_len;
   int lds_floats;
+  int split;                 // the launch carries kGruSplitBytes of LDS behind the transposing slabs (tail split)
 };
+
+// Tail split of the GRU: the accumulator groups of a unit meet in LDS, 2 x 4 KB per unit ({r} and {z}; {n_i, h_n} stay in
+// the registers of the wave that runs the epilogue) + one flag.  Six units fit next to the K = 256 slab (100 KB + 9 KB
+// of epilogue slabs + 48 KB = 157 of 160 KB); a K = 384 slab (146 KB) leaves no room: the last GGNN layer keeps whole units.
+constexpr int kGruSplitUnits = 6;
+constexpr size_t kGruSplitBytes = (size_t)kGruSplitUnits * 2 * 4096 + 32;
 
 // sigmoid / tanh on the hardware transcendentals (v_exp_f32, v_rcp_f32: 1 ulp each): absolute error
 // ~1.5e-7, against ~1700 VALU instructions per unit for the libm forms -- which made the epilogue 40 % of
@@ -569,7 +600,10 @@ __global__ __launch_bounds__(512, 2) void k_stream_gru(GruArgs p) {
   const Slab sl(K, 96);
   int *counter = reinterpret_cast<int *>(smem + p.lds_floats);
   float *const tq = smem + p.lds_floats + 4 + (threadIdx.x >> 6) * kTqFloats;
-  if (threadIdx.x == 0) *counter = 0;
+  float *const xch = smem + p.lds_floats + 4 + 8 * kTqFloats;             // p.split launches only: parked accumulators,
+  int *const flags = reinterpret_cast<int *>(xch + kGruSplitUnits * 2048);   // then one arrival count per tail unit
+  if (threadIdx.x == 0) counter[0] = counter[1] = 0;   // whole units, tail tickets
+  if (kSplitGru && p.split && threadIdx.x < 8) flags[threadIdx.x] = 0;
   const int j0 = slab * 32;
   {
     const int mq = p.M >> 2;
@@ -591,37 +625,91 @@ __global__ __launch_bounds__(512, 2) void k_stream_gru(GruArgs p) {
     const int64_t row = (int64_t)(rb0 + (u < count ? u : count - 1)) * 32 + li;
     return row < p.n ? row : p.n - 1;
   };
-  int cur = claim_unit(counter);
-  if (cur >= count) return;
-  int nxt = claim_unit(counter);
-  ARows rows;
-  {
-    const int64_t r0 = clampr(cur), r1 = clampr(nxt);
-    rows.c0 = p.a + r0 * p.ld_a + lofs; rows.c1 = p.h + r0 * p.ld_h + lofs;
-    rows.n0 = p.a + r1 * p.ld_a + lofs; rows.n1 = p.h + r1 * p.ld_h + lofs;
-  }
-  float4 a0[4], a1[4];
-  prologue_loads(a0, a1, rows, ch0, nch);
-  f32x16 acc[4];
-#pragma unroll
-  for (int n = 0; n < 4; ++n) acc[n] = zero16();
-
+  // tail split (p.split: the launch carries the exchange area; a run of 8 k + 7 units keeps whole units, seven do not fit)
+  int tail = kSplitGru && p.split ? count & 7 : 0;
+  if (tail > kGruSplitUnits) tail = 0;
+  const int whole = count - tail;
   const int j = j0 + li;
   const float bir = p.b_ih[j], biz = p.b_ih[p.H + j], bin = p.b_ih[2 * p.H + j];
   const float bhr = p.b_hh[j], bhz = p.b_hh[p.H + j], bhn = p.b_hh[2 * p.H + j];
 
-  while (cur < count) {
-    const int nn = claim_unit(counter);
-    unit_fence();
-    unit_kloop<3, 4, true>(acc, a0, a1, smem, sl, li, hi, rows, ch0, nch);
-    gru_epilogue(p, acc, tq, (int64_t)(rb0 + cur) * 32, j0, lane, li, hi, bir, biz, bin, bhr, bhz, bhn);
+  int cur = claim_unit(counter);
+  if (cur < whole) {
+    int nxt = claim_unit(counter);
+    ARows rows;
+    {
+      const int64_t r0 = clampr(cur), r1 = clampr(nxt);
+      rows.c0 = p.a + r0 * p.ld_a + lofs; rows.c1 = p.h + r0 * p.ld_h + lofs;
+      rows.n0 = p.a + r1 * p.ld_a + lofs; rows.n1 = p.h + r1 * p.ld_h + lofs;
+    }
+    float4 a0[4], a1[4];
+    prologue_loads(a0, a1, rows, ch0, nch);
+    f32x16 acc[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) acc[n] = zero16();
-    cur = nxt;
-    nxt = nn;
-    rows.c0 = rows.n0; rows.c1 = rows.n1;
-    const int64_t r1 = clampr(nxt);
-    rows.n0 = p.a + r1 * p.ld_a + lofs; rows.n1 = p.h + r1 * p.ld_h + lofs;
+
+    while (cur < whole) {
+      const int nn = claim_unit(counter);
+      unit_fence();
+      unit_kloop<3, 4, true>(acc, a0, a1, smem, sl, li, hi, rows, ch0, nch);
+      gru_epilogue(p, acc, tq, (int64_t)(rb0 + cur) * 32, j0, lane, li, hi, bir, biz, bin, bhr, bhz, bhn);
+#pragma unroll
+      for (int n = 0; n < 4; ++n) acc[n] = zero16();
+      cur = nxt;
+      nxt = nn;
+      rows.c0 = rows.n0; rows.c1 = rows.n1;
+      const int64_t r1 = clampr(nxt);
+      rows.n0 = p.a + r1 * p.ld_a + lofs; rows.n1 = p.h + r1 * p.ld_h + lofs;
+    }
+  }
+  if (tail > 0) {
+    // Sub-unit s = accumulator group s % 3 of unit whole + s / 3.  Groups 0 / 1 ({r}, {z}) park their accumulator in the
+    // exchange area in the C-fragment layout (4 KB) and bump the unit's flag; group 2 ({n_i, h_n}) waits for the flag,
+    // fetches both and runs the unit's epilogue.  A wave takes its sub-units in rising order and only a group 2 waits,
+    // for the two sub-units right below it: by induction over s nothing waits for ever.
+    const int nsub = 3 * tail;
+    int s = claim_unit(counter + 1);
+    if (s >= nsub) return;
+    const int cbs = 32 * sl.ld;
+    auto rows_of = [&](int q, const float *&ra, const float *&rh) {
+      const int64_t r = clampr(whole + (q < nsub ? q : nsub - 1) / 3);
+      ra = p.a + r * p.ld_a + lofs; rh = p.h + r * p.ld_h + lofs;
+    };
+    ARows rows;
+    rows_of(s, rows.c0, rows.c1);
+    rows_of(s + 8, rows.n0, rows.n1);
+    float4 a0[4], a1[4];
+    prologue_loads(a0, a1, rows, ch0, nch);
+    for (; s < nsub; s += 8) {
+      const int unit = s / 3, grp = s - unit * 3;
+      float4 *const park = reinterpret_cast<float4 *>(xch) + (unit * 2) * 256 + lane;   // accumulator g: + 256 g, piece q: + 64 q
+      unit_fence();
+      if (grp < 2) {
+        f32x16 acc[1] = {zero16()};
+        unit_kloop<1, 1, false>(acc, a0, a1, smem + grp * cbs, sl, li, hi, rows, ch0, nch);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          park[grp * 256 + q * 64] = make_float4(acc[0][4 * q], acc[0][4 * q + 1], acc[0][4 * q + 2], acc[0][4 * q + 3]);
+        if (lane == 0) __hip_atomic_fetch_add(flags + unit, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else {
+        f32x16 nh[2] = {zero16(), zero16()};
+        unit_kloop<1, 2, true>(nh, a0, a1, smem + 2 * cbs, sl, li, hi, rows, ch0, nch);
+        while (__hip_atomic_load(flags + unit, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 2) __builtin_amdgcn_s_sleep(1);
+        f32x16 acc[4];
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 v = park[g * 256 + q * 64];
+            acc[g][4 * q] = v.x; acc[g][4 * q + 1] = v.y; acc[g][4 * q + 2] = v.z; acc[g][4 * q + 3] = v.w;
+          }
+        }
+        acc[2] = nh[0]; acc[3] = nh[1];
+        gru_epilogue(p, acc, tq, (int64_t)(rb0 + whole + unit) * 32, j0, lane, li, hi, bir, biz, bin, bhr, bhz, bhn);
+      }
+      rows.c0 = rows.n0; rows.c1 = rows.n1;
+      rows_of(s + 16, rows.n0, rows.n1);
+    }
   }
 }
 
@@ -1430,6 +1518,7 @@ int stream_gru(const float *a, int64_t ld_a, const float *h, int64_t ld_h, const
   p.n = n; p.M = m; p.H = hd; p.out = out; p.ld_out = ld_out; p.gates = gates;
   p.nrb = (int)((n + 31) / 32);
   p.ncs = hd / 32;
+  p.split = 0;
   const char *ring_env = getenv("PTGNN_AMD_GRU_RING");                        // "1": A/B + parity tests at small K
   const bool force_ring = ring_env && ring_env[0] == '1';
   if ((lds > (size_t)kLdsBudget && !(ring_env && ring_env[0] == '0')) || force_ring) {
@@ -1446,11 +1535,14 @@ int stream_gru(const float *a, int64_t ld_a, const float *h, int64_t ld_h, const
   if (lds > (size_t)kLdsBudget) return 0;
   dense_runs(p.nrb, p.ncs, p.rps, p.run_len);
   p.lds_floats = (int)(slab / 4);
+  // inference launches whose slab leaves room for the exchange area split the tail of a run (training keeps whole units)
+  p.split = (kSplitGru && !gates && lds + kGruSplitBytes <= (size_t)kLdsBudget) ? 1 : 0;
+  const size_t lds_launch = p.split ? lds + kGruSplitBytes : lds;
   const unsigned grid = (unsigned)(p.ncs * p.rps);
   {
     auto kern = k_stream_gru;
-    if (!set_lds(kern, lds)) return 0;
-    kern<<<grid, 512, lds, st>>>(p);
+    if (!set_lds(kern, lds_launch)) return 0;
+    kern<<<grid, 512, lds_launch, st>>>(p);
   }
   count_launch(PTGNN_AMD_KERNEL_STREAM_GRU);
   return 1;
