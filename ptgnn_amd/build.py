@@ -18,6 +18,7 @@ SOURCES = ["errors.cpp", "csr_build.hip", "gather_reduce.hip", "dense_f32.hip", 
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "dense_common.h"), os.path.join(CSRC, "stream_gemm.h"), os.path.join(CSRC, "wgrad_stream.h"),
            os.path.join(CSRC, "gather_reduce_core.h"), os.path.join(CSRC, "segment_chunks.h"), os.path.join(CSRC, "attention_tile.h"),
            os.path.join(CSRC, "decode_common.h"), os.path.join(CSRC, "half16.h"),
+           os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "softmax_state.h"),
            os.path.join(INCLUDE, "ptgnn_amd.h")]
 EXPORTS = os.path.join(CSRC, "exports.map")   # only ptgnn_amd_* leaves the library
 ARCH = "gfx950"

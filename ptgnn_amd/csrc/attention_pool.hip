@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_pool_partial(
           sc[k] = v;
         }
       }
-      const float mnew = fmaxf(m_run, half_wave_max(fmaxf(sc[0], sc[1])));
+      const float mnew = fmaxf(m_run, group_max<32>(fmaxf(sc[0], sc[1])));
       const float alpha = m_run == -INFINITY ? 0.0f : expf(m_run - mnew);
       float sum = 0.0f;
 #pragma unroll
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_pool_partial(
         if (r < R) pt[r * HP + hh] = e;
         sum += e;
       }
-      l_run = fmaf(l_run, alpha, half_wave_sum(sum));
+      l_run = fmaf(l_run, alpha, group_sum<32>(sum));
       m_run = mnew;
       if (hl == 0) alpha_s[hh] = alpha;
     }
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_pool_backward(
     const float *gg = gseg + (int64_t)hh * dim;
     float v = 0.0f;
     for (int d = hl; d < dim; d += 32) v = fmaf(gg[d], pg[d], v);
-    abar = half_wave_sum(v);
+    abar = group_sum<32>(v);
     lse = stats[(int64_t)ch.seg * 2 * heads + heads + hh];
   }
   float uc[HP][COLS], gc[HP][COLS], dacc[HP][COLS];     // the thread's columns of u and dP, its du accumulators
@@ -364,8 +364,7 @@ __global__ __launch_bounds__(256) void k_head_contract(const float *__restrict__
   const float *br = b + (g * heads + j / dk) * dim;
   float v = 0.0f;
   for (int d = lane; d < dim; d += 64) v = fmaf(wr[d], br[d], v);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = group_sum(v);
   if (lane == 0) out[pair] = v * scale;
 }
 

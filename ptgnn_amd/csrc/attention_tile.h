@@ -1,14 +1,14 @@
 // The row tile of the segment kernels that dot every row of a chunk with a few per-segment vectors: attention_pool.hip
 // (heads of u, and of dP in its backward) and segment_scores.hip (the L decoder states of a sample).  One copy of the
-// staging of the vectors and of the rows into LDS, of the score walk and of the half-wave reductions, so the two kernels
+// staging of the vectors and of the rows into LDS and of the score walk, so the two kernels
 // read a tile the same way; and the one launch helper that opts a kernel into more than 64 KiB of LDS.
 //
 // A tile is R rows of a chunk (segment_chunks.h) staged as xs[r * S + :] with S = dim | 1 (odd: lanes reading 32 rows at
 // one column hit 32 banks); the vectors lie in LDS as [dim][HP] (HP = vectors padded to a float4, the padding 0) and are
 // read as broadcast float4.  Thread (row r, part p) of the score walk dots ITS column slice of x_r with every vector; a
-// half-wave then adds the parts of a row in a fixed order.
+// half-wave then adds the parts of a row in a fixed order (group_sum<32> / group_max<32> of wave_ops.h).
 #pragma once
-#include "common.h"
+#include "wave_ops.h"
 
 namespace ptgnn_amd {
 
@@ -90,18 +90,6 @@ __device__ __forceinline__ void attn_score_walk(const float *__restrict__ xr, co
       }
     }
   }
-}
-
-__device__ __forceinline__ float half_wave_max(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 32));
-  return v;
-}
-
-__device__ __forceinline__ float half_wave_sum(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-  return v;
 }
 
 // launch `kern` with `lds_bytes` of dynamic LDS, raising its limit first when that is more than the default 64 KiB

@@ -54,7 +54,6 @@ __global__ __launch_bounds__(kDecThreads) void k_beam_candidates(
   __shared__ int s_count;
   const int b = blockIdx.x / W, j = blockIdx.x % W;
   const int t = threadIdx.x;
-  const int lane = t & (kWave - 1), wave = t >> 6;
   const int64_t r = blockIdx.x;                              // b W + j
   float *out_v = cand_score + r * W;
   int64_t *out_id = cand_id + r * W;
@@ -73,18 +72,8 @@ __global__ __launch_bounds__(kDecThreads) void k_beam_candidates(
   // 1. the normaliser (k_decode_step's fold)
   MaxSum a{-INFINITY, 0.0f};
   for (int c = t; c < vocab; c += kDecThreads) push(a, score_at(row, bias, c));
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    MaxSum m;
-    m.m = __shfl_xor(a.m, o, kWave);
-    m.s = __shfl_xor(a.s, o, kWave);
-    a = combine(a, m);
-  }
-  if (lane == 0) s_ms[wave] = a;
   if (t == 0) s_count = 0;
-  __syncthreads();
-  a = s_ms[0];
-  for (int w = 1; w < kDecWaves; ++w) a = combine(a, s_ms[w]);   // wave order
+  a = waves_in_order<kDecWaves>(wave_fold(a, combine), s_ms, combine);
   a = combine(a, MaxSum{total_copy[r], 1.0f});
   const float top = a.m, log_sum = a.m == -INFINITY ? 0.0f : logf(a.s);
 
@@ -149,16 +138,7 @@ __global__ __launch_bounds__(kDecThreads) void k_beam_candidates(
       const Cand c{value_of[s], 1, g < 0 ? 0 : g};
       if ((k == 0 || before(prev, c)) && before(c, mine)) mine = c;
     }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      const Cand c = shfl_xor_cand(mine, o);
-      if (before(c, mine)) mine = c;
-    }
-    if (lane == 0) s_cand[wave] = mine;
-    __syncthreads();
-    mine = s_cand[0];
-    for (int w = 1; w < kDecWaves; ++w)
-      if (before(s_cand[w], mine)) mine = s_cand[w];
+    mine = waves_in_order<kDecWaves>(wave_fold(mine, first_by(before)), s_cand, first_by(before));
     __syncthreads();                                         // s_cand is written again in the next round
     if (t == 0) out_v[k] = mine.v, out_id[k] = mine.id, out_class[k] = mine.rank;
     if (mine.rank == kNoCand) {                              // workgroup-uniform; nothing is left (nan scores)

@@ -80,14 +80,6 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
 }
 
-// sum of `v` over the LPR consecutive lanes of a row group: xor butterfly, every lane ends with the same bits
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPR);
-  return v;
-}
-
 // VEC (4 or 1) consecutive floats of a row as one float4 or one float access
 template <int VEC>
 __device__ __forceinline__ void vec_load(const float *p, float (&o)[VEC]) {

@@ -32,7 +32,7 @@
 
 #include <atomic>
 
-#include "common.h"
+#include "wave_ops.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -197,12 +197,7 @@ __device__ __forceinline__ void lds_barrier() {
 template <int NW>
 __device__ __forceinline__ int block_scan(int v, int *tmp) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
+  const int inc = wave_inclusive_scan(v);
   lds_barrier();                   // tmp may still be read by the previous scan's consumers
   if (lane == 63) tmp[wave] = inc;
   lds_barrier();
@@ -288,12 +283,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan(int32_t *__restrict__ agg, i
   }
   // exclusive scan of the group sums along the column: within the wave by shuffles, across the column's 8 waves
   // through LDS
-  int inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
+  const int inc = wave_inclusive_scan(sum);
   if (lane == 63) wtot[wave] = inc;
   __syncthreads();
   constexpr int WPC = G / 64;                     // waves per column
@@ -724,11 +714,7 @@ __global__ __launch_bounds__(256) void k_max_degree(const int32_t *__restrict__ 
     const int d = rowptr[r + 1] - rowptr[r];
     best = d > best ? d : best;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int other = __shfl_xor(best, o, 64);
-    best = other > best ? other : best;
-  }
+  best = group_max(best);
   if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(out, best);
 }
 

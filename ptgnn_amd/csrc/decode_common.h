@@ -1,39 +1,17 @@
 // What the decoding-step kernels share (decode_step.hip: greedy, top-1; beam_step.hip: the W best across W parents): the
-// running soft-max state with its commutative combine, the candidate of an arg-max, the order-preserving key of a float,
+// running soft-max state (MaxSum of softmax_state.h), the candidate of an arg-max, the order-preserving key of a float,
 // and the radix select of the n-th largest entry of a row of raw vocabulary scores with its tie cut.  One workgroup of
 // kDecThreads threads per row; thread t owns the columns t, t + kDecThreads, ... in every pass.
 #pragma once
 #include <math.h>
 
 #include "segment_chunks.h"
+#include "softmax_state.h"
 
 namespace ptgnn_amd {
 
 constexpr int kDecThreads = 1024;
 constexpr int kDecWaves = kDecThreads / kWave;
-
-// running soft-max state: the maximum and sum exp(. - maximum); (-inf, 0) is empty
-struct MaxSum {
-  float m, s;
-};
-
-// commutative: combine(a, b) and combine(b, a) have the same bits
-__device__ __forceinline__ MaxSum combine(const MaxSum &a, const MaxSum &b) {
-  MaxSum o;
-  o.m = fmaxf(a.m, b.m);
-  const float sa = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - o.m);
-  const float sb = b.m == -INFINITY ? 0.0f : b.s * expf(b.m - o.m);
-  o.s = sa + sb;
-  return o;
-}
-
-__device__ __forceinline__ void push(MaxSum &a, float v) {
-  if (v > a.m) {
-    a.s = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - v);
-    a.m = v;
-  }
-  if (a.m != -INFINITY) a.s += expf(v - a.m);
-}
 
 // a candidate of an arg-max: `rank` orders equal values (decode_step: -1 the row's top-1, else the slot that starts the
 // run; beam_step: the tie class of the entry)
@@ -47,14 +25,8 @@ __device__ __forceinline__ bool better(const Cand &a, const Cand &b) {
   return a.v > b.v || (a.v == b.v && a.rank < b.rank);
 }
 
-__device__ __forceinline__ Cand shfl_xor_cand(const Cand &a, int o) {
-  Cand b;
-  b.v = __shfl_xor(a.v, o, kWave);
-  b.rank = __shfl_xor(a.rank, o, kWave);
-  const int lo = __shfl_xor((int)(uint32_t)(uint64_t)a.id, o, kWave);
-  const int hi = __shfl_xor((int)(uint32_t)((uint64_t)a.id >> 32), o, kWave);
-  b.id = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  return b;
+__device__ __forceinline__ Cand lane_xor(const Cand &a, int o) {
+  return Cand{lane_xor(a.v, o), lane_xor(a.rank, o), lane_xor(a.id, o)};
 }
 
 // larger float <=> larger key; -0 and +0 share a key
@@ -67,6 +39,7 @@ __device__ __forceinline__ float score_at(const float *__restrict__ row, const f
   return row[c] + (bias ? bias[c] : 0.0f);
 }
 
+// not log_sum_exp2 of vocab_loss.hip, which rounds as torch.logsumexp does
 __device__ __forceinline__ float log_add_exp(float a, float b) {
   const float hi = fmaxf(a, b), lo = fminf(a, b);
   if (lo == -INFINITY) return hi;

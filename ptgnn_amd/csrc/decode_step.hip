@@ -13,9 +13,8 @@
 // One workgroup of kDecThreads threads per sample (B is about 50 and V at most about 20 000: the launch is bound by the
 // latency of one row, not by the chip; a row split over workgroups would need a second launch or a cross-workgroup
 // hand-off for 80 KB of L2-resident reads).  Thread t owns the columns t, t + kDecThreads, ... in every pass.
-//   1. One pass over the row: the running (maximum, sum) of csrc/vocab_loss.hip -- merged by an xor butterfly with a
-//      commutative combine, then the waves in wave order -- joined with the copy term, and the top-1 (value, lowest
-//      index).
+//   1. One pass over the row: the running (maximum, sum) of csrc/softmax_state.h, its threads and waves merged as that
+//      header says, joined with the copy term, and the top-1 (value, lowest index).
 //   2. K < V only: the K-th largest value by a radix select, eight bits a pass, over the order-preserving bit pattern of
 //      the floats (-0 counted as +0), a 256-bin histogram in LDS counted with INTEGER atomics (their result does not
 //      depend on the order of arrival); the row is re-read from L2.  Entries equal to the K-th value are in the K by
@@ -32,6 +31,9 @@
 namespace ptgnn_amd {
 namespace {
 
+// the order of the row's top-1: the larger value, the lower column among equals
+__device__ __forceinline__ bool first_top(const Cand &a, const Cand &b) { return a.v > b.v || (a.v == b.v && a.id < b.id); }
+
 __global__ __launch_bounds__(kDecThreads) void k_decode_step(
     const float *__restrict__ scores, int64_t ld, const float *__restrict__ bias, const float *__restrict__ copy,
     const float *__restrict__ total_copy, const int32_t *__restrict__ slot_memory, const int32_t *__restrict__ rowptr,
@@ -43,7 +45,6 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
   __shared__ RadixSelect s_select;
   const int b = blockIdx.x;
   const int t = threadIdx.x;
-  const int lane = t & (kWave - 1), wave = t >> 6;
   if (done[b]) {                                             // workgroup-uniform
     if (t == 0) next_tokens[b] = end_id;
     return;
@@ -58,24 +59,11 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
     push(a, v);
     if (v > best.v || best.id == INT32_MAX) best.v = v, best.id = c;
   }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    MaxSum m;
-    m.m = __shfl_xor(a.m, o, kWave);
-    m.s = __shfl_xor(a.s, o, kWave);
-    a = combine(a, m);
-    const Cand c = shfl_xor_cand(best, o);
-    if (c.v > best.v || (c.v == best.v && c.id < best.id)) best = c;
-  }
-  if (lane == 0) s_ms[wave] = a, s_cand[wave] = best;
-  __syncthreads();
-  a = s_ms[0];
-  best = s_cand[0];
-  for (int w = 1; w < kDecWaves; ++w) {                      // wave order
-    a = combine(a, s_ms[w]);
-    const Cand c = s_cand[w];
-    if (c.v > best.v || (c.v == best.v && c.id < best.id)) best = c;
-  }
+  a = wave_fold(a, combine);
+  best = wave_fold(best, first_by(first_top));
+  leader_store(best, s_cand);
+  a = waves_in_order<kDecWaves>(a, s_ms, combine);           // its barrier is s_cand's too
+  best = fold_in_order<kDecWaves>(s_cand, first_by(first_top));
   a = combine(a, MaxSum{total_copy[b], 1.0f});               // -inf: (max, sum) unchanged, bit for bit
   const float top = a.m, log_sum = a.m == -INFINITY ? 0.0f : logf(a.s);
   best.v = (best.v - top) - log_sum;
@@ -114,19 +102,11 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
   }
   if (wrong && bad) atomicAdd(bad, wrong);
   if (t == 0 && better(best, mine)) mine = best;             // -inf everywhere: the top-1
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const Cand c = shfl_xor_cand(mine, o);
-    if (better(c, mine)) mine = c;
-  }
-  if (lane == 0) s_cand[wave] = mine;
-  __syncthreads();
+  mine = wave_fold(mine, first_by(better));
+  mine = waves_in_order<kDecWaves>(mine, s_cand, first_by(better), t == 0);   // thread 0 alone folds the waves
   if (t != 0) return;
 
   // 4. the state
-  mine = s_cand[0];
-  for (int w = 1; w < kDecWaves; ++w)
-    if (better(s_cand[w], mine)) mine = s_cand[w];
   if (!(mine.rank < INT32_MAX)) mine = best;                 // nothing compared greater (nan scores): the top-1
   logprobs[b] += mine.v;
   if (mine.id == end_id) {

@@ -89,8 +89,7 @@ __global__ __launch_bounds__(256) void k_egc_combine_bwd4(const float *__restric
         make_float4(w * g.x, w * g.y, w * g.z, w * g.w);
     p = a.x * g.x + a.y * g.y + a.z * g.z + a.w * g.w;
   }
-#pragma unroll
-  for (int o = P / 2; o > 0; o >>= 1) p += __shfl_xor(p, o, P);
+  p = group_sum<P>(p);
   if (valid && dq == 0) gcoef[row * ld_gcoef + kb] = p;
 }
 

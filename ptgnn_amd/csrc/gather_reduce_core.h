@@ -35,6 +35,7 @@
 #include <mutex>
 
 #include "dense_common.h"   // f32x16, kcol(), act_apply(): the fused node update below multiplies like the GEMM kernels
+#include "wave_ops.h"       // group_sum: the LayerNorm of the node update
 
 namespace ptgnn_amd {
 

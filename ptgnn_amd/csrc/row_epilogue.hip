@@ -17,7 +17,7 @@
 // exact-erf GELU), so the training forward equals the inference forward bit for bit.
 #include <type_traits>
 
-#include "common.h"
+#include "wave_ops.h"
 
 namespace ptgnn_amd {
 namespace {

@@ -15,7 +15,7 @@
 // Every block starts on a 256-byte boundary.  (The weighted pool's partial rows used to follow its chunk table without
 // that padding: its workspace grew by up to 252 bytes when it moved here, the other sizes are what they were.)
 #pragma once
-#include "common.h"
+#include "wave_ops.h"
 
 namespace ptgnn_amd {
 
@@ -70,12 +70,7 @@ struct SegmentScan {
 
   __device__ __forceinline__ int step(int c) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
+    const int inc = wave_inclusive_scan(c);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     int run = carry + inc - c;

@@ -104,12 +104,12 @@ __global__ __launch_bounds__(kAttnThreads) void k_scores_partial(
           scores[(int64_t)perm[t0 + r] * vectors + hh] = sv;
         }
       }
-      const float mnew = fmaxf(m_run, half_wave_max(fmaxf(sc[0], sc[1])));
+      const float mnew = fmaxf(m_run, group_max<32>(fmaxf(sc[0], sc[1])));
       const float alpha = m_run == -INFINITY ? 0.0f : expf(m_run - mnew);
       float sum = 0.0f;
 #pragma unroll
       for (int k = 0; k < 2; ++k) sum += hl + 32 * k < rows ? expf(sc[k] - mnew) : 0.0f;
-      l_run = fmaf(l_run, alpha, half_wave_sum(sum));
+      l_run = fmaf(l_run, alpha, group_sum<32>(sum));
       m_run = mnew;
     }
   }

@@ -13,8 +13,8 @@
 //   k_shard_counts   halo rows per owner range (slot(bounds[p+1]) - slot(bounds[p])) + totals for the ONE host read-back
 //   k_shard_remap    second pass over the edge lists: remote source -> n_local + its halo slot
 // HBM-bound integer work; nothing here synchronises with the host.
-#include "common.h"
 #include "stream_gemm.h"
+#include "wave_ops.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -97,8 +97,7 @@ __global__ __launch_bounds__(256) void k_shard_blocks(const uint32_t *__restrict
     const int64_t w = w0 + k * 256 + threadIdx.x;
     c += w < words ? __popc(bitmap[w]) : 0;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = group_sum(c);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) block_sum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
@@ -121,8 +120,7 @@ __global__ __launch_bounds__(256) void k_shard_compact(const uint32_t *__restric
   {   // slots in front of this block = sum of the earlier blocks' counts
     int c = 0;
     for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) c += block_sum[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = group_sum(c);
     if (lane == 0) wsum[wave] = c;
     __syncthreads();
     if (threadIdx.x == 0) base_s = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -131,12 +129,7 @@ __global__ __launch_bounds__(256) void k_shard_compact(const uint32_t *__restric
   const int64_t w = (int64_t)blockIdx.x * kBlockWords + threadIdx.x;
   uint32_t bits = w < words ? bitmap[w] : 0u;
   const int mine = __popc(bits);
-  int inc = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
+  const int inc = wave_inclusive_scan(mine);
   __syncthreads();                       // base_s / wsum of the prefix above are read by now
   if (lane == 63) wsum[wave] = inc;
   __syncthreads();
@@ -171,8 +164,7 @@ __global__ __launch_bounds__(64) void k_shard_counts(const uint32_t *__restrict_
                                                      unsigned long long *__restrict__ stats) {
   int c = 0;
   for (int j = threadIdx.x; j < nblocks; j += 64) c += block_sum[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = group_sum(c);
   const int64_t total_marked = c;
   if (threadIdx.x == 0) stats[world + 1] = (unsigned long long)total_marked;
   for (int p = threadIdx.x; p < world; p += 64) {
@@ -246,8 +238,7 @@ __global__ __launch_bounds__(256) void k_uniq_pack(const uint8_t *__restrict__ f
     bitmap[w] = bits;
   }
   int c = __popc(bits);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = group_sum(c);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) block_sum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
@@ -263,8 +254,7 @@ __device__ __forceinline__ void uniq_counts_wave(const uint32_t *__restrict__ bi
   const int lane = threadIdx.x & 63;
   int c = 0;
   for (int j = lane; j < nblocks; j += 64) c += block_sum[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = group_sum(c);
   const int64_t total = c;
   if (lane == 0) counts[num_types] = total;
   int64_t first = 0, rows = 0;                     // lane t: the rows of edge type t (num_types <= 64 with a table)
@@ -280,24 +270,14 @@ __device__ __forceinline__ void uniq_counts_wave(const uint32_t *__restrict__ bi
   // the excess comes from the type whose load per workgroup moves the maximum least.
   const bool live = lane < num_types;
   const int units = live ? (int)((rows + 31) / 32) : 0;
-  int unit_incl = units;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(unit_incl, o, 64);
-    if (lane >= o) unit_incl += v;
-  }
+  const int unit_incl = wave_inclusive_scan(units);
   const int total_units = __shfl(unit_incl, 63, 64);
   int budget = budget_cus;
   if (budget > total_units / 8 + 1) budget = total_units / 8 + 1;
   int w = units == 0 ? 0 : (int)((int64_t)units * budget / (total_units > 0 ? total_units : 1));
   if (units > 0 && w == 0) w = 1;
-  auto wave_sum = [](int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
-  int sum = wave_sum(w);
-  const int nonempty = wave_sum(units > 0 ? 1 : 0);
+  int sum = group_sum(w);
+  const int nonempty = group_sum(units > 0 ? 1 : 0);
   if (budget < nonempty) budget = nonempty;
   for (int it = 0; it < 4 * 64 + budget_cus && sum != budget; ++it) {
     const bool give = sum < budget;
@@ -319,12 +299,7 @@ __device__ __forceinline__ void uniq_counts_wave(const uint32_t *__restrict__ bi
     if (lane == who) w += give ? 1 : -1;
     sum += give ? 1 : -1;
   }
-  int wg_incl = w;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(wg_incl, o, 64);
-    if (lane >= o) wg_incl += v;
-  }
+  const int wg_incl = wave_inclusive_scan(w);
   if (live) {
     table->src[lane] = unique_src + first;
     table->dst[lane] = unique_src + first;

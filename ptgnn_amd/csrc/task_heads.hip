@@ -13,8 +13,7 @@
 //
 // a. ROW LOSS OVER A LOGIT MATRIX (logit_loss).  Rows are cut into the 128-row chunks of segment_chunks.h (one segment: all
 //    rows); a workgroup takes a chunk, a wave a row.  Mode 0 (softmax cross-entropy) walks the row ONCE with a running
-//    (max, sum, arg-max) per lane -- logits spanning more than 100 do not overflow -- merges the lanes with an xor
-//    butterfly whose combine step is commutative (every lane ends with the same bits) and reads logit[target] directly.
+//    (max, sum, arg-max) per lane, merges the lanes (Soft of softmax_state.h) and reads logit[target] directly.
 //    Mode 1 (sigmoid / BCE) adds max(l, 0) - l t + log1p(exp(-|l|)) and counts tp / fp / fn with the prediction l >= 0.
 //    Every logit is read from HBM once per pass, whatever C.  A chunk leaves (loss sum as float64 | three int64 counts);
 //    k_logit_merge adds the chunks IN CHUNK ORDER (thread t the t-th contiguous run of chunks, thread 0 the runs in thread
@@ -35,6 +34,7 @@
 #include <math.h>
 
 #include "segment_chunks.h"
+#include "softmax_state.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -42,71 +42,10 @@ namespace {
 constexpr int kHeadThreads = 256;
 constexpr int kHeadWaves = kHeadThreads / kWave;
 constexpr int kPartSlots = 4;          // a chunk's partial: loss sum (float64 bits) | three int64 counts
-constexpr int kNone = INT_MAX;
 constexpr int kCandMaxDim = 1024;
 
 // totals block, 8-byte slots (PTGNN_AMD_HEAD_TOTALS_BYTES = 64): see include/ptgnn_amd.h
 enum { kTotSum = 0, kTotDenom = 1, kTotA = 2, kTotB = 3, kTotC = 4, kTotRows = 5 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// running soft-max state: the maximum, sum exp(. - maximum) and where the maximum was first seen (lowest index on ties)
-struct Soft {
-  float m, s;
-  int idx;
-};
-
-__device__ __forceinline__ Soft soft_empty() { return Soft{-INFINITY, 0.0f, kNone}; }
-
-__device__ __forceinline__ void soft_push(Soft &a, float v, int at) {
-  if (a.idx == kNone || v > a.m) {
-    a.s = (a.m == -INFINITY ? 0.0f : a.s * expf(a.m - v)) + 1.0f;
-    a.m = v;
-    a.idx = at;
-  } else {
-    a.s += v == -INFINITY ? 0.0f : expf(v - a.m);
-  }
-}
-
-// commutative: soft_merge(a, b) and soft_merge(b, a) have the same bits
-__device__ __forceinline__ Soft soft_merge(const Soft &a, const Soft &b) {
-  Soft o;
-  o.m = fmaxf(a.m, b.m);
-  const float sa = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - o.m);
-  const float sb = b.m == -INFINITY ? 0.0f : b.s * expf(b.m - o.m);
-  o.s = sa + sb;
-  const bool take_b = b.idx != kNone && (a.idx == kNone || b.m > a.m || (b.m == a.m && b.idx < a.idx));
-  o.idx = take_b ? b.idx : a.idx;
-  return o;
-}
-
-__device__ __forceinline__ Soft soft_wave(Soft a) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    Soft b;
-    b.m = __shfl_xor(a.m, o, kWave);
-    b.s = __shfl_xor(a.s, o, kWave);
-    b.idx = __shfl_xor(a.idx, o, kWave);
-    a = soft_merge(a, b);
-  }
-  return a;
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // a. logit loss
@@ -132,7 +71,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_logit_loss(
       if constexpr (MODE == 0) {
         Soft a = soft_empty();
         for (int c = lane; c < classes; c += kWave) soft_push(a, row[c], c);
-        a = soft_wave(a);
+        a = wave_fold(a, soft_merge);
         const float l = a.m + logf(a.s);
         if (lane == 0) {
           lse[r] = l;
@@ -159,10 +98,10 @@ __global__ __launch_bounds__(kHeadThreads) void k_logit_loss(
           fp += p && !t ? 1 : 0;
           fn += !p && t ? 1 : 0;
         }
-        loss = wave_sum(part);
-        c0 = wave_sum(tp);
-        c1 = wave_sum(fp);
-        c2 = wave_sum(fn);
+        loss = group_sum(part);
+        c0 = group_sum(tp);
+        c1 = group_sum(fp);
+        c2 = group_sum(fn);
       }
       if (lane == 0 && row_loss) row_loss[r] = loss;
     }
@@ -175,10 +114,10 @@ __global__ __launch_bounds__(kHeadThreads) void k_logit_loss(
   }
   __syncthreads();
   if (wave == 0) {                     // the chunk's rows in a fixed tree: lane l adds rows l and l + 64, then the butterfly
-    const double l = wave_sum((double)s_loss[lane] + (double)s_loss[lane + kWave]);
-    const int a = wave_sum(s_c[0][lane] + s_c[0][lane + kWave]);
-    const int b = wave_sum(s_c[1][lane] + s_c[1][lane + kWave]);
-    const int c = wave_sum(s_c[2][lane] + s_c[2][lane + kWave]);
+    const double l = group_sum((double)s_loss[lane] + (double)s_loss[lane + kWave]);
+    const int a = group_sum(s_c[0][lane] + s_c[0][lane + kWave]);
+    const int b = group_sum(s_c[1][lane] + s_c[1][lane + kWave]);
+    const int c = group_sum(s_c[2][lane] + s_c[2][lane + kWave]);
     if (lane == 0) {
       int64_t *out = partial + (int64_t)blockIdx.x * kPartSlots;
       out[0] = __double_as_longlong(l);
@@ -317,7 +256,7 @@ __device__ __forceinline__ float wave_dot(const float *__restrict__ a, const flo
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc = fmaf(av[v], bv[v], acc);
   }
-  return wave_sum(acc);
+  return group_sum(acc);
 }
 
 // row id clamped into [0, num_nodes); `bad` counts the ids that were outside
@@ -350,28 +289,15 @@ __global__ __launch_bounds__(kHeadThreads) void k_candidate_scores(
     const int64_t nd = clamp_node(cand_idx[c], num_nodes, bad);
     const float sc = __fadd_rn(wave_dot<VEC>(x + nd * ld_x, w, dim, lane), sd);
     if (lane == 0) scores[c] = sc;
-    if (run.idx == kNone || sc > run.m || (sc == run.m && c < run.idx)) {
-      run.s = (run.m == -INFINITY ? 0.0f : run.s * expf(run.m - sc)) + 1.0f;
-      run.m = sc;
-      run.idx = c;
-    } else {
-      run.s += sc == -INFINITY ? 0.0f : expf(sc - run.m);
-    }
+    soft_push_lowest(run, sc, c);                                // plan order: not ascending in c
   }
-  if (lane == 0) {
-    s_run[wave] = run;
-    s_bad[wave] = bad;
-  }
-  __syncthreads();
+  if (lane == 0) s_bad[wave] = bad;
+  const Soft a = waves_in_order<kHeadWaves>(run, s_run, soft_merge, threadIdx.x == 0);
   if (threadIdx.x == 0) {
-    Soft a = s_run[0];
     int nb = s_bad[0] + bad_slot;
-    for (int v = 1; v < kHeadWaves; ++v) {                       // wave order
-      a = soft_merge(a, s_run[v]);
-      nb += s_bad[v];
-    }
-    lse[g] = a.idx == kNone ? -INFINITY : a.m + logf(a.s);
-    argmax[g] = a.idx == kNone ? (int64_t)num_candidates : (int64_t)a.idx;
+    for (int v = 1; v < kHeadWaves; ++v) nb += s_bad[v];
+    lse[g] = a.idx == kSoftNone ? -INFINITY : a.m + logf(a.s);
+    argmax[g] = a.idx == kSoftNone ? (int64_t)num_candidates : (int64_t)a.idx;
     bad_part[g] = nb;
   }
 }

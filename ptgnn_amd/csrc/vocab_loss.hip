@@ -13,14 +13,14 @@
 // Exact fp32, no float atomics; every result is a fixed function of the shapes.
 //
 // a. The columns of a row are cut into chunks of kFwdCols; workgroup (r, c) walks chunk c of row r ONCE with a running
-//    (max, sum) per thread -- logits spanning more than 100 do not overflow --, merges its threads (xor butterfly with a
-//    commutative combine, then the four waves in wave order) and leaves (max, sum) in the workspace.  The thread that meets
-//    column targets[r] leaves s[r, targets[r]] there as well, so no score is read twice.  k_vocab_loss_merge (a thread per
-//    row) folds the chunks IN CHUNK ORDER and adds the copy term.  It keeps the normaliser as the pair (maximum M, log of
-//    the sum relative to M): norm = M + log_sum is rounded at the magnitude of the logits (an ulp of 1.5e-5 at 140), the
-//    pair is not, so picked = (s - M) - log_sum and the backward's exp((s - M) - log_sum) stay accurate to 1e-7 however
-//    large the logits are.  Thread t of a workgroup owns the same columns whether the row is read with 16-byte loads or
-//    (unaligned rows, the ragged tail) dword loads: the bits do not depend on the alignment.
+//    (max, sum) per thread, merges its threads and its four waves (MaxSum of softmax_state.h, which says how) and leaves
+//    (max, sum) in the workspace.  The thread that meets column targets[r] leaves s[r, targets[r]] there as well, so no
+//    score is read twice.  k_vocab_loss_merge (a thread per row) folds the chunks IN CHUNK ORDER and adds the copy term.
+//    It keeps the normaliser as the pair (maximum M, log of the sum relative to M): norm = M + log_sum is rounded at the
+//    magnitude of the logits (an ulp of 1.5e-5 at 140), the pair is not, so picked = (s - M) - log_sum and the
+//    backward's exp((s - M) - log_sum) stay accurate to 1e-7 however large the logits are.  Thread t of a workgroup
+//    owns the same columns whether the row is read with 16-byte loads or (unaligned rows, the ragged tail) dword loads:
+//    the bits do not depend on the alignment.
 // b. Workgroup (row block, column chunk): kBwdRows rows x kBwdCols columns, thread t four columns; it walks its rows in
 //    row order, writes the gradient and keeps the column sums, which it leaves as the row block's partial of grad_bias --
 //    the same pass, no second read of [R, V].  k_vocab_bias_fold adds the partials IN ROW-BLOCK ORDER.
@@ -32,6 +32,7 @@
 #include <math.h>
 
 #include "segment_chunks.h"
+#include "softmax_state.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -42,30 +43,6 @@ constexpr int kFwdGroups = 2;                               // groups of four co
 constexpr int kFwdCols = kVocThreads * 4 * kFwdGroups;      // 2048 columns per forward workgroup
 constexpr int kBwdCols = kVocThreads * 4;                   // 1024 columns per backward workgroup
 constexpr int kBwdRows = 8;                                 // rows per backward workgroup = rows of one grad_bias partial
-
-// running soft-max state: the maximum and sum exp(. - maximum); (-inf, 0) is empty
-struct MaxSum {
-  float m, s;
-};
-
-// commutative: combine(a, b) and combine(b, a) have the same bits
-__device__ __forceinline__ MaxSum combine(const MaxSum &a, const MaxSum &b) {
-  MaxSum o;
-  o.m = fmaxf(a.m, b.m);
-  const float sa = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - o.m);
-  const float sb = b.m == -INFINITY ? 0.0f : b.s * expf(b.m - o.m);
-  o.s = sa + sb;
-  return o;
-}
-
-__device__ __forceinline__ void push4(MaxSum &a, const float (&v)[4]) {
-  const float gm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-  if (gm > a.m) {
-    a.s = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - gm);
-    a.m = gm;
-  }
-  if (a.m != -INFINITY) a.s += (expf(v[0] - a.m) + expf(v[1] - a.m)) + (expf(v[2] - a.m) + expf(v[3] - a.m));
-}
 
 // s[r, col0 .. col0 + 3]: one 16-byte load where the row allows it and the four columns exist, else dword loads; columns
 // past the vocabulary read as -inf
@@ -115,20 +92,8 @@ __global__ __launch_bounds__(kVocThreads) void k_vocab_loss_partial(
     push4(a, v[u]);
     if (tgt >= col0 && tgt < col0 + 4 && tgt < vocab) target_score[r] = v[u][(int)(tgt - col0)];
   }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    MaxSum b;
-    b.m = __shfl_xor(a.m, o, kWave);
-    b.s = __shfl_xor(a.s, o, kWave);
-    a = combine(a, b);
-  }
-  if ((t & (kWave - 1)) == 0) s_wave[t >> 6] = a;
-  __syncthreads();
-  if (t == 0) {
-    a = s_wave[0];
-    for (int w = 1; w < kVocWaves; ++w) a = combine(a, s_wave[w]);     // wave order
-    partial[blockIdx.x] = make_float2(a.m, a.s);
-  }
+  a = waves_in_order<kVocWaves>(wave_fold(a, combine), s_wave, combine, t == 0);
+  if (t == 0) partial[blockIdx.x] = make_float2(a.m, a.s);
 }
 
 // Thread per row: the chunks in chunk order, then the copy term and the picked entry.
@@ -222,7 +187,7 @@ __global__ __launch_bounds__(kVocThreads) void k_vocab_bias_fold(const float *__
 // c. the [B, L] tail (grucopydecoder.py:171-212)
 // ------------------------------------------------------------------------------------------------------------------
 // any = logsumexp(stack(gen', copied)) as torch computes it: the maximum (0 where it is infinite) taken out, no fused
-// multiply-add
+// multiply-add (not log_add_exp of decode_common.h, which is log1p-based and guards only lo = -inf)
 __device__ __forceinline__ float log_sum_exp2(float a, float b) {
   float m = fmaxf(a, b);
   if (fabsf(m) == INFINITY) m = 0.0f;

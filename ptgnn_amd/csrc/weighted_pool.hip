@@ -33,12 +33,6 @@ __device__ __forceinline__ float pool_sigmoid(float v) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
 }
 
-// group_sum of common.h for a lane count known only at run time (a power of two <= 64)
-__device__ __forceinline__ float lanes_sum(float v, int lanes) {
-  for (int o = lanes >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 constexpr int kPoolThreads = 256;
 // COLS = chunks (float4 or float) of one row a lane holds: 1 for dim <= lanes * VEC (hidden 64 ... 256), up to 16
 

@@ -227,6 +227,18 @@ def test_logit_loss_all_rows_ignored_and_ties():
     assert argmax.tolist() == [5, 3, 127]                                                 # the lowest index on ties
 
 
+def test_logit_loss_rows_that_are_or_start_with_minus_infinity():
+    """The edge rule of csrc/softmax_state.h for the state with an arg-max: it takes its first element unconditionally, so
+    a row of -inf has lse = -inf and its first index as the arg-max, and a leading -inf is forgotten by what follows."""
+    logits = torch.tensor([[-INF] * 5, [-INF, 0.5, -1.25, 2.0, 0.25], [0.75, -0.5, 1.5, -2.0, 0.0]])
+    _, lse, argmax, _, _ = ops.logit_loss(logits.to(DEV), None, "softmax")
+    exact = torch.logsumexp(logits.double(), dim=-1)                                      # on the CPU
+    assert exact.tolist()[0] == -INF and bool(torch.isfinite(exact[1:]).all())
+    assert torch.equal(torch.isnan(lse.cpu()), torch.isnan(exact))
+    assert attributed(lse, torch.logsumexp(logits, dim=-1), exact, "lse")                 # -inf at the same positions
+    assert argmax.tolist() == [0, 3, 2]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. the candidate kernel against float64
 # ---------------------------------------------------------------------------------------------------------------------
@@ -300,6 +312,42 @@ def test_candidate_tie_goes_to_the_lowest_position_and_bad_nodes_are_counted():
     assert int(argmax[1]) == 0 and float(scores[0]) == float(scores[2]) == float(scores[3])
     assert int(totals[4]) == 2                                         # clamped and counted, never used as an index
     assert bool(torch.isfinite(lse).all())
+
+
+def test_candidate_slots_whose_first_candidate_scores_minus_infinity():
+    """The edge rule of csrc/softmax_state.h through soft_push_lowest: the candidate a wave meets first (the first of the
+    slot in plan order) scores -inf and is taken unconditionally; finite ones behind it (slot 0: wave 0 also has the
+    slot's fifth) forget it, and a wave that holds nothing else (slot 1: three candidates, one per wave) adds nothing
+    to the slot's sum.  Slot 2 is finite.  A slot of -inf only cannot be built: its slot's own term is finite."""
+    D, slot_sizes = 8, [6, 3, 2]
+    gen = torch.Generator().manual_seed(4000)
+    G, Cn = len(slot_sizes), sum(slot_sizes)
+    cand_slot = torch.repeat_interleave(torch.arange(G), torch.tensor(slot_sizes))[torch.randperm(Cn, generator=gen)]
+    cand_idx, slot_idx = torch.arange(Cn), torch.arange(Cn, Cn + G)                       # candidate c is node c
+    x, w = torch.randn(Cn + G, D, generator=gen), torch.randn(1, 2 * D, generator=gen)
+    w[0, 0] = 0.75                                                                        # -inf * w stays -inf
+    plan = ops.build_plan([(cand_slot.to(DEV), cand_slot.to(DEV))], G)
+    plan.wait()
+    rowptr, perm = plan.rowptr.cpu().tolist(), plan.perm.cpu().tolist()
+    firsts = [perm[rowptr[g]] for g in (0, 1)]
+    assert [int(cand_slot[c]) for c in firsts] == [0, 1]
+    x[firsts, 0] = -INF
+    _, scores, lse, argmax, _ = ops.candidate_scores(x.to(DEV), cand_idx.to(DEV), slot_idx.to(DEV), cand_slot.to(DEV), plan,
+                                                     w.to(DEV), None)
+    want = {}
+    for dt in (torch.float32, torch.float64):                                             # on the CPU
+        s = x.to(dt)[cand_idx] @ w.to(dt)[0, :D] + (x.to(dt)[slot_idx] @ w.to(dt)[0, D:])[cand_slot]
+        want[dt] = s, torch.stack([torch.logsumexp(s[cand_slot == g], dim=0) for g in range(G)])
+    s64, lse64 = want[torch.float64]
+    assert (s64 == -INF).nonzero().flatten().tolist() == sorted(firsts) and bool(torch.isfinite(lse64).all())
+    assert not bool(torch.isnan(scores).any()) and not bool(torch.isnan(lse).any())
+    assert attributed(scores, want[torch.float32][0], s64, "scores")                      # -inf at the same positions
+    assert attributed(lse, want[torch.float32][1], lse64, "lse")
+    for g in range(G):
+        own = torch.nonzero(cand_slot == g).flatten()
+        top2 = s64[own].topk(2)[0]
+        assert float(top2[0] - top2[1]) > 1e-3                                            # a decision fp32 resolves
+        assert int(argmax[g]) == int(own[s64[own].argmax()]), g
 
 
 @pytest.mark.parametrize("D", [64, 6], ids=["kernel", "composed"])

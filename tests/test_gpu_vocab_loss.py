@@ -174,6 +174,27 @@ def test_an_out_of_range_target_gives_a_nan_for_its_row_only():
             assert bool(torch.isfinite(bad["grad_scores"]).all())     # the bad row has no picked entry: softmax term only
 
 
+def test_rows_that_are_or_start_with_minus_infinity():
+    """The edge rule of csrc/softmax_state.h for the plain (max, sum) state: a row of -inf stays empty, (-inf, 0), and
+    its norm is -inf, never nan; a leading -inf is forgotten by what follows.  9 columns: rows on a 16-byte stride run
+    the float4 path over columns 0 .. 7 and the ragged tail for column 8, the others the dword path."""
+    rows = torch.tensor([[-INF] * 9, [-INF, 0.5, -1.25, 2.0, 0.25, -0.75, 1.5, -2.0, 1.0]])
+    exact = torch.logsumexp(rows.double(), dim=-1)                     # on the CPU
+    want32 = torch.logsumexp(rows, dim=-1)
+    assert float(exact[0]) == -INF and math.isfinite(float(exact[1]))
+    norms = []
+    for pad in (3, 0):
+        storage = torch.zeros(2, 9 + pad)
+        storage[:, :9] = rows
+        norm, _, stats = ops.vocab_loss(storage.to(DEV)[:, :9])
+        norm = norm.cpu()
+        assert torch.equal(norm == -INF, exact == -INF) and torch.equal(torch.isnan(norm), torch.isnan(exact)), pad
+        assert stats[0].tolist() == [-INF, 0.0]                        # the empty state, and no logf(0)
+        assert attributed(norm[1:], want32[1:], exact[1:], f"norm ld=9+{pad}"), pad
+        norms.append(norm)
+    assert torch.equal(norms[0], norms[1])                             # the bits do not depend on the load path
+
+
 def test_two_calls_give_the_same_bits():
     for V, R, pad in ((20000, 14, 0), (2049, 9, 3), (23, 8, 3)):
         case = vocab_case(V, R, pad, True, "neg_inf", 60.0)
