@@ -212,6 +212,14 @@ enum {
   PTGNN_AMD_KERNEL_EDGE16_DST = PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_, /* ptgnn_amd_edge_dst_linear16 */
   PTGNN_AMD_KERNEL_EDGE16_DST_END_
 };
+/* A twelfth id range: the finishing route of the beam search (csrc/beam_step.hip: the step that writes back-pointer pairs,
+ * its two kernels counted as one, and the backtrack).  A range of its own, so the seventh range ends where it did. */
+enum {
+  PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_ = 704,
+  PTGNN_AMD_KERNEL_BEAM_STEP_LINKS = PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_, /* ptgnn_amd_search_step_links_f32 */
+  PTGNN_AMD_KERNEL_BEAM_BACKTRACK,                                        /* ptgnn_amd_search_backtrack */
+  PTGNN_AMD_KERNEL_BEAM_FINISH_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1316,6 +1324,63 @@ int ptgnn_amd_beam_step_f32(const float *scores, int64_t ld, const float *bias /
                             int32_t *done_out, int64_t *lengths_out, int64_t *tokens_out, int64_t *next_tokens,
                             int64_t *parent_rows, int32_t *bad /* nullable */, void *workspace, size_t workspace_bytes,
                             void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The finishing route of the beam search (csrc/beam_step.hip): length normalisation, back-pointers in place of copied
+ * histories, and a count of the live slots that lets the host leave its loop early.  Two entries beside the step above,
+ * which keeps its code and its bits.  (The names say "search" and "greedy": the symbol sets of the two steps above are
+ * closed.)
+ *
+ * ptgnn_amd_search_step_links_f32: the step above without tokens_in / tokens_out, with
+ *   key_scale float [max_steps + 1], every entry > 0: a candidate whose parent has lengths_in == l is PLACED by
+ *     key = score * key_scale[l + 1] in place of rule 1. (higher key; 2.-4. as above).  l + 1 counts the scored decisions
+ *     of the candidate -- the appended tokens, plus END's once it has finished -- and is the same for every candidate of a
+ *     parent, a finished parent standing for itself included, so the order inside a parent is that of the raw sums.  The
+ *     host makes the table (GNMT: ((5 + n) / 6) ** -alpha, in double, rounded once); nothing is raised to a power or
+ *     divided on the device.  -inf stays -inf and a nan never compares first.  beam_scores_out holds the RAW sums, in key
+ *     order: with a table that is not all ones they need not descend.  An all-ones table gives the bits of the step above.
+ *   links int32 [max_steps, B, W, 2]: slot p of sample b writes links[step, b, p] = (the id it appends, or -1 where it
+ *     is or becomes finished; its parent slot 0 .. W - 1).  Ids fit: element keys are below 2 ** 22, vocabulary ids below
+ *     the int32 limit the entry enforces.
+ *   live int32 [max_steps], nullable, zeroed by the caller once per call: the number of slots of the sample with
+ *     done_out == 0 is added to live[step], one integer atomic per sample.  Once live[s] == 0 every later step is the
+ *     identity (a finished slot is its own single candidate, its key does not change, the slots are in selection order).
+ *   The workspace is that of the step above: ptgnn_amd_beam_step_workspace_bytes(...).
+ * ptgnn_amd_search_backtrack: one launch per call, after the loop.  For every final slot (b, w) it walks
+ *   s = steps_run - 1 .. 0 through links: tokens[b, w, s] = id, slot = parent; and writes -1 at every column
+ *   >= steps_run, so tokens int64 [B, W, max_steps] needs no fill.  A token appended at step s sits at column s, because a
+ *   live hypothesis has appended at every earlier step: no length arithmetic.  Cost: one thread per final slot, a chain
+ *   of steps_run DEPENDENT 8-byte loads each, once per call, against 16 max_steps B W bytes of copied histories per STEP.
+ * Both: exact fp32, integer atomics only, fixed fold orders -- two calls give the same bits.  Before any device work a
+ * null key_scale / links / tokens, steps_run outside [0, max_steps] and the size conditions of the step above answer
+ * PTGNN_AMD_EINVAL, sizes beyond int32 indexing (2 B W max_steps pairs included) PTGNN_AMD_EUNSUPPORTED; num_samples == 0
+ * launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_search_step_links_f32(const float *scores, int64_t ld, const float *bias /* nullable */,
+                                    const float *copy_scores, const float *total_copy, const int32_t *slot_memory,
+                                    const int32_t *rowptr, const int64_t *slot_ids, int64_t num_samples,
+                                    int64_t num_memories, int32_t vocab, int32_t top_k, int32_t beam_width, int64_t unk_id,
+                                    int64_t end_id, int32_t step, int32_t max_steps, const float *key_scale,
+                                    const float *beam_scores_in, const int32_t *done_in, const int64_t *lengths_in,
+                                    float *beam_scores_out, int32_t *done_out, int64_t *lengths_out, int64_t *next_tokens,
+                                    int64_t *parent_rows, int32_t *links, int32_t *live /* nullable */,
+                                    int32_t *bad /* nullable */, void *workspace, size_t workspace_bytes, void *stream);
+int ptgnn_amd_search_backtrack(const int32_t *links, int64_t num_samples, int32_t beam_width, int32_t steps_run,
+                               int32_t max_steps, int64_t *tokens, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The greedy-decoding step (csrc/decode_step.hip, ptgnn_amd_decode_step_f32: the same kernel, arguments, checks, bits and
+ * counter family) with live int32 [max_steps], required, zeroed by the caller once per call: a sample that is not done
+ * AFTER the step adds 1 to live[step] (an integer atomic).  live[s] == 0: every later step changes nothing but
+ * next_tokens, and the host may leave its loop.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_greedy_step_live_f32(const float *scores, int64_t ld, const float *bias /* nullable */,
+                                   const float *copy_scores, const float *total_copy, const int32_t *slot_memory,
+                                   const int32_t *rowptr, const int64_t *slot_ids, int64_t num_samples,
+                                   int64_t num_memories, int32_t vocab, int32_t top_k, int64_t unk_id, int64_t end_id,
+                                   int32_t step, int32_t max_steps, int32_t *done, int64_t *lengths, float *logprobs,
+                                   int64_t *tokens, int64_t *next_tokens, int32_t *live, int32_t *bad /* nullable */,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks (csrc/half_gemm.hip).

@@ -190,6 +190,13 @@ SIGNATURES = {
     "ptgnn_amd_beam_step_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64,
                                            _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _c.c_size_t, _vp]),
+    "ptgnn_amd_search_step_links_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32,
+                                                   _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _c.c_size_t, _vp]),
+    "ptgnn_amd_search_backtrack": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "ptgnn_amd_greedy_step_live_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64,
+                                                  _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t,
+                                                  _vp]),
     "ptgnn_amd_half_supported": (_c.c_int, [_c.c_int, _i32, _i32, _c.c_int]),
     "ptgnn_amd_half_linear": (_c.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _c.c_int, _c.c_int, _vp, _i64, _vp]),
     "ptgnn_amd_half_gru_cell": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _c.c_int, _vp,

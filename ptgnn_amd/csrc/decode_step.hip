@@ -23,7 +23,9 @@
 //      whose slot starts a run walks it in slot order under a running maximum, subtracts the normaliser, merges with the
 //      id's vocabulary entry where step 2 admits it, and the workgroup takes the arg-max: larger value first, then the
 //      top-1 before any group, then the lower id (= the earlier run).
-//   4. Thread 0 updates the state.  A sample that is done is fed end_id and changes nothing else.
+//   4. Thread 0 updates the state.  A sample that is done is fed end_id and changes nothing else.  With `live` (the
+//      early exit of ptgnn_amd_greedy_step_live_f32) a sample that is not done after the step adds 1 to live[step]: an
+//      integer atomic, so the sum does not depend on the order of arrival.
 // Exact ties are the one place where the reference leaves the outcome open (to torch.topk and to dict order); here they
 // are decided as above.  No float atomics, fixed fold orders: two launches give the same bits.
 #include "decode_common.h"
@@ -39,7 +41,8 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
     const float *__restrict__ total_copy, const int32_t *__restrict__ slot_memory, const int32_t *__restrict__ rowptr,
     const int64_t *__restrict__ slot_ids, int64_t num_memories, int vocab, int top_k, int64_t unk_id, int64_t end_id,
     int step, int max_steps, int32_t *__restrict__ done, int64_t *__restrict__ lengths, float *__restrict__ logprobs,
-    int64_t *__restrict__ tokens, int64_t *__restrict__ next_tokens, int32_t *__restrict__ bad) {
+    int64_t *__restrict__ tokens, int64_t *__restrict__ next_tokens, int32_t *__restrict__ bad,
+    int32_t *__restrict__ live) {
   __shared__ MaxSum s_ms[kDecWaves];
   __shared__ Cand s_cand[kDecWaves];
   __shared__ RadixSelect s_select;
@@ -114,8 +117,40 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_step(
   } else {
     if (step < max_steps) tokens[(int64_t)b * max_steps + step] = mine.id;
     lengths[b] += 1;
+    if (live) atomicAdd(live + step, 1);
   }
   next_tokens[b] = mine.id < vocab ? mine.id : unk_id;
+}
+
+// what the two entries share: the checks, then the one launch
+int decode_step_launch(const float *scores, int64_t ld, const float *bias, const float *copy_scores, const float *total_copy,
+                       const int32_t *slot_memory, const int32_t *rowptr, const int64_t *slot_ids, int64_t num_samples,
+                       int64_t num_memories, int32_t vocab, int32_t top_k, int64_t unk_id, int64_t end_id, int32_t step,
+                       int32_t max_steps, int32_t *done, int64_t *lengths, float *logprobs, int64_t *tokens,
+                       int64_t *next_tokens, int32_t *bad, int32_t *live, bool needs_live, void *stream_) {
+  PTGNN_REQUIRE(num_samples >= 0 && num_memories >= 0 && vocab >= 1 && top_k >= 1, PTGNN_AMD_EINVAL,
+                "decode_step: bad sizes (samples %lld, memories %lld, vocab %d, top_k %d)", (long long)num_samples,
+                (long long)num_memories, vocab, top_k);
+  PTGNN_REQUIRE(ld >= vocab, PTGNN_AMD_EINVAL, "decode_step: leading dimension %lld < vocab %d", (long long)ld, vocab);
+  PTGNN_REQUIRE(step >= 0 && step < max_steps, PTGNN_AMD_EINVAL, "decode_step: step %d outside [0, %d)", step, max_steps);
+  PTGNN_REQUIRE(unk_id >= 0 && unk_id < vocab && end_id >= 0 && end_id < vocab, PTGNN_AMD_EINVAL,
+                "decode_step: unk_id %lld / end_id %lld outside the vocabulary of %d", (long long)unk_id,
+                (long long)end_id, vocab);
+  const int64_t lim = (int64_t)1 << 31;
+  PTGNN_REQUIRE(num_samples < lim && num_memories < lim && vocab < lim - kDecThreads &&
+                    num_samples <= (lim - 1) / max_steps,
+                PTGNN_AMD_EUNSUPPORTED, "decode_step: too many samples / memories / columns");
+  if (num_samples == 0) return PTGNN_AMD_OK;
+  PTGNN_REQUIRE(scores && total_copy && rowptr && done && lengths && logprobs && tokens && next_tokens &&
+                    (num_memories == 0 || (copy_scores && slot_memory && slot_ids)),
+                PTGNN_AMD_EINVAL, "decode_step: null pointer");
+  PTGNN_REQUIRE(live || !needs_live, PTGNN_AMD_EINVAL, "decode_step: null live counter");
+  k_decode_step<<<(unsigned)num_samples, kDecThreads, 0, (hipStream_t)stream_>>>(
+      scores, ld, bias, copy_scores, total_copy, slot_memory, rowptr, slot_ids, num_memories, vocab, top_k, unk_id, end_id,
+      step, max_steps, done, lengths, logprobs, tokens, next_tokens, bad, live);
+  PTGNN_LAUNCH_CHECK();
+  count_launch(PTGNN_AMD_KERNEL_DECODE_STEP);
+  return PTGNN_AMD_OK;
 }
 
 }  // namespace
@@ -136,26 +171,20 @@ extern "C" int ptgnn_amd_decode_step_f32(const float *scores, int64_t ld, const 
                                          int64_t *tokens, int64_t *next_tokens, int32_t *bad, void *workspace,
                                          size_t workspace_bytes, void *stream_) {
   (void)workspace, (void)workspace_bytes;
-  PTGNN_REQUIRE(num_samples >= 0 && num_memories >= 0 && vocab >= 1 && top_k >= 1, PTGNN_AMD_EINVAL,
-                "decode_step: bad sizes (samples %lld, memories %lld, vocab %d, top_k %d)", (long long)num_samples,
-                (long long)num_memories, vocab, top_k);
-  PTGNN_REQUIRE(ld >= vocab, PTGNN_AMD_EINVAL, "decode_step: leading dimension %lld < vocab %d", (long long)ld, vocab);
-  PTGNN_REQUIRE(step >= 0 && step < max_steps, PTGNN_AMD_EINVAL, "decode_step: step %d outside [0, %d)", step, max_steps);
-  PTGNN_REQUIRE(unk_id >= 0 && unk_id < vocab && end_id >= 0 && end_id < vocab, PTGNN_AMD_EINVAL,
-                "decode_step: unk_id %lld / end_id %lld outside the vocabulary of %d", (long long)unk_id,
-                (long long)end_id, vocab);
-  const int64_t lim = (int64_t)1 << 31;
-  PTGNN_REQUIRE(num_samples < lim && num_memories < lim && vocab < lim - kDecThreads &&
-                    num_samples <= (lim - 1) / max_steps,
-                PTGNN_AMD_EUNSUPPORTED, "decode_step: too many samples / memories / columns");
-  if (num_samples == 0) return PTGNN_AMD_OK;
-  PTGNN_REQUIRE(scores && total_copy && rowptr && done && lengths && logprobs && tokens && next_tokens &&
-                    (num_memories == 0 || (copy_scores && slot_memory && slot_ids)),
-                PTGNN_AMD_EINVAL, "decode_step: null pointer");
-  k_decode_step<<<(unsigned)num_samples, kDecThreads, 0, (hipStream_t)stream_>>>(
-      scores, ld, bias, copy_scores, total_copy, slot_memory, rowptr, slot_ids, num_memories, vocab, top_k, unk_id, end_id,
-      step, max_steps, done, lengths, logprobs, tokens, next_tokens, bad);
-  PTGNN_LAUNCH_CHECK();
-  count_launch(PTGNN_AMD_KERNEL_DECODE_STEP);
-  return PTGNN_AMD_OK;
+  return decode_step_launch(scores, ld, bias, copy_scores, total_copy, slot_memory, rowptr, slot_ids, num_samples,
+                            num_memories, vocab, top_k, unk_id, end_id, step, max_steps, done, lengths, logprobs, tokens,
+                            next_tokens, bad, nullptr, false, stream_);
+}
+
+extern "C" int ptgnn_amd_greedy_step_live_f32(const float *scores, int64_t ld, const float *bias, const float *copy_scores,
+                                              const float *total_copy, const int32_t *slot_memory, const int32_t *rowptr,
+                                              const int64_t *slot_ids, int64_t num_samples, int64_t num_memories,
+                                              int32_t vocab, int32_t top_k, int64_t unk_id, int64_t end_id, int32_t step,
+                                              int32_t max_steps, int32_t *done, int64_t *lengths, float *logprobs,
+                                              int64_t *tokens, int64_t *next_tokens, int32_t *live, int32_t *bad,
+                                              void *workspace, size_t workspace_bytes, void *stream_) {
+  (void)workspace, (void)workspace_bytes;
+  return decode_step_launch(scores, ld, bias, copy_scores, total_copy, slot_memory, rowptr, slot_ids, num_samples,
+                            num_memories, vocab, top_k, unk_id, end_id, step, max_steps, done, lengths, logprobs, tokens,
+                            next_tokens, bad, live, true, stream_);
 }

@@ -31,6 +31,7 @@ static std::atomic<int64_t> g_half_launches[PTGNN_AMD_KERNEL_HALF_END_ - PTGNN_A
 static std::atomic<int64_t> g_edge16_launches[PTGNN_AMD_KERNEL_EDGE16_END_ - PTGNN_AMD_KERNEL_EDGE16_FIRST_];
 static std::atomic<int64_t> g_half_train_launches[PTGNN_AMD_KERNEL_HALF_TRAIN_END_ - PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_];
 static std::atomic<int64_t> g_edge16_dst_launches[PTGNN_AMD_KERNEL_EDGE16_DST_END_ - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
+static std::atomic<int64_t> g_beam_finish_launches[PTGNN_AMD_KERNEL_BEAM_FINISH_END_ - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -53,6 +54,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_half_train_launches[kernel_id - PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_DST_END_)
     return &g_edge16_dst_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_BEAM_FINISH_END_)
+    return &g_beam_finish_launches[kernel_id - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -130,6 +133,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "edge16_dst"};
   if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_DST_END_)
     return edge16_dst_names[kernel_id - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
+  static const char *const beam_finish_names[PTGNN_AMD_KERNEL_BEAM_FINISH_END_ - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_] = {
+      "beam_step_links", "beam_backtrack"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_BEAM_FINISH_END_)
+    return beam_finish_names[kernel_id - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

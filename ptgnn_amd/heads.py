@@ -391,13 +391,14 @@ class Graph2SeqModule(ModuleWithMetrics):
         return loss
 
     def greedy_decode(self, *, encoder_mb_data: Dict[str, Any], input_element_ids, start_id: int, end_id: int,
-                      max_seq_len: int, top_k: int = 100):
+                      max_seq_len: int, top_k: int = 100, early_exit: int = 0):
         """graph2seq.py:175-204 without the host loop: the decoder inputs exactly as `forward` forms them, under
-        torch.no_grad(), handed to `sequence.GruCopyingDecoder.greedy_decode` (its argument and result conventions;
-        `input_element_ids` has one id per backbone node)."""
+        torch.no_grad(), handed to `sequence.GruCopyingDecoder.greedy_decode` (its argument and result conventions,
+        `early_exit` included; `input_element_ids` has one id per backbone node)."""
         with torch.no_grad():
             return self._decoder.greedy_decode(**self.__decoder_inputs(encoder_mb_data), input_element_ids=input_element_ids,
-                                               start_id=start_id, end_id=end_id, max_seq_len=max_seq_len, top_k=top_k)
+                                               start_id=start_id, end_id=end_id, max_seq_len=max_seq_len, top_k=top_k,
+                                               early_exit=early_exit)
 
     def beam_decode(self, *, encoder_mb_data: Dict[str, Any], input_element_ids, start_id: int, end_id: int,
                     max_seq_len: int, beam_width: int, top_k: int = 100):
@@ -407,6 +408,18 @@ class Graph2SeqModule(ModuleWithMetrics):
             return self._decoder.beam_decode(**self.__decoder_inputs(encoder_mb_data), input_element_ids=input_element_ids,
                                              start_id=start_id, end_id=end_id, max_seq_len=max_seq_len,
                                              beam_width=beam_width, top_k=top_k)
+
+    def beam_decode_finishing(self, *, encoder_mb_data: Dict[str, Any], input_element_ids, start_id: int, end_id: int,
+                              max_seq_len: int, beam_width: int, top_k: int = 100, length_penalty: float = 0.0,
+                              early_exit: int = 0):
+        """`beam_decode` with the decoder's `length_penalty` and `early_exit` (sequence.GruCopyingDecoder.beam_decode:
+        GNMT length normalisation, leaving the loop once every hypothesis has finished), on the same decoder inputs.  A
+        method of its own: the keyword list of `beam_decode` is pinned."""
+        with torch.no_grad():
+            return self._decoder.beam_decode(**self.__decoder_inputs(encoder_mb_data), input_element_ids=input_element_ids,
+                                             start_id=start_id, end_id=end_id, max_seq_len=max_seq_len,
+                                             beam_width=beam_width, top_k=top_k, length_penalty=length_penalty,
+                                             early_exit=early_exit)
 
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form."""

@@ -68,9 +68,13 @@ _HALF_TRAIN_FAMILY_FIRST = 576  # PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_: the opt-in
 _EDGE16_DST_FAMILY_FIRST = 640  # PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_: the 16-bit per-edge GEMM with a target-state half
 
 
+_BEAM_FINISH_FAMILY_FIRST = 704  # PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_: the beam search's finishing route
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
-                  edge16: bool = False, half_training: bool = False, edge16_dst: bool = False) -> dict:
+                  edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
+                  beam_finish: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -83,7 +87,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `half=True` the 16-bit-input dense blocks (half_linear, half_gru); `edge16=True` the 16-bit-input grouped per-edge
     GEMM's two launch forms (edge16, edge16_shared); `half_training=True` the 16-bit-input training launches
     (half_wgrad, half_gru_train, half_linear_add); `edge16_dst=True` the 16-bit-input per-edge GEMM with a target-state
-    half (edge16_dst: the MLP-MP message Linear)."""
+    half (edge16_dst: the MLP-MP message Linear); `beam_finish=True` the beam search's finishing route (beam_step_links,
+    beam_backtrack)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -91,7 +96,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_DECODE_FAMILY_FIRST,) if decode else ()) + ((_BEAM_FAMILY_FIRST,) if beam else ()) \
             + ((_HALF_FAMILY_FIRST,) if half else ()) + ((_EDGE16_FAMILY_FIRST,) if edge16 else ()) \
             + ((_HALF_TRAIN_FAMILY_FIRST,) if half_training else ()) \
-            + ((_EDGE16_DST_FAMILY_FIRST,) if edge16_dst else ()):
+            + ((_EDGE16_DST_FAMILY_FIRST,) if edge16_dst else ()) \
+            + ((_BEAM_FINISH_FAMILY_FIRST,) if beam_finish else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -105,7 +111,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
-                        edge16=True, half_training=True, edge16_dst=True)
+                        edge16=True, half_training=True, edge16_dst=True, beam_finish=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -3012,12 +3018,15 @@ def value_groups(index: torch.Tensor, ids: torch.Tensor, num_samples: int, num_i
 
 def decode_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores: torch.Tensor, total_copy: torch.Tensor,
                 groups, top_k: int, unk_id: int, end_id: int, step: int, done: torch.Tensor, lengths: torch.Tensor,
-                logprobs: torch.Tensor, tokens: torch.Tensor, next_tokens: torch.Tensor) -> None:
+                logprobs: torch.Tensor, tokens: torch.Tensor, next_tokens: torch.Tensor,
+                live: Optional[torch.Tensor] = None) -> None:
     """One greedy-decoding step of the copying decoder in one launch (ptgnn_amd_decode_step_f32;
     grucopydecoder.py:375-457): from the raw vocabulary scores [B, V], the copy scores [I] with their per-sample
     log-sum-exp [B] and `groups = value_groups(...)` to the prediction of every sample that is not done.  Updates the
     state IN PLACE: done int32 [B], lengths int64 [B], logprobs float32 [B], tokens int64 [B, T] (column `step`),
-    next_tokens int64 [B].  No host read-back; ids the kernel had to clamp are counted like the plan build's."""
+    next_tokens int64 [B].  No host read-back; ids the kernel had to clamp are counted like the plan build's.
+    With `live` (int32 [T], zeroed once per call) the step goes through ptgnn_amd_greedy_step_live_f32 -- the same kernel
+    and counter family -- and adds the number of samples that are not done after it to live[step]."""
     lib = _lib.load()
     _require_cuda_f32("scores", scores)
     scores = _rowmajor(scores)
@@ -3032,12 +3041,12 @@ def decode_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores:
                                ("slot_memory", slot_memory, (I,), torch.int32), ("slot_ids", slot_ids, (I,), torch.int64),
                                ("done", done, (B,), torch.int32), ("lengths", lengths, (B,), torch.int64),
                                ("logprobs", logprobs, (B,), torch.float32), ("tokens", tokens, (B, T), torch.int64),
-                               ("next_tokens", next_tokens, (B,), torch.int64)):
+                               ("next_tokens", next_tokens, (B,), torch.int64), ("live", live, (T,), torch.int32)):
         if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != shape):
             raise _lib.PtgnnAmdError(f"decode_step: {name} must be a CUDA {dt} {list(shape)} tensor on the scores' device "
                                      f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
     for name, t in (("done", done), ("lengths", lengths), ("logprobs", logprobs), ("tokens", tokens),
-                    ("next_tokens", next_tokens)):
+                    ("next_tokens", next_tokens)) + ((("live", live),) if live is not None else ()):
         if not t.is_contiguous():
             raise _lib.PtgnnAmdError(f"decode_step: {name} is updated in place and must be contiguous")
     if V < 1 or top_k < 1:
@@ -3050,6 +3059,15 @@ def decode_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores:
     bad = _bad_accumulator(_device_state(dev)) if VALIDATE_INDICES != "off" else None
     ws_bytes = int(lib.ptgnn_amd_decode_step_workspace_bytes(B, V, K))
     ws = _workspace(ws_bytes, dev)
+    if live is not None:
+        with _timed("decode_step", bytes=4.0 * B * V * (1 if K >= V else 5) + 4.0 * V + 16.0 * I + 40.0 * B):
+            rc = lib.ptgnn_amd_greedy_step_live_f32(
+                scores.data_ptr(), _ld(scores), _opt_ptr(bias), _opt_ptr(copy_scores), total_copy.data_ptr(),
+                _opt_ptr(slot_memory), rowptr.data_ptr(), _opt_ptr(slot_ids), B, I, V, K, int(unk_id), int(end_id), int(step),
+                T, done.data_ptr(), lengths.data_ptr(), logprobs.data_ptr(), tokens.data_ptr(), next_tokens.data_ptr(),
+                live.data_ptr(), bad.data_ptr() if bad is not None else None, ws.data_ptr(), ws_bytes, _stream(done))
+        _lib.check(rc, "ptgnn_amd_greedy_step_live_f32")
+        return
     with _timed("decode_step", bytes=4.0 * B * V * (1 if K >= V else 5) + 4.0 * V + 16.0 * I + 40.0 * B):
         rc = lib.ptgnn_amd_decode_step_f32(scores.data_ptr(), _ld(scores), _opt_ptr(bias), _opt_ptr(copy_scores),
                                            total_copy.data_ptr(), _opt_ptr(slot_memory), rowptr.data_ptr(),
@@ -3129,6 +3147,99 @@ def beam_step(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores: t
                                          parent_rows.data_ptr(), bad.data_ptr() if bad is not None else None,
                                          ws.data_ptr(), ws_bytes, _stream(beam_out))
     _lib.check(rc, "ptgnn_amd_beam_step_f32")
+
+
+def beam_step_links(scores: torch.Tensor, bias: Optional[torch.Tensor], copy_scores: torch.Tensor,
+                    total_copy: torch.Tensor, groups, top_k: int, unk_id: int, end_id: int, step: int,
+                    key_scale: torch.Tensor, state_in, state_out, next_tokens: torch.Tensor, parent_rows: torch.Tensor,
+                    links: torch.Tensor, live: Optional[torch.Tensor] = None) -> None:
+    """`beam_step` on the finishing route (ptgnn_amd_search_step_links_f32): the state is (scores float32 [B, W], done
+    int32 [B, W], lengths int64 [B, W]) without the histories; the candidates are placed by score * key_scale[lengths of
+    the parent + 1] (`key_scale` float32 [T + 1], positive; the state keeps the raw sums); slot p of sample b writes
+    links[step, b, p] = (the id it appends or -1, its parent slot) into `links` int32 [T, B, W, 2]; and with `live`
+    (int32 [T], zeroed once per call) the number of slots that are live after the step is added to live[step]."""
+    lib = _lib.load()
+    _require_cuda_f32("scores", scores)
+    scores = _rowmajor(scores)
+    R, V = scores.shape
+    dev = scores.device
+    rowptr, slot_memory, slot_ids = groups
+    I = int(slot_memory.shape[0])
+    beam_in, done_in, lengths_in = state_in
+    beam_out, done_out, lengths_out = state_out
+    if beam_in.dim() != 2 or beam_in.shape[1] < 1 or R % int(beam_in.shape[1]):
+        raise _lib.PtgnnAmdError(f"beam_step_links: the beam scores must be [B, W] with B W = {R} rows of vocabulary "
+                                 f"scores (got {tuple(beam_in.shape)})")
+    B, W = (int(v) for v in beam_in.shape)
+    T = int(links.shape[0]) if links.dim() == 4 else -1
+    for name, t, shape, dt in (("bias", bias, (V,), torch.float32), ("copy_scores", copy_scores, (I, W), torch.float32),
+                               ("total_copy", total_copy, (B, W), torch.float32),
+                               ("rowptr", rowptr, (B + 1,), torch.int32), ("slot_memory", slot_memory, (I,), torch.int32),
+                               ("slot_ids", slot_ids, (I,), torch.int64), ("key_scale", key_scale, (T + 1,), torch.float32),
+                               ("scores in", beam_in, (B, W), torch.float32), ("done in", done_in, (B, W), torch.int32),
+                               ("lengths in", lengths_in, (B, W), torch.int64),
+                               ("scores out", beam_out, (B, W), torch.float32), ("done out", done_out, (B, W), torch.int32),
+                               ("lengths out", lengths_out, (B, W), torch.int64),
+                               ("next_tokens", next_tokens, (B * W,), torch.int64),
+                               ("parent_rows", parent_rows, (B * W,), torch.int64),
+                               ("links", links, (T, B, W, 2), torch.int32), ("live", live, (T,), torch.int32)):
+        if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != shape):
+            raise _lib.PtgnnAmdError(f"beam_step_links: {name} must be a CUDA {dt} {list(shape)} tensor on the scores' "
+                                     f"device (got {t.dtype} {tuple(t.shape)} on {t.device})")
+    for name, t in (("key_scale", key_scale), ("scores in", beam_in), ("done in", done_in), ("lengths in", lengths_in),
+                    ("scores out", beam_out), ("done out", done_out), ("lengths out", lengths_out),
+                    ("next_tokens", next_tokens), ("parent_rows", parent_rows), ("links", links)) \
+            + ((("live", live),) if live is not None else ()):
+        if not t.is_contiguous():
+            raise _lib.PtgnnAmdError(f"beam_step_links: {name} is read or written in place and must be contiguous")
+    for a, b in zip(state_in, state_out):
+        if a.data_ptr() == b.data_ptr() and a.numel():
+            raise _lib.PtgnnAmdError("beam_step_links: the state out must not share buffers with the state in (slots are "
+                                     "reordered)")
+    K = int(min(top_k, V))
+    if V < 1 or top_k < 1 or not 1 <= W <= min(K, 8):
+        raise _lib.PtgnnAmdError(f"beam_step_links: needs top_k >= 1 and 1 <= beam width <= min(top_k, V, 8), the head "
+                                 f"limit of the fused attention pool (got V = {V}, top_k = {top_k}, beam width {W})")
+    if B == 0:
+        return
+    bias, copy_scores, total_copy, rowptr, slot_memory, slot_ids = (
+        t.contiguous() if t is not None else None for t in (bias, copy_scores, total_copy, rowptr, slot_memory, slot_ids))
+    bad = _bad_accumulator(_device_state(dev)) if VALIDATE_INDICES != "off" else None
+    ws_bytes = int(lib.ptgnn_amd_beam_step_workspace_bytes(B, I, V, K, W))
+    ws = _workspace(ws_bytes, dev)
+    passes = 2 + (4 if W < V else 0) + (4 if K < V and K != W else 0)      # normaliser, collect, the radix selects
+    with _timed("beam_step_links", bytes=4.0 * R * V * passes + 4.0 * V + (12.0 + 8.0 * W) * I * W + 20.0 * R * W
+                + 56.0 * R):
+        rc = lib.ptgnn_amd_search_step_links_f32(
+            scores.data_ptr(), _ld(scores), _opt_ptr(bias), _opt_ptr(copy_scores), total_copy.data_ptr(),
+            _opt_ptr(slot_memory), rowptr.data_ptr(), _opt_ptr(slot_ids), B, I, V, K, W, int(unk_id), int(end_id), int(step),
+            T, key_scale.data_ptr(), beam_in.data_ptr(), done_in.data_ptr(), lengths_in.data_ptr(), beam_out.data_ptr(),
+            done_out.data_ptr(), lengths_out.data_ptr(), next_tokens.data_ptr(), parent_rows.data_ptr(), links.data_ptr(),
+            _opt_ptr(live), bad.data_ptr() if bad is not None else None, ws.data_ptr(), ws_bytes, _stream(beam_out))
+    _lib.check(rc, "ptgnn_amd_search_step_links_f32")
+
+
+def beam_backtrack(links: torch.Tensor, steps_run: int, tokens: torch.Tensor) -> None:
+    """The histories of the finishing route in one launch (ptgnn_amd_search_backtrack): `links` int32 [T, B, W, 2] as
+    `beam_step_links` wrote its first `steps_run` steps -> tokens int64 [B, W, T], every column written (-1 from
+    `steps_run` on, and wherever a hypothesis had finished)."""
+    lib = _lib.load()
+    if not links.is_cuda or links.dtype != torch.int32 or links.dim() != 4 or links.shape[3] != 2 \
+            or not links.is_contiguous():
+        raise _lib.PtgnnAmdError("beam_backtrack: links must be a contiguous CUDA int32 [T, B, W, 2] tensor (GPU only)")
+    T, B, W = (int(v) for v in links.shape[:3])
+    if not tokens.is_cuda or tokens.device != links.device or tokens.dtype != torch.int64 \
+            or tuple(tokens.shape) != (B, W, T) or not tokens.is_contiguous():
+        raise _lib.PtgnnAmdError(f"beam_backtrack: tokens must be a contiguous CUDA int64 {[B, W, T]} tensor on the links' "
+                                 f"device (got {tokens.dtype} {tuple(tokens.shape)} on {tokens.device})")
+    if not 0 <= int(steps_run) <= T or not 1 <= W <= 8:
+        raise _lib.PtgnnAmdError(f"beam_backtrack: needs 0 <= steps_run <= {T} and a beam width in [1, 8] (got {steps_run}, "
+                                 f"{W})")
+    if B == 0 or T == 0:
+        return
+    with _timed("beam_backtrack", bytes=(8.0 * steps_run + 8.0 * T) * B * W):
+        rc = lib.ptgnn_amd_search_backtrack(links.data_ptr(), B, W, int(steps_run), T, tokens.data_ptr(), _stream(tokens))
+    _lib.check(rc, "ptgnn_amd_search_backtrack")
 
 
 def post_index_check(device) -> None:

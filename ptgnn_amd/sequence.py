@@ -25,7 +25,11 @@ GRU's output states [B, L, H]:
   * `beam_decode` is that loop for W <= 8 hypotheses per sample: the GRU cell and the vocabulary product on B W rows, the
     attention pool and the copy scores with L := W (the hypotheses of a sample are its heads), `ops.beam_step`
     (csrc/beam_step.hip), which writes the W best continuations of every sample, their parents and the reordered
-    token histories into a second set of state buffers, and the row gather of the new hidden states by parent;
+    token histories into a second set of state buffers, and the row gather of the new hidden states by parent.  With
+    `length_penalty` > 0 or `early_exit` > 0 it takes the finishing route: `ops.beam_step_links` places the candidates
+    by length-normalised key, writes a back-pointer pair per slot in place of the history and counts the live slots;
+    `ops.beam_backtrack` writes the histories once after the loop; the host leaves the loop on a lagged read-back of the
+    live count (`_LiveWatch`), which `greedy_decode(early_exit=n)` shares;
   * `fused_loss` (the training loss, what `heads.Graph2SeqModule` calls) keeps the same GRU, attention and copy scores and
     replaces that glue by csrc/vocab_loss.hip: `_VocabLoss` reads the RAW second Linear's output once -- bias, running
     maximum, joint normaliser with the copy term, the correct tokens' entries -- and its one-pass backward writes the
@@ -42,12 +46,49 @@ import math
 import torch
 from torch import nn
 
-from ptgnn_amd import _lib, dense, ops, scatter as scatter_facade
+from ptgnn_amd import _lib, _readback, dense, ops, scatter as scatter_facade
 from ptgnn_amd.layers import _index_plan, _no_grad_needed
 from ptgnn_amd.reduceops import _AttentionPool
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_scores
 
 _HALF = (torch.float16, torch.bfloat16)
+_LIVE_IN_FLIGHT = []         # read-backs of live counts that a decode loop left without looking at: reaped by the next call
+
+
+def _early_exit_lag(who: str, early_exit) -> int:
+    if isinstance(early_exit, bool) or not isinstance(early_exit, int) or early_exit < 0:
+        raise _lib.PtgnnAmdError(f"{who}: early_exit must be 0 (off) or a lag of n >= 1 steps (got {early_exit!r})")
+    return early_exit
+
+
+class _LiveWatch:
+    """The early exit of a device decode loop.  `live` int32 [T], zeroed once, is what the step kernels count the live
+    hypotheses of each step into.  After issuing step s the loop asks `nothing_live(s)`: the count of step s is sent on
+    its way to the host, and from s >= lag on the host waits for the read-back of step s - lag -- on that read-back's OWN
+    event, never on the stream -- and is told whether it was 0.  So the loop issues min(T, s* + lag + 1) steps, whatever
+    the timing, and never runs more than `lag` steps ahead of a count it has seen."""
+
+    def __init__(self, T: int, device, lag: int):
+        for old in _readback.take_arrived(_LIVE_IN_FLIGHT, keep=64):
+            old.values()                                        # back to the pool of pinned buffers
+        self.live = torch.zeros(T, dtype=torch.int32, device=device)
+        self.steps, self.lag = T, lag
+        self.sent = {}
+
+    def nothing_live(self, step: int) -> bool:
+        if step + self.lag < self.steps:                        # a count nobody will look at is not sent
+            self.sent[step] = _readback.Readback(self.live[step:step + 1])
+        if step < self.lag:
+            return False
+        return self.sent.pop(step - self.lag).values(wait=True)[0] == 0
+
+    def close(self) -> None:
+        """After the loop: what was sent and not looked at (an exit leaves up to `lag` of them) is reaped by a later call."""
+        with _readback.LOCK:
+            _LIVE_IN_FLIGHT.extend(self.sent.values())
+        self.sent = {}
+
+
 _MAX_ELEMENT_ID = 1 << 22    # greedy_decode: the value ids of a call index one plan build (a row pointer of that length)
 
 
@@ -394,7 +435,7 @@ class GruCopyingDecoder(nn.Module):
         done |= live & ends
 
     def greedy_decode(self, *, input_memories, input_memories_origin_idx, initial_states, input_element_ids, start_id: int,
-                      end_id: int, max_seq_len: int, top_k: int = 100):
+                      end_id: int, max_seq_len: int, top_k: int = 100, early_exit: int = 0):
         """The greedy decoding of GruCopyingDecoderModel.greedy_decode (grucopydecoder.py:375-457) without its host loop.
 
         :param input_memories: [num-inputs-flattened, D]
@@ -405,6 +446,12 @@ class GruCopyingDecoder(nn.Module):
             string that is not in the vocabulary (equal strings, equal keys; keys below 2 ** 22)
         :param start_id, end_id: the vocabulary ids of START and END
         :param top_k: the vocabulary candidates per step (the reference's 100)
+        :param early_exit: 0: every call runs `max_seq_len` steps.  n >= 1: the loop ends once every sample has predicted
+            END -- the results are the same bits.  CPU tensors leave right after that step s*; on GPU tensors the step
+            kernel counts the samples that are still live into an int32 [max_seq_len] tensor, and after issuing step s >= n
+            the host waits for the read-back of step s - n's count (on that read-back's own event, not on the stream) and
+            leaves when it is 0: exactly min(max_seq_len, s* + n + 1) steps are issued, the host is never more than n
+            steps ahead of what it has looked at
 
         :return: token_ids int64 [num-targets, max_seq_len] (row b holds the lengths[b] predicted tokens of sample b in the
             extended id space, END not included, then -1), lengths int64 [num-targets], logprobs float32 [num-targets]
@@ -424,6 +471,7 @@ class GruCopyingDecoder(nn.Module):
         if top_k < 1 or T < 0 or not (0 <= start_id < V and 0 <= end_id < V):
             raise _lib.PtgnnAmdError(f"greedy_decode: needs top_k >= 1, max_seq_len >= 0 and start_id / end_id inside the "
                                      f"vocabulary of {V} (got {top_k}, {T}, {start_id}, {end_id})")
+        lag = _early_exit_lag("greedy_decode", early_exit)
         dev = x.device
         tokens = torch.full((B, T), -1, dtype=torch.int64, device=dev)
         lengths = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -447,28 +495,42 @@ class GruCopyingDecoder(nn.Module):
                     h = state.squeeze(0)
                     self.__host_greedy_step(copy_logprobs.squeeze(1), target_logprobs.squeeze(1), index, ids, top_k, end_id,
                                             step, (done, lengths, logprobs, tokens, next_tokens))
+                    if lag and bool(done.all()):
+                        break
                 return tokens, lengths, logprobs
             done = torch.zeros(B, dtype=torch.int32, device=dev)
             groups = ops.value_groups(index, ids, B, span)
+            watch = _LiveWatch(T, dev, lag) if lag else None
             for step in range(T):
                 states, attention_out, copy_scores, total_copy, h, _ = self.__device_attention(
                     h, x, index, next_tokens.unsqueeze(1))
                 raw_scores = self.__raw_vocabulary_scores(attention_out, states)           # [B, V]
+                if watch is None:
+                    ops.decode_step(raw_scores, self.__vocab_bias, copy_scores, total_copy.reshape(B), groups, top_k,
+                                    self.__unk_id, end_id, step, done, lengths, logprobs, tokens, next_tokens)
+                    continue
                 ops.decode_step(raw_scores, self.__vocab_bias, copy_scores, total_copy.reshape(B), groups, top_k,
-                                self.__unk_id, end_id, step, done, lengths, logprobs, tokens, next_tokens)
+                                self.__unk_id, end_id, step, done, lengths, logprobs, tokens, next_tokens, live=watch.live)
+                if watch.nothing_live(step):
+                    break
+            if watch is not None:
+                watch.close()
             ops.post_index_check(dev)
         return tokens, lengths, logprobs
 
     # --------------------------------------------------------------------------------------------------------------
     # beam search: greedy decoding's dictionary, the W best continuations of W hypotheses per sample
     # --------------------------------------------------------------------------------------------------------------
-    def __host_beam_step(self, copy_logprobs, target_logprobs, row_of_memory, ids, top_k, W, end_id, step, state):
+    def __host_beam_step(self, copy_logprobs, target_logprobs, row_of_memory, ids, top_k, W, end_id, step, state,
+                         key_scale=None):
         """One beam step on torch operators, on [B W, V] / [W I] log-probabilities (row b W + j: slot j of sample b; the
         memories repeated once per slot, `row_of_memory` their rows): per live row the W best vocabulary entries -- with
         the row's value group merged in where the id has one -- and the row's other groups, merged as in
         `__host_greedy_step`; per finished row itself.  The candidates are sorted by (sample, higher score, lower parent,
         the W best vocabulary ids first, lower id) with stable sorts from the last key to the first, and the first W of
-        a sample are its new slots.  Returns (state, next tokens [B W], parent rows [B W])."""
+        a sample are its new slots.  With `key_scale` (float32 [T + 1], the finishing route) "higher score" is "higher
+        key", key = score * key_scale[lengths of the parent + 1] in float32; the state keeps the raw sums.  Returns (state,
+        next tokens [B W], parent rows [B W])."""
         beam, done, lengths, tokens = state
         R, V = target_logprobs.shape
         B = R // W
@@ -511,8 +573,9 @@ class GruCopyingDecoder(nn.Module):
         cand_id = torch.cat((cand_id[keep], torch.full_like(finished, -1)))
         cand_class = torch.cat((cand_class[keep], torch.zeros_like(finished)))
         score = beam.reshape(-1)[cand_row] + torch.cat((cand_value[keep], torch.zeros(finished.shape[0])))
+        placed_by = score if key_scale is None else score * key_scale[lengths.reshape(-1)[cand_row] + 1]
         perm = torch.sort(cand_id, stable=True).indices
-        for key, descending in ((cand_class, False), (cand_row % W, False), (score, True),
+        for key, descending in ((cand_class, False), (cand_row % W, False), (placed_by, True),
                                 (torch.div(cand_row, W, rounding_mode="floor"), False)):
             perm = perm[torch.sort(key[perm], descending=descending, stable=True).indices]
         sample = torch.div(cand_row[perm], W, rounding_mode="floor")
@@ -532,7 +595,8 @@ class GruCopyingDecoder(nn.Module):
         return state, next_tokens, parent
 
     def beam_decode(self, *, input_memories, input_memories_origin_idx, initial_states, input_element_ids, start_id: int,
-                    end_id: int, max_seq_len: int, beam_width: int, top_k: int = 100):
+                    end_id: int, max_seq_len: int, beam_width: int, top_k: int = 100, length_penalty: float = 0.0,
+                    early_exit: int = 0):
         """Beam search over the dictionary of `greedy_decode` (the reference has none: grucopydecoder.py:406-442 extended to
         the W = beam_width best hypotheses of every sample); tensor arguments and the extended id space as there.
 
@@ -543,10 +607,23 @@ class GruCopyingDecoder(nn.Module):
         sample that come first by: higher score; lower parent; inside a parent the ids of its W best vocabulary entries
         before its other entries (of equal vocabulary scores the lower id is the larger); lower id -- are the new slots
         0 .. W - 1, in that order.  END finishes a hypothesis (its log-probability included), anything else is appended;
-        no length normalisation, no early exit.  W = 1 is `greedy_decode`.
+        W = 1 is `greedy_decode`.
+
+        :param length_penalty: alpha >= 0 of the GNMT length normalisation.  A hypothesis with n scored decisions (its
+            appended tokens, plus one for END once it has finished) is RANKED by key = logprob_sum * scale[n], scale[n] =
+            ((5 + n) / 6) ** -alpha, made once per call in float64 for n = 0 .. max_seq_len and rounded to a float32 table
+            that the device and the CPU route both multiply by.  All candidates of a parent have the same n, so only the
+            selection ACROSS parents changes: "higher score" above reads "higher key".  The slots keep and return the raw
+            sums, in key order: with alpha > 0 `logprobs` need not be descending.  alpha = 0: the table is all ones
+        :param early_exit: 0, or the lag n >= 1 of `greedy_decode`'s early exit: the loop ends once no slot of any sample
+            is live (every later step would be the identity); min(max_seq_len, s* + n + 1) steps on GPU tensors
+        Without either the call runs exactly what it ran before there were these keywords.  With either it takes the
+        FINISHING route: the same step (ops.beam_step_links: the same candidates kernel), back-pointer pairs in place of
+        the histories copied every step, one backtrack launch after the loop (ops.beam_backtrack).  Its results for
+        alpha = 0 are the default route's bit for bit, for every `early_exit`.
 
         :return: token_ids int64 [num-targets, W, max_seq_len] (-1 after the tokens, END not included), lengths int64
-            [num-targets, W], logprobs float32 [num-targets, W], descending per sample.
+            [num-targets, W], logprobs float32 [num-targets, W], descending per sample (alpha = 0).
 
         On GPU tensors the W hypotheses of a sample ride through the fused attention pool and the copy-score kernel as
         W heads of one launch, the step between them is csrc/beam_step.hip and the hidden states are reordered by the row
@@ -569,6 +646,13 @@ class GruCopyingDecoder(nn.Module):
         if x.is_cuda and W > 8:
             raise _lib.PtgnnAmdError(f"beam_decode: beam_width {W} > 8, the head limit of the fused attention pool that "
                                      f"carries the hypotheses of a sample on the GPU")
+        lag = _early_exit_lag("beam_decode", early_exit)
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) \
+                or not math.isfinite(length_penalty) or length_penalty < 0:
+            raise _lib.PtgnnAmdError(f"beam_decode: length_penalty must be a finite number >= 0 (got {length_penalty!r})")
+        if length_penalty != 0 or lag:
+            return self.__finishing_beam_decode(x, index, h, ids, int(start_id), int(end_id), T, W, int(top_k),
+                                                float(length_penalty), lag)
         dev = x.device
         tokens = torch.full((B, W, T), -1, dtype=torch.int64, device=dev)
         lengths = torch.zeros(B, W, dtype=torch.int64, device=dev)
@@ -619,6 +703,76 @@ class GruCopyingDecoder(nn.Module):
                 h = ops.gather_rows(new_h, parent_rows)
             ops.post_index_check(dev)
         return state[3], state[2], state[0]
+
+    def __finishing_beam_decode(self, x, index, h, ids, start_id, end_id, T, W, top_k, alpha, lag):
+        """`beam_decode` with a length penalty and / or an early exit (the arguments are checked): candidates placed by
+        key, and on GPU tensors back-pointers, the live count and one backtrack in place of the copied histories."""
+        B, I, dev = int(h.shape[0]), int(x.shape[0]), x.device
+        lengths = torch.zeros(B, W, dtype=torch.int64, device=dev)
+        beam = torch.full((B, W), -math.inf, dtype=torch.float32, device=dev)
+        beam[:, :1] = 0.0
+        if B == 0 or T == 0:
+            return torch.full((B, W, T), -1, dtype=torch.int64, device=dev), lengths, beam
+        span = 1
+        if I:
+            low, high = (int(v) for v in torch.aminmax(ids))     # before the loop, as on the default route
+            if low < 0 or high >= _MAX_ELEMENT_ID:
+                raise _lib.PtgnnAmdError(f"beam_decode: input_element_ids must lie in [0, {_MAX_ELEMENT_ID}) (got "
+                                         f"{low} .. {high})")
+            span = high + 1
+        scale = ((5.0 + torch.arange(T + 1, dtype=torch.float64)) / 6.0).pow(-alpha).float()   # float64, rounded once
+        if not bool((scale > 0).all()):
+            raise _lib.PtgnnAmdError(f"beam_decode: length_penalty {alpha} over {T} steps leaves float32 (a scale of 0)")
+        next_tokens = torch.full((B * W,), start_id, dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            x, h = x.float(), h.float()                          # AMP: fp32 inside, as everywhere
+            h = h.unsqueeze(1).expand(B, W, h.shape[1]).reshape(B * W, -1).contiguous()    # row b W + j
+            if not x.is_cuda:    # device dispatch: the default route's CPU loop with the key order and the immediate exit
+                slot = torch.arange(W).repeat_interleave(I)
+                x_rows, row_of_memory, ids_rows = x.repeat(W, 1), index.repeat(W) * W + slot, ids.repeat(W)
+                state = (beam, torch.zeros(B, W, dtype=torch.bool), lengths, torch.full((B, W, T), -1, dtype=torch.int64))
+                for step in range(T):
+                    copy_logprobs, target_logprobs, new_h = self._compute_logprobs(h, x_rows, row_of_memory,
+                                                                                   next_tokens.unsqueeze(1))
+                    state, next_tokens, parent = self.__host_beam_step(
+                        copy_logprobs.squeeze(1), target_logprobs.squeeze(1), row_of_memory, ids_rows, top_k, W, end_id,
+                        step, state, key_scale=scale)
+                    if lag and bool(state[1].all()):
+                        break
+                    h = new_h.squeeze(0)[parent]
+                return state[3], state[2], state[0]
+            self.__check_index(x, index)
+            x = x.contiguous()
+            gru, H = self.__output_gru, h.shape[1]
+            plan = _index_plan(index, B)
+            groups = ops.value_groups(index, ids, B, span)
+            scale = scale.to(dev)
+            state = (beam, torch.zeros(B, W, dtype=torch.int32, device=dev), lengths)
+            spare = tuple(torch.empty_like(t) for t in state)
+            parent_rows = torch.empty(B * W, dtype=torch.int64, device=dev)
+            links = torch.empty(T, B, W, 2, dtype=torch.int32, device=dev)
+            watch = _LiveWatch(T, dev, lag) if lag else None
+            steps_run = 0
+            for step in range(T):
+                embedded = _rows(self.__embedding_layer.weight, next_tokens)               # [B W, E]
+                new_h = dense.gru_cell_weights(embedded, h, gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0,
+                                               gru.bias_hh_l0)
+                attention_out, copy_scores, total_copy = self.__attend(new_h.reshape(B, W, H), x, index, plan)
+                raw_scores = self.__raw_vocabulary_scores(attention_out, new_h)            # [B W, V]
+                ops.beam_step_links(raw_scores, self.__vocab_bias, copy_scores, total_copy, groups, top_k, self.__unk_id,
+                                    end_id, step, scale, state, spare, next_tokens, parent_rows, links,
+                                    watch.live if watch is not None else None)
+                state, spare = spare, state
+                steps_run = step + 1
+                if watch is not None and watch.nothing_live(step):
+                    break
+                h = ops.gather_rows(new_h, parent_rows)
+            if watch is not None:
+                watch.close()
+            tokens = torch.empty(B, W, T, dtype=torch.int64, device=dev)                   # every column is written
+            ops.beam_backtrack(links, steps_run, tokens)
+            ops.post_index_check(dev)
+        return tokens, state[2], state[0]
 
     def forward_sharded(self, *args, **kwargs):
         """The decoder attends over all memories of a sample: there is no sharded form (as for the attention reducers)."""
