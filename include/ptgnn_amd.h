@@ -220,6 +220,13 @@ enum {
   PTGNN_AMD_KERNEL_BEAM_BACKTRACK,                                        /* ptgnn_amd_search_backtrack */
   PTGNN_AMD_KERNEL_BEAM_FINISH_END_
 };
+/* A thirteenth id range: the 16-bit-input forward of the block attention (csrc/block_attention16.hip).  A range of its
+ * own, so the second range ends where it did. */
+enum {
+  PTGNN_AMD_KERNEL_ATTENTION16_FIRST_ = 768,
+  PTGNN_AMD_KERNEL_BLOCK_ATTENTION16 = PTGNN_AMD_KERNEL_ATTENTION16_FIRST_, /* ptgnn_amd_attention16_block */
+  PTGNN_AMD_KERNEL_ATTENTION16_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1542,6 +1549,37 @@ int ptgnn_amd_edge_dst_linear16(const float *x, int64_t ld_x, int64_t num_rows, 
                                 const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
                                 const int64_t *edges_per_type, const void *w, int32_t num_types, int32_t msg_dim,
                                 int act, int dtype, float *msg, int64_t ld_msg, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the block attention's inference forward (csrc/block_attention16.hip).
+ *
+ * Replaces: selfattmessagepassing.py:104-117 under autocast -- both einsums ("khd,vhd->khv" of line 107 and
+ *   "khv,vhd->khd" of line 112) in the autocast dtype, the softmax of line 110 in fp32 -- for inference (no dropout:
+ *   line 111 is the identity in eval()).  ptgnn_amd_block_attention_f32 is the fp32 launch and stays as it is.  OFF by
+ *   default: the host's ptgnn_amd.precision setting asks for it with `attention=True`.
+ *
+ *   S[k, v] = rnd(key_k) . rnd(query_v) / sqrt(dk)    m_k = max_v S[k, v]    E = exp(S - m)    l_k = sum_v E[k, v]
+ *   out_k = (sum_v rnd(E[k, v]) rnd(value_v)) / l_k   lse_k = m_k + log l_k
+ *   per window and head.  kqv, windows, num_windows, num_rows, max_num_nodes, out, lse as ptgnn_amd_block_attention_f32
+ *   takes them: kqv stays fp32 in memory and is read in place; keys, queries and values are rounded to `dtype`
+ *   (PTGNN_AMD_HALF_BF16 / _F16; round to nearest even with gradual underflow, as tensor.to(dtype)) on their way into
+ *   LDS, the unnormalised probabilities E in registers (with the running maximum of the 32-query tile they are formed
+ *   in).  Products on v_mfma_f32_32x32x16_{bf16,f16}; the scale, the mask, the running maximum and sum, exp, l (the sum
+ *   of the UNROUNDED E), the division and every accumulation are fp32.  A value beyond the fp16 range rounds to inf, as
+ *   tensor.half() gives.
+ *   ptgnn_amd_attention16_block_supported(dk, dv, dtype): 1 when the kernel takes the widths (1 <= dk, dv <= 128 and a
+ *     known dtype id), else 0; needs no device.
+ * kqv must be 4-byte aligned; with a 16-byte aligned base, ld_kqv % 4 == 0, dk % 4 == 0 and dv % 4 == 0 the rows are
+ * loaded as float4, else element by element -- the same values and bits either way.  Error codes as
+ * ptgnn_amd_block_attention_f32, plus EINVAL for an unknown dtype id; bad arguments are refused before any HIP call.
+ * Every sum runs in tile order inside one wave: no atomics, deterministic, and a window's rows do not depend on its place
+ * in the batch.  (The names put "attention16" before "block": the ptgnn_amd_block_attention* prefix is a closed set of
+ * four, and the ABI version stays -- the entries are additive, like every 16-bit entry before them.)
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_attention16_block_supported(int32_t dk, int32_t dv, int dtype);
+int ptgnn_amd_attention16_block(const float *kqv, int64_t ld_kqv, const int32_t *windows, int64_t num_windows,
+                                int64_t num_rows, int32_t max_num_nodes, int32_t num_heads, int32_t dk, int32_t dv,
+                                float *out, int64_t ld_out, float *lse, int dtype, void *stream);
 
 #pragma GCC visibility pop
 

@@ -217,6 +217,9 @@ SIGNATURES = {
     "ptgnn_amd_edge_dst_linear16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int]),
     "ptgnn_amd_edge_dst_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
                                                _vp, _i64, _vp]),
+    "ptgnn_amd_attention16_block_supported": (_c.c_int, [_i32, _i32, _c.c_int]),
+    "ptgnn_amd_attention16_block": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
+                                               _c.c_int, _vp]),
 }
 
 # The header version this host was written against (include/ptgnn_amd.h: PTGNN_AMD_VERSION).  A stale .so with an

@@ -34,21 +34,11 @@
 //
 // Dropout is the stateless hash of dense_common.h: element (global row r, head h, window column j) takes the multiplier of
 // row r heads + h, column j of a [N heads, W] mask with W = max_num_nodes rounded up to even.
-#include "dense_common.h"
+#include "block_attention.h"
 #include "segment_chunks.h"   // SegmentScan: the window table is the chunk table's scan with another count
 
 namespace ptgnn_amd {
 namespace {
-
-constexpr int kBaTile = 32;          // rows of one MFMA tile: a wave's rows, and the rows of a staged tile
-constexpr int kBaMaxWaves = 4;       // waves (32-row tiles) of a workgroup: 4, 2 or 1, the most whose LDS stays <= 64 KiB
-constexpr int kBaMaxDim = 128;
-constexpr float kLog2e = 1.4426950408889634f;
-
-// row of register r of a 32x32 accumulator tile in lane half h
-__device__ __forceinline__ int ba_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-__device__ __forceinline__ float ba_exp(float v) { return __builtin_amdgcn_exp2f(v * kLog2e); }
 
 // dst[r][c] (row stride ldd) = src[min(row0 + r, row_end - 1)][c] for c < width, 0 for width <= c < widthp
 __device__ __forceinline__ void ba_stage(float *__restrict__ dst, int ldd, const float *__restrict__ src, int64_t ld,
@@ -89,21 +79,6 @@ __device__ __forceinline__ void ba_tn(f32x16 (&z)[T], const f32x16 &x, const flo
 __device__ __forceinline__ float ba_keep(const DropoutParams &d, int64_t row, int j) {
   const uint32_t b = dropout_bits(d, row, j >> 1);
   return ((j & 1) ? (b >> 16) : (b & 0xffffu)) >= d.thr ? d.scale : 0.0f;
-}
-
-struct BaShape {
-  int heads, dk, dv, dkt, dvt, row_tiles;   // dkt / dvt: 32-column tiles of dk / dv
-  float scale;
-};
-
-// workgroup -> its window [start, end) and first row r0 inside it; false when it has no rows
-__device__ __forceinline__ bool ba_locate(const int32_t *__restrict__ windows, const BaShape &sh, int &start, int &end,
-                                          int &r0) {
-  const int w = blockIdx.x / sh.row_tiles, rt = blockIdx.x % sh.row_tiles;
-  start = windows[w];
-  end = windows[w + 1];
-  r0 = rt * kBaTile * (int)(blockDim.x >> 6);
-  return r0 < end - start;
 }
 
 // One workgroup builds the window table: windows[w] = first row of window w for the W windows of the batch (graph g owns
@@ -370,55 +345,13 @@ int ba_waves(int own_ld, int walk_ld, int extra) {
   return 1;
 }
 
-// a workgroup beyond 64 KiB of LDS (one wave at the widest heads) needs the kernel's limit raised first
-template <typename Kern>
-bool ba_lds_ok(Kern kern, size_t bytes) { return bytes <= 64 * 1024 || raise_dynamic_lds(kern, bytes); }
-
 int64_t ba_windows_bound(int64_t num_graphs, int64_t num_rows, int64_t max_nodes) {
   return (num_rows + max_nodes - 1) / max_nodes + num_graphs;
-}
-
-// the checks the forward and the backward share; 0 when the arguments are fine
-int ba_check(const char *what, const void *kqv, int64_t ld, const void *windows, int64_t num_windows, int64_t num_rows,
-             int32_t max_nodes, int32_t heads, int32_t dk, int32_t dv, float p) {
-  PTGNN_REQUIRE(num_windows >= 0 && num_rows >= 0 && max_nodes > 0 && heads > 0 && dk > 0 && dv > 0, PTGNN_AMD_EINVAL,
-                "%s: bad sizes", what);
-  PTGNN_REQUIRE(dk <= kBaMaxDim && dv <= kBaMaxDim, PTGNN_AMD_EUNSUPPORTED,
-                "%s: key / value dimension (%d, %d) exceeds %d", what, dk, dv, kBaMaxDim);
-  PTGNN_REQUIRE(p >= 0.0f && p < 1.0f, PTGNN_AMD_EINVAL, "%s: dropout rate %g outside [0, 1)", what, (double)p);
-  PTGNN_REQUIRE(heads <= 65535, PTGNN_AMD_EUNSUPPORTED, "%s: more than 65535 heads", what);
-  if (num_rows == 0) return PTGNN_AMD_OK;
-  PTGNN_REQUIRE(kqv && windows, PTGNN_AMD_EINVAL, "%s: null pointer", what);
-  PTGNN_REQUIRE(num_windows > 0, PTGNN_AMD_EINVAL, "%s: rows without windows", what);
-  PTGNN_REQUIRE(ld >= (int64_t)heads * (2 * dk + dv), PTGNN_AMD_EINVAL, "%s: bad leading dimension", what);
-  PTGNN_REQUIRE(num_rows * heads < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED, "%s: too many rows", what);
-  return PTGNN_AMD_OK;
-}
-
-BaShape ba_shape(int32_t heads, int32_t dk, int32_t dv, int nw, int64_t num_rows, int32_t max_nodes) {
-  BaShape sh;
-  sh.heads = heads;
-  sh.dk = dk;
-  sh.dv = dv;
-  sh.dkt = (dk + 31) / 32;
-  sh.dvt = (dv + 31) / 32;
-  const int64_t longest = num_rows < max_nodes ? num_rows : max_nodes;      // no window is longer
-  sh.row_tiles = (int)((longest + kBaTile * nw - 1) / (kBaTile * nw));
-  sh.scale = (float)(1.0 / sqrt((double)dk));
-  return sh;
 }
 
 DropoutParams ba_dropout(float p, uint64_t seed, int32_t max_nodes) {
   return make_dropout(p, seed, (max_nodes + 1) / 2 * 2);
 }
-
-#define BA_TILES(n, ...)          \
-  switch (n) {                    \
-    case 1: { constexpr int TT = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int TT = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int TT = 3; __VA_ARGS__; } break; \
-    default: { constexpr int TT = 4; __VA_ARGS__; } break; \
-  }
 
 template <int DKT>
 int ba_launch_dqv(int dvt, dim3 grid, int nw, size_t bytes, hipStream_t st, const float *kqv, int64_t ld, const float *go,

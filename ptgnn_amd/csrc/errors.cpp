@@ -32,6 +32,7 @@ static std::atomic<int64_t> g_edge16_launches[PTGNN_AMD_KERNEL_EDGE16_END_ - PTG
 static std::atomic<int64_t> g_half_train_launches[PTGNN_AMD_KERNEL_HALF_TRAIN_END_ - PTGNN_AMD_KERNEL_HALF_TRAIN_FIRST_];
 static std::atomic<int64_t> g_edge16_dst_launches[PTGNN_AMD_KERNEL_EDGE16_DST_END_ - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
 static std::atomic<int64_t> g_beam_finish_launches[PTGNN_AMD_KERNEL_BEAM_FINISH_END_ - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
+static std::atomic<int64_t> g_attention16_launches[PTGNN_AMD_KERNEL_ATTENTION16_END_ - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -56,6 +57,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_edge16_dst_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_BEAM_FINISH_END_)
     return &g_beam_finish_launches[kernel_id - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_ATTENTION16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ATTENTION16_END_)
+    return &g_attention16_launches[kernel_id - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -137,6 +140,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "beam_step_links", "beam_backtrack"};
   if (kernel_id >= PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_BEAM_FINISH_END_)
     return beam_finish_names[kernel_id - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
+  static const char *const attention16_names[PTGNN_AMD_KERNEL_ATTENTION16_END_ - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_] = {
+      "block_attention16"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_ATTENTION16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ATTENTION16_END_)
+    return attention16_names[kernel_id - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

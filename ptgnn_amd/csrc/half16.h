@@ -1,6 +1,7 @@
-// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip, wgrad16.hip): the MFMA of each 16-bit type and
-// its fragment maps, the per-wave tile, the rounded LDS panel (row and transposed fragments), the fragment epilogue, and
-// the host's dispatch and alignment checks.
+// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip, wgrad16.hip, block_attention16.hip): the MFMA of
+// each 16-bit type and its fragment maps, the per-wave tile, the rounded LDS panel (row and transposed fragments), the
+// rounding store and the transposed read of an LDS image, the fragment epilogue, and the host's dispatch and alignment
+// checks.
 //
 // Operands.  fp32 rows stay fp32 in HBM.  A lane's MFMA A fragment (v_mfma_f32_32x32x16_{bf16,f16}: lane l = row l & 31,
 // k = 8 (l >> 5) + j: cdna_hip_programming.md section 3) is 8 consecutive values of its row, rounded to the 16-bit type
@@ -65,6 +66,29 @@ __device__ __forceinline__ typename Half16<DT>::vec round8(const float *__restri
 template <int DT>
 __device__ __forceinline__ typename Half16<DT>::vec load8(const uint16_t *__restrict__ p) {
   return *reinterpret_cast<const typename Half16<DT>::vec *>(p);
+}
+
+// 4 fp32 values rounded to nearest even into 4 consecutive 16-bit elements (8-byte aligned) of an LDS image
+template <int DT>
+__device__ __forceinline__ void store4(uint16_t *dst, const float4 &v) {
+  using half4 = __attribute__((ext_vector_type(4))) typename Half16<DT>::elem;
+  const f32x4 f = {v.x, v.y, v.z, v.w};
+  *reinterpret_cast<half4 *>(dst) = __builtin_convertvector(f, half4);
+}
+
+// A transposed fragment from two ds_read_b64_tr_b16 (cdna_hip_programming.md T10), through the v4i16 builtin -- bits are
+// bits for both 16-bit types, and the files stay free of inline assembly.  Per 16-lane group the instruction gathers a
+// 4-row x 16-column block: lane 4 q + p of the group supplies the address of the block's row q, columns 4 p .. 4 p + 3
+// (`lo`, and `up` for the second block), and lane i receives column i, rows ascending: lo's in elements 0 .. 3, up's in
+// 4 .. 7.  The instruction needs EXEC all ones.
+template <int DT>
+__device__ __forceinline__ typename Half16<DT>::vec tr8(const uint16_t *lo, const uint16_t *up) {
+  using i16x4 = __attribute__((ext_vector_type(4))) short;
+  using i16x8 = __attribute__((ext_vector_type(8))) short;
+  using lds_i16x4 = __attribute__((address_space(3))) i16x4;
+  const i16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)lo);
+  const i16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)up);
+  return __builtin_bit_cast(typename Half16<DT>::vec, (i16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 __device__ __forceinline__ void zero(f32x16 &acc) {
@@ -213,12 +237,9 @@ struct RoundedPanel {
   // lane 4 q + p of the group supplies the address of the block's row q, columns 4 p .. 4 p + 3, and lane i receives
   // column i.  Groups 0, 1 are the two column halves of the rows 8 hi .. (lane half hi = 0), groups 2, 3 of hi = 1.
   __device__ __forceinline__ vec frag_tr(int row0, int col0) const {
-    using lds_i16x4 = __attribute__((address_space(3))) i16x4;
     const int l = threadIdx.x & 63, q = (l >> 2) & 3, p = l & 3, g = (l >> 4) & 1;
     const uint16_t *at = buffer(cur) + (row0 + 8 * (l >> 5) + q) * LD + col0 + 16 * g + 4 * p;
-    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)at);
-    const i16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)(at + 4 * LD));
-    return __builtin_bit_cast(vec, (i16x8)__builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7));
+    return tr8<DT>(at, at + 4 * LD);
   }
   __device__ __forceinline__ void flip() {
     park(cur ^ 1);

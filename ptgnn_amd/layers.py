@@ -864,7 +864,10 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
 
     GPU tensors: dense.linear -> the fused block attention of csrc/block_attention.hip (the [n, n] scores never reach
     HBM; dropout on P is the stateless hash mask) -> W_s with the residual -> LayerNorm -> Linear + ReLU -> W_o with the
-    residual -> LayerNorm, all HIP.  CPU tensors: torch_route.self_attention_message_passing."""
+    residual -> LayerNorm, all HIP.  CPU tensors: torch_route.self_attention_message_passing.
+    Under the `attention=True` matrix-input setting (ptgnn_amd/precision.py, off by default) the inference forward rounds
+    the operands of the four Linears and of both attention products (csrc/block_attention16.hip) to the 16-bit type;
+    the softmax, LayerNorms, residuals, every store and the whole training branch stay fp32."""
 
     def __init__(self, input_state_dimension: int, key_query_dimension: int, value_dimension: int,
                  output_dimension: int, intermediate_dimension: int, num_heads: int, dropout_rate: float = 0.0,
@@ -906,8 +909,15 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
         w_h, w_s = self.__selfatt_head_transforms, self.__summarization_layer
         w_i, w_o, ln1, ln2 = self.__intermediate_layer, self.__output_layer, self.__layer_norm1, self.__layer_norm2
         if _on_host(x):
+            # the attention=True matrix-input setting as the CPU route applies it: fp32 states, inference only (as on
+            # the GPU: nothing needs a gradient, dropout inactive)
+            host_dt = torch.float32
+            if x.dtype == torch.float32 and not (self.training and self.__dropout_layer.p > 0) \
+                    and _no_grad_needed(x, residual, *self.parameters()):
+                host_dt = precision.attention_inputs(x)
             return torch_route.self_attention_message_passing(x, residual, graph_idx, w_h, w_s, w_i, w_o, ln1, ln2,
-                                                              self.__dropout_layer, heads, dk, dv, self.__max_num_nodes)
+                                                              self.__dropout_layer, heads, dk, dv, self.__max_num_nodes,
+                                                              inputs=host_dt)
         if x.dtype in _AMP_DTYPES:   # AMP: fp32 inside, the caller's dtype outside
             return self.__transform(x.float(), residual.float(), graph_idx).to(x.dtype)
         if x.dtype != torch.float32:
@@ -933,13 +943,21 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
         params = [w_h.weight, w_s.weight, w_i.weight, w_i.bias, w_o.weight, w_o.bias, ln1.weight, ln1.bias, ln2.weight,
                   ln2.bias]
         if _no_grad_needed(x, residual, *params) and drop == 0:
-            kqv = ops.linear(x, w_h.weight)
-            values, _ = ops.block_attention(kqv, windows, self.__max_num_nodes, heads, dk, dv)
-            a = ops.row_epilogue(ops.linear_add(values, w_s.weight, residual), ops.EPI_LAYERNORM, ln1.weight, ln1.bias,
-                                 ln1.eps)
-            hidden = ops.linear(a, w_i.weight, w_i.bias, act="relu")
-            return ops.row_epilogue(ops.linear_add(hidden, w_o.weight, a, bias=w_o.bias), ops.EPI_LAYERNORM, ln2.weight,
-                                    ln2.bias, ln2.eps)
+            # float32 unless the setting was made with attention=True (ptgnn_amd/precision.py): then the four Linears and
+            # both products of the attention take 16-bit operands, as under autocast in the reference
+            dt = precision.attention_inputs(x)
+
+            def w16(name: str, lin: nn.Linear):
+                return _half_weights(self, name, dt, ops.HALF_KIND_LINEAR, lin.in_features, lin.out_features,
+                                     lambda: lin.weight.detach().to(dt).contiguous())
+            kqv = ops.linear(x, w_h.weight, inputs=dt, rounded=w16("att_w_h16", w_h))
+            values, _ = ops.block_attention(kqv, windows, self.__max_num_nodes, heads, dk, dv, inputs=dt)
+            a = ops.row_epilogue(ops.linear_add(values, w_s.weight, residual, inputs=dt, rounded=w16("att_w_s16", w_s)),
+                                 ops.EPI_LAYERNORM, ln1.weight, ln1.bias, ln1.eps)
+            hidden = ops.linear(a, w_i.weight, w_i.bias, act="relu", inputs=dt, rounded=w16("att_w_i16", w_i))
+            return ops.row_epilogue(ops.linear_add(hidden, w_o.weight, a, bias=w_o.bias, inputs=dt,
+                                                   rounded=w16("att_w_o16", w_o)),
+                                    ops.EPI_LAYERNORM, ln2.weight, ln2.bias, ln2.eps)
         kqv = dense.linear(x, w_h.weight)
         values = block_attention_autograd(kqv, windows, self.__max_num_nodes, heads, dk, dv, drop, seed)
         a = dense.row_epilogue(self.__linear_dropout(values, w_s, None, drop) + residual, False, ln1)

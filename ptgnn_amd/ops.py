@@ -71,10 +71,13 @@ _EDGE16_DST_FAMILY_FIRST = 640  # PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_: the 16-bit
 _BEAM_FINISH_FAMILY_FIRST = 704  # PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_: the beam search's finishing route
 
 
+_ATTENTION16_FAMILY_FIRST = 768  # PTGNN_AMD_KERNEL_ATTENTION16_FIRST_: the opt-in 16-bit-input block attention
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
-                  beam_finish: bool = False) -> dict:
+                  beam_finish: bool = False, attention16: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -88,7 +91,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     GEMM's two launch forms (edge16, edge16_shared); `half_training=True` the 16-bit-input training launches
     (half_wgrad, half_gru_train, half_linear_add); `edge16_dst=True` the 16-bit-input per-edge GEMM with a target-state
     half (edge16_dst: the MLP-MP message Linear); `beam_finish=True` the beam search's finishing route (beam_step_links,
-    beam_backtrack)."""
+    beam_backtrack); `attention16=True` the 16-bit-input block attention (block_attention16)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -97,7 +100,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_HALF_FAMILY_FIRST,) if half else ()) + ((_EDGE16_FAMILY_FIRST,) if edge16 else ()) \
             + ((_HALF_TRAIN_FAMILY_FIRST,) if half_training else ()) \
             + ((_EDGE16_DST_FAMILY_FIRST,) if edge16_dst else ()) \
-            + ((_BEAM_FINISH_FAMILY_FIRST,) if beam_finish else ()):
+            + ((_BEAM_FINISH_FAMILY_FIRST,) if beam_finish else ()) \
+            + ((_ATTENTION16_FAMILY_FIRST,) if attention16 else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -111,7 +115,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
-                        edge16=True, half_training=True, edge16_dst=True, beam_finish=True)
+                        edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2516,6 +2520,14 @@ def block_attention_supported(dk: int, dv: int) -> bool:
     return bool(_lib.load().ptgnn_amd_block_attention_supported(int(dk), int(dv)))
 
 
+def block_attention16_supported(dk: int, dv: int, dtype) -> bool:
+    """Whether the 16-bit-input block attention takes these widths and this dtype (ptgnn_amd_attention16_block_supported;
+    needs no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_attention16_block_supported(int(dk), int(dv), HALF_IDS[dtype]))
+
+
 def attention_windows(plan: GraphPlan, max_num_nodes: int) -> torch.Tensor:
     """Window table of selfattmessagepassing.py:59-75 from the plan of a node -> graph map (ptgnn_amd_attention_windows):
     int32 [bound + 1], bound = ceil(N / max_num_nodes) + G.  Entry w is the first row of window w for the W windows of
@@ -2549,16 +2561,28 @@ def _block_attention_args(kqv: torch.Tensor, windows: torch.Tensor, heads: int, 
 
 
 def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int,
-                    p: float = 0.0, seed: int = 0):
+                    p: float = 0.0, seed: int = 0, inputs=None):
     """Softmax attention among the rows of every window, per head (ptgnn_amd_block_attention_f32;
     selfattmessagepassing.py:104-117): kqv [N, heads (2 dk + dv)] read in place -> (out [N, heads dv], lse [N, heads]).
     `p` > 0 applies the hash dropout mask of `seed` to the probabilities (row r heads + h, column j of a
-    [N heads, max_num_nodes rounded up to even] mask)."""
+    [N heads, max_num_nodes rounded up to even] mask).
+    `inputs` = torch.bfloat16 / torch.float16: keys, queries, values and the unnormalised probabilities are rounded to
+    that type and both products run on the 16-bit matrix cores (ptgnn_amd_attention16_block: fp32 softmax, accumulation
+    and output) where p == 0, `block_attention16_supported` takes the widths and kqv has 16-byte aligned rows; otherwise
+    the fp32 kernel runs, silently."""
     lib = _lib.load()
     kqv, windows = _block_attention_args(kqv, windows, heads, dk, dv, "block_attention")
     n = kqv.shape[0]
     out = torch.empty(n, heads * dv, dtype=torch.float32, device=kqv.device)
     lse = torch.empty(n, heads, dtype=torch.float32, device=kqv.device)
+    half = _half_inputs(inputs)
+    if n and half is not None and p == 0 and block_attention16_supported(dk, dv, half) and _half_rows_ok(kqv):
+        with _timed("block_attention16", bytes=4.0 * n * heads * (2 * dk + 2 * dv + 1)):
+            rc = lib.ptgnn_amd_attention16_block(kqv.data_ptr(), _ld(kqv), windows.data_ptr(), windows.numel() - 1, n,
+                                                 int(max_num_nodes), heads, dk, dv, out.data_ptr(), heads * dv,
+                                                 lse.data_ptr(), HALF_IDS[half], _stream(out))
+        _lib.check(rc, "ptgnn_amd_attention16_block")
+        return out, lse
     if n:
         with _timed("block_attention", bytes=4.0 * n * heads * (2 * dk + 2 * dv + 1)):
             rc = lib.ptgnn_amd_block_attention_f32(kqv.data_ptr(), _ld(kqv), windows.data_ptr(), windows.numel() - 1, n,

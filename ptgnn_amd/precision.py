@@ -1,4 +1,5 @@
-"""Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks and the MLP-MP layer's message GEMMs.
+"""Opt-in 16-bit matrix-core inputs for the GGNN layer's dense blocks, the MLP-MP layer's message GEMMs and the
+attention layer's inference forward.
 
 The default is `torch.float32`: every dense block runs the exact-fp32 MFMA kernels, bit for bit as without this module.
 With `torch.bfloat16` / `torch.float16` the INFERENCE routes of `GatedMessagePassingLayer` (and, with `training=True`,
@@ -62,17 +63,42 @@ updates in ONE launch, and that launch is still taken); deeper or biased edge ML
 aggregation modules other than exactly `PnaMessageAggregation`; `_forward_general`; `forward_sharded`; every training
 route.
 
+The attention layer (`MultiHeadSelfAttentionMessagePassing`) has a switch of its own too -- it stayed fp32 under every
+setting above, and existing users keep their bits:
+
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, attention=True):   # also set_matrix_inputs(v, attention=True)
+        out = model(batch)
+
+With the flag the layer's INFERENCE forward (nothing needs a gradient, dropout inactive) runs what autocast runs in the
+16-bit type in the reference (selfattmessagepassing.py:92-122): the four Linears (head transforms, summarisation,
+intermediate, output: ptgnn_amd_half_linear / ptgnn_amd_linear_add16, operands rounded, fp32 accumulation) and both
+products of the block attention (csrc/block_attention16.hip: keys, queries and values rounded on their way into LDS,
+the unnormalised probabilities rounded in registers).  The softmax (scale, mask, running maximum and sum -- of the
+unrounded probabilities -- exp, the division), both LayerNorms, the residuals, bias, ReLU and every store stay fp32.
+Every call without the keyword means `attention=False`; `set_matrix_inputs(torch.float32)` resets it, and
+`attention=True` with float32 is accepted and means fp32.  The flag is independent of `edge_gemm`, `training` and
+`mlp`: a GGNN or MLP-MP layer under `attention=True` alone behaves as under the plain dtype setting.  The AMP up-cast
+path (16-bit states) and `target_reference != "all"` go through the same branch.  Widths the 16-bit Linear does not take
+(not multiples of 32) run that Linear in fp32, silently; the attention kernel takes every dk, dv in 1..128.
+
+What deliberately stays fp32 in the attention layer under `attention=True`: its training branch (any parameter or state
+that needs a gradient, or dropout > 0 in train()), including the attention backward.
+
 What stays fp32 under every setting: without `training=True` every training route (anything that needs a gradient);
 with it still the edge-form and edge-feature training GEMMs (`_EdgeLinear`, `_EdgeLinearFeat`), `_general_messages`
-and `forward_sharded`, every MLP-MP training route, EGC and the attention layers, the reducers, the heads and the
-decoder; without `mlp=True` all of MLP-MP; CPU tensors in
+and `forward_sharded`, every MLP-MP training route, the attention layer's training, EGC, the attention pooling
+reducers and the other reducers, the heads and the decoder; without `mlp=True` all of MLP-MP; without `attention=True`
+all of the attention layer; CPU tensors in
 training (the torch route rounds nothing where a gradient is needed); the edge-feature route's grouped GEMM; without
 `edge_gemm=True` also the grouped per-edge GEMM of the edge form.  Shapes the 16-bit kernels do not take (widths that are not multiples of 32; for the per-edge
 GEMM also fewer than 2 or more than 64 edge types) run the fp32 kernels, silently.  CPU tensors
 (ptgnn_amd/torch_route.py) round the same operands with torch under the dtype setting alone -- message operands
 included, so the flag changes nothing there -- and a checkpoint behaves alike on both devices; the MLP-MP layer's CPU
 route rounds the node states and the message Linears' weights under `mlp=True` under the same conditions as the GPU
-routes (fp32 states, nothing needs a gradient); "autocast" never touches CPU tensors.
+routes (fp32 states, nothing needs a gradient); the attention layer's CPU route rounds the Linear operands, k, q, v and
+the probabilities under `attention=True` under those conditions too (the NORMALISED probabilities, as autocast does;
+the kernel rounds the unnormalised ones -- either way each probability carries one rounding of the 16-bit type);
+"autocast" never touches CPU tensors.
 
 The setting is process-wide (like `ops.set_gemm_mode`); the layers read it, `ptgnn_amd.ops` never does -- its
 `inputs=` keyword is explicit, because inside an autograd `Function.forward` grad mode is off and an op could not tell
@@ -91,6 +117,7 @@ _setting = torch.float32
 _edge_gemm = False
 _training = False
 _mlp = False
+_attention = False
 
 
 def _checked(v):
@@ -99,18 +126,19 @@ def _checked(v):
     return v
 
 
-def _set(v, edge_gemm, training=False, mlp=False):
-    global _setting, _edge_gemm, _training, _mlp
-    prev = (_setting, _edge_gemm, _training, _mlp)
-    _setting, _edge_gemm, _training, _mlp = _checked(v), bool(edge_gemm), bool(training), bool(mlp)
+def _set(v, edge_gemm, training=False, mlp=False, attention=False):
+    global _setting, _edge_gemm, _training, _mlp, _attention
+    prev = (_setting, _edge_gemm, _training, _mlp, _attention)
+    _setting, _edge_gemm, _training, _mlp, _attention = \
+        _checked(v), bool(edge_gemm), bool(training), bool(mlp), bool(attention)
     return prev
 
 
-def set_matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False):
+def set_matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False, attention=False):
     """Set the operand type of the GGNN inference GEMMs, whether the edge form's grouped per-edge GEMM follows it,
-    whether the GGNN training routes do, and whether the MLP-MP layer's inference message GEMMs do; returns the previous
-    dtype setting."""
-    return _set(v, edge_gemm, training, mlp)[0]
+    whether the GGNN training routes do, whether the MLP-MP layer's inference message GEMMs do, and whether the attention
+    layer's inference forward does; returns the previous dtype setting."""
+    return _set(v, edge_gemm, training, mlp, attention)[0]
 
 
 def get_matrix_inputs():
@@ -118,8 +146,8 @@ def get_matrix_inputs():
 
 
 @contextlib.contextmanager
-def matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False):
-    prev = _set(v, edge_gemm, training, mlp)
+def matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False, attention=False):
+    prev = _set(v, edge_gemm, training, mlp, attention)
     try:
         yield
     finally:
@@ -154,3 +182,9 @@ def mlp_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the MLP-MP layer's inference message GEMMs for a layer call on `tensor`: `resolve(tensor)` when the
     setting was made with `mlp=True`, else float32."""
     return resolve(tensor) if _mlp else torch.float32
+
+
+def attention_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the attention layer's inference Linears and block attention for a layer call on `tensor`:
+    `resolve(tensor)` when the setting was made with `attention=True`, else float32."""
+    return resolve(tensor) if _attention else torch.float32

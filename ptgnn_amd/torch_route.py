@@ -125,10 +125,14 @@ def attention_window_bounds(node_to_graph_idx: torch.Tensor, max_num_nodes: int)
 
 
 def block_attention(kqv: torch.Tensor, bounds, num_heads: int, dk: int, dv: int, dropout_p: float = 0.0,
-                    training: bool = False) -> torch.Tensor:
+                    training: bool = False, inputs: torch.dtype = torch.float32) -> torch.Tensor:
     """selfattmessagepassing.py:104-117 in the dtype of `kqv` [N, heads (2 dk + dv)]: per window and head
-    softmax_v(key_k . query_v / sqrt(dk)), dropout, times the values -> [N, heads dv]."""
+    softmax_v(key_k . query_v / sqrt(dk)), dropout, times the values -> [N, heads dv].
+    `inputs` = torch.bfloat16 / torch.float16: k, q, v and the probabilities in front of the value product are rounded
+    to that type with torch (the softmax itself stays fp32)."""
     n = kqv.shape[0]
+    if inputs != torch.float32:
+        kqv = _rounded(kqv, inputs)
     per_head = kqv.reshape(n, num_heads, 2 * dk + dv).permute(1, 0, 2)             # [heads, N, 2 dk + dv]
     pieces = []
     for lo, hi in bounds:
@@ -136,6 +140,8 @@ def block_attention(kqv: torch.Tensor, bounds, num_heads: int, dk: int, dv: int,
         keys, queries, values = block[..., :dk], block[..., dk:2 * dk], block[..., 2 * dk:]
         probs = torch.softmax(keys @ queries.transpose(1, 2) / dk ** 0.5, dim=-1)   # [heads, key, query]
         probs = nn.functional.dropout(probs, dropout_p, training)
+        if inputs != torch.float32:
+            probs = _rounded(probs, inputs)
         pieces.append(probs @ values)                                               # [heads, n, dv]
     if not pieces:
         return kqv.new_zeros(n, num_heads * dv)
@@ -146,16 +152,30 @@ def self_attention_message_passing(node_states: torch.Tensor, residual_states: t
                                    node_to_graph_idx: torch.Tensor, head_transforms: nn.Linear, summarization: nn.Linear,
                                    intermediate: nn.Linear, output: nn.Linear, layer_norm1: nn.LayerNorm,
                                    layer_norm2: nn.LayerNorm, dropout: nn.Module, num_heads: int, dk: int, dv: int,
-                                   max_num_nodes: int) -> torch.Tensor:
+                                   max_num_nodes: int, inputs: torch.dtype = torch.float32) -> torch.Tensor:
     """MultiHeadSelfAttentionMessagePassing.forward (selfattmessagepassing.py:92-123) on torch's operators, any dtype:
-    `node_states` are the rows that attend (line 89), `residual_states` what line 119 adds."""
+    `node_states` are the rows that attend (line 89), `residual_states` what line 119 adds.
+    `inputs` = torch.bfloat16 / torch.float16 (the caller's `attention=True` matrix-input setting; fp32 states,
+    inference only): the operands the GPU route rounds are rounded here with torch and multiplied by the fp32 operators
+    -- the inputs and weights of the four Linears, k, q and v, and the probabilities in front of the value product.  This
+    route rounds the NORMALISED probabilities, as autocast does; the kernel (csrc/block_attention16.hip) rounds the
+    unnormalised ones and divides by the unrounded sum.  Either way every probability is within one unit roundoff of
+    the 16-bit type (2^-8 / 2^-11 relative) of its unrounded value.  Softmax, LayerNorms, residuals, bias and ReLU stay
+    fp32."""
     _host_only(node_states, node_to_graph_idx)
-    kqv = head_transforms(node_states)
+    if inputs == torch.float32:
+        def lin(layer, x):
+            return layer(x)
+    else:
+        def lin(layer, x):
+            return nn.functional.linear(_rounded(x, inputs), _rounded(layer.weight, inputs), layer.bias)
+    kqv = lin(head_transforms, node_states)
     bounds = attention_window_bounds(node_to_graph_idx, max_num_nodes)
-    values = block_attention(kqv, bounds, num_heads, dk, dv, float(getattr(dropout, "p", 0.0)), dropout.training)
-    attention_output = layer_norm1(dropout(summarization(values)) + residual_states)
-    hidden = nn.functional.relu(intermediate(attention_output))
-    return layer_norm2(dropout(output(hidden)) + attention_output)
+    values = block_attention(kqv, bounds, num_heads, dk, dv, float(getattr(dropout, "p", 0.0)), dropout.training,
+                             inputs=inputs)
+    attention_output = layer_norm1(dropout(lin(summarization, values)) + residual_states)
+    hidden = nn.functional.relu(lin(intermediate, attention_output))
+    return layer_norm2(dropout(lin(output, hidden)) + attention_output)
 
 
 # ------------------------------------------------------------------------------------------------------------------
