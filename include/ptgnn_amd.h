@@ -227,6 +227,14 @@ enum {
   PTGNN_AMD_KERNEL_BLOCK_ATTENTION16 = PTGNN_AMD_KERNEL_ATTENTION16_FIRST_, /* ptgnn_amd_attention16_block */
   PTGNN_AMD_KERNEL_ATTENTION16_END_
 };
+/* A fourteenth id range: the 16-bit-input launches of the GGNN edge-form TRAINING step (csrc/edge_gemm16.hip's masked
+ * forms, csrc/edge_wgrad16.hip).  A range of its own, so the ninth and tenth ranges end where they did. */
+enum {
+  PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_ = 832,
+  PTGNN_AMD_KERNEL_EDGE16_MASKED = PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_, /* ptgnn_amd_edge_masked_linear16, modes 1, 2 */
+  PTGNN_AMD_KERNEL_EDGE_WGRAD16,                                         /* ptgnn_amd_edge_weight_grad16 */
+  PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1549,6 +1557,64 @@ int ptgnn_amd_edge_dst_linear16(const float *x, int64_t ld_x, int64_t num_rows, 
                                 const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
                                 const int64_t *edges_per_type, const void *w, int32_t num_types, int32_t msg_dim,
                                 int act, int dtype, float *msg, int64_t ld_msg, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the GGNN layer's edge-form TRAINING step: the grouped per-edge GEMM with the
+ * per-edge dropout mask (csrc/edge_gemm16.hip: the same two kernels as ptgnn_amd_edge_linear16, with a compile-time mask
+ * mode) and the per-type weight gradient (csrc/edge_wgrad16.hip).
+ *
+ * Replaces: `edge_transformation_layer(self.__dropout(message_input))` of gatedmessagepassing.py:57-61 under autocast
+ *   in training, and its autograd (ptgnn_amd_edge_linear_masked_f32 / ptgnn_amd_edge_weight_grad_masked_f32 and the
+ *   other fp32 launches stay as they are).  OFF by default: the host's ptgnn_amd.precision setting asks for it with
+ *   `edge_training=True`.
+ *
+ * ptgnn_amd_edge_masked_linear16: the arguments of ptgnn_amd_edge_linear16 (no target-state half, no activation) plus
+ *   (dropout_mode, dropout_p, mask_bits).  mask_bits: the keep mask as bits exactly as ptgnn_amd_edge_linear_masked_f32
+ *   takes it (ptgnn_amd_dropout_bitmask; [message rows][width / 32] dwords, bit b of dword c = column 32 c + b; width =
+ *   state_dim in mode 1, msg_dim in mode 2); scale = 1.0f / (1.0f - dropout_p) in fp32, dropout_p == 0 means mode 0.
+ *     mode 1 (the forward)       : msg[r] = rnd(keep ? x[src[r]] * scale : 0) rnd(W_t)^T -- mask and fp32 scale BEFORE the
+ *       one rounding, as autocast applies nn.Dropout before the 16-bit Linear;
+ *     mode 2 (the input gradient): out[r] = (rnd(x[r]) rnd(W_t)^T) * keep * scale -- x the incoming gradient over an
+ *       identity index, w the rounded TRANSPOSED [num_types, state_dim_fwd, msg_dim_fwd] stack; mask and scale on the
+ *       fp32 accumulator, before the store;
+ *     mask_bits == NULL or mode 0: the launch and the bits of ptgnn_amd_edge_linear16 on the same arguments.
+ *   ptgnn_amd_edge_masked_linear16_supported(state_dim, msg_dim, num_types, dtype, mode): mode 1 or 2, the width the mask
+ *     covers a multiple of 32, and otherwise the limits of ptgnn_amd_edge_linear16_supported.  Needs no device.
+ *   Alignment and error codes as ptgnn_amd_edge_linear16 (mask_bits 4-byte aligned); every message starts
+ *   "edge_linear16: masked:" and answers before anything touches the device.  Row independence as there: the bits of
+ *   output row r depend on x[src[r]], W_t and the row's keep bits only -- with dropout_p == 0 a training forward has
+ *   the bits of the inference per-edge launch.
+ *
+ * ptgnn_amd_edge_weight_grad16: grad_w[t] = rnd(g_t)^T rnd(keep ? x[src_t[e]] * scale : 0) for every type in one launch,
+ *   fp32 [num_types, msg_dim, state_dim]; g_t = the type's rows of grad_msg [edges, msg_dim] (ld_grad_msg) in type-major
+ *   order; ids clamped into [0, num_rows), num_rows < 2^31.  Both fp32 operands are rounded in the kernel, the mask and
+ *   the fp32 scale applied before the rounding; mask_bits (the mode-1 mask) is nullable: without it, or with
+ *   dropout_p == 0, nothing is dropped and scale = 1.  A type without edges gets zeros.  Deterministic: a type's chunks
+ *   of ptgnn_amd_edge_wgrad16_chunk_edges(num_edges, num_types, msg_dim, state_dim) edges (a chunk never crosses a type)
+ *   each write one partial into the workspace (ptgnn_amd_edge_wgrad16_workspace_bytes(...) bytes, 16-byte aligned) and a
+ *   second launch adds them in a fixed order; no atomics -- two calls give the same bits.
+ *   ptgnn_amd_edge_weight_grad16_supported(state_dim, msg_dim, num_types, dtype): state_dim % 32 == 0, msg_dim % 32 == 0,
+ *     both <= 1024, 2 <= num_types <= 64.  Needs no device; the two size queries answer 0 for other shapes.
+ *   x, grad_msg, grad_w and the workspace must be 16-byte aligned with ld % 4 == 0.  Error codes as above; every message
+ *   starts "edge_weight_grad16:".
+ * (The names keep "linear16" last, like ptgnn_amd_edge_dst_linear16: the ptgnn_amd_edge_linear16* prefix is a closed set
+ * of three.  The entries are additive and the ABI version stays.)
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_edge_masked_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype,
+                                             int dropout_mode);
+int ptgnn_amd_edge_masked_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                   const int64_t *const *src_per_type, const int64_t *edges_per_type, const void *w,
+                                   int32_t num_types, int32_t msg_dim, int dtype, float *msg, int64_t ld_msg,
+                                   int dropout_mode, float dropout_p, const uint32_t *mask_bits /* nullable */,
+                                   void *stream);
+int ptgnn_amd_edge_weight_grad16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype);
+int64_t ptgnn_amd_edge_wgrad16_chunk_edges(int64_t num_edges, int32_t num_types, int32_t msg_dim, int32_t state_dim);
+size_t ptgnn_amd_edge_wgrad16_workspace_bytes(int64_t num_edges, int32_t num_types, int32_t msg_dim, int32_t state_dim);
+int ptgnn_amd_edge_weight_grad16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                 const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                 const float *grad_msg, int64_t ld_grad_msg, int32_t num_types, int32_t msg_dim,
+                                 int dtype, float dropout_p, const uint32_t *mask_bits /* nullable */, float *grad_w,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Opt-in 16-bit matrix-core inputs for the block attention's inference forward (csrc/block_attention16.hip).

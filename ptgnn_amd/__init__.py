@@ -22,7 +22,7 @@ def __getattr__(name):
         from ptgnn_amd import embeddings
         return getattr(embeddings, name)
     if name in ("set_matrix_inputs", "get_matrix_inputs", "matrix_inputs", "edge_gemm_inputs", "training_inputs",
-                "mlp_inputs", "attention_inputs"):
+                "edge_training_inputs", "mlp_inputs", "attention_inputs"):
         from ptgnn_amd import precision
         return getattr(precision, name)
     raise AttributeError(f"module 'ptgnn_amd' has no attribute {name!r}")

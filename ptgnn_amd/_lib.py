@@ -217,6 +217,14 @@ SIGNATURES = {
     "ptgnn_amd_edge_dst_linear16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int]),
     "ptgnn_amd_edge_dst_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
                                                _vp, _i64, _vp]),
+    "ptgnn_amd_edge_masked_linear16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int, _c.c_int]),
+    "ptgnn_amd_edge_masked_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _c.c_int, _vp, _i64,
+                                                  _c.c_int, _c.c_float, _vp, _vp]),
+    "ptgnn_amd_edge_weight_grad16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int]),
+    "ptgnn_amd_edge_wgrad16_chunk_edges": (_i64, [_i64, _i32, _i32, _i32]),
+    "ptgnn_amd_edge_wgrad16_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32, _i32]),
+    "ptgnn_amd_edge_weight_grad16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _c.c_int,
+                                                _c.c_float, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "ptgnn_amd_attention16_block_supported": (_c.c_int, [_i32, _i32, _c.c_int]),
     "ptgnn_amd_attention16_block": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
                                                _c.c_int, _vp]),

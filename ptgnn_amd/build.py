@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libptgnn_amd.so")
-SOURCES = ["errors.cpp", "csr_build.hip", "gather_reduce.hip", "dense_f32.hip", "stream_gemm.hip", "edge_gemm.hip", "edge_wgrad.hip", "wgrad_stream.hip", "batching.hip", "row_epilogue.hip", "shard_index.hip", "segment_mul.hip", "weighted_pool.hip", "egc_combine.hip", "pna_aggregate.hip", "attention_pool.hip", "graph_norm.hip", "block_attention.hip", "block_attention16.hip", "segment_scores.hip", "embedding_bag.hip", "char_conv.hip", "task_heads.hip", "vocab_loss.hip", "decode_step.hip", "beam_step.hip", "half_gemm.hip", "edge_gemm16.hip", "wgrad16.hip"]
+SOURCES = ["errors.cpp", "csr_build.hip", "gather_reduce.hip", "dense_f32.hip", "stream_gemm.hip", "edge_gemm.hip", "edge_wgrad.hip", "wgrad_stream.hip", "batching.hip", "row_epilogue.hip", "shard_index.hip", "segment_mul.hip", "weighted_pool.hip", "egc_combine.hip", "pna_aggregate.hip", "attention_pool.hip", "graph_norm.hip", "block_attention.hip", "block_attention16.hip", "segment_scores.hip", "embedding_bag.hip", "char_conv.hip", "task_heads.hip", "vocab_loss.hip", "decode_step.hip", "beam_step.hip", "half_gemm.hip", "edge_gemm16.hip", "wgrad16.hip", "edge_wgrad16.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "dense_common.h"), os.path.join(CSRC, "stream_gemm.h"), os.path.join(CSRC, "wgrad_stream.h"),
            os.path.join(CSRC, "gather_reduce_core.h"), os.path.join(CSRC, "segment_chunks.h"), os.path.join(CSRC, "attention_tile.h"), os.path.join(CSRC, "block_attention.h"),
            os.path.join(CSRC, "decode_common.h"), os.path.join(CSRC, "half16.h"),

@@ -9,6 +9,11 @@
 //   ptgnn_amd_edge_linear16        : one row per edge in type-major order, from host arrays of per-type `src` pointers
 // and, for the MLP-MP layer's message Linear (mlpmessagepassing.py:88-98), the per-edge form WITH a target-state half,
 //   ptgnn_amd_edge_dst_linear16    : msg[r, :] = act( rnd(X[src[r]]) . rnd(W_t[:, :H])^T + rnd(X[dst[r]]) . rnd(W_t[:, H:])^T )
+// and, for the GGNN layer's edge-form TRAINING step (gatedmessagepassing.py:57-61 with its per-edge dropout),
+//   ptgnn_amd_edge_masked_linear16 : the per-edge form with the dropout mask from its keep bits (template flag MASK) --
+//                                    1: on the gathered input before it is rounded (the forward); 2: on the fp32
+//                                    accumulator before the store (the input gradient, over an identity index)
+// The DST form runs
 // over the same two kernels (template flag DST): the unit carries a second id list, W_t is [M, 2 H], and the chain runs
 // over the source half and then over the target half into the same accumulators.  k_edge16_ws takes it at 2 H in
 // {128, 256} (its KS = 8 and 16 register budgets; the panel row is [x[src] | x[dst]]), k_edge16 everywhere else.  There
@@ -53,6 +58,12 @@ struct Edge16Args {
   int H, M, act;
   float *msg;
   int64_t ld_msg;
+  // the masked forms (template flag MASK != 0): the keep bits of the per-edge dropout, [message rows][mask_ld] dwords,
+  // bit b of dword c = column 32 c + b of the row the mask covers -- the gathered input row (MASK 1: the forward), the
+  // output row (MASK 2: the input gradient) -- and 1 / (1 - p).  Last, so the fields above keep their kernarg offsets.
+  const uint32_t *mask;
+  int mask_ld;
+  float scale;
 };
 
 // The id lists are global memory; read out of a table in device memory the pointers would be generic and their loads
@@ -94,9 +105,43 @@ __device__ __forceinline__ Unit locate(const StreamEdgeTable &tab, int v_unit, i
 
 constexpr int kTiles = 4;   // 32-column tiles per wave of k_edge16
 
+// wave_tile (half16.h) with the dropout of MASK 1 on its A operand: the row's keep word of every 32 columns rides with
+// the row's two k-steps there, and the kept values are scaled in fp32 BEFORE the one rounding (autocast applies
+// nn.Dropout before the 16-bit Linear).  The same chain: one accumulator per tile, zeroed, k ascending in steps of 16.
+template <int DT, int TILES>
+__device__ __forceinline__ void wave_tile_masked(const float *__restrict__ arow, const uint32_t *__restrict__ mrow,
+                                                 float scale, const uint16_t *__restrict__ w, int K, int col0, int tiles,
+                                                 f32x16 (&acc)[TILES]) {
+  using H = Half16<DT>;
+  const int li = frag_li(), hi = frag_hi();
+  const float *ap = arow + 8 * hi;
+  const uint16_t *bp[TILES];
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) {
+    const int tc = t < tiles ? t : tiles - 1;
+    bp[t] = w + (int64_t)(col0 + tc * 32 + li) * K + 8 * hi;
+    zero(acc[t]);
+  }
+  for (int kk = 0; kk < K; kk += 32) {
+    const uint32_t word = mrow[kk >> 5] >> (8 * hi);   // bit b + j: column kk + b + 8 hi + j
+#pragma unroll
+    for (int b = 0; b < 32; b += 16) {
+      const float4 lo = keep_scaled4(*reinterpret_cast<const float4 *>(ap + kk + b), word, b, scale);
+      const float4 up = keep_scaled4(*reinterpret_cast<const float4 *>(ap + kk + b + 4), word, b + 4, scale);
+      const f32x8 v = {lo.x, lo.y, lo.z, lo.w, up.x, up.y, up.z, up.w};
+      const typename H::vec a = __builtin_convertvector(v, typename H::vec);
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) acc[t] = H::mfma(a, load8<DT>(bp[t] + kk + b), acc[t]);
+    }
+  }
+}
+
 // DST (both kernels): the message input is [x[src] | x[dst]] and W_t is [M, 2 H] -- one chain over the source half, then
 // over the target half, into the same accumulators.
-template <int DT, bool INDIRECT, bool DST = false>
+// MASK (both kernels; per-edge form without a target half, no activation): the per-edge dropout of the training step from
+// its keep bits.  1: on the gathered input, before it is rounded (the forward); 2: on the fp32 accumulator, before the
+// store (the input gradient).  0: no mask -- the code of the unmasked instantiations is what it was.
+template <int DT, bool INDIRECT, bool DST = false, int MASK = 0>
 __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
@@ -118,6 +163,10 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
       for (int n = 0; n < kTiles; ++n) zero(acc[n]);
       wave_tile_more<DT>(q.row(p.x, p.ld_x, p.num_rows, li), w, 2 * p.H, p.H, col0, tiles, acc);
       wave_tile_more<DT>(q.dst_row(p.x, p.ld_x, p.num_rows, li), w + p.H, 2 * p.H, p.H, col0, tiles, acc);
+    } else if constexpr (MASK == 1) {   // the mask row of a row past the type's end: the last row's, like the gather
+      const uint32_t *mrow = p.mask + (q.out0 + (li < q.left ? li : q.left - 1)) * p.mask_ld;
+      wave_tile_masked<DT>(q.row(p.x, p.ld_x, p.num_rows, li), mrow, p.scale, p.w + (int64_t)q.t * p.M * p.H, p.H, col0,
+                           tiles, acc);
     } else {
       wave_tile<DT>(q.row(p.x, p.ld_x, p.num_rows, li), p.w + (int64_t)q.t * p.M * p.H, p.H, col0, tiles, acc);
     }
@@ -126,14 +175,17 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
       if (n < tiles) {
         const int col = col0 + n * 32 + li;
         for_frag_rows(q.out0, q.out0 + q.left, [&](int r, int64_t row) {
-          p.msg[row * p.ld_msg + col] = act_runtime(acc[n][r], p.act);
+          if constexpr (MASK == 2)      // the keep word of this row's 32-column tile; this lane's column is bit li
+            p.msg[row * p.ld_msg + col] = keep_scaled(acc[n][r], p.mask[row * p.mask_ld + (col >> 5)], li, p.scale);
+          else
+            p.msg[row * p.ld_msg + col] = act_runtime(acc[n][r], p.act);
         });
       }
     }
   }
 }
 
-template <int DT, int KS, bool INDIRECT, bool DST = false>
+template <int DT, int KS, bool INDIRECT, bool DST = false, int MASK = 0>
 __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   using Hf = Half16<DT>;
   using vec = typename Hf::vec;
@@ -165,27 +217,62 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
     };
   };
 
+  // MASK 1: one keep word per staged float4 (8 threads share a word: one request) rides with the unit's rows and is
+  // consumed while they are rounded into the panel -- the kept values scaled in fp32 before the one rounding.
+  using Panel = RoundedPanel<DT, 32, H>;
+  const uint32_t *const mask = p.mask;
+  const int mask_ld = p.mask_ld;
+  const float scale = p.scale;
+  uint32_t mw[MASK == 1 ? Panel::NV : 1];
+  auto fetch_mask = [&](const Unit &q) {
+#pragma unroll
+    for (int i = 0; i < Panel::NV; ++i) {
+      const int v = threadIdx.x + i * 256, r = v / Panel::RV, c = (v % Panel::RV) * 4;
+      mw[i] = mask[(q.out0 + (r < q.left ? r : q.left - 1)) * mask_ld + (c >> 5)];   // past the end: the last row's
+    }
+  };
+  auto drop = [&](int i, int, int c, float4 &v) { v = keep_scaled4(v, mw[i], c & 31, scale); };
+
   vec bw[KS];                            // columns j of W_t, all of K
   int t_loaded = -1;
   Unit cur = locate<DST>(tab, v_unit, u_begin);
-  panel.prime(rows_of(cur));
+  if constexpr (MASK == 1) {
+    panel.fetch(rows_of(cur));
+    fetch_mask(cur);
+    panel.edit(drop);
+    panel.start();
+  } else {
+    panel.prime(rows_of(cur));
+  }
   for (int u = u_begin; u < u_end; ++u) {
     const Unit nxt = locate<DST>(tab, v_unit, u + 1 < u_end ? u + 1 : u);   // no branch around the loads: the last trip
     panel.fetch(rows_of(nxt));                                          // re-reads its own unit
+    if constexpr (MASK == 1) fetch_mask(nxt);
     if (active) {
       if (cur.t != t_loaded) {           // wave-uniform
         t_loaded = cur.t;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) bw[ks] = load8<DT>(p.w + ((int64_t)cur.t * p.M + j) * H + ks * 16 + 8 * hi);
       }
+      // MASK 2: lane l asks for the keep word of the unit's row l & 31 (word `wave` of a row: columns 32 wave ..; a row past
+      // the type's end reads the last row's) before the chain -- one register; the fragment epilogue reads the words of
+      // its 16 rows out of the lanes (register r is row frag_row(r, 0) in the lower lane half, 4 further in the upper)
+      uint32_t mrow = 0;
+      if constexpr (MASK == 2) mrow = mask[(cur.out0 + (li < cur.left ? li : cur.left - 1)) * mask_ld + wave];
       f32x16 acc;
       zero(acc);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) acc = Hf::mfma(panel.frag(li, ks), bw[ks], acc);
       for_frag_rows(cur.out0, cur.out0 + cur.left, [&](int r, int64_t row) {
-        p.msg[row * p.ld_msg + j] = act_runtime(acc[r], p.act);
+        if constexpr (MASK == 2) {
+          const uint32_t lo = __builtin_amdgcn_readlane(mrow, frag_row(r, 0)), up = __builtin_amdgcn_readlane(mrow, frag_row(r, 1));
+          p.msg[row * p.ld_msg + j] = keep_scaled(acc[r], hi ? up : lo, li, scale);
+        } else {
+          p.msg[row * p.ld_msg + j] = act_runtime(acc[r], p.act);
+        }
       });
     }
+    if constexpr (MASK == 1) panel.edit(drop);
     panel.flip();
     cur = nxt;
   }
@@ -259,11 +346,11 @@ int host_table(const char *who, const int64_t *const *src_per_type, const int64_
 // Workgroups of a weight-stationary instance that one CU holds at once (registers and LDS decide; asked once).  The
 // launch is ONE such round: measured at the cfg3 layer shapes, any grid that needs a partly filled second round loses
 // 15 - 20 % to it (profiles/edge_inputs_notes.md).
-template <int DT, int KS, bool INDIRECT, bool DST>
+template <int DT, int KS, bool INDIRECT, bool DST, int MASK>
 int ws_resident_per_cu() {
   static const int per_cu = [] {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST>, 256, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST, MASK>, 256, 0) != hipSuccess ||
         n < 1) {
       (void)hipGetLastError();
       n = 2;
@@ -275,7 +362,7 @@ int ws_resident_per_cu() {
 
 // `units` < 0: unknown on the host (shared form) -- the launch is sized for the device, workgroups without units leave
 // DST: the chain is 2 H long, so the weight-stationary register budgets (KS = 8, 16) hold H in {64, 128}
-template <bool INDIRECT, bool DST = false>
+template <bool INDIRECT, bool DST = false, int MASK = 0>
 int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
   const int64_t cus = num_compute_units();
   const int k = DST ? 2 * p.H : p.H;
@@ -286,9 +373,9 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
     with_dtype(dtype, [&](auto dt) {
       auto run = [&](auto ks) {
         constexpr int DT = decltype(dt)::value, KS = decltype(ks)::value;
-        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST>());
+        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST, MASK>());
         if (units >= 0 && units < grid) grid = units;
-        k_edge16_ws<DT, KS, INDIRECT, DST><<<(unsigned)grid, 256, 0, st>>>(p);
+        k_edge16_ws<DT, KS, INDIRECT, DST, MASK><<<(unsigned)grid, 256, 0, st>>>(p);
       };
       if constexpr (DST) with_case<8, 16>(k / 16, run); else with_case<4, 8, 16>(k / 16, run);
     });
@@ -297,11 +384,12 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
     int64_t grid = cus * 8;
     if (units >= 0 && (units * col_groups + 3) / 4 < grid) grid = (units * col_groups + 3) / 4;
     with_dtype(dtype,
-               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST><<<(unsigned)grid, 256, 0, st>>>(p); });
+               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST, MASK><<<(unsigned)grid, 256, 0, st>>>(p); });
   }
   PTGNN_LAUNCH_CHECK();
-  count_launch(DST ? PTGNN_AMD_KERNEL_EDGE16_DST
-                   : (INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16));
+  count_launch(MASK ? PTGNN_AMD_KERNEL_EDGE16_MASKED
+                    : (DST ? PTGNN_AMD_KERNEL_EDGE16_DST
+                           : (INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16)));
   return PTGNN_AMD_OK;
 }
 
@@ -327,6 +415,39 @@ extern "C" int ptgnn_amd_edge_linear16(const float *x, int64_t ld_x, int64_t num
   p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
   p.H = state_dim; p.M = msg_dim; p.act = act; p.msg = msg; p.ld_msg = ld_msg;
   return launch<false>(p, dtype, units, (hipStream_t)stream_);
+}
+
+extern "C" int ptgnn_amd_edge_masked_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype,
+                                                        int dropout_mode) {
+  // the mask covers state_dim (mode 1) or msg_dim (mode 2) columns in 32-bit words: both are multiples of 32 already
+  return (dropout_mode == 1 || dropout_mode == 2) && dtype_ok(dtype) && shape_ok(state_dim, msg_dim, num_types) ? 1 : 0;
+}
+
+extern "C" int ptgnn_amd_edge_masked_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                              const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                              const void *w, int32_t num_types, int32_t msg_dim, int dtype, float *msg,
+                                              int64_t ld_msg, int dropout_mode, float dropout_p,
+                                              const uint32_t *mask_bits, void *stream_) {
+  PTGNN_REQUIRE(dropout_mode >= 0 && dropout_mode <= 2 && dropout_p >= 0.f && dropout_p < 1.f, PTGNN_AMD_EINVAL,
+                "edge_linear16: masked: bad dropout mode / probability");
+  if (dropout_p == 0.f || mask_bits == nullptr) dropout_mode = 0;
+  if (const int rc = check_shape(" masked:", state_dim, num_types, msg_dim, PTGNN_AMD_ACT_NONE, dtype)) return rc;
+  Edge16Args p{};
+  int64_t units = 0;
+  if (const int rc = host_table(" masked:", src_per_type, nullptr, edges_per_type, num_types, false, p.tab, units))
+    return rc;
+  if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
+  if (const int rc = check_operands(" masked:", x, ld_x, num_rows, state_dim, w, msg_dim, msg, ld_msg)) return rc;
+  PTGNN_REQUIRE(dropout_mode == 0 || aligned4(mask_bits), PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: masked: mask_bits must be 4-byte aligned");
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = PTGNN_AMD_ACT_NONE; p.msg = msg; p.ld_msg = ld_msg;
+  if (dropout_mode == 0) return launch<false>(p, dtype, units, (hipStream_t)stream_);   // the unmasked launch, its bits
+  p.mask = mask_bits;
+  p.mask_ld = (dropout_mode == 2 ? msg_dim : state_dim) / 32;
+  p.scale = 1.0f / (1.0f - dropout_p);
+  return dropout_mode == 1 ? launch<false, false, 1>(p, dtype, units, (hipStream_t)stream_)
+                           : launch<false, false, 2>(p, dtype, units, (hipStream_t)stream_);
 }
 
 extern "C" int ptgnn_amd_edge_dst_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype) {

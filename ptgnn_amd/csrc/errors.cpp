@@ -33,6 +33,7 @@ static std::atomic<int64_t> g_half_train_launches[PTGNN_AMD_KERNEL_HALF_TRAIN_EN
 static std::atomic<int64_t> g_edge16_dst_launches[PTGNN_AMD_KERNEL_EDGE16_DST_END_ - PTGNN_AMD_KERNEL_EDGE16_DST_FIRST_];
 static std::atomic<int64_t> g_beam_finish_launches[PTGNN_AMD_KERNEL_BEAM_FINISH_END_ - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
 static std::atomic<int64_t> g_attention16_launches[PTGNN_AMD_KERNEL_ATTENTION16_END_ - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
+static std::atomic<int64_t> g_edge16_train_launches[PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_ - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -59,6 +60,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_beam_finish_launches[kernel_id - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_ATTENTION16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ATTENTION16_END_)
     return &g_attention16_launches[kernel_id - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_)
+    return &g_edge16_train_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -144,6 +147,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "block_attention16"};
   if (kernel_id >= PTGNN_AMD_KERNEL_ATTENTION16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ATTENTION16_END_)
     return attention16_names[kernel_id - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
+  static const char *const edge16_train_names[PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_ - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_] = {
+      "edge16_masked", "edge_wgrad16"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_)
+    return edge16_train_names[kernel_id - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

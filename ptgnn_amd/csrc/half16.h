@@ -1,4 +1,5 @@
-// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip, wgrad16.hip, block_attention16.hip): the MFMA of
+// What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip, wgrad16.hip, edge_wgrad16.hip,
+// block_attention16.hip): the MFMA of
 // each 16-bit type and its fragment maps, the per-wave tile, the rounded LDS panel (row and transposed fragments), the
 // rounding store and the transposed read of an LDS image, the fragment epilogue, and the host's dispatch and alignment
 // checks.
@@ -115,6 +116,19 @@ __device__ __forceinline__ void for_frag_rows(int64_t row0, int64_t end, F &&fn)
   }
 }
 
+// The per-edge dropout of the masked forms (edge_gemm16.hip, edge_wgrad16.hip) on one value: v * scale where bit `bit` of
+// the keep word is set, else +0 -- the bit spread over the word and ANDed in, as the fp32 streaming kernel does it, so a
+// dropped inf or NaN is a zero too.
+__device__ __forceinline__ float keep_scaled(float v, uint32_t word, int bit, float scale) {
+  const int t = ((int)(word << (31 - bit))) >> 31;
+  return __uint_as_float(__float_as_uint(v * scale) & (uint32_t)t);
+}
+// ... on the 4 consecutive values whose keep bits are bits `bit` .. `bit + 3` of the word
+__device__ __forceinline__ float4 keep_scaled4(float4 v, uint32_t word, int bit, float scale) {
+  return make_float4(keep_scaled(v.x, word, bit, scale), keep_scaled(v.y, word, bit + 1, scale),
+                     keep_scaled(v.z, word, bit + 2, scale), keep_scaled(v.w, word, bit + 3, scale));
+}
+
 __device__ __forceinline__ float act_runtime(float v, int act) {
   if (act == PTGNN_AMD_ACT_TANH) return fast_tanh(v);
   if (act == PTGNN_AMD_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -206,6 +220,17 @@ struct RoundedPanel {
                                : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
+  // ... for callers that keep state per staged float4 (edge_wgrad16.hip: the gathered row ids, asked for one panel
+  // ahead): src(i, r, c) also gets the slot
+  template <class Src>
+  __device__ __forceinline__ void fetch_slots(Src &&src, int live) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      stage[i] = v / RV < live ? *reinterpret_cast<const float4 *>(src(i, v / RV, (v % RV) * 4))
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
   __device__ __forceinline__ void park(int buf) {      // registers -> rounded 16-bit panel in LDS
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -214,12 +239,26 @@ struct RoundedPanel {
       *reinterpret_cast<half4 *>(buffer(buf) + (v / RV) * LD + (v % RV) * 4) = __builtin_convertvector(f, half4);
     }
   }
-  template <class Src>
-  __device__ __forceinline__ void prime(Src &&src) {
-    fetch(src);
+  // The hook of the masked forms: fn(i, row, col, value) on each staged float4 (slot i; row, col as `src` got them) of
+  // the panel last fetched, before `park` rounds it.  A masked walk is fetch(src); edit(fn); start(); and per panel
+  // fetch(next); MFMAs; stores; edit(fn); flip();
+  template <class Fn>
+  __device__ __forceinline__ void edit(Fn &&fn) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      fn(i, v / RV, (v % RV) * 4, stage[i]);
+    }
+  }
+  __device__ __forceinline__ void start() {            // the fetched panel becomes the current one
     park(0);
     __syncthreads();
     cur = 0;
+  }
+  template <class Src>
+  __device__ __forceinline__ void prime(Src &&src) {
+    fetch(src);
+    start();
   }
   // this lane's A fragment of k-step ks in row `row` of the current panel
   __device__ __forceinline__ vec frag(int row, int ks) const {
@@ -228,9 +267,7 @@ struct RoundedPanel {
   template <class Src>
   __device__ __forceinline__ void prime(Src &&src, int live) {
     fetch(src, live);
-    park(0);
-    __syncthreads();
-    cur = 0;
+    start();
   }
   // The transposed fragment: rows row0 + 8 hi .. + 7 (row0 % 8 == 0) of column col0 + li (col0 % 32 == 0) of the
   // current panel, rows ascending in the vector.  Per 16-lane group the instruction gathers a 4-row x 16-column block:

@@ -40,7 +40,9 @@ grouped GEMM, `forward_sharded`, every other layer and the decoder stay fp32 und
 training route unless the setting was made with `training=True`: then the GRU cell at the end of every GGNN training
 route and the table-form training Linear are 16-bit autograd nodes (`dense._GruCell`, `dense._Linear` with `inputs=`:
 forward, input gradients and weight gradients on csrc/half_gemm.hip and csrc/wgrad16.hip); `_EdgeLinear`,
-`_EdgeLinearFeat` and `_general_messages` stay fp32.
+`_EdgeLinearFeat` and `_general_messages` stay fp32.  With `edge_training=True` (a flag of its own again) the edge-form
+training branch of the GGNN layer runs `_EdgeLinear` with 16-bit operands: the masked per-edge forward and input
+gradient on csrc/edge_gemm16.hip, the per-type weight gradient on csrc/edge_wgrad16.hip.
 
 Device dispatch (round 5): tensors on the CPU take `ptgnn_amd/torch_route.py` (plain torch operators, so that the
 reference's `predict.py` -- which restores and runs on "cpu" -- and a CPU `ModelTrainer` work with these layers);
@@ -232,12 +234,15 @@ def _dropout_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
-def _train_edge_messages(owner, x, plan, weights, use_dst: bool, p: float = 0.0, seed_xor: int = 0, key: str = "edge_w"):
+def _train_edge_messages(owner, x, plan, weights, use_dst: bool, p: float = 0.0, seed_xor: int = 0, key: str = "edge_w",
+                         inputs=None):
     """Training, edge form: the grouped per-edge GEMM as one autograd node (forward + both gradients on HIP) over the
     per-type weights stacked once per forward scope, with the reference's per-edge input dropout folded in as a hash
-    mask (one seed draw per call with p > 0; `seed_xor` tells the ranks of a sharded graph apart)."""
+    mask (one seed draw per call with p > 0; `seed_xor` tells the ranks of a sharded graph apart).  `inputs`: the 16-bit
+    operand type of the node's three GEMMs (precision.edge_training_inputs; None / float32: the fp32 node)."""
     w_stack = _scoped(owner, key, lambda: torch.stack(weights))
-    return edge_linear_autograd(x, plan, w_stack, use_dst, p, (_dropout_seed() ^ seed_xor) if p > 0 else 0)
+    return edge_linear_autograd(x, plan, w_stack, use_dst, p, (_dropout_seed() ^ seed_xor) if p > 0 else 0,
+                                inputs=inputs)
 
 
 _AMP_DTYPES = (torch.float16, torch.bfloat16)
@@ -525,8 +530,11 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
         if (not has_feats and node_states.dtype == torch.float32 and _edge_training_ok(H, M)
                 and (p > 0 or _prefer_edge_path(plan.num_edges, num_nodes, len(ws), H, M))):
             # training, edge form: grouped per-edge GEMM with the reference's per-edge input dropout
-            # folded in (forward + both gradients on HIP), HIP segment reduce, torch GRU cell
-            agg = segment_reduce(_train_edge_messages(self, node_states, plan, ws, False, p), plan, agg_fn)
+            # folded in (forward + both gradients on HIP), HIP segment reduce, torch GRU cell.  The node's three GEMMs
+            # take 16-bit operands when the matrix-input setting was made with edge_training=True.
+            agg = segment_reduce(_train_edge_messages(self, node_states, plan, ws, False, p,
+                                                      inputs=precision.edge_training_inputs(node_states)),
+                                 plan, agg_fn)
         elif self._table_ok(node_states, edge_features):
             # training without per-edge dropout, few edge types: differentiable HIP GEMM nodes (ptgnn_amd/dense.py)
             # for the dense blocks, the HIP kernel (forward + backward) for the aggregation

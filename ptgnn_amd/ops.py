@@ -74,10 +74,13 @@ _BEAM_FINISH_FAMILY_FIRST = 704  # PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_: the beam
 _ATTENTION16_FAMILY_FIRST = 768  # PTGNN_AMD_KERNEL_ATTENTION16_FIRST_: the opt-in 16-bit-input block attention
 
 
+_EDGE16_TRAIN_FAMILY_FIRST = 832  # PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_: the 16-bit-input edge-form training launches
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
-                  beam_finish: bool = False, attention16: bool = False) -> dict:
+                  beam_finish: bool = False, attention16: bool = False, edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -91,7 +94,9 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     GEMM's two launch forms (edge16, edge16_shared); `half_training=True` the 16-bit-input training launches
     (half_wgrad, half_gru_train, half_linear_add); `edge16_dst=True` the 16-bit-input per-edge GEMM with a target-state
     half (edge16_dst: the MLP-MP message Linear); `beam_finish=True` the beam search's finishing route (beam_step_links,
-    beam_backtrack); `attention16=True` the 16-bit-input block attention (block_attention16)."""
+    beam_backtrack); `attention16=True` the 16-bit-input block attention (block_attention16); `edge16_training=True`
+    the 16-bit-input edge-form training launches (edge16_masked: the masked per-edge GEMM in its forward and
+    input-gradient modes; edge_wgrad16: the per-type weight gradient)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -101,7 +106,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_HALF_TRAIN_FAMILY_FIRST,) if half_training else ()) \
             + ((_EDGE16_DST_FAMILY_FIRST,) if edge16_dst else ()) \
             + ((_BEAM_FINISH_FAMILY_FIRST,) if beam_finish else ()) \
-            + ((_ATTENTION16_FAMILY_FIRST,) if attention16 else ()):
+            + ((_ATTENTION16_FAMILY_FIRST,) if attention16 else ()) \
+            + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -115,7 +121,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
 def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
-                        edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True)
+                        edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
+                        edge16_training=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -526,6 +533,32 @@ def edge_linear16_dst_supported(state_dim: int, msg_dim: int, num_types: int, dt
         return False
     return bool(_lib.load().ptgnn_amd_edge_dst_linear16_supported(int(state_dim), int(msg_dim), int(num_types),
                                                                  HALF_IDS[dtype]))
+
+
+def edge_linear16_masked_supported(state_dim: int, msg_dim: int, num_types: int, dtype, mode: int) -> bool:
+    """Whether the 16-bit grouped per-edge GEMM takes the shape with the per-edge dropout mask in `mode` (1: on the
+    gathered input, the forward; 2: on the output, the input gradient) -- ptgnn_amd_edge_masked_linear16_supported;
+    needs no device."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_edge_masked_linear16_supported(int(state_dim), int(msg_dim), int(num_types),
+                                                                     HALF_IDS[dtype], int(mode)))
+
+
+def edge_weight_grad16_supported(state_dim: int, msg_dim: int, num_types: int, dtype) -> bool:
+    """Whether the 16-bit per-type weight gradient takes the shape (ptgnn_amd_edge_weight_grad16_supported; needs no
+    device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_edge_weight_grad16_supported(int(state_dim), int(msg_dim), int(num_types),
+                                                                   HALF_IDS[dtype]))
+
+
+def edge_wgrad16_chunk_edges(num_edges: int, num_types: int, msg_dim: int, state_dim: int) -> int:
+    """Edges one workgroup partial of the 16-bit per-type weight gradient covers -- a type of n edges is ceil(n / it)
+    partials (ptgnn_amd_edge_wgrad16_chunk_edges; needs no device); 0 for a shape the kernel does not take."""
+    return int(_lib.load().ptgnn_amd_edge_wgrad16_chunk_edges(int(num_edges), int(num_types), int(msg_dim),
+                                                              int(state_dim)))
 
 
 def _edge16_stack(ws: Sequence[torch.Tensor], dtype: torch.dtype, given: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1436,12 +1469,18 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     (mode 2, the input-gradient form) with the hash mask of ptgnn_amd_edge_linear_dropout_f32; with
     `mask_bits` (`dropout_bitmask` of the same p and seed) the streaming kernel applies the mask from its bits.
     `inputs` / `rounded`: the 16-bit matrix-core form, as `edge_linear_shared` takes them; with `use_dst` the launch is
-    ptgnn_amd_edge_dst_linear16 (`edge_linear16_dst_supported`; `rounded` is then the [T, M, 2 H] stack).  With dropout
-    or edge features a 16-bit `inputs` raises, and with `use_dst` it wants GPU states."""
+    ptgnn_amd_edge_dst_linear16 (`edge_linear16_dst_supported`; `rounded` is then the [T, M, 2 H] stack).  With
+    `dropout` AND `mask_bits` (no target half) the launch is ptgnn_amd_edge_masked_linear16 where
+    `edge_linear16_masked_supported` takes the shape -- mode 1 rounds (keep ? x * scale : 0), mode 2 masks and scales the
+    fp32 accumulator -- and the fp32 masked route otherwise, silently.  With edge features, with dropout but no
+    `mask_bits`, or with dropout and a target half, a 16-bit `inputs` raises, and with `use_dst` it wants GPU states."""
     half = _half_inputs(inputs)
-    if half is not None and ((dropout is not None and dropout[0] != 0 and dropout[1] > 0.0)
-                             or (edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats))):
+    dropping = dropout is not None and dropout[0] != 0 and dropout[1] > 0.0
+    if half is not None and edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats):
         raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout nor edge features")
+    if half is not None and dropping and (use_dst or mask_bits is None):
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take dropout only as mask_bits (`dropout_bitmask`) and "
+                                 "without a target-state half")
     if half is not None and use_dst and not x.is_cuda:
         raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs with a target-state half run on the GPU kernel only "
                                  f"(got states on {x.device})")
@@ -1481,7 +1520,23 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
                                                  ACT_IDS[act], HALF_IDS[half], msg.data_ptr(), M, _stream(msg))
         _lib.check(rc, "ptgnn_amd_edge_dst_linear16")
         return msg[:E] if E > 0 else msg[:0]
-    if half is not None and not use_dst and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
+    if (half is not None and dropping and not use_dst and act is None and mask_bits is not None and E > 0
+            and edge_linear16_masked_supported(H, M, T, half, dropout[0]) and _half_rows_ok(x)):
+        words = (M if dropout[0] == 2 else H) // 32
+        if tuple(mask_bits.shape) != (E, words) or mask_bits.dtype != torch.int32 or not mask_bits.is_cuda:
+            raise _lib.PtgnnAmdError(f"edge_linear: mask_bits must be int32 [{E}, {words}] on the device")
+        mask_bits = mask_bits.contiguous()
+        w16 = _edge16_stack(ws, half, rounded)
+        with _timed("edge_linear16_masked", flops=2.0 * E * H * M,
+                    bytes=4.0 * (E * H + E * M) + 2.0 * T * M * H + 8.0 * E + 4.0 * E * words):
+            rc = lib.ptgnn_amd_edge_masked_linear16(x.data_ptr(), _ld(x), x.shape[0], H,
+                                                    ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(cn, ctypes.c_void_p),
+                                                    w16.data_ptr(), T, M, HALF_IDS[half], msg.data_ptr(), M,
+                                                    int(dropout[0]), float(dropout[1]), mask_bits.data_ptr(),
+                                                    _stream(msg))
+        _lib.check(rc, "ptgnn_amd_edge_masked_linear16")
+        return msg[:E]
+    if half is not None and not dropping and not use_dst and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
         w16 = _edge16_stack(ws, half, rounded)
         with _timed("edge_linear16", flops=2.0 * E * H * M, bytes=4.0 * (E * H + E * M) + 2.0 * T * M * H + 8.0 * E):
             rc = lib.ptgnn_amd_edge_linear16(x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),
@@ -1492,7 +1547,7 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     dp = PtrArr(*[d.data_ptr() if d.numel() else None for d in dsts])
     wp = PtrArr(*[w.data_ptr() for w in ws])
     K = H * (2 if use_dst else 1)
-    if dropout is not None and dropout[0] != 0 and dropout[1] > 0.0:
+    if dropping:
         if use_dst or act is not None:
             raise _lib.PtgnnAmdError("edge_linear: dropout supports the GGNN form only (no target half, no act)")
         if mask_bits is not None and E > 0 and edge_linear_masked_supported(H, M, dropout[0]):
@@ -1580,9 +1635,13 @@ def _edge_linear_feat(x, adjacency_lists, weights, use_dst: bool, act, edge_feat
 
 def edge_weight_grad(x: torch.Tensor, adjacency_lists, grad_msg: torch.Tensor, use_dst: bool,
                      dropout_p: float = 0.0, dropout_seed: int = 0,
-                     mask_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     mask_bits: Optional[torch.Tensor] = None, inputs=None) -> torch.Tensor:
     """grad_w[t] = grad_msg_t^T . [x[src_t] ; x[dst_t] (if use_dst)]  for all types -> [T, M, K].
-    `mask_bits`: the dropout keep mask as bits (`dropout_bitmask` of the same p and seed) instead of the hash."""
+    `mask_bits`: the dropout keep mask as bits (`dropout_bitmask` of the same p and seed) instead of the hash.
+    `inputs` = torch.bfloat16 / torch.float16: both operands -- grad_msg and the gathered, masked, scaled x -- are rounded
+    to that type in the kernel and multiplied on the 16-bit matrix cores (ptgnn_amd_edge_weight_grad16: fp32 accumulation
+    and output, deterministic) where `edge_weight_grad16_supported` takes the shape, there is no target half, the rows are
+    16-byte aligned and dropout (if any) comes with `mask_bits`; otherwise the fp32 kernels run, silently."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
     _require_cuda_f32("grad_msg", grad_msg)
@@ -1600,6 +1659,26 @@ def edge_weight_grad(x: torch.Tensor, adjacency_lists, grad_msg: torch.Tensor, u
     dp = PtrArr(*[d.data_ptr() if d.numel() else None for d in dsts])
     cn = CntArr(*counts)
     grad_w = torch.empty(T, M, K, dtype=torch.float32, device=x.device)
+    half = _half_inputs(inputs)
+    if (half is not None and not use_dst and E > 0 and (dropout_p <= 0.0 or mask_bits is not None)
+            and edge_weight_grad16_supported(H, M, T, half) and _half_rows_ok(x) and _half_rows_ok(grad_msg)):
+        if dropout_p > 0.0:
+            if tuple(mask_bits.shape) != (E, H // 32) or mask_bits.dtype != torch.int32 or not mask_bits.is_cuda:
+                raise _lib.PtgnnAmdError(f"edge_weight_grad: mask_bits must be int32 [{E}, {H // 32}] on the device")
+            mask_bits = mask_bits.contiguous()
+        ws_bytes = lib.ptgnn_amd_edge_wgrad16_workspace_bytes(E, T, M, H)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+        # roofline bytes: the fp32 operand rows once, the ids, the mask, the result, and the partials written and read once
+        with _timed("edge_weight_grad16", flops=2.0 * E * H * M,
+                    bytes=4.0 * (E * H + E * M + T * M * H) + 8.0 * E + (E * H / 8.0 if dropout_p > 0.0 else 0.0)
+                    + 2.0 * ws_bytes):
+            rc = lib.ptgnn_amd_edge_weight_grad16(
+                x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(cn, ctypes.c_void_p),
+                grad_msg.data_ptr(), _ld(grad_msg), T, M, HALF_IDS[half], float(dropout_p),
+                mask_bits.data_ptr() if dropout_p > 0.0 else None, grad_w.data_ptr(), ws.data_ptr(), ws_bytes,
+                _stream(grad_w))
+        _lib.check(rc, "ptgnn_amd_edge_weight_grad16")
+        return grad_w
     ws_bytes = lib.ptgnn_amd_edge_wgrad_workspace_bytes(E, T, M, K)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
     gm_ptr = grad_msg.data_ptr() if E > 0 else x.data_ptr()

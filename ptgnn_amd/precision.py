@@ -84,8 +84,30 @@ path (16-bit states) and `target_reference != "all"` go through the same branch.
 What deliberately stays fp32 in the attention layer under `attention=True`: its training branch (any parameter or state
 that needs a gradient, or dropout > 0 in train()), including the attention backward.
 
-What stays fp32 under every setting: without `training=True` every training route (anything that needs a gradient);
-with it still the edge-form and edge-feature training GEMMs (`_EdgeLinear`, `_EdgeLinearFeat`), `_general_messages`
+The edge form of the GGNN TRAINING step -- what a Graph2Class batch takes, and every batch once the layer has per-edge
+dropout (`dropout_rate > 0` in train(): the reference's Typilus configuration) -- has a switch of its own as well; it
+stayed fp32 under `training=True`, and existing users keep their bits:
+
+    ptgnn_amd.set_matrix_inputs("autocast", training=True, edge_training=True)
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, edge_training=True):
+        loss = model(batch); loss.backward()
+
+With the flag the edge-form training branch of `GatedMessagePassingLayer.forward` runs its autograd node
+(`scatter._EdgeLinear`) with 16-bit operands in all three GEMMs: the grouped per-edge forward rounds
+(keep ? x[src] * scale : 0) -- the dropout mask and its fp32 scale 1 / (1 - p) applied BEFORE the one rounding, as
+autocast applies nn.Dropout before the 16-bit Linear -- against the rounded [T, M, H] weights; the input gradient rounds
+the incoming gradient against the rounded transposed weights and applies mask and scale to the fp32 accumulator
+(csrc/edge_gemm16.hip, the masked forms); the per-type weight gradient rounds both the incoming gradient and the
+gathered, masked, scaled states (csrc/edge_wgrad16.hip, deterministic).  Saved tensors, the mask bits, grad_msg, the
+[E, K] input gradient, both segment sums, d x, d W and the GRU node (which follows `training=True`, independently) stay
+fp32.  Every call without the keyword means `edge_training=False`; `set_matrix_inputs(torch.float32)` resets it, and
+`edge_training=True` with float32 is accepted and means fp32.  The flag is independent of the other four.  With
+dropout 0 a training forward under the flag has the bits of the inference per-edge launch under `edge_gemm=True`.
+
+What stays fp32 under every setting: without `training=True` every training route (anything that needs a gradient)
+except, with `edge_training=True`, the edge-form node above;
+with it still the edge-form training GEMMs (`_EdgeLinear`) unless `edge_training=True`; under every flag the
+edge-feature training GEMMs (`_EdgeLinearFeat`), `_general_messages`
 and `forward_sharded`, every MLP-MP training route, the attention layer's training, EGC, the attention pooling
 reducers and the other reducers, the heads and the decoder; without `mlp=True` all of MLP-MP; without `attention=True`
 all of the attention layer; CPU tensors in
@@ -118,6 +140,7 @@ _edge_gemm = False
 _training = False
 _mlp = False
 _attention = False
+_edge_training = False
 
 
 def _checked(v):
@@ -126,19 +149,20 @@ def _checked(v):
     return v
 
 
-def _set(v, edge_gemm, training=False, mlp=False, attention=False):
-    global _setting, _edge_gemm, _training, _mlp, _attention
-    prev = (_setting, _edge_gemm, _training, _mlp, _attention)
-    _setting, _edge_gemm, _training, _mlp, _attention = \
-        _checked(v), bool(edge_gemm), bool(training), bool(mlp), bool(attention)
+def _set(v, edge_gemm, training=False, mlp=False, attention=False, edge_training=False):
+    global _setting, _edge_gemm, _training, _mlp, _attention, _edge_training
+    prev = (_setting, _edge_gemm, _training, _mlp, _attention, _edge_training)
+    _setting, _edge_gemm, _training, _mlp, _attention, _edge_training = \
+        _checked(v), bool(edge_gemm), bool(training), bool(mlp), bool(attention), bool(edge_training)
     return prev
 
 
-def set_matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False, attention=False):
+def set_matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False, attention=False, edge_training=False):
     """Set the operand type of the GGNN inference GEMMs, whether the edge form's grouped per-edge GEMM follows it,
-    whether the GGNN training routes do, whether the MLP-MP layer's inference message GEMMs do, and whether the attention
-    layer's inference forward does; returns the previous dtype setting."""
-    return _set(v, edge_gemm, training, mlp, attention)[0]
+    whether the GGNN training routes do, whether the MLP-MP layer's inference message GEMMs do, whether the attention
+    layer's inference forward does, and whether the GGNN edge-form training node does; returns the previous dtype
+    setting."""
+    return _set(v, edge_gemm, training, mlp, attention, edge_training)[0]
 
 
 def get_matrix_inputs():
@@ -146,8 +170,8 @@ def get_matrix_inputs():
 
 
 @contextlib.contextmanager
-def matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False, attention=False):
-    prev = _set(v, edge_gemm, training, mlp, attention)
+def matrix_inputs(v, *, edge_gemm=False, training=False, mlp=False, attention=False, edge_training=False):
+    prev = _set(v, edge_gemm, training, mlp, attention, edge_training)
     try:
         yield
     finally:
@@ -176,6 +200,12 @@ def training_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the GGNN training routes' 16-bit autograd nodes for a layer call on `tensor`: `resolve(tensor)` when
     the setting was made with `training=True` and the tensor is on a GPU, else float32."""
     return resolve(tensor) if _training and tensor.is_cuda else torch.float32
+
+
+def edge_training_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the GGNN edge-form training node's three GEMMs for a layer call on `tensor`: `resolve(tensor)` when
+    the setting was made with `edge_training=True` and the tensor is on a GPU, else float32."""
+    return resolve(tensor) if _edge_training and tensor.is_cuda else torch.float32
 
 
 def mlp_inputs(tensor: torch.Tensor) -> torch.dtype:

@@ -459,19 +459,33 @@ class _EdgeLinear(torch.autograd.Function):
               d x    = segment-sum of d in over the source rows (+ over the destination rows for the
                        target-state half): the HIP segment reduce over the transposed / forward plan.
     No [E, K] gathered input is kept between forward and backward, and the mask only as bits (E * K / 8 bytes).
+
+    `inputs` = torch.bfloat16 / torch.float16 (the edge-form training switch of ptgnn_amd/precision.py; no target half):
+    the three GEMMs round their operands to that type -- the gathered, masked, scaled states and the incoming gradient in
+    the kernels, the [T, M, H] weight stack and its transpose by torch, once per call -- and run on the 16-bit matrix
+    cores (csrc/edge_gemm16.hip's masked forms, csrc/edge_wgrad16.hip) where the ops take the shape; saved tensors,
+    grad_msg, the [E, K] input gradient, the segment sums, d x and d W stay fp32.  None / float32: the fp32 kernels.
     """
 
     @staticmethod
-    def forward(ctx, x, plan, use_dst, dropout_p, dropout_seed, w_stack):
+    def forward(ctx, x, plan, use_dst, dropout_p, dropout_seed, w_stack, inputs=None):
         adj = plan._adj
+        if use_dst or inputs == torch.float32:
+            inputs = None
         drop = (1, dropout_p, dropout_seed) if dropout_p > 0.0 else None
         # the keep mask as one bit per element (E * H / 8 bytes), generated once and shared by the forward, the input
         # gradient and the weight gradient: the hash inside three GEMMs is kernel time (fp32 MFMA shares the VALU lanes)
         bits = None
         if drop is not None and not use_dst and plan.num_edges > 0:
             bits = ops.dropout_bitmask(plan.num_edges, x.shape[1], dropout_p, dropout_seed, x.device)
-        msg = ops.edge_linear(x, adj, list(w_stack.unbind(0)), use_dst, dropout=drop, mask_bits=bits)
-        ctx.plan, ctx.use_dst, ctx.drop, ctx.bits = plan, use_dst, (dropout_p, dropout_seed), bits
+        if drop is not None and bits is None:
+            inputs = None                  # the hash form of the mask (a width off the 32-bit words): fp32 kernels only
+        if inputs is None:
+            msg = ops.edge_linear(x, adj, list(w_stack.unbind(0)), use_dst, dropout=drop, mask_bits=bits)
+        else:
+            msg = ops.edge_linear(x, adj, list(w_stack.unbind(0)), False, dropout=drop, mask_bits=bits, inputs=inputs,
+                                  rounded=_rounded_stack(w_stack, inputs))
+        ctx.plan, ctx.use_dst, ctx.drop, ctx.bits, ctx.inputs = plan, use_dst, (dropout_p, dropout_seed), bits, inputs
         ctx.save_for_backward(x, w_stack)
         return msg
 
@@ -484,9 +498,10 @@ class _EdgeLinear(torch.autograd.Function):
         H = x.shape[1]
         gm = grad_msg.contiguous()
         need_x = ctx.needs_input_grad[0]
+        inputs = ctx.inputs
         d_x = d_w = None
         if ctx.needs_input_grad[5]:
-            d_w = ops.edge_weight_grad(x, adj, gm, use_dst, p, seed, mask_bits=ctx.bits)   # [T, M, K], one tensor
+            d_w = ops.edge_weight_grad(x, adj, gm, use_dst, p, seed, mask_bits=ctx.bits, inputs=inputs)   # [T, M, K]
         if need_x:
             if plan.num_edges == 0:
                 d_x = torch.zeros_like(x)
@@ -494,7 +509,8 @@ class _EdgeLinear(torch.autograd.Function):
                 wt = w_stack.detach().transpose(1, 2).contiguous()                             # [T, K, M]
                 drop = (2, p, seed) if p > 0.0 else None
                 g_in = ops.edge_linear(gm, [(i, i) for i in plan.identity_index()], list(wt.unbind(0)),
-                                       False, dropout=drop, mask_bits=ctx.bits)               # [E, K]
+                                       False, dropout=drop, mask_bits=ctx.bits, inputs=inputs,
+                                       rounded=_rounded_stack(wt, inputs))  # [E, K]
                 tp = plan.transposed_plan()
                 d_x = ops.gather_reduce(g_in[:, :H] if use_dst else g_in, tp, H, "sum", type_bits=0,
                                         col=tp.perm)
@@ -506,7 +522,18 @@ class _EdgeLinear(torch.autograd.Function):
                         d_x = d_x + d_dst
                     else:
                         d_x[: d_dst.shape[0]] += d_dst
-        return d_x, None, None, None, None, d_w
+        return d_x, None, None, None, None, d_w, None
+
+
+def _rounded_stack(stack: torch.Tensor, inputs):
+    """The [T, n_out, k] weight stack of `_EdgeLinear` rounded by torch to the 16-bit `inputs`, made once per call where
+    the 16-bit per-edge GEMM takes the shape (else None: the op runs fp32 and wants no copy)."""
+    if inputs is None:
+        return None
+    T, n_out, k = stack.shape
+    if not ops.edge_linear16_supported(k, n_out, T, inputs):
+        return None
+    return stack.detach().to(inputs).contiguous()
 
 
 class _EdgeLinearFeat(torch.autograd.Function):
@@ -592,10 +619,12 @@ def edge_linear_feat(x: torch.Tensor, plan: "ops.GraphPlan", weights, use_dst: b
 
 
 def edge_linear(x: torch.Tensor, plan: "ops.GraphPlan", weights, use_dst: bool, dropout_p: float = 0.0,
-                dropout_seed: int = 0) -> torch.Tensor:
+                dropout_seed: int = 0, inputs=None) -> torch.Tensor:
     """Differentiable grouped per-edge Linear over the plan's adjacency lists (see `_EdgeLinear`).
     `weights`: the per-type nn.Linear weights as a list, or already stacked [T, M, K] (a stack shared by
-    the tied layers of a forward makes autograd accumulate ONE [T, M, K] gradient per use instead of T)."""
+    the tied layers of a forward makes autograd accumulate ONE [T, M, K] gradient per use instead of T).
+    `inputs`: torch.bfloat16 / torch.float16 run the node's three GEMMs on the 16-bit matrix cores (no target half; see
+    `_EdgeLinear`); None or float32 is the fp32 node, and so is `use_dst=True` under any `inputs`."""
     if plan._adj is None:
         raise _lib.PtgnnAmdError("edge_linear: the plan must keep its adjacency lists")
     w_stack = weights if isinstance(weights, torch.Tensor) else torch.stack(list(weights))
@@ -604,7 +633,12 @@ def edge_linear(x: torch.Tensor, plan: "ops.GraphPlan", weights, use_dst: bool, 
         # every element is kept, and "dropout off" (no mask, no 1 / (1 - p) scale) is the one consistent reading for the
         # forward, the input gradient and the weight gradient alike
         dropout_p = 0.0
-    return _EdgeLinear.apply(x, plan, bool(use_dst), float(dropout_p), int(dropout_seed), w_stack)
+    if inputs is None or inputs == torch.float32 or use_dst:
+        return _EdgeLinear.apply(x, plan, bool(use_dst), float(dropout_p), int(dropout_seed), w_stack, None)
+    if inputs not in ops.HALF_IDS:
+        raise _lib.PtgnnAmdError(f"edge_linear: inputs must be None, torch.float32, torch.bfloat16 or torch.float16 "
+                                 f"(got {inputs!r})")
+    return _EdgeLinear.apply(x, plan, False, float(dropout_p), int(dropout_seed), w_stack, inputs)
 
 
 class _GatherReduce(torch.autograd.Function):
