@@ -235,6 +235,15 @@ enum {
   PTGNN_AMD_KERNEL_EDGE_WGRAD16,                                         /* ptgnn_amd_edge_weight_grad16 */
   PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_
 };
+/* A fifteenth id range: the 16-bit-input launches of the attention layer's TRAINING step (csrc/block_attention16.hip with
+ * dropout, csrc/block_attention16_backward.hip).  A range of its own, so the second and thirteenth ranges end where they
+ * did. */
+enum {
+  PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_ = 896,
+  PTGNN_AMD_KERNEL_ATTENTION_TRAIN16 = PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_, /* ptgnn_amd_selfatt_train16_forward, p > 0 */
+  PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_BACKWARD,                                    /* ptgnn_amd_selfatt_train16_backward */
+  PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1646,6 +1655,46 @@ int ptgnn_amd_attention16_block_supported(int32_t dk, int32_t dv, int dtype);
 int ptgnn_amd_attention16_block(const float *kqv, int64_t ld_kqv, const int32_t *windows, int64_t num_windows,
                                 int64_t num_rows, int32_t max_num_nodes, int32_t num_heads, int32_t dk, int32_t dv,
                                 float *out, int64_t ld_out, float *lse, int dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit matrix-core inputs for the block attention's TRAINING step (csrc/block_attention16.hip with its
+ * compile-time dropout mode; csrc/block_attention16_backward.hip).
+ *
+ * Replaces: selfattmessagepassing.py:104-117 under autocast in train(), forward and backward -- both einsums and the
+ *   four products of their backward in the autocast dtype; the softmax of line 110, nn.Dropout of line 111 and the
+ *   softmax backward in fp32.  OFF by default: the host asks for it with ptgnn_amd.set_attention_training.
+ *
+ * Forward (ptgnn_amd_selfatt_train16_forward): ptgnn_amd_attention16_block with dropout.  E = exp(S - m) as there;
+ *   l_k = sum_v E[k, v] over the UNROUNDED, UNMASKED E; then out_k = (sum_v rnd(M[k, v] E[k, v]) rnd(value_v)) / l_k with
+ *   M the keep multiplier (1 / (1 - p) or 0) of ptgnn_amd_block_attention_f32's hash mask -- element (row r, head h,
+ *   window column j) takes row r heads + h, column j of the [N heads, max_num_nodes rounded up to even] mask, bit for
+ *   bit, so the same seed drops the same probabilities on both routes.  The multiplier is applied in fp32 BEFORE the
+ *   one rounding: autocast's order (softmax fp32 -> nn.Dropout -> cast -> einsum).  dropout_p == 0 IS the launch of
+ *   ptgnn_amd_attention16_block (same bits, counted as block_attention16); dropout_p > 0 counts attention_train16.
+ * Backward (ptgnn_amd_selfatt_train16_backward): arguments of ptgnn_amd_block_attention_backward_f32 plus dtype; the
+ *   workspace is ptgnn_amd_block_attention_backward_workspace_bytes (D).  P = exp(S / sqrt(dk) - lse) with S recomputed
+ *   from the rounded keys and queries, D_k = sum_d dOut[k, d] out[k, d] in fp32 on the unrounded operands,
+ *   dP = rnd(dOut) rnd(V)^T, dS = P o (M o dP - D) in fp32, and
+ *     d key = scale rnd(dS) rnd(Q)    d query = scale rnd(dS)^T rnd(K)    d value = rnd(M o P)^T rnd(dOut)
+ *   on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulation; kqv, out, lse, grad_out and grad_kqv are fp32 in memory.
+ *   Nothing is clamped: fp16 underflows gradually and a rounded gradient beyond its range is inf, as tensor.half()
+ *   gives and GradScaler expects.  Counts attention_train16_backward.
+ * ptgnn_amd_selfatt_train16_supported(dk, dv, dtype): 1 for 1 <= dk, dv <= 128 and a known dtype id; needs no device.
+ * kqv and grad_out must be 4-byte aligned; 16-byte aligned rows with dk % 4 == 0 and dv % 4 == 0 are loaded as float4,
+ * anything else element by element -- the same values and bits.  Error codes as the fp32 entries, plus EINVAL for an
+ * unknown dtype id; bad arguments are refused before any HIP call.  Every sum runs in tile order inside one wave: no
+ * atomics, deterministic, and a window's rows do not depend on its place in the batch.  Additive: the ABI version stays.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_selfatt_train16_supported(int32_t dk, int32_t dv, int dtype);
+int ptgnn_amd_selfatt_train16_forward(const float *kqv, int64_t ld_kqv, const int32_t *windows, int64_t num_windows,
+                                      int64_t num_rows, int32_t max_num_nodes, int32_t num_heads, int32_t dk, int32_t dv,
+                                      float *out, int64_t ld_out, float *lse, int dtype, float dropout_p, uint64_t seed,
+                                      void *stream);
+int ptgnn_amd_selfatt_train16_backward(const float *kqv, int64_t ld_kqv, const float *out, int64_t ld_out,
+                                       const float *lse, const float *grad_out, int64_t ld_go, const int32_t *windows,
+                                       int64_t num_windows, int64_t num_rows, int32_t max_num_nodes, int32_t num_heads,
+                                       int32_t dk, int32_t dv, float dropout_p, uint64_t seed, float *grad_kqv,
+                                       int64_t ld_gkqv, void *workspace, size_t workspace_bytes, int dtype, void *stream);
 
 #pragma GCC visibility pop
 

@@ -228,6 +228,12 @@ SIGNATURES = {
     "ptgnn_amd_attention16_block_supported": (_c.c_int, [_i32, _i32, _c.c_int]),
     "ptgnn_amd_attention16_block": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
                                                _c.c_int, _vp]),
+    "ptgnn_amd_selfatt_train16_supported": (_c.c_int, [_i32, _i32, _c.c_int]),
+    "ptgnn_amd_selfatt_train16_forward": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
+                                                     _c.c_int, _f32, _c.c_uint64, _vp]),
+    "ptgnn_amd_selfatt_train16_backward": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32,
+                                                      _i32, _i32, _f32, _c.c_uint64, _vp, _i64, _vp, _c.c_size_t,
+                                                      _c.c_int, _vp]),
 }
 
 # The header version this host was written against (include/ptgnn_amd.h: PTGNN_AMD_VERSION).  A stale .so with an

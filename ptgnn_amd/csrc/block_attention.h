@@ -1,6 +1,8 @@
-// What the block-attention kernels share (block_attention.hip: exact fp32; block_attention16.hip: 16-bit matrix-core
-// inputs): the 32-row tile and its accumulator-row map, the workgroup <-> (window, head, row block) map, the argument
-// checks and the host-side shape.  One copy, so both forwards cut a batch into workgroups the same way.
+// What the block-attention kernels share (block_attention.hip: exact fp32; block_attention16.hip and
+// block_attention16_backward.hip: 16-bit matrix-core inputs): the 32-row tile and its accumulator-row map, the workgroup
+// <-> (window, head, row block) map, the dropout multiplier of a probability, the row-dot kernel of the backwards, the
+// argument checks and the host-side shape.  One copy, so every kernel cuts a batch into workgroups the same way and the
+// same seed drops the same probabilities on both routes.
 #pragma once
 #include "dense_common.h"
 
@@ -20,6 +22,32 @@ struct BaShape {
 __device__ __forceinline__ int ba_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ float ba_exp(float v) { return __builtin_amdgcn_exp2f(v * kLog2e); }
+
+// The dropout multiplier (scale or 0) of the probability of (mask row, window column j): the stateless hash of
+// dense_common.h on a [N heads, W] mask, W = max_num_nodes rounded up to even (ba_dropout), mask row = r heads + h.
+__device__ __forceinline__ float ba_keep(const DropoutParams &d, int64_t row, int j) {
+  const uint32_t b = dropout_bits(d, row, j >> 1);
+  return ((j & 1) ? (b >> 16) : (b & 0xffffu)) >= d.thr ? d.scale : 0.0f;
+}
+
+inline DropoutParams ba_dropout(float p, uint64_t seed, int32_t max_nodes) {
+  return make_dropout(p, seed, (max_nodes + 1) / 2 * 2);
+}
+
+// D[r, head] = sum_d grad_out[r, head dv + d] out[r, head dv + d], d ascending (fp32, unrounded operands)
+static __global__ __launch_bounds__(256) void k_block_attention_rowdot(const float *__restrict__ go, int64_t ld_go,
+                                                                       const float *__restrict__ out, int64_t ld_out,
+                                                                       int64_t num_rows, int heads, int dv,
+                                                                       float *__restrict__ D) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_rows * heads) return;
+  const int64_t r = i / heads;
+  const int head = (int)(i % heads);
+  const float *a = go + r * ld_go + (int64_t)head * dv, *b = out + r * ld_out + (int64_t)head * dv;
+  float t = 0.0f;
+  for (int d = 0; d < dv; ++d) t = fmaf(a[d], b[d], t);
+  D[i] = t;
+}
 
 // workgroup -> its window [start, end) and first row r0 inside it; false when it has no rows
 __device__ __forceinline__ bool ba_locate(const int32_t *__restrict__ windows, const BaShape &sh, int &start, int &end,

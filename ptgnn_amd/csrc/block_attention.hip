@@ -76,11 +76,6 @@ __device__ __forceinline__ void ba_tn(f32x16 (&z)[T], const f32x16 &x, const flo
   }
 }
 
-__device__ __forceinline__ float ba_keep(const DropoutParams &d, int64_t row, int j) {
-  const uint32_t b = dropout_bits(d, row, j >> 1);
-  return ((j & 1) ? (b >> 16) : (b & 0xffffu)) >= d.thr ? d.scale : 0.0f;
-}
-
 // One workgroup builds the window table: windows[w] = first row of window w for the W windows of the batch (graph g owns
 // the rows rowptr[g] .. rowptr[g + 1] - 1 and is cut every max_nodes rows), windows[W .. bound] = num_rows.
 __global__ __launch_bounds__(256) void k_attention_windows(const int32_t *__restrict__ rowptr, int num_graphs,
@@ -179,21 +174,6 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void k_block_attention(
         if (32 * t + c < sh.dv) dst[32 * t + c] = o[t][r] * a;
     }
   }
-}
-
-// D[r, head] = sum_d grad_out[r, head dv + d] out[r, head dv + d], d ascending
-__global__ __launch_bounds__(256) void k_block_attention_rowdot(const float *__restrict__ go, int64_t ld_go,
-                                                                const float *__restrict__ out, int64_t ld_out,
-                                                                int64_t num_rows, int heads, int dv,
-                                                                float *__restrict__ D) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= num_rows * heads) return;
-  const int64_t r = i / heads;
-  const int head = (int)(i % heads);
-  const float *a = go + r * ld_go + (int64_t)head * dv, *b = out + r * ld_out + (int64_t)head * dv;
-  float t = 0.0f;
-  for (int d = 0; d < dv; ++d) t = fmaf(a[d], b[d], t);
-  D[i] = t;
 }
 
 // grad_kqv[k, head: keys] of the rows of one (window, head) row block
@@ -347,10 +327,6 @@ int ba_waves(int own_ld, int walk_ld, int extra) {
 
 int64_t ba_windows_bound(int64_t num_graphs, int64_t num_rows, int64_t max_nodes) {
   return (num_rows + max_nodes - 1) / max_nodes + num_graphs;
-}
-
-DropoutParams ba_dropout(float p, uint64_t seed, int32_t max_nodes) {
-  return make_dropout(p, seed, (max_nodes + 1) / 2 * 2);
 }
 
 template <int DKT>

@@ -1,6 +1,8 @@
 // The 16-bit-input forward of the block self-attention (block_attention.hip; selfattmessagepassing.py:104-117 as an
-// `enable_amp` user of the reference runs it: both einsums in the autocast dtype, the softmax in fp32).  Inference only:
-// no dropout, no backward.  Same window table, same kqv [N, heads (2 dk + dv)] (fp32 in HBM, read in place), same fp32
+// `enable_amp` user of the reference runs it: both einsums in the autocast dtype, the softmax in fp32), in two
+// compile-time modes: inference (no dropout; ptgnn_amd_attention16_block) and the training forward with the hash dropout
+// mask on the probabilities (ptgnn_amd_selfatt_train16_forward; its backward is block_attention16_backward.hip).  Same
+// window table, same kqv [N, heads (2 dk + dv)] (fp32 in HBM, read in place), same fp32
 // out / lse, and the same workgroup <-> (window, head, row block) map (block_attention.h) with 4 waves = 128 key rows.
 //
 // Operands.  Keys, queries and values are rounded to bf16 / fp16 (round to nearest even, gradual underflow: what
@@ -25,42 +27,24 @@
 // Every sum runs in tile order inside one wave: no atomics, deterministic, and a window's result does not depend on
 // where the window sits in the batch (alignment only chooses between one float4 load and four scalar loads of the
 // same values).
-#include "block_attention.h"
-#include "half16.h"
+#include "block_attention16.h"
 
 namespace ptgnn_amd {
 namespace {
 
 using namespace half16;
 
-constexpr int kBa16Threads = 64 * kBaMaxWaves;
-constexpr int kBa16Rows = kBaTile * kBaMaxWaves;   // key rows of a workgroup
-
-// LDS row strides in 16-bit elements: keys / queries (row reads), values (transposed reads)
-inline int ba16_ldk(int dk) { return (dk + 15) / 16 * 16 + 8; }
-constexpr int ba16_ldv(int dvt) { return 32 * (dvt | 1); }
-
 size_t ba16_lds_bytes(int dk, int dvt) {
   return sizeof(uint16_t) * ((size_t)(kBa16Rows + 2 * kBaTile) * ba16_ldk(dk) + (size_t)2 * kBaTile * ba16_ldv(dvt));
 }
 
-// columns c .. c + 3 of a row of `width` live columns (c % 4 == 0; columns past the width: 0).  `vec`: the row is 16-byte
-// aligned and width % 4 == 0, so a live c has all four
-__device__ __forceinline__ float4 ba16_load4(const float *__restrict__ row, int c, int width, bool vec) {
-  if (vec) return c < width ? *reinterpret_cast<const float4 *>(row + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v;
-  v.x = c < width ? row[c] : 0.f;
-  v.y = c + 1 < width ? row[c + 1] : 0.f;
-  v.z = c + 2 < width ? row[c + 2] : 0.f;
-  v.w = c + 3 < width ? row[c + 3] : 0.f;
-  return v;
-}
-
-// out[k, head dv + :] and lse[k, head] of the rows of one (window, head) row block
-template <int DT, int DVT>
+// out[k, head dv + :] and lse[k, head] of the rows of one (window, head) row block.  DROP: the training forward --
+// the unnormalised probabilities take their keep multiplier (ba_keep: scale or 0) in fp32 AFTER they were added to l
+// and BEFORE the one rounding, the order autocast gives (softmax fp32 -> nn.Dropout -> cast -> einsum).
+template <int DT, int DVT, bool DROP>
 __global__ __launch_bounds__(kBa16Threads) void k_block_attention16(
-    const float *__restrict__ kqv, int64_t ld, const int32_t *__restrict__ windows, BaShape sh, int vec,
-    float *__restrict__ out, int64_t ld_out, float *__restrict__ lse) {
+    const float *__restrict__ kqv, int64_t ld, const int32_t *__restrict__ windows, BaShape sh, DropoutParams drop,
+    int vec, float *__restrict__ out, int64_t ld_out, float *__restrict__ lse) {
   using H = Half16<DT>;
   using vec8 = typename H::vec;
   extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(kBa16Threads) void k_block_attention16(
   const int64_t krow = (int64_t)start + wrow + c;  // the lane's key row (not stored when >= end)
   const uint16_t *Kw = Ks + (kBaTile * wave + c) * ldk + 8 * h;
   // this lane's address inside a 4-row x 16-column block of a transposed read (half16.h, tr8)
-  const int tr_off = (4 * h + ((lane >> 2) & 3)) * ldv + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int tr_off = ba16_tr_off(lane, ldv);
 
   f32x16 o[DVT];
 #pragma unroll
@@ -147,6 +131,10 @@ __global__ __launch_bounds__(kBa16Threads) void k_block_attention16(
       psum += __shfl_xor(psum, 32, 64);
       l = l * alpha + psum;
       m = mnew;
+      if (DROP) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[r] *= ba_keep(drop, krow * sh.heads + head, j0 + ba_row(r, h));
+      }
       if (__ballot(alpha != 1.0f)) {                        // some row's maximum moved
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -158,9 +146,7 @@ __global__ __launch_bounds__(kBa16Threads) void k_block_attention16(
       const uint16_t *Vb = Vs + cur * kBaTile * ldv + tr_off;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const f32x8 pf = {x[8 * s], x[8 * s + 1], x[8 * s + 2], x[8 * s + 3],
-                          x[8 * s + 4], x[8 * s + 5], x[8 * s + 6], x[8 * s + 7]};
-        const vec8 p = __builtin_convertvector(pf, vec8);   // rows ba_row(8 s + i, h) of the tile, i = 0 .. 7
+        const vec8 p = ba16_round8<DT>(x, s);               // rows ba_row(8 s + i, h) of the tile, i = 0 .. 7
 #pragma unroll
         for (int t = 0; t < DVT; ++t) {
           const uint16_t *at = Vb + 16 * s * ldv + 32 * t;
@@ -197,40 +183,64 @@ extern "C" int ptgnn_amd_attention16_block_supported(int32_t dk, int32_t dv, int
   return half16::dtype_ok(dtype) && dk >= 1 && dk <= kBaMaxDim && dv >= 1 && dv <= kBaMaxDim ? 1 : 0;
 }
 
+// the launch both entries share: dropout_p == 0 is the inference kernel (DROP off), counted as `kernel_id`
+static int ba16_forward(const char *what, const float *kqv, int64_t ld_kqv, const int32_t *windows, int64_t num_windows,
+                        int64_t num_rows, int32_t max_num_nodes, int32_t num_heads, int32_t dk, int32_t dv,
+                        float dropout_p, uint64_t seed, float *out, int64_t ld_out, float *lse, int32_t dtype,
+                        int kernel_id, void *stream_) {
+  PTGNN_REQUIRE(half16::dtype_ok(dtype), PTGNN_AMD_EINVAL, "%s: unknown dtype id %d", what, dtype);
+  const int rc = ba_check(what, kqv, ld_kqv, windows, num_windows, num_rows, max_num_nodes, num_heads, dk, dv, dropout_p);
+  if (rc != PTGNN_AMD_OK || num_rows == 0) return rc;
+  PTGNN_REQUIRE(out && lse, PTGNN_AMD_EINVAL, "%s: null pointer", what);
+  PTGNN_REQUIRE(ld_out >= (int64_t)num_heads * dv, PTGNN_AMD_EINVAL, "%s: bad leading dimension", what);
+  PTGNN_REQUIRE(half16::aligned4(kqv), PTGNN_AMD_EINVAL, "%s: kqv is not 4-byte aligned", what);
+  const int dvt = (dv + 31) / 32;
+  const size_t bytes = ba16_lds_bytes(dk, dvt);
+  const BaShape sh = ba_shape(num_heads, dk, dv, kBaMaxWaves, num_rows, max_num_nodes);
+  PTGNN_REQUIRE(num_windows * sh.row_tiles < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED, "%s: too many windows", what);
+  // every float4 of a head's keys, queries and values is 16-byte aligned
+  const int vec = half16::rows16(kqv, ld_kqv) && dk % 4 == 0 && dv % 4 == 0 ? 1 : 0;
+  const DropoutParams drop = ba_dropout(dropout_p, seed, max_num_nodes);
+  const dim3 grid((unsigned)(num_windows * sh.row_tiles), (unsigned)num_heads);
+  hipStream_t st = (hipStream_t)stream_;
+  int rc2 = PTGNN_AMD_OK;
+  auto launch = [&](auto kern) {
+    if (!ba_lds_ok(kern, bytes)) {
+      rc2 = PTGNN_AMD_EHIP;
+      return;
+    }
+    kern<<<grid, kBa16Threads, bytes, st>>>(kqv, ld_kqv, windows, sh, drop, vec, out, ld_out, lse);
+  };
+  half16::with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    BA_TILES(dvt, {
+      if (drop.thr)
+        launch(k_block_attention16<DT, TT, true>);
+      else
+        launch(k_block_attention16<DT, TT, false>);
+    })
+  });
+  PTGNN_REQUIRE(rc2 == PTGNN_AMD_OK, PTGNN_AMD_EHIP, "%s: %zu bytes of LDS refused", what, bytes);
+  PTGNN_LAUNCH_CHECK();
+  count_launch(kernel_id);
+  return PTGNN_AMD_OK;
+}
+
 extern "C" int ptgnn_amd_attention16_block(const float *kqv, int64_t ld_kqv, const int32_t *windows,
                                            int64_t num_windows, int64_t num_rows, int32_t max_num_nodes,
                                            int32_t num_heads, int32_t dk, int32_t dv, float *out, int64_t ld_out,
                                            float *lse, int32_t dtype, void *stream_) {
-  PTGNN_REQUIRE(half16::dtype_ok(dtype), PTGNN_AMD_EINVAL, "block_attention16: unknown dtype id %d", dtype);
-  const int rc = ba_check("block_attention16", kqv, ld_kqv, windows, num_windows, num_rows, max_num_nodes, num_heads, dk,
-                          dv, 0.0f);
-  if (rc != PTGNN_AMD_OK || num_rows == 0) return rc;
-  PTGNN_REQUIRE(out && lse, PTGNN_AMD_EINVAL, "block_attention16: null pointer");
-  PTGNN_REQUIRE(ld_out >= (int64_t)num_heads * dv, PTGNN_AMD_EINVAL, "block_attention16: bad leading dimension");
-  PTGNN_REQUIRE(half16::aligned4(kqv), PTGNN_AMD_EINVAL, "block_attention16: kqv is not 4-byte aligned");
-  const int dvt = (dv + 31) / 32;
-  const size_t bytes = ba16_lds_bytes(dk, dvt);
-  const BaShape sh = ba_shape(num_heads, dk, dv, kBaMaxWaves, num_rows, max_num_nodes);
-  PTGNN_REQUIRE(num_windows * sh.row_tiles < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED,
-                "block_attention16: too many windows");
-  // every float4 of a head's keys, queries and values is 16-byte aligned
-  const int vec = half16::rows16(kqv, ld_kqv) && dk % 4 == 0 && dv % 4 == 0 ? 1 : 0;
-  const dim3 grid((unsigned)(num_windows * sh.row_tiles), (unsigned)num_heads);
-  hipStream_t st = (hipStream_t)stream_;
-  int rc2 = PTGNN_AMD_OK;
-  half16::with_dtype(dtype, [&](auto dt) {
-    constexpr int DT = decltype(dt)::value;
-    BA_TILES(dvt, {
-      auto kern = k_block_attention16<DT, TT>;
-      if (!ba_lds_ok(kern, bytes)) {
-        rc2 = PTGNN_AMD_EHIP;
-        return;
-      }
-      kern<<<grid, kBa16Threads, bytes, st>>>(kqv, ld_kqv, windows, sh, vec, out, ld_out, lse);
-    })
-  });
-  PTGNN_REQUIRE(rc2 == PTGNN_AMD_OK, PTGNN_AMD_EHIP, "block_attention16: %zu bytes of LDS refused", bytes);
-  PTGNN_LAUNCH_CHECK();
-  count_launch(PTGNN_AMD_KERNEL_BLOCK_ATTENTION16);
-  return PTGNN_AMD_OK;
+  return ba16_forward("block_attention16", kqv, ld_kqv, windows, num_windows, num_rows, max_num_nodes, num_heads, dk, dv,
+                      0.0f, 0, out, ld_out, lse, dtype, PTGNN_AMD_KERNEL_BLOCK_ATTENTION16, stream_);
+}
+
+extern "C" int ptgnn_amd_selfatt_train16_forward(const float *kqv, int64_t ld_kqv, const int32_t *windows,
+                                                 int64_t num_windows, int64_t num_rows, int32_t max_num_nodes,
+                                                 int32_t num_heads, int32_t dk, int32_t dv, float *out, int64_t ld_out,
+                                                 float *lse, int32_t dtype, float dropout_p, uint64_t seed,
+                                                 void *stream_) {
+  const bool drop = dropout_p > 0.0f && (uint32_t)((double)dropout_p * 65536.0 + 0.5) > 0;   // make_dropout's threshold
+  return ba16_forward("selfatt_train16_forward", kqv, ld_kqv, windows, num_windows, num_rows, max_num_nodes, num_heads,
+                      dk, dv, dropout_p, seed, out, ld_out, lse, dtype,
+                      drop ? PTGNN_AMD_KERNEL_ATTENTION_TRAIN16 : PTGNN_AMD_KERNEL_BLOCK_ATTENTION16, stream_);
 }

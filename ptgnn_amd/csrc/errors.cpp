@@ -34,6 +34,7 @@ static std::atomic<int64_t> g_edge16_dst_launches[PTGNN_AMD_KERNEL_EDGE16_DST_EN
 static std::atomic<int64_t> g_beam_finish_launches[PTGNN_AMD_KERNEL_BEAM_FINISH_END_ - PTGNN_AMD_KERNEL_BEAM_FINISH_FIRST_];
 static std::atomic<int64_t> g_attention16_launches[PTGNN_AMD_KERNEL_ATTENTION16_END_ - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
 static std::atomic<int64_t> g_edge16_train_launches[PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_ - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_];
+static std::atomic<int64_t> g_attention_train16_launches[PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_ - PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -62,6 +63,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_attention16_launches[kernel_id - PTGNN_AMD_KERNEL_ATTENTION16_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_)
     return &g_edge16_train_launches[kernel_id - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_)
+    return &g_attention_train16_launches[kernel_id - PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -151,6 +154,11 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "edge16_masked", "edge_wgrad16"};
   if (kernel_id >= PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_EDGE16_TRAIN_END_)
     return edge16_train_names[kernel_id - PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_];
+  static const char *const attention_train16_names[PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_ -
+                                                   PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_] = {
+      "attention_train16", "attention_train16_backward"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_)
+    return attention_train16_names[kernel_id - PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

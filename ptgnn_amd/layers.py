@@ -875,7 +875,11 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
     residual -> LayerNorm, all HIP.  CPU tensors: torch_route.self_attention_message_passing.
     Under the `attention=True` matrix-input setting (ptgnn_amd/precision.py, off by default) the inference forward rounds
     the operands of the four Linears and of both attention products (csrc/block_attention16.hip) to the 16-bit type;
-    the softmax, LayerNorms, residuals, every store and the whole training branch stay fp32."""
+    the softmax, LayerNorms, residuals, every store and the whole training branch stay fp32.
+    Under `ptgnn_amd.set_attention_training(True)` (off by default) the TRAINING branch runs the head-transform Linear as
+    the 16-bit Linear node and the attention as the 16-bit attention node (csrc/block_attention16.hip with dropout,
+    csrc/block_attention16_backward.hip); the summarisation, intermediate and output Linears stay on the fused fp32
+    Linear + activation + dropout node (the next step), as do LayerNorms and residuals."""
 
     def __init__(self, input_state_dimension: int, key_query_dimension: int, value_dimension: int,
                  output_dimension: int, intermediate_dimension: int, num_heads: int, dropout_rate: float = 0.0,
@@ -966,8 +970,11 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
             return ops.row_epilogue(ops.linear_add(hidden, w_o.weight, a, bias=w_o.bias, inputs=dt,
                                                    rounded=w16("att_w_o16", w_o)),
                                     ops.EPI_LAYERNORM, ln2.weight, ln2.bias, ln2.eps)
-        kqv = dense.linear(x, w_h.weight)
-        values = block_attention_autograd(kqv, windows, self.__max_num_nodes, heads, dk, dv, drop, seed)
+        # float32 unless ptgnn_amd.set_attention_training is on (ptgnn_amd/precision.py): then the head transforms and the
+        # attention node (forward with dropout, backward) take 16-bit operands, as under autocast in the reference
+        dt = precision.attention_training_inputs(x)
+        kqv = dense.linear(x, w_h.weight, inputs=dt)
+        values = block_attention_autograd(kqv, windows, self.__max_num_nodes, heads, dk, dv, drop, seed, inputs=dt)
         a = dense.row_epilogue(self.__linear_dropout(values, w_s, None, drop) + residual, False, ln1)
         hidden = self.__linear_dropout(a, w_i, "relu", 0.0)
         return dense.row_epilogue(self.__linear_dropout(hidden, w_o, None, drop) + a, False, ln2)

@@ -77,10 +77,14 @@ _ATTENTION16_FAMILY_FIRST = 768  # PTGNN_AMD_KERNEL_ATTENTION16_FIRST_: the opt-
 _EDGE16_TRAIN_FAMILY_FIRST = 832  # PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_: the 16-bit-input edge-form training launches
 
 
+_ATTENTION_TRAIN16_FAMILY_FIRST = 896  # PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_: the 16-bit attention training launches
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
-                  beam_finish: bool = False, attention16: bool = False, edge16_training: bool = False) -> dict:
+                  beam_finish: bool = False, attention16: bool = False, attention16_training: bool = False,
+                  edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -94,7 +98,9 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     GEMM's two launch forms (edge16, edge16_shared); `half_training=True` the 16-bit-input training launches
     (half_wgrad, half_gru_train, half_linear_add); `edge16_dst=True` the 16-bit-input per-edge GEMM with a target-state
     half (edge16_dst: the MLP-MP message Linear); `beam_finish=True` the beam search's finishing route (beam_step_links,
-    beam_backtrack); `attention16=True` the 16-bit-input block attention (block_attention16); `edge16_training=True`
+    beam_backtrack); `attention16=True` the 16-bit-input block attention (block_attention16); `attention16_training=True`
+    the 16-bit-input attention training launches (attention_train16: the forward with dropout; attention_train16_backward);
+    `edge16_training=True`
     the 16-bit-input edge-form training launches (edge16_masked: the masked per-edge GEMM in its forward and
     input-gradient modes; edge_wgrad16: the per-type weight gradient)."""
     lib = _lib.load()
@@ -107,6 +113,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_EDGE16_DST_FAMILY_FIRST,) if edge16_dst else ()) \
             + ((_BEAM_FINISH_FAMILY_FIRST,) if beam_finish else ()) \
             + ((_ATTENTION16_FAMILY_FIRST,) if attention16 else ()) \
+            + ((_ATTENTION_TRAIN16_FAMILY_FIRST,) if attention16_training else ()) \
             + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()):
         i = first
         while True:
@@ -122,7 +129,7 @@ def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
                         edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
-                        edge16_training=True)
+                        attention16_training=True, edge16_training=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2607,6 +2614,14 @@ def block_attention16_supported(dk: int, dv: int, dtype) -> bool:
     return bool(_lib.load().ptgnn_amd_attention16_block_supported(int(dk), int(dv), HALF_IDS[dtype]))
 
 
+def selfatt_train16_supported(dk: int, dv: int, dtype) -> bool:
+    """Whether the 16-bit-input attention training kernels (forward with dropout, backward) take these widths and this
+    dtype (ptgnn_amd_selfatt_train16_supported; needs no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_selfatt_train16_supported(int(dk), int(dv), HALF_IDS[dtype]))
+
+
 def attention_windows(plan: GraphPlan, max_num_nodes: int) -> torch.Tensor:
     """Window table of selfattmessagepassing.py:59-75 from the plan of a node -> graph map (ptgnn_amd_attention_windows):
     int32 [bound + 1], bound = ceil(N / max_num_nodes) + G.  Entry w is the first row of window w for the W windows of
@@ -2640,7 +2655,7 @@ def _block_attention_args(kqv: torch.Tensor, windows: torch.Tensor, heads: int, 
 
 
 def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int,
-                    p: float = 0.0, seed: int = 0, inputs=None):
+                    p: float = 0.0, seed: int = 0, inputs=None, masked16: bool = False):
     """Softmax attention among the rows of every window, per head (ptgnn_amd_block_attention_f32;
     selfattmessagepassing.py:104-117): kqv [N, heads (2 dk + dv)] read in place -> (out [N, heads dv], lse [N, heads]).
     `p` > 0 applies the hash dropout mask of `seed` to the probabilities (row r heads + h, column j of a
@@ -2648,7 +2663,9 @@ def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int
     `inputs` = torch.bfloat16 / torch.float16: keys, queries, values and the unnormalised probabilities are rounded to
     that type and both products run on the 16-bit matrix cores (ptgnn_amd_attention16_block: fp32 softmax, accumulation
     and output) where p == 0, `block_attention16_supported` takes the widths and kqv has 16-byte aligned rows; otherwise
-    the fp32 kernel runs, silently."""
+    the fp32 kernel runs, silently.  With p > 0 that is the fp32 kernel unless `masked16` asks for the 16-bit forward's
+    dropout mode (ptgnn_amd_selfatt_train16_forward: the same mask, applied in fp32 before the one rounding; what the
+    training node `scatter.block_attention(inputs=)` passes) and `selfatt_train16_supported` takes the widths."""
     lib = _lib.load()
     kqv, windows = _block_attention_args(kqv, windows, heads, dk, dv, "block_attention")
     n = kqv.shape[0]
@@ -2662,6 +2679,13 @@ def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int
                                                  lse.data_ptr(), HALF_IDS[half], _stream(out))
         _lib.check(rc, "ptgnn_amd_attention16_block")
         return out, lse
+    if n and half is not None and p > 0 and masked16 and selfatt_train16_supported(dk, dv, half) and _half_rows_ok(kqv):
+        with _timed("attention_train16", bytes=4.0 * n * heads * (2 * dk + 2 * dv + 1)):
+            rc = lib.ptgnn_amd_selfatt_train16_forward(
+                kqv.data_ptr(), _ld(kqv), windows.data_ptr(), windows.numel() - 1, n, int(max_num_nodes), heads, dk, dv,
+                out.data_ptr(), heads * dv, lse.data_ptr(), HALF_IDS[half], float(p), int(seed), _stream(out))
+        _lib.check(rc, "ptgnn_amd_selfatt_train16_forward")
+        return out, lse
     if n:
         with _timed("block_attention", bytes=4.0 * n * heads * (2 * dk + 2 * dv + 1)):
             rc = lib.ptgnn_amd_block_attention_f32(kqv.data_ptr(), _ld(kqv), windows.data_ptr(), windows.numel() - 1, n,
@@ -2673,9 +2697,14 @@ def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int
 
 def block_attention_backward(kqv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, grad_out: torch.Tensor,
                              windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int, p: float = 0.0,
-                             seed: int = 0) -> torch.Tensor:
+                             seed: int = 0, inputs=None) -> torch.Tensor:
     """grad_kqv [N, heads (2 dk + dv)] of `block_attention` from grad_out = dL/dout and the forward's out / lse
-    (ptgnn_amd_block_attention_backward_f32: the probabilities are recomputed; deterministic, no float atomics)."""
+    (ptgnn_amd_block_attention_backward_f32: the probabilities are recomputed; deterministic, no float atomics).
+    `inputs` = torch.bfloat16 / torch.float16: the four products of the backward take operands rounded to that type
+    (ptgnn_amd_selfatt_train16_backward: keys, queries, values and grad_out on their way into LDS, dS and the masked
+    probabilities in registers; the softmax backward, D, accumulation and grad_kqv fp32) where
+    `selfatt_train16_supported` takes the widths and kqv has 16-byte aligned rows; otherwise the fp32 kernels run,
+    silently."""
     lib = _lib.load()
     kqv, windows = _block_attention_args(kqv, windows, heads, dk, dv, "block_attention_backward")
     n = kqv.shape[0]
@@ -2689,6 +2718,16 @@ def block_attention_backward(kqv: torch.Tensor, out: torch.Tensor, lse: torch.Te
     if n:
         ws_bytes = int(lib.ptgnn_amd_block_attention_backward_workspace_bytes(n, heads))
         ws = _workspace(ws_bytes, kqv.device)
+        half = _half_inputs(inputs)
+        if half is not None and selfatt_train16_supported(dk, dv, half) and _half_rows_ok(kqv):
+            with _timed("attention_train16_backward", bytes=4.0 * n * heads * (4 * dk + 5 * dv + 2)):
+                rc = lib.ptgnn_amd_selfatt_train16_backward(
+                    kqv.data_ptr(), _ld(kqv), out.data_ptr(), heads * dv, lse.data_ptr(), grad_out.data_ptr(),
+                    _ld(grad_out), windows.data_ptr(), windows.numel() - 1, n, int(max_num_nodes), heads, dk, dv, float(p),
+                    int(seed), gkqv.data_ptr(), heads * (2 * dk + dv), ws.data_ptr(), ws_bytes, HALF_IDS[half],
+                    _stream(gkqv))
+            _lib.check(rc, "ptgnn_amd_selfatt_train16_backward")
+            return gkqv
         with _timed("block_attention_backward", bytes=4.0 * n * heads * (4 * dk + 5 * dv + 2)):
             rc = lib.ptgnn_amd_block_attention_backward_f32(
                 kqv.data_ptr(), _ld(kqv), out.data_ptr(), heads * dv, lse.data_ptr(), grad_out.data_ptr(), _ld(grad_out),

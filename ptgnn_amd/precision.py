@@ -84,6 +84,27 @@ path (16-bit states) and `target_reference != "all"` go through the same branch.
 What deliberately stays fp32 in the attention layer under `attention=True`: its training branch (any parameter or state
 that needs a gradient, or dropout > 0 in train()), including the attention backward.
 
+That training branch has a switch of its own -- a setting beside `set_matrix_inputs`, whose keyword list is closed; it
+stayed fp32 under every setting above, and existing users keep their bits:
+
+    ptgnn_amd.set_matrix_inputs("autocast"); ptgnn_amd.set_attention_training(True)     # next to enable_amp
+    with ptgnn_amd.matrix_inputs(torch.bfloat16), ptgnn_amd.attention_training():
+        loss = model(batch); loss.backward()
+
+With the switch the training branch of `MultiHeadSelfAttentionMessagePassing` runs the block attention as a 16-bit
+autograd node (`scatter.block_attention(inputs=)`): the forward is csrc/block_attention16.hip -- with dropout > 0 in
+its dropout mode: the same hash mask as the fp32 kernel, applied with its fp32 scale to the unnormalised probabilities
+after they were summed and BEFORE their one rounding, as autocast applies nn.Dropout before the 16-bit einsum -- and the
+backward is csrc/block_attention16_backward.hip: S and dP recomputed from the rounded keys, queries, values and dOut, the
+softmax backward in fp32, rnd(dS) and rnd(M o P) fed to the three gradient products from registers.  The head-transform
+Linear in front of it becomes the 16-bit Linear node of `training=True` (ptgnn_amd/dense.py).  kqv, out, lse, the saved
+tensors, D = sum dOut o out, every gradient in memory and every accumulation stay fp32; fp16 overflow of a rounded
+gradient becomes inf, as `tensor.half()` gives and `GradScaler` expects.  The dtype comes from `set_matrix_inputs`
+("autocast" included); the switch is off by default, independent of the five flags, untouched by `set_matrix_inputs`
+and `matrix_inputs`, and with a float32 dtype setting it means fp32.  What stays fp32 under the switch: the
+summarisation, intermediate and output Linears (the fused fp32 Linear + activation + dropout node) -- the next step --,
+both LayerNorms, the residuals, CPU tensors and the inference branch (which follows `attention=True` alone).
+
 The edge form of the GGNN TRAINING step -- what a Graph2Class batch takes, and every batch once the layer has per-edge
 dropout (`dropout_rate > 0` in train(): the reference's Typilus configuration) -- has a switch of its own as well; it
 stayed fp32 under `training=True`, and existing users keep their bits:
@@ -141,6 +162,7 @@ _training = False
 _mlp = False
 _attention = False
 _edge_training = False
+_attention_training = False
 
 
 def _checked(v):
@@ -218,3 +240,27 @@ def attention_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the attention layer's inference Linears and block attention for a layer call on `tensor`:
     `resolve(tensor)` when the setting was made with `attention=True`, else float32."""
     return resolve(tensor) if _attention else torch.float32
+
+
+def set_attention_training(on) -> bool:
+    """Whether the attention layer's TRAINING branch (block attention forward with dropout, its backward, the
+    head-transform Linear) takes the 16-bit type of the dtype setting; returns the previous value.  A setting of its own:
+    `set_matrix_inputs` / `matrix_inputs` neither read nor reset it."""
+    global _attention_training
+    prev, _attention_training = _attention_training, bool(on)
+    return prev
+
+
+@contextlib.contextmanager
+def attention_training(on=True):
+    prev = set_attention_training(on)
+    try:
+        yield
+    finally:
+        set_attention_training(prev)
+
+
+def attention_training_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the attention layer's training branch for a layer call on `tensor`: `resolve(tensor)` when
+    `set_attention_training` is on and the tensor is on a GPU, else float32."""
+    return resolve(tensor) if _attention_training and tensor.is_cuda else torch.float32

@@ -147,25 +147,30 @@ def graph_norm(x: torch.Tensor, gamma: torch.Tensor, alpha: torch.Tensor, bias: 
 class _BlockAttention(torch.autograd.Function):
     """The attention core of MultiHeadSelfAttentionMessagePassing (selfattmessagepassing.py:104-117) over a window table
     as ONE node: forward and backward are the two entry points of csrc/block_attention.hip.  Saves kqv, out and the
-    log-sum-exp of every score row; the probabilities (and the dropout mask of `seed`) are recomputed in the backward."""
+    log-sum-exp of every score row; the probabilities (and the dropout mask of `seed`) are recomputed in the backward.
+    `inputs` = a 16-bit dtype: forward and backward are the entry points of csrc/block_attention16.hip (in its dropout
+    mode where p > 0) and csrc/block_attention16_backward.hip; the saved tensors stay the fp32 kqv, out and lse."""
 
     @staticmethod
-    def forward(ctx, kqv, windows, max_num_nodes, heads, dk, dv, p, seed):
-        out, lse = ops.block_attention(kqv, windows, max_num_nodes, heads, dk, dv, p, seed)
-        ctx.args = (windows, max_num_nodes, heads, dk, dv, p, seed)
+    def forward(ctx, kqv, windows, max_num_nodes, heads, dk, dv, p, seed, inputs=None):
+        out, lse = ops.block_attention(kqv, windows, max_num_nodes, heads, dk, dv, p, seed, inputs=inputs, masked16=True)
+        ctx.args = (windows, max_num_nodes, heads, dk, dv, p, seed, inputs)
         ctx.save_for_backward(kqv, out, lse)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         kqv, out, lse = ctx.saved_tensors
-        return (ops.block_attention_backward(kqv, out, lse, grad_out, *ctx.args),) + (None,) * 7
+        return (ops.block_attention_backward(kqv, out, lse, grad_out, *ctx.args),) + (None,) * 8
 
 
 def block_attention(kqv: torch.Tensor, windows: torch.Tensor, max_num_nodes: int, heads: int, dk: int, dv: int,
-                    p: float = 0.0, seed: int = 0) -> torch.Tensor:
-    """Differentiable fused softmax attention among the rows of every window of fp32 kqv [N, heads (2 dk + dv)]."""
-    return _BlockAttention.apply(kqv, windows, int(max_num_nodes), int(heads), int(dk), int(dv), float(p), int(seed))
+                    p: float = 0.0, seed: int = 0, inputs=None) -> torch.Tensor:
+    """Differentiable fused softmax attention among the rows of every window of fp32 kqv [N, heads (2 dk + dv)].
+    `inputs` = torch.bfloat16 / torch.float16: 16-bit matrix-core operands in the forward and the backward (fp32 where
+    the 16-bit kernels do not take the call: `ops.block_attention`, `ops.block_attention_backward`)."""
+    return _BlockAttention.apply(kqv, windows, int(max_num_nodes), int(heads), int(dk), int(dv), float(p), int(seed),
+                                 inputs)
 
 
 class _SegmentScores(torch.autograd.Function):
