@@ -244,6 +244,14 @@ enum {
   PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_BACKWARD,                                    /* ptgnn_amd_selfatt_train16_backward */
   PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_
 };
+/* A sixteenth id range: the score-free loss of the copying decoder (csrc/projection_loss.hip).  A range of its own, so
+ * the fifth range ends where it did. */
+enum {
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_ = 960,
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS = PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_, /* ptgnn_amd_projection_loss_f32 */
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS_BACKWARD,                                  /* ptgnn_amd_projection_loss_backward_f32 */
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1267,6 +1275,44 @@ int ptgnn_amd_copy_loss_finish_f32(const float *gen, const float *copied, const 
                                    const int64_t *targets, int64_t unk_id, const int64_t *lengths, int64_t num_samples,
                                    int32_t steps, float *loss, float *d_gen, float *d_copied, void *workspace,
                                    size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same loss with the second vocabulary Linear inside it (csrc/projection_loss.hip), replacing ptgnn/neuralmodels/
+ * sequence/grucopydecoder.py:111-135, 178-181 from the einsum's last factor on: the scores [rows, vocab] are never written.
+ * projected [rows, dim] (ld_p >= dim) is the output of the first Linear, table [vocab, dim] (ld_t >= dim) the (dropped-out)
+ * embedding table, s[r, v] = projected[r] . table[v] + bias[v]; bias, extra, targets, norm, picked and stats are those of
+ * ptgnn_amd_vocab_loss_f32, with its edge rules (extra = -inf, targets outside [0, vocab), all scores -inf).  Exact fp32
+ * matrix instructions, no float atomics, fixed fold orders (two calls give the same bits, whatever the leading
+ * dimensions); rows == 0 launches nothing.  1 <= dim <= 256 (ptgnn_amd_projection_loss_supported; needs no device).
+ *
+ * ptgnn_amd_projection_loss_f32: workgroup (64 rows, 256 columns) forms its score tiles in registers and keeps a running
+ *   (max, sum) per row; the per-(row, column chunk) partials are merged in chunk order by the merge launch of ptgnn_amd_vocab_loss_f32.
+ *   workspace: 8 rows ceil(vocab / 256) + 4 rows bytes (+ 256-byte alignment), 8-byte aligned.
+ * ptgnn_amd_projection_loss_backward_f32: stats [rows, 2] of the forward; g_norm, g_picked [rows] device memory,
+ *   nullable = 0.  With c[r] = g_norm[r] - g_picked[r] and
+ *     G[r, v] = c[r] exp((s[r, v] - M[r]) - log_sum[r]) + g_picked[r] [v == targets[r]]    (recomputed, never stored)
+ *     grad_projected = G table        (ld_gp; column chunks of 1024 through the workspace, added in chunk order)
+ *     grad_table     = G^T projected  (ld_gt; a workgroup owns 64 vocabulary entries and walks all rows in row order)
+ *     grad_bias[v]   = sum_r G[r, v]                                       nullable
+ *     grad_extra[r]  = c[r] exp((extra[r] - M[r]) - log_sum[r])            nullable; 0 for extra[r] = -inf
+ *   workspace: 4 ceil(vocab / 1024) rows dim bytes.  rows == 0 writes nothing: the caller zeroes grad_table / grad_bias.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_projection_loss_supported(int32_t dim);
+size_t ptgnn_amd_projection_loss_workspace_bytes(int64_t rows, int32_t vocab);
+int ptgnn_amd_projection_loss_f32(const float *projected, int64_t ld_p, const float *table, int64_t ld_t, int64_t rows,
+                                  int32_t vocab, int32_t dim, const float *bias /* nullable */,
+                                  const float *extra /* nullable */, const int64_t *targets /* nullable */, float *norm,
+                                  float *picked /* with targets */, float *stats, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+size_t ptgnn_amd_projection_loss_backward_workspace_bytes(int64_t rows, int32_t vocab, int32_t dim);
+int ptgnn_amd_projection_loss_backward_f32(const float *projected, int64_t ld_p, const float *table, int64_t ld_t,
+                                           int64_t rows, int32_t vocab, int32_t dim, const float *bias /* nullable */,
+                                           const float *extra /* nullable */, const int64_t *targets /* nullable */,
+                                           const float *stats, const float *g_norm /* nullable */,
+                                           const float *g_picked /* nullable */, float *grad_projected, int64_t ld_gp,
+                                           float *grad_table, int64_t ld_gt, float *grad_bias /* nullable */,
+                                           float *grad_extra /* nullable */, void *workspace, size_t workspace_bytes,
+                                           void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * One step of the copying decoder's greedy decoding (csrc/decode_step.hip), replacing the per-step host work of

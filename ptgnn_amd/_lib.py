@@ -183,6 +183,13 @@ SIGNATURES = {
     "ptgnn_amd_copy_loss_finish_workspace_bytes": (_c.c_size_t, [_i64]),
     "ptgnn_amd_copy_loss_finish_f32": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
                                                   _c.c_size_t, _vp]),
+    "ptgnn_amd_projection_loss_supported": (_c.c_int, [_i32]),
+    "ptgnn_amd_projection_loss_workspace_bytes": (_c.c_size_t, [_i64, _i32]),
+    "ptgnn_amd_projection_loss_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _c.c_size_t, _vp]),
+    "ptgnn_amd_projection_loss_backward_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
+    "ptgnn_amd_projection_loss_backward_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "ptgnn_amd_decode_step_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
     "ptgnn_amd_decode_step_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i64,
                                              _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),

@@ -40,42 +40,6 @@
 namespace ptgnn_amd {
 namespace {
 
-// dst[r][c] (row stride ldd) = src[min(row0 + r, row_end - 1)][c] for c < width, 0 for width <= c < widthp
-__device__ __forceinline__ void ba_stage(float *__restrict__ dst, int ldd, const float *__restrict__ src, int64_t ld,
-                                         int row0, int row_end, int rows, int width, int widthp) {
-  const int step = blockDim.x >> 5;
-  for (int r = threadIdx.x >> 5; r < rows; r += step) {
-    int64_t g = (int64_t)row0 + r;
-    if (g >= row_end) g = row_end - 1;
-    const float *p = src + g * ld;
-    for (int c = threadIdx.x & 31; c < widthp; c += 32) dst[r * ldd + c] = c < width ? p[c] : 0.0f;
-  }
-}
-
-// C[i, j] = sum_d A[i, d] B[j, d]
-__device__ __forceinline__ f32x16 ba_nt(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
-                                        int ksteps, int lane) {
-  f32x16 c;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) c[r] = 0.0f;
-  const float *a = A + (lane & 31) * lda + (lane >> 5);
-  const float *b = B + (lane & 31) * ldb + (lane >> 5);
-  for (int s = 0; s < ksteps; ++s) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s], b[2 * s], c, 0, 0, 0);
-  return c;
-}
-
-// Z_t[i, j] += sum_r X[r, i] B[r, 32 t + j], t < T
-template <int T>
-__device__ __forceinline__ void ba_tn(f32x16 (&z)[T], const f32x16 &x, const float *__restrict__ B, int ldb, int lane) {
-  const int h = lane >> 5;
-#pragma unroll
-  for (int s = 0; s < 16; ++s) {
-    const float *b = B + ba_row(s, h) * ldb + (lane & 31);
-#pragma unroll
-    for (int t = 0; t < T; ++t) z[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[s], b[32 * t], z[t], 0, 0, 0);
-  }
-}
-
 // One workgroup builds the window table: windows[w] = first row of window w for the W windows of the batch (graph g owns
 // the rows rowptr[g] .. rowptr[g + 1] - 1 and is cut every max_nodes rows), windows[W .. bound] = num_rows.
 __global__ __launch_bounds__(256) void k_attention_windows(const int32_t *__restrict__ rowptr, int num_graphs,

@@ -33,6 +33,7 @@
 
 #include "segment_chunks.h"
 #include "softmax_state.h"
+#include "vocab_loss.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -270,6 +271,14 @@ int vocab_check(const char *what, int64_t rows, int32_t vocab, int64_t ld) {
 }
 
 }  // namespace
+
+void launch_vocab_loss_merge(const float2 *partial, const float *target_score, int64_t rows, int32_t vocab, int chunks,
+                             const float *extra, const int64_t *targets, float *norm, float *picked, float2 *stats,
+                             hipStream_t st) {
+  k_vocab_loss_merge<<<(unsigned)((rows + kVocThreads - 1) / kVocThreads), kVocThreads, 0, st>>>(
+      partial, target_score, rows, vocab, chunks, extra, targets, norm, picked, stats);
+}
+
 }  // namespace ptgnn_amd
 
 using namespace ptgnn_amd;
@@ -299,8 +308,8 @@ extern "C" int ptgnn_amd_vocab_loss_f32(const float *scores, int64_t ld, int64_t
   else
     k_vocab_loss_partial<1><<<grid, kVocThreads, 0, st>>>(scores, ld, vocab, chunks, bias, targets, partial, target_score);
   PTGNN_LAUNCH_CHECK();
-  k_vocab_loss_merge<<<(unsigned)((rows + kVocThreads - 1) / kVocThreads), kVocThreads, 0, st>>>(
-      partial, target_score, rows, vocab, chunks, extra, targets, norm, picked, reinterpret_cast<float2 *>(stats));
+  launch_vocab_loss_merge(partial, target_score, rows, vocab, chunks, extra, targets, norm, picked,
+                          reinterpret_cast<float2 *>(stats), st);
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_VOCAB_LOSS);
   return PTGNN_AMD_OK;

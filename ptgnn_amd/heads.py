@@ -19,7 +19,8 @@ GPU route (node states on the GPU; csrc/task_heads.hip):
     segment sum over the plan of the candidate and slot ids).  Node states whose width is not a multiple of 4 up to 1024
     compose the HIP row gather, `dense.linear` and the facade's scatter_log_softmax / scatter_max.
   * Graph2Seq: the backbone nodes' states by the differentiable HIP row gather, the summariser of `reduceops`, and the
-    decoder's loss on the fused vocabulary-loss kernels (`sequence.GruCopyingDecoder.fused_loss`, csrc/vocab_loss.hip);
+    decoder's loss on the fused vocabulary-loss kernels (`sequence.GruCopyingDecoder.fused_loss`, csrc/vocab_loss.hip;
+    with `use_score_free_loss` its `score_free_loss`, csrc/projection_loss.hip, which forms no [B L, V] scores);
     the loss is added into a per-device accumulator tensor, read in `_module_metrics` only.
   * fp16 / bf16 node states and parameters are up-cast; the loss is fp32.
   * NO call of `forward` or `predict` waits for the device.  The metrics live in a lazily allocated per-device block that
@@ -333,6 +334,9 @@ class Graph2SeqModule(ModuleWithMetrics):
     # `ptgnn_amd.sequence.GruCopyingDecoder.fused_loss` instead of the decoder's `forward`; any other decoder module is
     # called as the reference calls it.  profiles/graph2seq_notes.md holds the comparison behind the default.
     use_fused_loss = True
+    # `score_free_loss` of that decoder instead: the raw scores [B L, V] and their gradient are not formed either
+    # (csrc/projection_loss.hip).  Off by default; profiles/projection_loss_notes.md holds the comparison.
+    use_score_free_loss = False
 
     def __init__(self, gnn: nn.Module, decoder: nn.Module, node_to_graph_representation: nn.Module):
         super().__init__()
@@ -376,8 +380,10 @@ class Graph2SeqModule(ModuleWithMetrics):
 
     def forward(self, *, encoder_mb_data: Dict[str, Any], decoder_mb_data: Dict[str, Any]):
         decoder = self._decoder
-        fused = self.use_fused_loss and isinstance(decoder, sequence.GruCopyingDecoder)
-        loss = (decoder.fused_loss if fused else decoder)(**self.__decoder_inputs(encoder_mb_data), **decoder_mb_data)
+        own = isinstance(decoder, sequence.GruCopyingDecoder)
+        route = decoder.score_free_loss if own and self.use_score_free_loss else \
+            decoder.fused_loss if own and self.use_fused_loss else decoder
+        loss = route(**self.__decoder_inputs(encoder_mb_data), **decoder_mb_data)
         with torch.no_grad():
             if loss.is_cuda:               # no call of forward waits for the device
                 acc = self.__device_loss_sums.get(loss.device)

@@ -80,11 +80,14 @@ _EDGE16_TRAIN_FAMILY_FIRST = 832  # PTGNN_AMD_KERNEL_EDGE16_TRAIN_FIRST_: the 16
 _ATTENTION_TRAIN16_FAMILY_FIRST = 896  # PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_: the 16-bit attention training launches
 
 
+_PROJECTION_LOSS_FAMILY_FIRST = 960  # PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_: the copying decoder's score-free loss
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
-                  beam_finish: bool = False, attention16: bool = False, attention16_training: bool = False,
-                  edge16_training: bool = False) -> dict:
+                  beam_finish: bool = False, attention16: bool = False, projection_loss: bool = False,
+                  attention16_training: bool = False, edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -102,7 +105,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     the 16-bit-input attention training launches (attention_train16: the forward with dropout; attention_train16_backward);
     `edge16_training=True`
     the 16-bit-input edge-form training launches (edge16_masked: the masked per-edge GEMM in its forward and
-    input-gradient modes; edge_wgrad16: the per-type weight gradient)."""
+    input-gradient modes; edge_wgrad16: the per-type weight gradient); `projection_loss=True` the copying decoder's
+    score-free loss (projection_loss, projection_loss_backward)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -114,7 +118,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_BEAM_FINISH_FAMILY_FIRST,) if beam_finish else ()) \
             + ((_ATTENTION16_FAMILY_FIRST,) if attention16 else ()) \
             + ((_ATTENTION_TRAIN16_FAMILY_FIRST,) if attention16_training else ()) \
-            + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()):
+            + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()) \
+            + ((_PROJECTION_LOSS_FAMILY_FIRST,) if projection_loss else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -129,7 +134,7 @@ def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
                         edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
-                        attention16_training=True, edge16_training=True)
+                        attention16_training=True, edge16_training=True, projection_loss=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -3133,6 +3138,89 @@ def copy_loss_finish(gen: torch.Tensor, copied: torch.Tensor, rowptr: Optional[t
                                                 _stream(loss))
     _lib.check(rc, "ptgnn_amd_copy_loss_finish_f32")
     return loss.view(()), d_gen, d_copied
+
+
+# ------------------------------------------------------------------------------------------------
+# the copying decoder's score-free loss (csrc/projection_loss.hip)
+# ------------------------------------------------------------------------------------------------
+def projection_loss_supported(dim: int) -> bool:
+    """Whether the projection-loss kernels take an embedding width (ptgnn_amd_projection_loss_supported; needs no device)."""
+    return bool(_lib.load().ptgnn_amd_projection_loss_supported(int(dim)))
+
+
+def _projection_args(projected: torch.Tensor, table: torch.Tensor, bias, extra, targets, what: str):
+    _require_cuda_f32("projected", projected)
+    _require_cuda_f32("table", table)
+    projected, table = _rowmajor(projected), _rowmajor(table)
+    (R, E), V = projected.shape, table.shape[0]
+    if table.shape[1] != E or table.device != projected.device or V < 1 or not projection_loss_supported(E):
+        raise _lib.PtgnnAmdError(f"{what}: projected [R, E] and table [V, E] must share a device and a supported width E, "
+                                 f"with V >= 1 (got {tuple(projected.shape)} and {tuple(table.shape)})")
+    dev = projected.device
+    for name, t, n, dt in (("bias", bias, V, torch.float32), ("extra", extra, R, torch.float32),
+                           ("targets", targets, R, torch.int64)):
+        if t is not None and (not t.is_cuda or t.device != dev or t.dtype != dt or tuple(t.shape) != (n,)):
+            raise _lib.PtgnnAmdError(f"{what}: {name} must be a CUDA {dt} [{n}] tensor on the operands' device (got "
+                                     f"{t.dtype} {tuple(t.shape)} on {t.device})")
+    return projected, table, *(t.contiguous() if t is not None else None for t in (bias, extra, targets)), R, V, E
+
+
+def projection_loss(projected: torch.Tensor, table: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    extra: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None):
+    """(norm [R], picked [R] or None, stats [R, 2]) of `vocab_loss` over the scores projected [R, E] @ table [V, E]^T, which
+    are formed tile by tile in registers and never written (ptgnn_amd_projection_loss_f32; grucopydecoder.py:111-135,
+    178-181).  Rows of `projected` and `table` may be padded (unit inner stride)."""
+    lib = _lib.load()
+    projected, table, bias, extra, targets, R, V, E = _projection_args(projected, table, bias, extra, targets,
+                                                                        "projection_loss")
+    dev = projected.device
+    norm = torch.empty(R, dtype=torch.float32, device=dev)
+    picked = torch.empty(R, dtype=torch.float32, device=dev) if targets is not None else None
+    stats = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    if R == 0:
+        return norm, picked, stats
+    ws_bytes = int(lib.ptgnn_amd_projection_loss_workspace_bytes(R, V))
+    ws = _workspace(ws_bytes, dev)
+    with _timed("projection_loss", flops=2.0 * R * V * E, bytes=4.0 * ((R + 63) // 64) * V * E + 4.0 * R * E * ((V + 255) // 256)):
+        rc = lib.ptgnn_amd_projection_loss_f32(projected.data_ptr(), _ld(projected), table.data_ptr(), _ld(table), R, V, E,
+                                               _opt_ptr(bias), _opt_ptr(extra), _opt_ptr(targets), norm.data_ptr(),
+                                               _opt_ptr(picked), stats.data_ptr(), ws.data_ptr(), ws_bytes, _stream(norm))
+    _lib.check(rc, "ptgnn_amd_projection_loss_f32")
+    return norm, picked, stats
+
+
+def projection_loss_backward(projected: torch.Tensor, table: torch.Tensor, bias: Optional[torch.Tensor],
+                             extra: Optional[torch.Tensor], targets: Optional[torch.Tensor], stats: torch.Tensor,
+                             g_norm: Optional[torch.Tensor], g_picked: Optional[torch.Tensor], want_bias: bool = True):
+    """(d_projected [R, E], d_table [V, E], d_bias [V] or None, d_extra [R] or None) of `projection_loss` from its `stats`
+    and the gradients of its norm and picked outputs (device tensors, None = 0): the scores are recomputed twice, once by
+    workgroups that own vocabulary entries (d_table, d_bias) and once by workgroups that own rows (d_projected, d_extra);
+    no [R, V] gradient exists (ptgnn_amd_projection_loss_backward_f32)."""
+    lib = _lib.load()
+    projected, table, bias, extra, targets, R, V, E = _projection_args(projected, table, bias, extra, targets,
+                                                                        "projection_loss_backward")
+    dev = projected.device
+    for name, t, shape in (("stats", stats, (R, 2)), ("g_norm", g_norm, (R,)), ("g_picked", g_picked, (R,))):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise _lib.PtgnnAmdError(f"projection_loss_backward: {name} must be a CUDA float32 {list(shape)} tensor")
+    stats, g_norm, g_picked = (t.contiguous() if t is not None else None for t in (stats, g_norm, g_picked))
+    d_projected = torch.empty(R, E, dtype=torch.float32, device=dev)
+    d_extra = torch.empty(R, dtype=torch.float32, device=dev) if extra is not None else None
+    if R == 0:
+        return d_projected, torch.zeros(V, E, dtype=torch.float32, device=dev), \
+            torch.zeros(V, dtype=torch.float32, device=dev) if want_bias else None, d_extra
+    d_table = torch.empty(V, E, dtype=torch.float32, device=dev)
+    d_bias = torch.empty(V, dtype=torch.float32, device=dev) if want_bias else None
+    ws_bytes = int(lib.ptgnn_amd_projection_loss_backward_workspace_bytes(R, V, E))
+    ws = _workspace(ws_bytes, dev)
+    with _timed("projection_loss_backward", flops=8.0 * R * V * E,
+                bytes=4.0 * V * E * (2 + (R + 63) // 64) + 4.0 * R * E * ((V + 63) // 64 + 3 * ((V + 1023) // 1024))):
+        rc = lib.ptgnn_amd_projection_loss_backward_f32(
+            projected.data_ptr(), _ld(projected), table.data_ptr(), _ld(table), R, V, E, _opt_ptr(bias), _opt_ptr(extra),
+            _opt_ptr(targets), stats.data_ptr(), _opt_ptr(g_norm), _opt_ptr(g_picked), d_projected.data_ptr(), E,
+            d_table.data_ptr(), E, _opt_ptr(d_bias), _opt_ptr(d_extra), ws.data_ptr(), ws_bytes, _stream(d_table))
+    _lib.check(rc, "ptgnn_amd_projection_loss_backward_f32")
+    return d_projected, d_table, d_bias, d_extra
 
 
 # ------------------------------------------------------------------------------------------------

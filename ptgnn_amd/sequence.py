@@ -37,6 +37,9 @@ GRU's output states [B, L, H]:
     minus the normaliser of their own (sample of the memory, step), their per-location log-sum-exp runs on the facade's
     segment kernels, and `_CopyLossFinish` is the [B, L] tail in one launch.  Neither `target_logprobs` [B, L, V] nor
     `copy_logprobs` [I, L] exists on that route; on shapes beyond the fused range only its attention part is composed.
+  * `score_free_loss` is `fused_loss` with the second vocabulary Linear inside the loss node (`_ProjectionLoss`,
+    csrc/projection_loss.hip): the raw scores [B L, V] and their gradient do not exist either; forward and backward
+    recompute the score tiles in registers.  Opt-in (`heads.Graph2SeqModule.use_score_free_loss`), for its memory.
 Shapes beyond that range compose the reference's operator sequence from the HIP Linear, the fused cell, the row gather
 and the facade's segment kernels.  CPU tensors take the reference's own operator order on torch (device dispatch as in
 every layer of the package); fp16 / bf16 inputs are up-cast on entry and the results cast back.
@@ -121,6 +124,28 @@ class _VocabLoss(torch.autograd.Function):
         grad, g_extra, g_bias = ops.vocab_loss_backward(raw_scores, bias, total_copy, targets, stats, g_norm, g_picked,
                                                         want_bias=bias is not None and ctx.needs_input_grad[1])
         return grad, g_bias, g_extra if ctx.needs_input_grad[2] else None, None
+
+
+class _ProjectionLoss(torch.autograd.Function):
+    """(norm [R], picked [R]) = ops.projection_loss(projected [R, E], table [V, E], bias, total_copy [R], targets [R]) as one
+    node: `_VocabLoss` with the second vocabulary Linear (grucopydecoder.py:111-118) inside it.  Neither the raw scores
+    [R, V] nor their gradient exists; the backward recomputes the score tiles and returns the gradients of the projected
+    states and of the (dropped-out) table."""
+
+    @staticmethod
+    def forward(ctx, projected, table, bias, total_copy, targets):
+        norm, picked, stats = ops.projection_loss(projected, table, bias, total_copy, targets)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(projected, table, bias, total_copy, targets, stats)
+        return norm, picked
+
+    @staticmethod
+    def backward(ctx, g_norm, g_picked):
+        projected, table, bias, total_copy, targets, stats = ctx.saved_tensors
+        d_projected, d_table, d_bias, d_extra = ops.projection_loss_backward(
+            projected, table, bias, total_copy, targets, stats, g_norm, g_picked,
+            want_bias=bias is not None and ctx.needs_input_grad[2])
+        return d_projected, d_table, d_bias, d_extra if ctx.needs_input_grad[3] else None, None
 
 
 class _CopyLossFinish(torch.autograd.Function):
@@ -212,11 +237,15 @@ class GruCopyingDecoder(nn.Module):
             states.append(h)
         return torch.stack(states, dim=1), h
 
+    def __projected_states(self, attention_out, output_states):
+        """The first factor of grucopydecoder.py:111-118 on [B * L, .] matrices: one HIP Linear."""
+        hidden = torch.cat((self.__dropout(attention_out), output_states), dim=-1)         # [B * L, 2 H]
+        return dense.linear(hidden, self.__hidden_to_vocab.t())                            # [B * L, E]
+
     def __raw_vocabulary_scores(self, attention_out, output_states):
         """grucopydecoder.py:111-118 on [B * L, .] matrices: two HIP Linears, the bias not added."""
-        hidden = torch.cat((self.__dropout(attention_out), output_states), dim=-1)         # [B * L, 2 H]
-        projected = dense.linear(hidden, self.__hidden_to_vocab.t())                       # [B * L, E]
-        return dense.linear(projected, self.__dropout(self.__embedding_layer.weight))
+        return dense.linear(self.__projected_states(attention_out, output_states),
+                            self.__dropout(self.__embedding_layer.weight))
 
     def __vocabulary_scores(self, attention_out, output_states):
         """grucopydecoder.py:111-119: the raw scores and the bias."""
@@ -365,14 +394,47 @@ class GruCopyingDecoder(nn.Module):
                 initial_states=initial_states, target_token_ids=target_token_ids,
                 copyable_elements_idxs=copyable_elements_idxs,
                 copyable_elements_sample_idxs=copyable_elements_sample_idxs, target_lengths=target_lengths)
+        return self.__device_loss(False, input_memories, input_memories_origin_idx, initial_states, target_token_ids,
+                                  copyable_elements_idxs, copyable_elements_sample_idxs, target_lengths)
+
+    def score_free_loss(self, *, input_memories, input_memories_origin_idx, initial_states, target_token_ids,
+                        copyable_elements_idxs, copyable_elements_sample_idxs, target_lengths):
+        """The loss of `fused_loss` (same keyword arguments, same value) without the raw scores [B L, V] either: the second
+        vocabulary Linear runs inside `_ProjectionLoss` (csrc/projection_loss.hip), which forms the score tiles in
+        registers, and its backward recomputes them instead of writing and re-reading an [B L, V] gradient.  The first
+        Linear (hidden -> projected) stays `dense.linear`; the table is the dropped-out embedding matrix, made as in
+        `fused_loss`, and its gradient flows back through the dropout.  CPU tensors, B = 0 / L = 0 and an embedding width
+        the kernels do not take go to `fused_loss`."""
+        B, L = target_token_ids.shape[0], target_token_ids.shape[1] - 1
+        score_free = input_memories.is_cuda and B > 0 and L > 0 \
+            and ops.projection_loss_supported(self.__embedding_layer.embedding_dim)
+        if not score_free:
+            return self.fused_loss(
+                input_memories=input_memories, input_memories_origin_idx=input_memories_origin_idx,
+                initial_states=initial_states, target_token_ids=target_token_ids,
+                copyable_elements_idxs=copyable_elements_idxs,
+                copyable_elements_sample_idxs=copyable_elements_sample_idxs, target_lengths=target_lengths)
+        return self.__device_loss(True, input_memories, input_memories_origin_idx, initial_states, target_token_ids,
+                                  copyable_elements_idxs, copyable_elements_sample_idxs, target_lengths)
+
+    def __device_loss(self, score_free, input_memories, index, initial_states, target_token_ids, copyable_elements_idxs,
+                      copyable_elements_sample_idxs, target_lengths):
+        """`fused_loss` and `score_free_loss` on GPU tensors: they differ in the node that turns the vocabulary product
+        into (norm, picked) only."""
+        B, L = target_token_ids.shape[0], target_token_ids.shape[1] - 1
         if input_memories.dtype in _HALF or initial_states.dtype in _HALF:       # AMP: fp32 inside, an fp32 loss
             input_memories, initial_states = input_memories.float(), initial_states.float()
-        index = input_memories_origin_idx
         states, attention_out, copy_scores, total_copy, _, _ = self.__device_attention(
             initial_states, input_memories, index, target_token_ids[:, :-1])
         targets = target_token_ids[:, 1:].contiguous()                                     # [B, L]
-        raw_scores = self.__raw_vocabulary_scores(attention_out, states)                   # [B * L, V]: the only one
-        norm, picked = _VocabLoss.apply(raw_scores, self.__vocab_bias, total_copy.reshape(B * L), targets.reshape(B * L))
+        if score_free:
+            projected = self.__projected_states(attention_out, states)                     # [B * L, E]
+            norm, picked = _ProjectionLoss.apply(projected, self.__dropout(self.__embedding_layer.weight),
+                                                 self.__vocab_bias, total_copy.reshape(B * L), targets.reshape(B * L))
+        else:
+            raw_scores = self.__raw_vocabulary_scores(attention_out, states)               # [B * L, V]: the only one
+            norm, picked = _VocabLoss.apply(raw_scores, self.__vocab_bias, total_copy.reshape(B * L),
+                                            targets.reshape(B * L))
         if copyable_elements_idxs.shape[0] == 0:
             copied, rowptr = torch.full((B, L), -math.inf, dtype=torch.float32, device=norm.device), None
         else:
