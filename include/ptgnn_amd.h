@@ -252,6 +252,16 @@ enum {
   PTGNN_AMD_KERNEL_PROJECTION_LOSS_BACKWARD,                                  /* ptgnn_amd_projection_loss_backward_f32 */
   PTGNN_AMD_KERNEL_PROJECTION_LOSS_END_
 };
+/* ... and one for the opt-in 16-bit message rows (csrc/gather_reduce16.hip and the row-storing forms of
+ * csrc/edge_gemm16.hip, csrc/half_gemm.hip) */
+enum {
+  PTGNN_AMD_KERNEL_ROWS16_FIRST_ = 1024,
+  PTGNN_AMD_KERNEL_AGG16 = PTGNN_AMD_KERNEL_ROWS16_FIRST_, /* ptgnn_amd_gather_reduce16 */
+  PTGNN_AMD_KERNEL_EDGE16_ROWS16,                          /* ptgnn_amd_edge_rows16_linear16 */
+  PTGNN_AMD_KERNEL_EDGE16_SHARED_ROWS16,                   /* ptgnn_amd_edge_shared_rows16_linear16 */
+  PTGNN_AMD_KERNEL_LINEAR_ROWS16,                          /* ptgnn_amd_linear_rows16 */
+  PTGNN_AMD_KERNEL_ROWS16_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1741,6 +1751,59 @@ int ptgnn_amd_selfatt_train16_backward(const float *kqv, int64_t ld_kqv, const f
                                        int64_t num_windows, int64_t num_rows, int32_t max_num_nodes, int32_t num_heads,
                                        int32_t dk, int32_t dv, float dropout_p, uint64_t seed, float *grad_kqv,
                                        int64_t ld_gkqv, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit GGNN MESSAGE ROWS: producers that store them and the aggregation that reads them
+ * (csrc/gather_reduce16.hip; the row-storing forms of csrc/edge_gemm16.hip and csrc/half_gemm.hip).
+ *
+ * Replaces: the message tensors of gatedmessagepassing.py:57-61 as an `enable_amp` user of the reference gets them
+ *   (trainer.py:205,221: the message Linears run under autocast, so their OUTPUT is a 16-bit tensor) and the up-cast of
+ *   abstractmessagepassing.py:43-50, which makes them fp32 only inside `_aggregate_messages` (torch_scatter.scatter on
+ *   messages.to(torch.float32)): one rounding of each message, fp32 accumulation in the scatter.  OFF by default: the
+ *   host's ptgnn_amd.precision.set_half_messages asks for it; every fp32-row entry above is what it was.
+ *
+ * Producers.  The three entries below are ptgnn_amd_edge_linear16, ptgnn_amd_edge_linear16_shared and
+ *   ptgnn_amd_half_linear with a 16-bit output: same arguments, same kernels, same accumulators, and
+ *       msg16[r, c] = rnd(act(accumulator[r, c] (+ bias[c])))           rounded to nearest even as tensor.to(dtype) does
+ *   i.e. exactly `fp32 entry(...).to(dtype)`; `msg16` / `y16` is a 16-bit [rows, n] array of `dtype` (the dtype of the
+ *   operands) with leading dimension ld in ELEMENTS, 4-byte aligned with an even ld: a lane stores two neighbouring
+ *   columns as one dword.  Both launch forms of the per-edge GEMM give the same bits per row.  Shapes, error codes and
+ *   messages as the fp32-output entries ("edge_linear16:" / "linear_rows16:"), plus PTGNN_AMD_EUNSUPPORTED for an odd ld
+ *   or a base that is not 4-byte aligned.
+ *   (The names keep "linear16" last / carry a "16" suffix: the ptgnn_amd_edge_linear16* and ptgnn_amd_half_* prefixes are
+ *   closed sets of three.)
+ *
+ * ptgnn_amd_gather_reduce16:  out[v, :] = reduce over the CSR slots i of row v, row_begin <= v < row_end, of
+ *       float(rows16[col[i] >> type_bits, (col[i] & ((1 << type_bits) - 1)) * msg_dim : + msg_dim])
+ *   rows16 16-bit of `dtype` with leading dimension ld_rows (elements); rowptr / col / type_bits as
+ *   ptgnn_amd_gather_reduce_f32 takes them (the table form [N, T * msg_dim] addresses column block t * msg_dim; the edge
+ *   form passes type_bits 0 and the slot -> row map as `col`); reduce = PTGNN_AMD_SUM / MEAN / MAX / MIN, empty rows 0;
+ *   fp32 accumulation in CSR order and fp32 out [num_nodes, msg_dim] (ld_out); rows outside [row_begin, row_end) are
+ *   neither read nor written.  No destination term, no argout, no epilogue (those stay on the fp32 rows).
+ *   Rows of up to `hub_threshold` in-edges fold serially in CSR order (the bits of the serial fp32 fold of the up-cast
+ *   values).  Rows beyond it (0 = none) are folded by a whole workgroup in contiguous runs combined in a fixed order
+ *   inside the same launch: no hub list, no tickets, no workspace, deterministic; their sums' fold order differs from
+ *   the serial order (fp32 rounding only), max / min are exact everywhere.  `num_edges` only tells an edge-free plan
+ *   (rows16 may then be NULL).
+ *   ptgnn_amd_gather_reduce16_supported(msg_dim, dtype): msg_dim % 32 == 0, msg_dim <= 256, a known dtype; no device.
+ *   rows16 and out must be 16-byte aligned with ld_rows % 8 == 0 and ld_out % 4 == 0 (PTGNN_AMD_EUNSUPPORTED otherwise);
+ *   bad sizes / enums / null pointers answer PTGNN_AMD_EINVAL; all with a message that starts "gather_reduce16:" and
+ *   before anything touches the device.  Additive: the ABI version stays.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_gather_reduce16_supported(int32_t msg_dim, int dtype);
+int ptgnn_amd_gather_reduce16(const void *rows16, int64_t ld_rows, int dtype, const int32_t *rowptr, const int32_t *col,
+                              int32_t type_bits, int64_t num_nodes, int32_t msg_dim, int reduce, float *out,
+                              int64_t ld_out, int64_t num_edges, int32_t hub_threshold, int64_t row_begin,
+                              int64_t row_end, void *stream);
+int ptgnn_amd_edge_rows16_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                   const int64_t *const *src_per_type, const int64_t *edges_per_type, const void *w,
+                                   int32_t num_types, int32_t msg_dim, int act, int dtype, void *msg16, int64_t ld_msg,
+                                   void *stream);
+int ptgnn_amd_edge_shared_rows16_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                          const void *edge_table, const void *w, int32_t num_types, int32_t msg_dim,
+                                          int act, int dtype, void *msg16, int64_t ld_msg, void *stream);
+int ptgnn_amd_linear_rows16(const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w, int32_t n_out,
+                            const float *bias /* nullable */, int act, int dtype, void *y16, int64_t ld_y, void *stream);
 
 #pragma GCC visibility pop
 

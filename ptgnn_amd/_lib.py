@@ -221,6 +221,15 @@ SIGNATURES = {
                                            _i64, _vp]),
     "ptgnn_amd_edge_linear16_shared": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int, _vp,
                                                   _i64, _vp]),
+    # the opt-in 16-bit message rows (csrc/gather_reduce16.hip and the row-storing forms of the 16-bit GEMMs)
+    "ptgnn_amd_gather_reduce16_supported": (_c.c_int, [_i32, _c.c_int]),
+    "ptgnn_amd_gather_reduce16": (_c.c_int, [_vp, _i64, _c.c_int, _vp, _vp, _i32, _i64, _i32, _c.c_int, _vp, _i64, _i64,
+                                             _i32, _i64, _i64, _vp]),
+    "ptgnn_amd_edge_rows16_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
+                                                  _vp, _i64, _vp]),
+    "ptgnn_amd_edge_shared_rows16_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
+                                                         _vp, _i64, _vp]),
+    "ptgnn_amd_linear_rows16": (_c.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _c.c_int, _c.c_int, _vp, _i64, _vp]),
     "ptgnn_amd_edge_dst_linear16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int]),
     "ptgnn_amd_edge_dst_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
                                                _vp, _i64, _vp]),

@@ -64,6 +64,9 @@ struct Edge16Args {
   const uint32_t *mask;
   int mask_ld;
   float scale;
+  // the row-storing forms (template flag ROWS16): the messages leave as 16-bit rows of the operand type, rounded in the
+  // fragment epilogue (half16.h store_frag_rows16); ld_msg is then in 16-bit elements and `msg` is unused
+  uint16_t *msg16;
 };
 
 // The id lists are global memory; read out of a table in device memory the pointers would be generic and their loads
@@ -141,7 +144,9 @@ __device__ __forceinline__ void wave_tile_masked(const float *__restrict__ arow,
 // MASK (both kernels; per-edge form without a target half, no activation): the per-edge dropout of the training step from
 // its keep bits.  1: on the gathered input, before it is rounded (the forward); 2: on the fp32 accumulator, before the
 // store (the input gradient).  0: no mask -- the code of the unmasked instantiations is what it was.
-template <int DT, bool INDIRECT, bool DST = false, int MASK = 0>
+// ROWS16 (both kernels; unmasked, no target half): the accumulators are those of the fp32-output launch and leave rounded
+// to the operand type as 16-bit message rows -- the bits of `msg.to(dtype)`, whichever kernel and launch form ran.
+template <int DT, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
 __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
@@ -174,6 +179,10 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
     for (int n = 0; n < kTiles; ++n) {
       if (n < tiles) {
         const int col = col0 + n * 32 + li;
+        if constexpr (ROWS16) {
+          store_frag_rows16<DT>(p.msg16, p.ld_msg, q.out0, q.out0 + q.left, col,
+                                [&](int r) { return act_runtime(acc[n][r], p.act); });
+        } else
         for_frag_rows(q.out0, q.out0 + q.left, [&](int r, int64_t row) {
           if constexpr (MASK == 2)      // the keep word of this row's 32-column tile; this lane's column is bit li
             p.msg[row * p.ld_msg + col] = keep_scaled(acc[n][r], p.mask[row * p.mask_ld + (col >> 5)], li, p.scale);
@@ -185,7 +194,7 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   }
 }
 
-template <int DT, int KS, bool INDIRECT, bool DST = false, int MASK = 0>
+template <int DT, int KS, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
 __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   using Hf = Half16<DT>;
   using vec = typename Hf::vec;
@@ -263,6 +272,10 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
       zero(acc);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) acc = Hf::mfma(panel.frag(li, ks), bw[ks], acc);
+      if constexpr (ROWS16) {
+        store_frag_rows16<DT>(p.msg16, p.ld_msg, cur.out0, cur.out0 + cur.left, j,
+                              [&](int r) { return act_runtime(acc[r], p.act); });
+      } else
       for_frag_rows(cur.out0, cur.out0 + cur.left, [&](int r, int64_t row) {
         if constexpr (MASK == 2) {
           const uint32_t lo = __builtin_amdgcn_readlane(mrow, frag_row(r, 0)), up = __builtin_amdgcn_readlane(mrow, frag_row(r, 1));
@@ -346,11 +359,11 @@ int host_table(const char *who, const int64_t *const *src_per_type, const int64_
 // Workgroups of a weight-stationary instance that one CU holds at once (registers and LDS decide; asked once).  The
 // launch is ONE such round: measured at the cfg3 layer shapes, any grid that needs a partly filled second round loses
 // 15 - 20 % to it (profiles/edge_inputs_notes.md).
-template <int DT, int KS, bool INDIRECT, bool DST, int MASK>
+template <int DT, int KS, bool INDIRECT, bool DST, int MASK, bool ROWS16>
 int ws_resident_per_cu() {
   static const int per_cu = [] {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST, MASK>, 256, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST, MASK, ROWS16>, 256, 0) != hipSuccess ||
         n < 1) {
       (void)hipGetLastError();
       n = 2;
@@ -362,8 +375,9 @@ int ws_resident_per_cu() {
 
 // `units` < 0: unknown on the host (shared form) -- the launch is sized for the device, workgroups without units leave
 // DST: the chain is 2 H long, so the weight-stationary register budgets (KS = 8, 16) hold H in {64, 128}
-template <bool INDIRECT, bool DST = false, int MASK = 0>
+template <bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
 int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
+  static_assert(!ROWS16 || (!DST && MASK == 0), "16-bit message rows: the unmasked forms without a target half");
   const int64_t cus = num_compute_units();
   const int k = DST ? 2 * p.H : p.H;
   const bool ws = (k == 128 || k == 256 || (!DST && k == 64)) && p.M <= 128 &&
@@ -373,9 +387,9 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
     with_dtype(dtype, [&](auto dt) {
       auto run = [&](auto ks) {
         constexpr int DT = decltype(dt)::value, KS = decltype(ks)::value;
-        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST, MASK>());
+        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST, MASK, ROWS16>());
         if (units >= 0 && units < grid) grid = units;
-        k_edge16_ws<DT, KS, INDIRECT, DST, MASK><<<(unsigned)grid, 256, 0, st>>>(p);
+        k_edge16_ws<DT, KS, INDIRECT, DST, MASK, ROWS16><<<(unsigned)grid, 256, 0, st>>>(p);
       };
       if constexpr (DST) with_case<8, 16>(k / 16, run); else with_case<4, 8, 16>(k / 16, run);
     });
@@ -384,9 +398,13 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
     int64_t grid = cus * 8;
     if (units >= 0 && (units * col_groups + 3) / 4 < grid) grid = (units * col_groups + 3) / 4;
     with_dtype(dtype,
-               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST, MASK><<<(unsigned)grid, 256, 0, st>>>(p); });
+               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST, MASK, ROWS16><<<(unsigned)grid, 256, 0, st>>>(p); });
   }
   PTGNN_LAUNCH_CHECK();
+  if (ROWS16) {
+    count_launch(INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED_ROWS16 : PTGNN_AMD_KERNEL_EDGE16_ROWS16);
+    return PTGNN_AMD_OK;
+  }
   count_launch(MASK ? PTGNN_AMD_KERNEL_EDGE16_MASKED
                     : (DST ? PTGNN_AMD_KERNEL_EDGE16_DST
                            : (INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED : PTGNN_AMD_KERNEL_EDGE16)));
@@ -487,4 +505,50 @@ extern "C" int ptgnn_amd_edge_linear16_shared(const float *x, int64_t ld_x, int6
   p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
   p.H = state_dim; p.M = msg_dim; p.act = act; p.msg = msg; p.ld_msg = ld_msg;
   return launch<true>(p, dtype, -1, (hipStream_t)stream_);
+}
+
+// The row-storing forms: the two entries above with 16-bit message rows (contract: include/ptgnn_amd.h).
+static int check_rows16(const void *msg16, int64_t ld_msg) {
+  PTGNN_REQUIRE(aligned4(msg16) && ld_msg % 2 == 0, PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: rows16: msg16 must be 4-byte aligned with an even ld_msg (ld_msg=%lld)", (long long)ld_msg);
+  return PTGNN_AMD_OK;
+}
+
+extern "C" int ptgnn_amd_edge_rows16_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                              const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                              const void *w, int32_t num_types, int32_t msg_dim, int act, int dtype,
+                                              void *msg16, int64_t ld_msg, void *stream_) {
+  if (const int rc = check_shape(" rows16:", state_dim, num_types, msg_dim, act, dtype)) return rc;
+  Edge16Args p{};
+  int64_t units = 0;
+  if (const int rc = host_table(" rows16:", src_per_type, nullptr, edges_per_type, num_types, false, p.tab, units))
+    return rc;
+  if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
+  if (const int rc = check_operands(" rows16:", x, ld_x, num_rows, state_dim, w, msg_dim,
+                                    static_cast<const float *>(msg16), ld_msg))
+    return rc;
+  if (const int rc = check_rows16(msg16, ld_msg)) return rc;
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = act; p.msg16 = static_cast<uint16_t *>(msg16); p.ld_msg = ld_msg;
+  return launch<false, false, 0, true>(p, dtype, units, (hipStream_t)stream_);
+}
+
+extern "C" int ptgnn_amd_edge_shared_rows16_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                                     const void *edge_table, const void *w, int32_t num_types,
+                                                     int32_t msg_dim, int act, int dtype, void *msg16, int64_t ld_msg,
+                                                     void *stream_) {
+  if (const int rc = check_shape(" rows16:", state_dim, num_types, msg_dim, act, dtype)) return rc;
+  PTGNN_REQUIRE(edge_table, PTGNN_AMD_EINVAL, "edge_linear16: rows16: shared: null edge table");
+  if (const int rc = check_operands(" rows16:", x, ld_x, num_rows, state_dim, w, msg_dim,
+                                    static_cast<const float *>(msg16), ld_msg))
+    return rc;
+  if (const int rc = check_rows16(msg16, ld_msg)) return rc;
+  PTGNN_REQUIRE(num_rows * num_types < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: rows16: shared: too many (type, source) pairs (%lld rows x %d types)",
+                (long long)num_rows, num_types);
+  Edge16Args p{};
+  p.tab_dev = static_cast<const StreamEdgeTable *>(edge_table);
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = act; p.msg16 = static_cast<uint16_t *>(msg16); p.ld_msg = ld_msg;
+  return launch<true, false, 0, true>(p, dtype, -1, (hipStream_t)stream_);
 }

@@ -116,6 +116,40 @@ __device__ __forceinline__ void for_frag_rows(int64_t row0, int64_t end, F &&fn)
   }
 }
 
+// The ROUNDING store of the fragment epilogue (the 16-bit message rows: edge_gemm16.hip, half_gemm.hip): the tile whose
+// first row is `row0` leaves as 16-bit values of type DT in out16[row, col], ld in elements, rows below `end` only.
+// value(r) is the fp32 the fp32-output launch would store for C-fragment register r of this lane (column `col`; its
+// parity is the lane's); it is rounded to nearest even by the same fptrunc as the operands -- what tensor.to(dtype)
+// does -- so the stored bits are those of `fp32 launch(...).to(dtype)`.
+// Two values per dword: neighbouring columns live in neighbouring lanes, neighbouring rows in neighbouring registers.
+// Per register pair (r, r + 1) the lanes of a column pair swap ONE value through a quad permute (DPP, no LDS): the even
+// lane keeps row(r) and receives its neighbour's column of it, the odd lane keeps row(r + 1): 8 dword stores per lane
+// and tile instead of 16 short ones, every lane storing.  out16 must be 4-byte aligned with an even ld.  The permute
+// reads the neighbour's register: every caller runs it with the whole wave active (rows past `end` are computed on
+// clamped operands like everywhere here, and only the store is masked).  Plain vector stores.
+template <int DT>
+__device__ __forceinline__ uint32_t pack2(float lo, float up) {
+  using half2 = __attribute__((ext_vector_type(2))) typename Half16<DT>::elem;
+  using f32x2 = __attribute__((ext_vector_type(2))) float;
+  const f32x2 f = {lo, up};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, half2));
+}
+template <int DT, class V>
+__device__ __forceinline__ void store_frag_rows16(uint16_t *__restrict__ out16, int64_t ld, int64_t row0, int64_t end,
+                                                  int col, V &&value) {
+  const int hi = frag_hi();
+  const bool odd = (col & 1) != 0;
+#pragma unroll
+  for (int r = 0; r < 16; r += 2) {
+    const float v0 = value(r), v1 = value(r + 1);
+    // quad_perm [1, 0, 3, 2]: lane l reads lane l ^ 1
+    const float got = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(odd ? v0 : v1), 0xB1, 0xF, 0xF, false));
+    const int64_t row = row0 + frag_row(r, hi) + (odd ? 1 : 0);
+    const uint32_t w = odd ? pack2<DT>(got, v1) : pack2<DT>(v0, got);
+    if (row < end) *reinterpret_cast<uint32_t *>(out16 + row * ld + (col & ~1)) = w;
+  }
+}
+
 // The per-edge dropout of the masked forms (edge_gemm16.hip, edge_wgrad16.hip) on one value: v * scale where bit `bit` of
 // the keep word is set, else +0 -- the bit spread over the word and ANDed in, as the fp32 streaming kernel does it, so a
 // dropped inf or NaN is a zero too.

@@ -32,7 +32,9 @@ using namespace half16;
 constexpr int kLinTiles = 4;   // 32-column tiles per wave of the Linear
 
 // ADD: y = act(..) + addend (fp32 [rows, n_out], ld_add) in the store epilogue: ptgnn_amd_linear_add16
-template <int DT, bool ADD>
+// ROWS16 (without ADD): the same accumulators leave rounded to the operand type as 16-bit rows -- `y` then points at a
+// 16-bit array and ld_y counts its elements (ptgnn_amd_linear_rows16: the GGNN message table in its half-width form)
+template <int DT, bool ADD, bool ROWS16 = false>
 __global__ __launch_bounds__(256) void k_half_linear(const float *__restrict__ x, int64_t rows, int K, int64_t ld_x,
                                                      const uint16_t *__restrict__ w, int n_out,
                                                      const float *__restrict__ bias, int act, float *__restrict__ y,
@@ -54,6 +56,11 @@ __global__ __launch_bounds__(256) void k_half_linear(const float *__restrict__ x
     if (t < tiles) {
       const int col = col0 + t * 32 + li;
       const float bv = bias ? bias[col] : 0.f;
+      if constexpr (ROWS16) {
+        store_frag_rows16<DT>(reinterpret_cast<uint16_t *>(y), ld_y, row0, rows, col,
+                              [&](int r) { return act_runtime(acc[t][r] + bv, act); });
+        continue;
+      }
       // not for_frag_rows: under it the 16 row addresses are hoisted out of the tile loop (76 -> 102 VGPRs), measured
       // 0.7 % slower at the cfg3 shape (profiles/half16_refactor_notes.md)
       float av[16];
@@ -273,7 +280,7 @@ extern "C" int ptgnn_amd_half_supported(int kind, int32_t k_or_m, int32_t n_out_
 }
 
 // the two Linear entries: `what` names the entry in the messages; ADD: with the fp32 addend
-template <bool ADD>
+template <bool ADD, bool ROWS16 = false>
 static int half_linear_entry(const char *what, const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w,
                              int32_t n_out, const float *bias, int act, int dtype, const float *addend, int64_t ld_add,
                              float *y, int64_t ld_y, void *stream_) {
@@ -285,6 +292,8 @@ static int half_linear_entry(const char *what, const float *x, int64_t rows, int
   if (rows == 0) return PTGNN_AMD_OK;
   PTGNN_REQUIRE(x && w && y && ld_x >= k && ld_y >= n_out, PTGNN_AMD_EINVAL, "%s: null/ld", what);
   PTGNN_REQUIRE(!ADD || (addend && ld_add >= n_out), PTGNN_AMD_EINVAL, "%s: null/ld of the addend", what);
+  PTGNN_REQUIRE(!ROWS16 || ld_y % 2 == 0, PTGNN_AMD_EUNSUPPORTED, "%s: 16-bit rows need an even ld_y (ld_y=%lld)", what,
+                (long long)ld_y);
   PTGNN_REQUIRE(rows16(x, ld_x) && aligned16(w) && aligned4(y) && (!bias || aligned4(bias)) &&
                     (!ADD || aligned4(addend)),
                 PTGNN_AMD_EUNSUPPORTED,
@@ -296,11 +305,13 @@ static int half_linear_entry(const char *what, const float *x, int64_t rows, int
   hipStream_t st = (hipStream_t)stream_;
   const uint16_t *w16 = static_cast<const uint16_t *>(w);
   with_dtype(dtype, [&](auto dt) {
-    k_half_linear<decltype(dt)::value, ADD><<<(unsigned)blocks, 256, 0, st>>>(x, rows, k, ld_x, w16, n_out, bias, act, y,
-                                                                              ld_y, col_groups, addend, ld_add);
+    k_half_linear<decltype(dt)::value, ADD, ROWS16><<<(unsigned)blocks, 256, 0, st>>>(x, rows, k, ld_x, w16, n_out, bias,
+                                                                                      act, y, ld_y, col_groups, addend,
+                                                                                      ld_add);
   });
   PTGNN_LAUNCH_CHECK();
-  count_launch(ADD ? PTGNN_AMD_KERNEL_HALF_LINEAR_ADD : PTGNN_AMD_KERNEL_HALF_LINEAR);
+  count_launch(ROWS16 ? PTGNN_AMD_KERNEL_LINEAR_ROWS16
+                      : (ADD ? PTGNN_AMD_KERNEL_HALF_LINEAR_ADD : PTGNN_AMD_KERNEL_HALF_LINEAR));
   return PTGNN_AMD_OK;
 }
 
@@ -316,6 +327,13 @@ extern "C" int ptgnn_amd_linear_add16(const float *x, int64_t rows, int32_t k, i
                                       int64_t ld_add, float *y, int64_t ld_y, void *stream_) {
   return half_linear_entry<true>("linear_add16", x, rows, k, ld_x, w, n_out, bias, act, dtype, addend, ld_add, y, ld_y,
                                  stream_);
+}
+
+// ptgnn_amd_half_linear with 16-bit output rows of the operand type: the bits of `half_linear(...).to(dtype)`
+extern "C" int ptgnn_amd_linear_rows16(const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w, int32_t n_out,
+                                       const float *bias, int act, int dtype, void *y16, int64_t ld_y, void *stream_) {
+  return half_linear_entry<false, true>("linear_rows16", x, rows, k, ld_x, w, n_out, bias, act, dtype, nullptr, 0,
+                                        static_cast<float *>(y16), ld_y, stream_);
 }
 
 // the two GRU entries: `what` names the entry in the messages; TRAIN: also writes gates [n, 4 hd]

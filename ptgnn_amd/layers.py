@@ -194,16 +194,17 @@ def _kernel_act(act: Optional[nn.Module]) -> Optional[str]:
     return "tanh" if isinstance(act, nn.Tanh) else ("relu" if isinstance(act, nn.ReLU) else None)
 
 
-def _edge_messages(table: torch.Tensor, adjacency_lists, plan, weights, inputs=None, rounded=None):
+def _edge_messages(table: torch.Tensor, adjacency_lists, plan, weights, inputs=None, rounded=None, rows=None):
     """GGNN messages of the edge form (inference) and the `col` that maps CSR slots to their rows: one row per distinct
     (edge type, source) pair of the plan where the shared-row launch applies (GraphPlan.unique_messages), else one row
     per edge in reference order (gatedmessagepassing.py:50-61).  The aggregate has the same bits either way -- also
-    under 16-bit `inputs` (with `rounded`, the [T, M, H] stack of the rounded weights), which both launches follow."""
+    under 16-bit `inputs` (with `rounded`, the [T, M, H] stack of the rounded weights), which both launches follow, and
+    with 16-bit message `rows` (ops.edge_linear), which both launches store with the same bits."""
     if UNIQUE_MESSAGES and ops.edge_linear_shared_supported(table.shape[1], weights[0].shape[0], len(weights)):
         uniq = plan.unique_messages()
         if uniq is not None:
-            return ops.edge_linear_shared(table, uniq, weights, inputs=inputs, rounded=rounded), uniq.slot_row
-    return ops.edge_linear(table, adjacency_lists, weights, False, inputs=inputs, rounded=rounded), plan.perm
+            return ops.edge_linear_shared(table, uniq, weights, inputs=inputs, rounded=rounded, rows=rows), uniq.slot_row
+    return ops.edge_linear(table, adjacency_lists, weights, False, inputs=inputs, rounded=rounded, rows=rows), plan.perm
 
 
 def _feat_gemm_ok(node_states, edge_features, state_dim: int, out_dim: int, *params, shapes_only: bool = False) -> bool:
@@ -265,7 +266,8 @@ def _amp_forward(layer, node_states, adjacency_lists, edge_features, cast_featur
     like any fp32 states: rounding an up-cast value is exact."""
     if cast_features:
         edge_features = [f.float() if f is not None and f.dtype in _AMP_DTYPES else f for f in edge_features]
-    return layer.forward(node_states.float(), adjacency_lists, None, None, None, edge_features).to(node_states.dtype)
+    with precision.half_messages(False):      # the up-cast route keeps fp32 message rows (precision.py: out of scope)
+        return layer.forward(node_states.float(), adjacency_lists, None, None, None, edge_features).to(node_states.dtype)
 
 
 def _overlap_reduces():
@@ -511,10 +513,11 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
                 edge_features: List[torch.Tensor]) -> torch.Tensor:
         assert len(adjacency_lists) == len(self.__edge_message_transformation_layers)
         if _on_host(node_states):
+            host_inputs = self._host_matrix_inputs(node_states, edge_features)
             return torch_route.ggnn_layer(node_states, adjacency_lists, edge_features,
                                           list(self.__edge_message_transformation_layers), self.__dropout,
-                                          self.__state_update, self.__aggregation_fn,
-                                          inputs=self._host_matrix_inputs(node_states, edge_features))
+                                          self.__state_update, self.__aggregation_fn, inputs=host_inputs,
+                                          rows=host_inputs if precision.get_half_messages() else torch.float32)
         if node_states.dtype in _AMP_DTYPES:
             return _amp_forward(self, node_states, adjacency_lists, edge_features)
         num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
@@ -571,7 +574,9 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
         """Inference: message table (or edge form) -> aggregation -> GRU cell, pipelined over destination-row ranges on
         large minibatches (ops.aggregate_gru).  Under a 16-bit matrix-input setting the table Linear and the GRU cell
         take the 16-bit kernels; the grouped per-edge GEMM of the edge form does when the setting was made with
-        `edge_gemm=True` (both of its launch forms, so the back-off between them never changes the numerics)."""
+        `edge_gemm=True` (both of its launch forms, so the back-off between them never changes the numerics).  With
+        `precision.half_messages()` the producer stores its messages as 16-bit rows and the aggregation reads those
+        (csrc/gather_reduce16.hip) wherever both ends take the shape; the GRU cell reads the fp32 aggregate as before."""
         num_nodes, H, M = node_states.shape[0], self.__state_dimension, self._message_dimension
         gru = self.__state_update
         inputs = precision.resolve(node_states)
@@ -586,13 +591,20 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             if edge_inputs != torch.float32 and ops.edge_linear16_supported(H, M, len(weights), edge_inputs):
                 w16 = _scoped(self, ("edge_stack16", edge_inputs),
                               lambda: torch.stack([w.detach() for w in weights]).to(edge_inputs))
-            msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights, inputs=edge_inputs, rounded=w16)
+            rows = precision.message_rows(node_states, True)
+            if w16 is None or not ops.message_rows16_supported(node_states, M, rows):
+                rows = None         # a shape either end does not take: fp32 rows, silently
+            msgs, col = _edge_messages(node_states, adjacency_lists, plan, weights, inputs=edge_inputs, rounded=w16,
+                                       rows=rows)
             tb = 0
         else:
             w = self._stacked_edge_weights()
             w16 = _half_weights(self, "edge_w16", inputs, ops.HALF_KIND_LINEAR, H, w.shape[0],
                                 lambda: w.to(inputs).contiguous())
-            msgs, col, tb = ops.linear(node_states, w, inputs=inputs, rounded=w16), None, None      # [N, T*M]
+            rows = precision.message_rows(node_states, False)
+            if w16 is None or not ops.message_rows16_supported(node_states, M, rows):
+                rows = None         # a shape either end does not take: fp32 rows, silently
+            msgs, col, tb = ops.linear(node_states, w, inputs=inputs, rounded=w16, rows=rows), None, None      # [N, T*M]
         return ops.aggregate_gru(msgs, plan, M, self.__aggregation_fn, node_states, gru.weight_ih, gru.weight_hh,
                                  gru.bias_ih, gru.bias_hh, type_bits=tb, col=col,
                                  out=_take_output_hint(num_nodes, H, node_states), inputs=inputs,

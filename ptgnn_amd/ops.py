@@ -83,11 +83,14 @@ _ATTENTION_TRAIN16_FAMILY_FIRST = 896  # PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRS
 _PROJECTION_LOSS_FAMILY_FIRST = 960  # PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_: the copying decoder's score-free loss
 
 
+_ROWS16_FAMILY_FIRST = 1024  # PTGNN_AMD_KERNEL_ROWS16_FIRST_: the opt-in 16-bit message rows (producers + aggregation)
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
                   beam_finish: bool = False, attention16: bool = False, projection_loss: bool = False,
-                  attention16_training: bool = False, edge16_training: bool = False) -> dict:
+                  rows16: bool = False, attention16_training: bool = False, edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -106,7 +109,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `edge16_training=True`
     the 16-bit-input edge-form training launches (edge16_masked: the masked per-edge GEMM in its forward and
     input-gradient modes; edge_wgrad16: the per-type weight gradient); `projection_loss=True` the copying decoder's
-    score-free loss (projection_loss, projection_loss_backward)."""
+    score-free loss (projection_loss, projection_loss_backward); `rows16=True` the opt-in 16-bit message rows (agg16: the
+    aggregation over them; edge16_rows16, edge16_shared_rows16, linear_rows16: the producers that store them)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -119,7 +123,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_ATTENTION16_FAMILY_FIRST,) if attention16 else ()) \
             + ((_ATTENTION_TRAIN16_FAMILY_FIRST,) if attention16_training else ()) \
             + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()) \
-            + ((_PROJECTION_LOSS_FAMILY_FIRST,) if projection_loss else ()):
+            + ((_PROJECTION_LOSS_FAMILY_FIRST,) if projection_loss else ()) \
+            + ((_ROWS16_FAMILY_FIRST,) if rows16 else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -134,7 +139,7 @@ def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
                         edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
-                        attention16_training=True, edge16_training=True, projection_loss=True)
+                        attention16_training=True, edge16_training=True, projection_loss=True, rows16=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -586,14 +591,17 @@ def _edge16_stack(ws: Sequence[torch.Tensor], dtype: torch.dtype, given: Optiona
 
 
 def edge_linear_shared(x: torch.Tensor, uniq: UniqueMessages, weights: Sequence[torch.Tensor],
-                       act: Optional[str] = None, inputs=None, rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       act: Optional[str] = None, inputs=None, rounded: Optional[torch.Tensor] = None,
+                       rows=None) -> torch.Tensor:
     """msg[r] = act(W_t x[unique_src[r]]) over the message rows of `uniq` (GraphPlan.unique_messages): the grouped
     per-edge GEMM of `edge_linear` with one row per distinct (edge type, source) pair; rows beyond the table's count
     are not written.  The launch geometry comes from the device-resident table: no host synchronisation.
     `inputs` = torch.bfloat16 / torch.float16: the gathered rows and the weights are rounded to that type and multiplied
     on the 16-bit matrix cores (fp32 accumulation and output) where `edge_linear16_supported` takes the shape and x has
     16-byte aligned rows; otherwise the fp32 kernel runs, silently.  `rounded`: the caller's [T, M, H] stack of
-    `weight.to(inputs)`, to save the conversion."""
+    `weight.to(inputs)`, to save the conversion.  `rows` = the same 16-bit type: the messages are stored as 16-bit rows
+    of that type, `msg.to(rows)` bit for bit (ptgnn_amd_edge_shared_rows16_linear16; `gather_reduce` reads them); raises
+    where the 16-bit launch does not take the call."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
     x = _rowmajor(x)
@@ -606,22 +614,35 @@ def edge_linear_shared(x: torch.Tensor, uniq: UniqueMessages, weights: Sequence[
             raise _lib.PtgnnAmdError(f"edge_linear_shared: weight shape {tuple(w.shape)} does not match [{M}, {H}]")
     msg = torch.empty(uniq.capacity, M, dtype=torch.float32, device=x.device)
 
-    def rows():                       # resolved when the timer is summarised: the count is back by then
+    def rows_():                      # resolved when the timer is summarised: the count is back by then
         r = uniq.rows(wait=True)
         return float(r if r is not None else uniq.num_edges)
     half = _half_inputs(inputs)
+    if _half_rows(rows, half, "edge_linear_shared") is not None:
+        if not (edge_linear16_supported(H, M, T, half) and _half_rows_ok(x)):
+            raise _lib.PtgnnAmdError(f"edge_linear_shared: 16-bit message rows need a shape the 16-bit GEMM takes "
+                                     f"(state_dim={H}, msg_dim={M}, {T} edge types) and 16-byte aligned states")
+        w16 = _edge16_stack(ws, half, rounded)
+        msg = torch.empty(uniq.capacity, M, dtype=half, device=x.device)
+        with _timed("edge_linear16_shared_rows16", flops=lambda: 2.0 * rows_() * H * M,
+                    bytes=lambda: rows_() * (4.0 * H + 2.0 * M) + 2.0 * T * M * H + 8.0 * rows_()):
+            rc = lib.ptgnn_amd_edge_shared_rows16_linear16(x.data_ptr(), _ld(x), x.shape[0], H,
+                                                           uniq.edge_table.data_ptr(), w16.data_ptr(), T, M,
+                                                           ACT_IDS[act], HALF_IDS[half], msg.data_ptr(), M, _stream(msg))
+        _lib.check(rc, "ptgnn_amd_edge_shared_rows16_linear16")
+        return msg
     if half is not None and edge_linear16_supported(H, M, T, half) and _half_rows_ok(x):
         w16 = _edge16_stack(ws, half, rounded)
-        with _timed("edge_linear16_shared", flops=lambda: 2.0 * rows() * H * M,
-                    bytes=lambda: 4.0 * (rows() * H + rows() * M) + 2.0 * T * M * H + 8.0 * rows()):
+        with _timed("edge_linear16_shared", flops=lambda: 2.0 * rows_() * H * M,
+                    bytes=lambda: 4.0 * (rows_() * H + rows_() * M) + 2.0 * T * M * H + 8.0 * rows_()):
             rc = lib.ptgnn_amd_edge_linear16_shared(x.data_ptr(), _ld(x), x.shape[0], H, uniq.edge_table.data_ptr(),
                                                     w16.data_ptr(), T, M, ACT_IDS[act], HALF_IDS[half],
                                                     msg.data_ptr(), M, _stream(msg))
         _lib.check(rc, "ptgnn_amd_edge_linear16_shared")
         return msg
     wp = (ctypes.c_void_p * T)(*[w.data_ptr() for w in ws])
-    with _timed("edge_linear_shared", flops=lambda: 2.0 * rows() * H * M,
-                bytes=lambda: 4.0 * (rows() * H + rows() * M + T * M * H) + 8.0 * rows()):
+    with _timed("edge_linear_shared", flops=lambda: 2.0 * rows_() * H * M,
+                bytes=lambda: 4.0 * (rows_() * H + rows_() * M + T * M * H) + 8.0 * rows_()):
         rc = lib.ptgnn_amd_edge_linear_shared_f32(x.data_ptr(), _ld(x), x.shape[0], H, uniq.edge_table.data_ptr(),
                                                   ctypes.cast(wp, ctypes.c_void_p), T, M, ACT_IDS[act],
                                                   msg.data_ptr(), M, _stream(msg))
@@ -950,7 +971,12 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
                   rows: Optional[Tuple[int, int]] = None):
     """out[v] = EPI(reduce_{slots of v} ysrc[src, t*M:(t+1)*M] (+ ydst[v, t*M:(t+1)*M])).
     `out`: optional caller-owned [num_nodes, msg_dim] fp32 destination (e.g. one half of a stacked buffer).
-    `rows` = (lo, hi): only the destination rows [lo, hi) are computed and written (needs `out`, no arg)."""
+    `rows` = (lo, hi): only the destination rows [lo, hi) are computed and written (needs `out`, no arg).
+    A bfloat16 / float16 `ysrc` (the opt-in 16-bit message rows a producer stored with `rows=`) is up-cast in registers
+    and accumulated in fp32 by the kernel of its own (ptgnn_amd_gather_reduce16) where `gather_reduce16_supported` takes
+    the width, without `ydst`, arg or epilogue; anything else with 16-bit rows raises."""
+    if ysrc.dtype in HALF_IDS:
+        return _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, return_arg, type_bits, col, out, rows)
     lib = _lib.load()
     _require_cuda_f32("ysrc", ysrc)
     ysrc = _rowmajor(ysrc)
@@ -1004,6 +1030,62 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
             *hub, lo, hi, hdr.data_ptr() if hdr is not None else None, _stream(out))
     _lib.check(rc, "ptgnn_amd_gather_reduce_hdr_f32")
     return (out, arg) if return_arg else out
+
+
+def gather_reduce16_supported(msg_dim: int, dtype) -> bool:
+    """Whether the aggregation over 16-bit message rows takes the width (ptgnn_amd_gather_reduce16_supported; needs no
+    device): msg_dim % 32 == 0, msg_dim <= 256, bfloat16 / float16."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_gather_reduce16_supported(int(msg_dim), HALF_IDS[dtype]))
+
+
+def message_rows16_supported(x: torch.Tensor, msg_dim: int, dtype) -> bool:
+    """Whether a layer may ask its message producer for 16-bit rows of `dtype` (`rows=`) from the states `x`: the
+    aggregation takes the width and the 16-bit GEMMs' fragment loads can read x.  (The producer's own shape predicate --
+    `edge_linear16_supported` / `half_supported` -- is the caller's to check.)"""
+    return gather_reduce16_supported(msg_dim, dtype) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 \
+        and _half_rows_ok(_rowmajor(x))
+
+
+def _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, return_arg, type_bits, col, out, rows):
+    """`gather_reduce` over 16-bit rows: one launch of csrc/gather_reduce16.hip (rows beyond HUB_THRESHOLD in-edges are
+    folded by a whole workgroup inside it)."""
+    lib = _lib.load()
+    if not ysrc.is_cuda or ysrc.dim() != 2:
+        raise _lib.PtgnnAmdError(f"gather_reduce: 16-bit message rows must be a 2-D GPU tensor (got {tuple(ysrc.shape)} "
+                                 f"on {ysrc.device})")
+    if ydst is not None or epilogue != EPI_NONE or return_arg:
+        raise _lib.PtgnnAmdError("gather_reduce: 16-bit message rows take no destination term, no arg output and no "
+                                 "epilogue (those stay on float32 rows)")
+    if reduce not in REDUCE_IDS:
+        raise ValueError(f"unknown aggregation function {reduce!r}")
+    ysrc = _rowmajor(ysrc)
+    ld_y = _ld(ysrc)
+    if not gather_reduce16_supported(msg_dim, ysrc.dtype) or ysrc.data_ptr() % 16 != 0 or ld_y % 8 != 0:
+        raise _lib.PtgnnAmdError(f"gather_reduce: 16-bit message rows need msg_dim % 32 == 0, msg_dim <= 256 and 16-byte "
+                                 f"aligned rows (msg_dim={msg_dim}, row stride {ld_y})")
+    N = plan.num_nodes
+    if out is None:
+        if rows is not None:
+            raise _lib.PtgnnAmdError("gather_reduce: a row range needs a caller-owned `out` (the other rows are not "
+                                     "written)")
+        out = torch.empty(N, msg_dim, dtype=torch.float32, device=ysrc.device)
+    elif (tuple(out.shape) != (N, msg_dim) or out.dtype != torch.float32 or not out.is_contiguous()
+            or out.data_ptr() % 16 != 0):
+        raise _lib.PtgnnAmdError(f"gather_reduce: `out` must be a contiguous, 16-byte aligned float32 [{N}, {msg_dim}] "
+                                 "tensor")
+    plan.wait()
+    tb, colt = _slot_map(plan, type_bits, col)
+    lo, hi = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    # algorithmic bytes: per edge one 16-bit message row + its col entry; per node the fp32 output row + its rowptr entry
+    nbytes = (plan.num_edges * (2.0 * msg_dim + 4) + N * (4.0 * msg_dim + 4)) * ((hi - lo) / max(N, 1))
+    with _timed("gather_reduce16", bytes=nbytes):
+        rc = lib.ptgnn_amd_gather_reduce16(_ptr_or(ysrc, plan.rowptr), ld_y, HALF_IDS[ysrc.dtype], plan.rowptr.data_ptr(),
+                                           colt.data_ptr(), tb, N, msg_dim, REDUCE_IDS[reduce], out.data_ptr(), msg_dim,
+                                           plan.num_edges, HUB_THRESHOLD, lo, hi, _stream(out))
+    _lib.check(rc, "ptgnn_amd_gather_reduce16")
+    return out
 
 
 # The fused aggregation + node update serves minibatch-sized plans (every row folds serially: no hub launches)
@@ -1353,6 +1435,17 @@ def _half_inputs(inputs) -> Optional[torch.dtype]:
     return inputs
 
 
+def _half_rows(rows, half, what: str) -> Optional[torch.dtype]:
+    """The `rows=` keyword of the message producers (linear, edge_linear, edge_linear_shared): None and float32 mean
+    fp32 rows; a 16-bit type must be the type of `inputs=` (the rows are the rounded accumulators of that launch)."""
+    if rows is None or rows == torch.float32:
+        return None
+    if rows not in HALF_IDS or rows != half:
+        raise _lib.PtgnnAmdError(f"{what}: rows must be None, torch.float32 or the 16-bit type of `inputs` "
+                                 f"(got rows={rows!r}, inputs={half!r})")
+    return rows
+
+
 def _half_rows_ok(t: torch.Tensor) -> bool:
     """An fp32 operand the 16-bit kernels' fragment loads can read: 16-byte aligned rows."""
     return t.data_ptr() % 16 == 0 and _ld(t) % 4 == 0
@@ -1370,24 +1463,40 @@ def _rounded_weight(w: torch.Tensor, dtype: torch.dtype, given: Optional[torch.T
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
            act: Optional[str] = None, out: Optional[torch.Tensor] = None, inputs=None,
-           rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
+           rounded: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
     """y = act(x W^T + b) on fp32 MFMA.  weight is nn.Linear layout [n_out, k].
     `inputs` = torch.bfloat16 / torch.float16: x and the weight are rounded to that type and multiplied on the 16-bit
     matrix cores (fp32 accumulation and output) where `half_supported` takes the shape and x has 16-byte aligned rows;
-    otherwise the fp32 kernel runs, silently.  `rounded`: the caller's `weight.to(inputs)`, to save the conversion."""
+    otherwise the fp32 kernel runs, silently.  `rounded`: the caller's `weight.to(inputs)`, to save the conversion.
+    `rows` = the same 16-bit type: y is stored as 16-bit rows of that type, `y.to(rows)` bit for bit
+    (ptgnn_amd_linear_rows16: the GGNN message table in its half-width form; `gather_reduce` reads it); raises where the
+    16-bit launch does not take the call, and takes no `out`."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
     _require_cuda_f32("weight", weight)
     x, weight = _rowmajor(x), weight.contiguous()
-    rows, k = x.shape
+    n_rows, k = x.shape
     n_out = weight.shape[0]
     if weight.shape[1] != k:
         raise _lib.PtgnnAmdError(f"linear: x has {k} columns but weight expects {weight.shape[1]}")
+    half = _half_inputs(inputs)
+    if _half_rows(rows, half, "linear") is not None:
+        if out is not None or not (half_supported(HALF_KIND_LINEAR, k, n_out, half) and _half_rows_ok(x)):
+            raise _lib.PtgnnAmdError(f"linear: 16-bit rows need a shape the 16-bit Linear takes (k={k}, n_out={n_out}), "
+                                     "16-byte aligned x and no caller-owned `out`")
+        w16 = _rounded_weight(weight, half, rounded)
+        y16 = torch.empty(n_rows, n_out, dtype=half, device=x.device)
+        with _timed("linear_rows16", flops=2.0 * n_rows * k * n_out, bytes=n_rows * (4.0 * k + 2.0 * n_out) + 2.0 * n_out * k):
+            rc = lib.ptgnn_amd_linear_rows16(x.data_ptr(), n_rows, k, _ld(x), w16.data_ptr(), n_out,
+                                             bias.contiguous().data_ptr() if bias is not None else None, ACT_IDS[act],
+                                             HALF_IDS[half], y16.data_ptr(), n_out, _stream(y16))
+        _lib.check(rc, "ptgnn_amd_linear_rows16")
+        return y16
+    rows = n_rows
     if out is None:
         out = torch.empty(rows, n_out, dtype=torch.float32, device=x.device)
     if bias is not None:
         bias = bias.contiguous()
-    half = _half_inputs(inputs)
     if half is not None and half_supported(HALF_KIND_LINEAR, k, n_out, half) and _half_rows_ok(x):
         w16 = _rounded_weight(weight, half, rounded)
         with _timed("half_linear", flops=2.0 * rows * k * n_out, bytes=4.0 * rows * (k + n_out) + 2.0 * n_out * k):
@@ -1472,7 +1581,7 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
                 act: Optional[str] = None, dropout: Optional[Tuple[int, float, int]] = None,
                 mask_bits: Optional[torch.Tensor] = None,
                 edge_feats: Optional[Sequence[Optional[torch.Tensor]]] = None, inputs=None,
-                rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
+                rounded: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
     """msg[off_t + e] = act([x[src_t[e]] ; x[dst_t[e]] (if use_dst)] W_t^T) for every edge type in one
     launch; rows in type-major message order.  weights[t] is the type's nn.Linear weight.
     `edge_feats[t]` = [E_t, F] per-edge feature rows appended to the message input (weights [M, H (+H) + F];
@@ -1485,9 +1594,16 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     `dropout` AND `mask_bits` (no target half) the launch is ptgnn_amd_edge_masked_linear16 where
     `edge_linear16_masked_supported` takes the shape -- mode 1 rounds (keep ? x * scale : 0), mode 2 masks and scales the
     fp32 accumulator -- and the fp32 masked route otherwise, silently.  With edge features, with dropout but no
-    `mask_bits`, or with dropout and a target half, a 16-bit `inputs` raises, and with `use_dst` it wants GPU states."""
+    `mask_bits`, or with dropout and a target half, a 16-bit `inputs` raises, and with `use_dst` it wants GPU states.
+    `rows` = the same 16-bit type (no target half, no dropout, no edge features): the messages are stored as 16-bit
+    rows of that type, `msg.to(rows)` bit for bit (ptgnn_amd_edge_rows16_linear16; `gather_reduce` reads them); raises
+    where the 16-bit launch does not take the call."""
     half = _half_inputs(inputs)
     dropping = dropout is not None and dropout[0] != 0 and dropout[1] > 0.0
+    rows16 = _half_rows(rows, half, "edge_linear")
+    if rows16 is not None and (use_dst or dropping or
+                               (edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats))):
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit message rows take no target-state half, dropout or edge features")
     if half is not None and edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats):
         raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout nor edge features")
     if half is not None and dropping and (use_dst or mask_bits is None):
@@ -1519,6 +1635,18 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     PtrArr, CntArr = ctypes.c_void_p * T, ctypes.c_int64 * T
     sp = PtrArr(*[s.data_ptr() if s.numel() else None for s in srcs])
     cn = CntArr(*counts)
+    if rows16 is not None:
+        if not (edge_linear16_supported(H, M, T, half) and _half_rows_ok(x)):
+            raise _lib.PtgnnAmdError(f"edge_linear: 16-bit message rows need a shape the 16-bit GEMM takes "
+                                     f"(state_dim={H}, msg_dim={M}, {T} edge types) and 16-byte aligned states")
+        w16 = _edge16_stack(ws, half, rounded)
+        msg = torch.empty(max(E, 1), M, dtype=half, device=x.device)
+        with _timed("edge_linear16_rows16", flops=2.0 * E * H * M, bytes=E * (4.0 * H + 2.0 * M) + 2.0 * T * M * H + 8.0 * E):
+            rc = lib.ptgnn_amd_edge_rows16_linear16(x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),
+                                                    ctypes.cast(cn, ctypes.c_void_p), w16.data_ptr(), T, M, ACT_IDS[act],
+                                                    HALF_IDS[half], msg.data_ptr(), M, _stream(msg))
+        _lib.check(rc, "ptgnn_amd_edge_rows16_linear16")
+        return msg[:E] if E > 0 else msg[:0]
     if half is not None and use_dst and edge_linear16_dst_supported(H, M, T, half) and _half_rows_ok(x):
         w16 = _edge16_stack(ws, half, rounded)
         if any(d.numel() != c for d, c in zip(dsts, counts)):

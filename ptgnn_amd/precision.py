@@ -143,6 +143,28 @@ the probabilities under `attention=True` under those conditions too (the NORMALI
 the kernel rounds the unnormalised ones -- either way each probability carries one rounding of the 16-bit type);
 "autocast" never touches CPU tensors.
 
+The GGNN MESSAGE ROWS have a switch of their own -- a setting beside `set_matrix_inputs`, whose keyword list is closed.
+Under every setting above a message row leaves its GEMM as fp32 and the aggregation reads it as fp32; the reference's
+`enable_amp` produces the messages as 16-bit tensors and up-casts them only inside `_aggregate_messages`
+(abstractmessagepassing.py:43-50): one rounding of each message, then fp32 accumulation in the scatter.
+
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, edge_gemm=True), ptgnn_amd.half_messages():
+        out = model(batch)                                  # also ptgnn_amd.set_half_messages(True)
+
+With the switch the inference route of `GatedMessagePassingLayer` (`_forward_fused`) stores its messages as 16-bit rows
+of the dtype setting -- the table form's [N, T M] Linear under the plain dtype setting (ptgnn_amd_linear_rows16), the
+edge form's grouped per-edge GEMM under `edge_gemm=True` (both launch forms: csrc/edge_gemm16.hip, same bits per row) --
+each value exactly rnd(accumulator of the 16-bit launch), and aggregates them with csrc/gather_reduce16.hip: rows
+up-cast in registers, fp32 accumulation in CSR order, an fp32 aggregate for the GRU cell as before.  Half the bytes of
+every message row, written and read.  `message_rows(tensor, edge_form)` is what the layer reads.  The switch is off by
+default, untouched by `set_matrix_inputs` / `matrix_inputs`, independent of the five flags, and takes its dtype from the
+dtype setting ("autocast" included); with float32 it means fp32 rows.  Widths the aggregation does not take (message
+widths that are not multiples of 32 or beyond 256) or the 16-bit GEMM does not take keep fp32 rows, silently.  CPU
+tensors (torch_route.ggnn_layer) round the messages with torch under the switch, under the same inference-only
+conditions as the operands, so a checkpoint behaves alike on both devices.  Out of scope, fp32 rows under the switch:
+every training route; MLP-MP (its aggregation has a destination term and epilogues); EGC and PNA; `forward_sharded`; the
+edge-feature route; `_amp_forward`.
+
 The setting is process-wide (like `ops.set_gemm_mode`); the layers read it, `ptgnn_amd.ops` never does -- its
 `inputs=` keyword is explicit, because inside an autograd `Function.forward` grad mode is off and an op could not tell
 inference from training.
@@ -163,6 +185,7 @@ _mlp = False
 _attention = False
 _edge_training = False
 _attention_training = False
+_half_messages = False
 
 
 def _checked(v):
@@ -264,3 +287,34 @@ def attention_training_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the attention layer's training branch for a layer call on `tensor`: `resolve(tensor)` when
     `set_attention_training` is on and the tensor is on a GPU, else float32."""
     return resolve(tensor) if _attention_training and tensor.is_cuda else torch.float32
+
+
+def set_half_messages(on) -> bool:
+    """Whether the GGNN inference route stores its messages as 16-bit rows of the dtype setting and aggregates them with
+    the 16-bit-row kernel; returns the previous value.  A setting of its own: `set_matrix_inputs` / `matrix_inputs`
+    neither read nor reset it."""
+    global _half_messages
+    prev, _half_messages = _half_messages, bool(on)
+    return prev
+
+
+def get_half_messages() -> bool:
+    return _half_messages
+
+
+@contextlib.contextmanager
+def half_messages(on=True):
+    prev = set_half_messages(on)
+    try:
+        yield
+    finally:
+        set_half_messages(prev)
+
+
+def message_rows(tensor: torch.Tensor, edge_form: bool) -> torch.dtype:
+    """The dtype of the GGNN message rows for a layer call on `tensor`: with `set_half_messages` on, the dtype of the
+    GEMM that produces them -- `edge_gemm_inputs(tensor)` for the edge form, `resolve(tensor)` for the table form --
+    else float32."""
+    if not _half_messages:
+        return torch.float32
+    return edge_gemm_inputs(tensor) if edge_form else resolve(tensor)

@@ -341,13 +341,17 @@ def _rounded(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 
 def ggnn_layer(node_states, adjacency_lists, edge_features, edge_linears: Sequence[nn.Linear], dropout: nn.Module,
-               gru: nn.GRUCell, reduce: str, inputs: torch.dtype = torch.float32) -> torch.Tensor:
+               gru: nn.GRUCell, reduce: str, inputs: torch.dtype = torch.float32,
+               rows: torch.dtype = torch.float32) -> torch.Tensor:
     """gatedmessagepassing.py:46-69 on host tensors: per type W_t . Dropout([x_src ; f_e]), type-major messages,
     segment reduce onto the targets, GRUCell(aggregate, state).
     `inputs` = torch.bfloat16 / torch.float16 (the caller's matrix-input setting, inference only): the operands the GPU
     routes round are rounded here with torch and multiplied by the fp32 operators -- the message Linear's (without edge
     features: the GPU's table form; with them the per-edge GEMM stays fp32 there and here) and the GRU gate GEMMs', with
-    the unrounded state in the blend."""
+    the unrounded state in the blend.
+    `rows` = the same 16-bit type (the caller's `precision.half_messages` switch, under the same conditions): the messages
+    themselves are rounded once more before the fp32 scatter, as the GPU route stores them (not with edge features:
+    that route keeps fp32 rows on the GPU too)."""
     _host_only(node_states)
     if inputs == torch.float32:
         msgs = [lin(dropout(inp)) for inp, lin in
@@ -356,6 +360,8 @@ def ggnn_layer(node_states, adjacency_lists, edge_features, edge_linears: Sequen
         plain = all(f is None or f.shape[-1] == 0 for f in edge_features)
         msgs = [nn.functional.linear(_rounded(inp, inputs), _rounded(lin.weight, inputs)) if plain else lin(inp)
                 for inp, lin in zip(_message_inputs(node_states, adjacency_lists, edge_features, False), edge_linears)]
+        if rows != torch.float32 and plain:
+            msgs = [_rounded(m, rows) for m in msgs]
     targets = torch.cat([d for _, d in adjacency_lists])
     agg = aggregate(torch.cat(msgs, dim=0), targets, node_states.shape[0], reduce)
     if inputs == torch.float32:
