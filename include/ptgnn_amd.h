@@ -260,6 +260,8 @@ enum {
   PTGNN_AMD_KERNEL_EDGE16_ROWS16,                          /* ptgnn_amd_edge_rows16_linear16 */
   PTGNN_AMD_KERNEL_EDGE16_SHARED_ROWS16,                   /* ptgnn_amd_edge_shared_rows16_linear16 */
   PTGNN_AMD_KERNEL_LINEAR_ROWS16,                          /* ptgnn_amd_linear_rows16 */
+  PTGNN_AMD_KERNEL_AGG16_EPI,                              /* ptgnn_amd_gather_reduce16_epi */
+  PTGNN_AMD_KERNEL_EDGE16_DST_ROWS16,                      /* ptgnn_amd_edge_rows16_dst_linear16 */
   PTGNN_AMD_KERNEL_ROWS16_END_
 };
 int64_t ptgnn_amd_launch_count(int kernel_id);
@@ -1804,6 +1806,50 @@ int ptgnn_amd_edge_shared_rows16_linear16(const float *x, int64_t ld_x, int64_t 
                                           int act, int dtype, void *msg16, int64_t ld_msg, void *stream);
 int ptgnn_amd_linear_rows16(const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w, int32_t n_out,
                             const float *bias /* nullable */, int act, int dtype, void *y16, int64_t ld_y, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit MLP-MP MESSAGE ROWS: the aggregation with a destination term and a GELU / LayerNorm finish over 16-bit
+ * rows (csrc/gather_reduce16_epi.hip) and the per-edge GEMM over [x[src] | x[dst]] that stores 16-bit rows
+ * (csrc/edge_gemm16.hip, template flags DST + ROWS16).
+ *
+ * Replaces: the message tensors of mlpmessagepassing.py:88-98 as an `enable_amp` user of the reference gets them (the
+ *   edge MLPs run under autocast, trainer.py:205,221: their OUTPUT is a 16-bit tensor), the up-cast of
+ *   abstractmessagepassing.py:43-50 inside `_aggregate_messages`, and what follows it in mlpmessagepassing.py:107-117
+ *   (message activation, LayerNorm) as the fp32 entry ptgnn_amd_gather_reduce_f32 folds them into its epilogue.  OFF by
+ *   default: the host's ptgnn_amd.precision.set_half_messages(True, mlp=True) asks for it.
+ *
+ * ptgnn_amd_gather_reduce16_epi:  out[v, :] = EPI( reduce over the CSR slots i of row v, row_begin <= v < row_end, of
+ *       float(rows16[col[i] >> type_bits, t_i * msg_dim : + msg_dim]) + float(dst16[v, t_i * msg_dim : + msg_dim]) )
+ *   t_i = col[i] & ((1 << type_bits) - 1).  Everything ptgnn_amd_gather_reduce16 says about rows16, the slot map, the
+ *   reduce, the row range, `hub_threshold` and `num_edges` holds.  dst16 (nullable: no destination term) is a 16-bit
+ *   [num_nodes, T * msg_dim] table of the same dtype with leading dimension ld_dst (elements): one IEEE fp32 addition
+ *   per value and slot BEFORE the fold, so max / min are max_i (fp32(a_i) + fp32(b_i)) exactly and the sums of rows up
+ *   to `hub_threshold` in-edges the serial fp32 fold of those sums in CSR order.  `epilogue` = PTGNN_AMD_EPI_* flags, as
+ *   ptgnn_amd_gather_reduce_f32 takes them, with ln_gamma / ln_beta [msg_dim] (needed with PTGNN_AMD_EPI_LAYERNORM) and
+ *   ln_eps: after the mean and the empty-row rule (max / min: 0) erf-GELU per value, then the affine LayerNorm over the
+ *   row in the fp32 entry's order of operations (mean, centred sum of squares, 1 / sqrt(var + eps), * gamma + beta), all
+ *   fp32; an empty row still runs it (LayerNorm(0) = beta).  fp32 out [num_nodes, msg_dim] (ld_out).
+ *   Shapes: ptgnn_amd_gather_reduce16_supported(msg_dim, dtype).  rows16, dst16, out, ln_gamma and ln_beta must be
+ *   16-byte aligned with ld_rows % 8 == 0, ld_dst % 8 == 0, ld_out % 4 == 0 (PTGNN_AMD_EUNSUPPORTED otherwise); bad sizes
+ *   / enums / null pointers answer PTGNN_AMD_EINVAL; all with a message that starts "gather_reduce16_epi:" and before
+ *   anything touches the device.
+ *
+ * ptgnn_amd_edge_rows16_dst_linear16:  ptgnn_amd_edge_dst_linear16 with a 16-bit output -- same arguments, same kernels,
+ *   same accumulators, msg16[r, c] = rnd(act(accumulator[r, c])), i.e. exactly `fp32 entry(...).to(dtype)`; msg16 as
+ *   ptgnn_amd_edge_rows16_linear16 takes it.  Shapes: ptgnn_amd_edge_dst_linear16_supported.  Messages start
+ *   "edge_linear16: rows16: dst:".  (The name keeps the closed ptgnn_amd_edge_dst_* pair closed.)
+ * Additive: the ABI version stays.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_gather_reduce16_epi(const void *rows16, int64_t ld_rows, const void *dst16 /* nullable */, int64_t ld_dst,
+                                  int dtype, const int32_t *rowptr, const int32_t *col, int32_t type_bits,
+                                  int64_t num_nodes, int32_t msg_dim, int reduce, int epilogue,
+                                  const float *ln_gamma /* nullable */, const float *ln_beta /* nullable */, float ln_eps,
+                                  float *out, int64_t ld_out, int64_t num_edges, int32_t hub_threshold, int64_t row_begin,
+                                  int64_t row_end, void *stream);
+int ptgnn_amd_edge_rows16_dst_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                       const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
+                                       const int64_t *edges_per_type, const void *w, int32_t num_types, int32_t msg_dim,
+                                       int act, int dtype, void *msg16, int64_t ld_msg, void *stream);
 
 #pragma GCC visibility pop
 

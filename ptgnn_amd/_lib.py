@@ -230,6 +230,11 @@ SIGNATURES = {
     "ptgnn_amd_edge_shared_rows16_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
                                                          _vp, _i64, _vp]),
     "ptgnn_amd_linear_rows16": (_c.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _c.c_int, _c.c_int, _vp, _i64, _vp]),
+    # ... and their MLP-MP forms (csrc/gather_reduce16_epi.hip; the target-state half of csrc/edge_gemm16.hip)
+    "ptgnn_amd_gather_reduce16_epi": (_c.c_int, [_vp, _i64, _vp, _i64, _c.c_int, _vp, _vp, _i32, _i64, _i32, _c.c_int,
+                                                 _c.c_int, _vp, _vp, _c.c_float, _vp, _i64, _i64, _i32, _i64, _i64, _vp]),
+    "ptgnn_amd_edge_rows16_dst_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _c.c_int,
+                                                      _c.c_int, _vp, _i64, _vp]),
     "ptgnn_amd_edge_dst_linear16_supported": (_c.c_int, [_i32, _i32, _i32, _c.c_int]),
     "ptgnn_amd_edge_dst_linear16": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _c.c_int, _c.c_int,
                                                _vp, _i64, _vp]),

@@ -9,6 +9,7 @@
 //   ptgnn_amd_edge_linear16        : one row per edge in type-major order, from host arrays of per-type `src` pointers
 // and, for the MLP-MP layer's message Linear (mlpmessagepassing.py:88-98), the per-edge form WITH a target-state half,
 //   ptgnn_amd_edge_dst_linear16    : msg[r, :] = act( rnd(X[src[r]]) . rnd(W_t[:, :H])^T + rnd(X[dst[r]]) . rnd(W_t[:, H:])^T )
+//   ptgnn_amd_edge_rows16_dst_linear16 : the same launch storing rnd(accumulator) as 16-bit message rows (flag ROWS16)
 // and, for the GGNN layer's edge-form TRAINING step (gatedmessagepassing.py:57-61 with its per-edge dropout),
 //   ptgnn_amd_edge_masked_linear16 : the per-edge form with the dropout mask from its keep bits (template flag MASK) --
 //                                    1: on the gathered input before it is rounded (the forward); 2: on the fp32
@@ -144,8 +145,9 @@ __device__ __forceinline__ void wave_tile_masked(const float *__restrict__ arow,
 // MASK (both kernels; per-edge form without a target half, no activation): the per-edge dropout of the training step from
 // its keep bits.  1: on the gathered input, before it is rounded (the forward); 2: on the fp32 accumulator, before the
 // store (the input gradient).  0: no mask -- the code of the unmasked instantiations is what it was.
-// ROWS16 (both kernels; unmasked, no target half): the accumulators are those of the fp32-output launch and leave rounded
-// to the operand type as 16-bit message rows -- the bits of `msg.to(dtype)`, whichever kernel and launch form ran.
+// ROWS16 (both kernels; unmasked, with or without a target half): the accumulators are those of the fp32-output launch and
+// leave rounded to the operand type as 16-bit message rows -- the bits of `msg.to(dtype)`, whichever kernel and launch
+// form ran.
 template <int DT, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
 __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   const StreamEdgeTable *tabp;
@@ -377,7 +379,7 @@ int ws_resident_per_cu() {
 // DST: the chain is 2 H long, so the weight-stationary register budgets (KS = 8, 16) hold H in {64, 128}
 template <bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
 int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
-  static_assert(!ROWS16 || (!DST && MASK == 0), "16-bit message rows: the unmasked forms without a target half");
+  static_assert(!ROWS16 || MASK == 0, "16-bit message rows: the unmasked forms");
   const int64_t cus = num_compute_units();
   const int k = DST ? 2 * p.H : p.H;
   const bool ws = (k == 128 || k == 256 || (!DST && k == 64)) && p.M <= 128 &&
@@ -402,7 +404,8 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
   }
   PTGNN_LAUNCH_CHECK();
   if (ROWS16) {
-    count_launch(INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED_ROWS16 : PTGNN_AMD_KERNEL_EDGE16_ROWS16);
+    count_launch(DST ? PTGNN_AMD_KERNEL_EDGE16_DST_ROWS16
+                     : (INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED_ROWS16 : PTGNN_AMD_KERNEL_EDGE16_ROWS16));
     return PTGNN_AMD_OK;
   }
   count_launch(MASK ? PTGNN_AMD_KERNEL_EDGE16_MASKED
@@ -531,6 +534,26 @@ extern "C" int ptgnn_amd_edge_rows16_linear16(const float *x, int64_t ld_x, int6
   p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
   p.H = state_dim; p.M = msg_dim; p.act = act; p.msg16 = static_cast<uint16_t *>(msg16); p.ld_msg = ld_msg;
   return launch<false, false, 0, true>(p, dtype, units, (hipStream_t)stream_);
+}
+
+extern "C" int ptgnn_amd_edge_rows16_dst_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                                  const int64_t *const *src_per_type,
+                                                  const int64_t *const *dst_per_type, const int64_t *edges_per_type,
+                                                  const void *w, int32_t num_types, int32_t msg_dim, int act, int dtype,
+                                                  void *msg16, int64_t ld_msg, void *stream_) {
+  if (const int rc = check_shape(" rows16: dst:", state_dim, num_types, msg_dim, act, dtype)) return rc;
+  Edge16Args p{};
+  int64_t units = 0;
+  if (const int rc = host_table(" rows16: dst:", src_per_type, dst_per_type, edges_per_type, num_types, true, p.tab, units))
+    return rc;
+  if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
+  if (const int rc = check_operands(" rows16: dst:", x, ld_x, num_rows, state_dim, w, msg_dim,
+                                    static_cast<const float *>(msg16), ld_msg))
+    return rc;
+  if (const int rc = check_rows16(msg16, ld_msg)) return rc;
+  p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = act; p.msg16 = static_cast<uint16_t *>(msg16); p.ld_msg = ld_msg;
+  return launch<false, true, 0, true>(p, dtype, units, (hipStream_t)stream_);
 }
 
 extern "C" int ptgnn_amd_edge_shared_rows16_linear16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,

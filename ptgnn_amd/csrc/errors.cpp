@@ -171,7 +171,7 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
   if (kernel_id >= PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PROJECTION_LOSS_END_)
     return projection_loss_names[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_];
   static const char *const rows16_names[PTGNN_AMD_KERNEL_ROWS16_END_ - PTGNN_AMD_KERNEL_ROWS16_FIRST_] = {
-      "agg16", "edge16_rows16", "edge16_shared_rows16", "linear_rows16"};
+      "agg16", "edge16_rows16", "edge16_shared_rows16", "linear_rows16", "agg16_epi", "edge16_dst_rows16"};
   if (kernel_id >= PTGNN_AMD_KERNEL_ROWS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ROWS16_END_)
     return rows16_names[kernel_id - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;

@@ -23,10 +23,12 @@
 //     the q-th contiguous run of the row's slots, the partials meet in LDS and group 0 folds them in run order.  One
 //     launch, fixed order: deterministic, and for max / min the earliest slot still wins a tie of zeros.  The fold
 //     ORDER of a hub row's sum differs from the serial order (fp32 rounding only), as the fp32 hub rows' does.
-// No destination term, no arg output, no epilogue, no mask: those stay on the fp32 rows.
+// No destination term, no arg output, no epilogue, no mask here: the destination term and the GELU / LayerNorm finish
+// of the MLP-MP layer are gather_reduce16_epi.hip (same mapping); arg and mask stay on the fp32 rows.
 #include <float.h>
 
 #include "common.h"
+#include "gather_reduce16.h"
 
 namespace ptgnn_amd {
 namespace {
@@ -44,23 +46,6 @@ struct Args16 {
   float *out;
   int64_t ld_out;
 };
-
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-// the two 16-bit values of a dword as fp32: element 0 is the low half
-template <int DT>
-__device__ __forceinline__ void widen2(uint32_t w, float &lo, float &hi) {
-  if constexpr (DT == PTGNN_AMD_HALF_BF16) {
-    lo = __uint_as_float(w << 16);
-    hi = __uint_as_float(w & 0xffff0000u);
-  } else {
-    const f32x2 f = __builtin_convertvector(__builtin_bit_cast(f16x2, w), f32x2);
-    lo = f[0];
-    hi = f[1];
-  }
-}
 
 // One lane's share (8 columns from `colx`) of one destination row, or of one run of a hub row.
 template <int DT, int REDUCE>
@@ -197,9 +182,6 @@ __global__ __launch_bounds__(256) void k_gather_reduce16(Args16 a) {
     __syncthreads();                      // group 0 is done with `part` before the next long row fills it
   }
 }
-
-bool shape_ok16(int32_t msg_dim) { return msg_dim > 0 && msg_dim % 32 == 0 && msg_dim <= 256; }
-bool dtype_ok16(int dtype) { return dtype == PTGNN_AMD_HALF_BF16 || dtype == PTGNN_AMD_HALF_F16; }
 
 template <int DT, int LPR>
 void launch_reduce(const Args16 &a0, int reduce, hipStream_t st) {

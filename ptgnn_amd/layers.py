@@ -1158,11 +1158,7 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
             from ptgnn_amd import sharded
             shard, work, table_of = two_block
             agg = sharded.aggregate_two_blocks(shard, work, table_of, M, self.__aggregation_fn, ydst=ydst, **epi)
-        elif (epi and ydst is None and self._dense is not None
-              and (self._dense_act is None or _kernel_act(self._dense_act) is not None)
-              and not (self.training and getattr(self._dropout, "p", 0.0) > 0)
-              and _no_grad_needed(ysrc, *self._dense.parameters())
-              and ops.gather_update_supported(M, self._dense.out_features, plan)):
+        elif ydst is None and ysrc.dtype == torch.float32 and self._one_launch_update_ok(epi, ysrc, plan):
             # hidden 64 (the README's default architecture, BASELINE config 4), edge form: aggregation, GELU, LayerNorm,
             # Linear and Tanh in ONE launch -- the [N, M] aggregate never exists in memory (gather_reduce.hip)
             # (the fused launch stores 16-byte vectors: a hint whose rows are not 16-byte aligned -- the right half of a
@@ -1176,6 +1172,32 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         else:
             agg = ops.gather_reduce(ysrc, plan, M, self.__aggregation_fn, ydst=ydst, col=col, type_bits=type_bits, **epi)
         return self._update(agg, bool(epi))
+
+    def _one_launch_update_ok(self, epi: dict, like: torch.Tensor, plan) -> bool:
+        """Whether an aggregation without a destination term runs as `ops.gather_update` (aggregation, epilogue, dense
+        update and its activation in one launch; fp32 message rows)."""
+        return bool(epi and self._dense is not None
+                    and (self._dense_act is None or _kernel_act(self._dense_act) is not None)
+                    and not (self.training and getattr(self._dropout, "p", 0.0) > 0)
+                    and _no_grad_needed(like, *self._dense.parameters())
+                    and ops.gather_update_supported(self._message_dimension, self._dense.out_features, plan))
+
+    def _message_rows(self, node_states, plan, num_types: int, edge_form: bool):
+        """The 16-bit type `_forward_fused` asks its message producer for under `precision.half_messages(mlp=True)`, or
+        None for fp32 rows -- decided before the producer is launched: both ends must take the call (the 16-bit GEMM of
+        the form its shape, the aggregation over 16-bit rows the width and the stock activation / LayerNorm as its
+        epilogue), and the one-launch `ops.gather_update` route keeps its fp32 rows where it applies."""
+        rows = precision.mlp_message_rows(node_states)
+        if rows == torch.float32:
+            return None
+        M, use_dst = self._message_dimension, self.__use_target_state_as_message_input
+        epi = self._epilogue(M, 512, cap_without_ln=False)
+        if not epi or ((edge_form or not use_dst) and self._one_launch_update_ok(epi, node_states, plan)):
+            return None
+        if not ops.mlp_message_rows16_supported(node_states, M, rows, self.__input_state_dim, num_types, edge_form,
+                                                use_dst):
+            return None
+        return rows
 
     def _aggregate_edge_messages(self, messages, plan, inference: bool) -> torch.Tensor:
         """Aggregation + update over [E, M] messages in type-major order: the fused launches in inference (reduce set of
@@ -1301,11 +1323,13 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         assert len(adjacency_lists) == len(self.__edge_message_transformation_layers), \
             "The number of adjacency lists must be equal to the number of edge types."
         if _on_host(node_states):
+            inputs = self._host_matrix_inputs(node_states, edge_features)
+            # the message rows follow `half_messages(mlp=True)` where the GPU routes' do: string aggregations only
+            rows = inputs if precision.get_half_messages_mlp() and isinstance(self.__aggregation_fn, str) else torch.float32
             return torch_route.mlp_layer(node_states, adjacency_lists, edge_features,
                                          list(self.__edge_message_transformation_layers),
                                          self.__use_target_state_as_message_input, self.__aggregation_fn,
-                                         self.__message_activation, self.__state_update,
-                                         inputs=self._host_matrix_inputs(node_states, edge_features))
+                                         self.__message_activation, self.__state_update, inputs=inputs, rows=rows)
         if node_states.dtype in _AMP_DTYPES:
             return _amp_forward(self, node_states, adjacency_lists, edge_features)
 
@@ -1340,26 +1364,28 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         N, T = node_states.shape[0], len(adjacency_lists)
         plan = ops.plan_for(adjacency_lists, N)
         if _prefer_edge_path(plan.num_edges, N, T, self.__input_state_dim, self._message_dimension):
-            msgs = self._edge_form_messages(node_states, adjacency_lists)
+            msgs = self._edge_form_messages(node_states, adjacency_lists, rows=self._message_rows(node_states, plan, T, True))
             return self._aggregate_and_update(msgs, None, plan, col=plan.perm, type_bits=0)
-        ysrc, ydst = self._table_halves(self._message_table(node_states), T)
+        table = self._message_table(node_states, rows=self._message_rows(node_states, plan, T, False))
+        ysrc, ydst = self._table_halves(table, T)
         return self._aggregate_and_update(ysrc, ydst, plan)
 
-    def _message_table(self, node_states) -> torch.Tensor:
+    def _message_table(self, node_states, rows=None) -> torch.Tensor:
         """Inference, table form: [N, (1|2) T M] = X [W^s_0; ...; W^d_0; ...]^T.  Under a 16-bit matrix-input setting made
         with `mlp=True` (ptgnn_amd/precision.py) the states and the stacked weights are rounded and multiplied on the
-        16-bit matrix cores, as the GGNN table form does; widths the kernel declines run fp32."""
+        16-bit matrix cores, as the GGNN table form does; widths the kernel declines run fp32.  `rows` (`_message_rows`):
+        the table leaves that launch as 16-bit rows."""
         w = self._stacked_edge_weights()
         inputs = precision.mlp_inputs(node_states)
         w16 = _half_weights(self, "mlp_table_w16", inputs, ops.HALF_KIND_LINEAR, self.__input_state_dim, w.shape[0],
                             lambda: w.to(inputs).contiguous())
-        return ops.linear(node_states, w, inputs=inputs, rounded=w16)
+        return ops.linear(node_states, w, inputs=inputs, rounded=w16, rows=rows)
 
-    def _edge_form_messages(self, node_states, adjacency_lists) -> torch.Tensor:
+    def _edge_form_messages(self, node_states, adjacency_lists, rows=None) -> torch.Tensor:
         """Inference, edge form: the grouped per-edge GEMM over [x[src] | x[dst]] (or x[src] alone), one row per edge in
         type-major order.  Under `mlp=True` it takes the 16-bit launch (ptgnn_amd_edge_dst_linear16, or
         ptgnn_amd_edge_linear16 without a target-state half) on a [T, M, (1|2) H] stack rounded once per forward scope;
-        shapes the launch declines run fp32."""
+        shapes the launch declines run fp32.  `rows` (`_message_rows`): the messages leave that launch as 16-bit rows."""
         ws = self._first_weights()
         use_dst = self.__use_target_state_as_message_input
         H, M, T = self.__input_state_dim, self._message_dimension, len(ws)
@@ -1368,7 +1394,7 @@ class MlpMessagePassingLayer(AbstractMessagePassingLayer):
         if inputs != torch.float32 and (ops.edge_linear16_dst_supported if use_dst
                                         else ops.edge_linear16_supported)(H, M, T, inputs):
             w16 = _scoped(self, ("mlp_edge_stack16", inputs), lambda: torch.stack([w.detach() for w in ws]).to(inputs))
-        return ops.edge_linear(node_states, adjacency_lists, ws, use_dst, inputs=inputs, rounded=w16)
+        return ops.edge_linear(node_states, adjacency_lists, ws, use_dst, inputs=inputs, rounded=w16, rows=rows)
 
     def _host_matrix_inputs(self, node_states, edge_features):
         """The `mlp=True` matrix-input setting as the CPU route applies it: fp32 states, inference only (as on the GPU),

@@ -110,7 +110,9 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     the 16-bit-input edge-form training launches (edge16_masked: the masked per-edge GEMM in its forward and
     input-gradient modes; edge_wgrad16: the per-type weight gradient); `projection_loss=True` the copying decoder's
     score-free loss (projection_loss, projection_loss_backward); `rows16=True` the opt-in 16-bit message rows (agg16: the
-    aggregation over them; edge16_rows16, edge16_shared_rows16, linear_rows16: the producers that store them)."""
+    aggregation over them; edge16_rows16, edge16_shared_rows16, linear_rows16: the producers that store them; agg16_epi:
+    the MLP-MP aggregation with a destination term and / or an epilogue; edge16_dst_rows16: the per-edge GEMM with a
+    target-state half storing them)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -974,9 +976,12 @@ def gather_reduce(ysrc: torch.Tensor, plan: GraphPlan, msg_dim: int, reduce: str
     `rows` = (lo, hi): only the destination rows [lo, hi) are computed and written (needs `out`, no arg).
     A bfloat16 / float16 `ysrc` (the opt-in 16-bit message rows a producer stored with `rows=`) is up-cast in registers
     and accumulated in fp32 by the kernel of its own (ptgnn_amd_gather_reduce16) where `gather_reduce16_supported` takes
-    the width, without `ydst`, arg or epilogue; anything else with 16-bit rows raises."""
-    if ysrc.dtype in HALF_IDS:
-        return _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, return_arg, type_bits, col, out, rows)
+    the width; with a 16-bit `ydst` of the same dtype and / or an epilogue by its MLP-MP form
+    (ptgnn_amd_gather_reduce16_epi: the destination term added per slot in fp32, GELU / LayerNorm in fp32).  16-bit rows
+    with an arg output, a width outside the kernel's, or one half 16-bit and the other float32, raise."""
+    if ysrc.dtype in HALF_IDS or (ydst is not None and ydst.dtype in HALF_IDS):
+        return _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, ln_weight, ln_bias, ln_eps, return_arg,
+                                type_bits, col, out, rows)
     lib = _lib.load()
     _require_cuda_f32("ysrc", ysrc)
     ysrc = _rowmajor(ysrc)
@@ -1048,21 +1053,43 @@ def message_rows16_supported(x: torch.Tensor, msg_dim: int, dtype) -> bool:
         and _half_rows_ok(_rowmajor(x))
 
 
-def _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, return_arg, type_bits, col, out, rows):
-    """`gather_reduce` over 16-bit rows: one launch of csrc/gather_reduce16.hip (rows beyond HUB_THRESHOLD in-edges are
-    folded by a whole workgroup inside it)."""
+def mlp_message_rows16_supported(x: torch.Tensor, msg_dim: int, dtype, state_dim: int, num_types: int,
+                                 edge_form: bool, use_dst: bool) -> bool:
+    """Whether the MLP-MP layer may ask its message producer for 16-bit rows of `dtype` from the states `x`, decided
+    before the producer is launched: `message_rows16_supported`, and the 16-bit GEMM of the form takes the shape -- the
+    [N, (1|2) T M] table Linear (`half_supported`) or the grouped per-edge GEMM with / without a target-state half.  The
+    table's halves start at column T M of 16-bit rows: 16-byte aligned because M % 32 == 0."""
+    if not message_rows16_supported(x, msg_dim, dtype):
+        return False
+    if not edge_form:
+        return half_supported(HALF_KIND_LINEAR, state_dim, (2 if use_dst else 1) * num_types * msg_dim, dtype)
+    return (edge_linear16_dst_supported if use_dst else edge_linear16_supported)(state_dim, msg_dim, num_types, dtype)
+
+
+def _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, ln_weight, ln_bias, ln_eps, return_arg, type_bits, col,
+                     out, rows):
+    """`gather_reduce` over 16-bit rows: one launch of csrc/gather_reduce16.hip, or with a destination term and / or an
+    epilogue of csrc/gather_reduce16_epi.hip (rows beyond HUB_THRESHOLD in-edges are folded by a whole workgroup inside
+    either)."""
     lib = _lib.load()
-    if not ysrc.is_cuda or ysrc.dim() != 2:
+    if ysrc.dtype not in HALF_IDS or (ydst is not None and ydst.dtype != ysrc.dtype):
+        raise _lib.PtgnnAmdError(f"gather_reduce: 16-bit message rows need both halves in the same 16-bit type (got "
+                                 f"{ysrc.dtype} and {ydst.dtype})")
+    if not ysrc.is_cuda or ysrc.dim() != 2 or (ydst is not None and (not ydst.is_cuda or ydst.dim() != 2)):
         raise _lib.PtgnnAmdError(f"gather_reduce: 16-bit message rows must be a 2-D GPU tensor (got {tuple(ysrc.shape)} "
                                  f"on {ysrc.device})")
-    if ydst is not None or epilogue != EPI_NONE or return_arg:
-        raise _lib.PtgnnAmdError("gather_reduce: 16-bit message rows take no destination term, no arg output and no "
-                                 "epilogue (those stay on float32 rows)")
+    if return_arg:
+        raise _lib.PtgnnAmdError("gather_reduce: 16-bit message rows take no arg output (that stays on float32 rows)")
     if reduce not in REDUCE_IDS:
         raise ValueError(f"unknown aggregation function {reduce!r}")
     ysrc = _rowmajor(ysrc)
     ld_y = _ld(ysrc)
-    if not gather_reduce16_supported(msg_dim, ysrc.dtype) or ysrc.data_ptr() % 16 != 0 or ld_y % 8 != 0:
+    ld_yd = 0
+    if ydst is not None:
+        ydst = _rowmajor(ydst)
+        ld_yd = _ld(ydst)
+    if (not gather_reduce16_supported(msg_dim, ysrc.dtype) or ysrc.data_ptr() % 16 != 0 or ld_y % 8 != 0
+            or (ydst is not None and (ydst.data_ptr() % 16 != 0 or ld_yd % 8 != 0))):
         raise _lib.PtgnnAmdError(f"gather_reduce: 16-bit message rows need msg_dim % 32 == 0, msg_dim <= 256 and 16-byte "
                                  f"aligned rows (msg_dim={msg_dim}, row stride {ld_y})")
     N = plan.num_nodes
@@ -1080,6 +1107,21 @@ def _gather_reduce16(ysrc, plan, msg_dim, reduce, ydst, epilogue, return_arg, ty
     lo, hi = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
     # algorithmic bytes: per edge one 16-bit message row + its col entry; per node the fp32 output row + its rowptr entry
     nbytes = (plan.num_edges * (2.0 * msg_dim + 4) + N * (4.0 * msg_dim + 4)) * ((hi - lo) / max(N, 1))
+    if ydst is not None or epilogue != EPI_NONE:
+        if epilogue & EPI_LAYERNORM:      # the kernel reads gamma / beta as 16-byte vectors
+            ln_weight, ln_bias = (t.detach().contiguous() for t in (ln_weight, ln_bias))
+            ln_weight, ln_bias = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (ln_weight, ln_bias))
+        if ydst is not None:              # the destination-term row of every node, once (its T blocks are cache hits)
+            nbytes += N * 2.0 * ydst.shape[1] * ((hi - lo) / max(N, 1))
+        with _timed("gather_reduce16_epi", bytes=nbytes):
+            rc = lib.ptgnn_amd_gather_reduce16_epi(
+                _ptr_or(ysrc, plan.rowptr), ld_y, ydst.data_ptr() if ydst is not None else None, ld_yd,
+                HALF_IDS[ysrc.dtype], plan.rowptr.data_ptr(), colt.data_ptr(), tb, N, msg_dim, REDUCE_IDS[reduce],
+                int(epilogue), ln_weight.data_ptr() if epilogue & EPI_LAYERNORM else None,
+                ln_bias.data_ptr() if epilogue & EPI_LAYERNORM else None, float(ln_eps), out.data_ptr(), msg_dim,
+                plan.num_edges, HUB_THRESHOLD, lo, hi, _stream(out))
+        _lib.check(rc, "ptgnn_amd_gather_reduce16_epi")
+        return out
     with _timed("gather_reduce16", bytes=nbytes):
         rc = lib.ptgnn_amd_gather_reduce16(_ptr_or(ysrc, plan.rowptr), ld_y, HALF_IDS[ysrc.dtype], plan.rowptr.data_ptr(),
                                            colt.data_ptr(), tb, N, msg_dim, REDUCE_IDS[reduce], out.data_ptr(), msg_dim,
@@ -1595,15 +1637,15 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     `edge_linear16_masked_supported` takes the shape -- mode 1 rounds (keep ? x * scale : 0), mode 2 masks and scales the
     fp32 accumulator -- and the fp32 masked route otherwise, silently.  With edge features, with dropout but no
     `mask_bits`, or with dropout and a target half, a 16-bit `inputs` raises, and with `use_dst` it wants GPU states.
-    `rows` = the same 16-bit type (no target half, no dropout, no edge features): the messages are stored as 16-bit
-    rows of that type, `msg.to(rows)` bit for bit (ptgnn_amd_edge_rows16_linear16; `gather_reduce` reads them); raises
-    where the 16-bit launch does not take the call."""
+    `rows` = the same 16-bit type (no dropout, no edge features): the messages are stored as 16-bit rows of that type,
+    `msg.to(rows)` bit for bit (ptgnn_amd_edge_rows16_linear16, with `use_dst` ptgnn_amd_edge_rows16_dst_linear16;
+    `gather_reduce` reads them); raises where the 16-bit launch does not take the call."""
     half = _half_inputs(inputs)
     dropping = dropout is not None and dropout[0] != 0 and dropout[1] > 0.0
     rows16 = _half_rows(rows, half, "edge_linear")
-    if rows16 is not None and (use_dst or dropping or
+    if rows16 is not None and (dropping or
                                (edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats))):
-        raise _lib.PtgnnAmdError("edge_linear: 16-bit message rows take no target-state half, dropout or edge features")
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit message rows take no dropout or edge features")
     if half is not None and edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats):
         raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout nor edge features")
     if half is not None and dropping and (use_dst or mask_bits is None):
@@ -1636,11 +1678,23 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     sp = PtrArr(*[s.data_ptr() if s.numel() else None for s in srcs])
     cn = CntArr(*counts)
     if rows16 is not None:
-        if not (edge_linear16_supported(H, M, T, half) and _half_rows_ok(x)):
+        if not ((edge_linear16_dst_supported if use_dst else edge_linear16_supported)(H, M, T, half) and _half_rows_ok(x)):
             raise _lib.PtgnnAmdError(f"edge_linear: 16-bit message rows need a shape the 16-bit GEMM takes "
                                      f"(state_dim={H}, msg_dim={M}, {T} edge types) and 16-byte aligned states")
         w16 = _edge16_stack(ws, half, rounded)
         msg = torch.empty(max(E, 1), M, dtype=half, device=x.device)
+        if use_dst:
+            if any(d.numel() != c for d, c in zip(dsts, counts)):
+                raise _lib.PtgnnAmdError("edge_linear: source and target id lists differ in length")
+            dp = PtrArr(*[d.data_ptr() if d.numel() else None for d in dsts])
+            with _timed("edge_linear16_dst_rows16", flops=4.0 * E * H * M,
+                        bytes=E * (8.0 * H + 2.0 * M) + 4.0 * T * M * H + 16.0 * E):
+                rc = lib.ptgnn_amd_edge_rows16_dst_linear16(
+                    x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),
+                    ctypes.cast(dp, ctypes.c_void_p), ctypes.cast(cn, ctypes.c_void_p), w16.data_ptr(), T, M,
+                    ACT_IDS[act], HALF_IDS[half], msg.data_ptr(), M, _stream(msg))
+            _lib.check(rc, "ptgnn_amd_edge_rows16_dst_linear16")
+            return msg[:E] if E > 0 else msg[:0]
         with _timed("edge_linear16_rows16", flops=2.0 * E * H * M, bytes=E * (4.0 * H + 2.0 * M) + 2.0 * T * M * H + 8.0 * E):
             rc = lib.ptgnn_amd_edge_rows16_linear16(x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),
                                                     ctypes.cast(cn, ctypes.c_void_p), w16.data_ptr(), T, M, ACT_IDS[act],

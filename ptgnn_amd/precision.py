@@ -162,8 +162,28 @@ dtype setting ("autocast" included); with float32 it means fp32 rows.  Widths th
 widths that are not multiples of 32 or beyond 256) or the 16-bit GEMM does not take keep fp32 rows, silently.  CPU
 tensors (torch_route.ggnn_layer) round the messages with torch under the switch, under the same inference-only
 conditions as the operands, so a checkpoint behaves alike on both devices.  Out of scope, fp32 rows under the switch:
-every training route; MLP-MP (its aggregation has a destination term and epilogues); EGC and PNA; `forward_sharded`; the
+every training route; MLP-MP (a part of the switch of its own: below); EGC and PNA; `forward_sharded`; the
 edge-feature route; `_amp_forward`.
+
+The MLP-MP MESSAGE ROWS are a second part of that switch -- `set_half_messages(True)` keeps meaning "GGNN only", and its
+users keep their bits:
+
+    with ptgnn_amd.matrix_inputs(torch.bfloat16, mlp=True), ptgnn_amd.half_messages(mlp=True):
+        out = model(batch)                                  # also ptgnn_amd.set_half_messages(True, mlp=True)
+
+With `mlp=True` on BOTH settings the inference routes of `MlpMessagePassingLayer._forward_fused` store their messages as
+16-bit rows and aggregate them with csrc/gather_reduce16_epi.hip.  Table form: the [N, (1|2) T M] table leaves its
+16-bit Linear as 16-bit rows (ptgnn_amd_linear_rows16), and the aggregation adds the slot's source block and the
+node's destination block in fp32 before the fold.  Edge form: the grouped per-edge GEMM over [x[src] | x[dst]] (or
+x[src] alone) stores rnd(accumulator) per edge (ptgnn_amd_edge_rows16_dst_linear16 / ptgnn_amd_edge_rows16_linear16).
+Either way the fold, the mean, GELU and LayerNorm are fp32 inside the aggregation launch and the aggregate is fp32, as
+before.  `mlp_message_rows(tensor)` is what the layer reads: the 16-bit type only for fp32 GPU states with both parts
+on.  Anything either end declines (a message width that is not a multiple of 32 or beyond 256, a shape the 16-bit GEMM
+does not take, unaligned states, a non-stock activation or LayerNorm) runs exactly what it runs without the switch.
+Deliberately fp32 rows under the switch: the one-launch `ops.gather_update` route at hidden 64 (still taken when it
+applies), `_forward_pna`, deep or biased edge MLPs, edge features, `_forward_general`, `forward_sharded`, every training
+route.  CPU tensors (torch_route.mlp_layer) round each message once with torch under the same conditions (string
+aggregations only) -- the edge form's values; the GPU table form rounds the two halves separately.
 
 The setting is process-wide (like `ops.set_gemm_mode`); the layers read it, `ptgnn_amd.ops` never does -- its
 `inputs=` keyword is explicit, because inside an autograd `Function.forward` grad mode is off and an op could not tell
@@ -186,6 +206,7 @@ _attention = False
 _edge_training = False
 _attention_training = False
 _half_messages = False
+_half_messages_mlp = False
 
 
 def _checked(v):
@@ -289,12 +310,18 @@ def attention_training_inputs(tensor: torch.Tensor) -> torch.dtype:
     return resolve(tensor) if _attention_training and tensor.is_cuda else torch.float32
 
 
-def set_half_messages(on) -> bool:
+def set_half_messages(on, mlp=False) -> bool:
     """Whether the GGNN inference route stores its messages as 16-bit rows of the dtype setting and aggregates them with
-    the 16-bit-row kernel; returns the previous value.  A setting of its own: `set_matrix_inputs` / `matrix_inputs`
-    neither read nor reset it."""
-    global _half_messages
-    prev, _half_messages = _half_messages, bool(on)
+    the 16-bit-row kernel -- and, with `mlp=True`, whether the MLP-MP layer's inference routes do too; returns the
+    previous value of the first.  A setting of its own: `set_matrix_inputs` / `matrix_inputs` neither read nor reset it.
+    Every call without the keyword means `mlp=False`."""
+    return _set_half_messages(on, mlp)[0]
+
+
+def _set_half_messages(on, mlp):
+    global _half_messages, _half_messages_mlp
+    prev = (_half_messages, _half_messages_mlp)
+    _half_messages, _half_messages_mlp = bool(on), bool(on) and bool(mlp)
     return prev
 
 
@@ -302,13 +329,19 @@ def get_half_messages() -> bool:
     return _half_messages
 
 
+def get_half_messages_mlp() -> bool:
+    """Whether the switch is on with `mlp=True` (what the MLP-MP layer's CPU route reads; GPU routes read
+    `mlp_message_rows`)."""
+    return _half_messages and _half_messages_mlp
+
+
 @contextlib.contextmanager
-def half_messages(on=True):
-    prev = set_half_messages(on)
+def half_messages(on=True, mlp=False):
+    prev = _set_half_messages(on, mlp)
     try:
         yield
     finally:
-        set_half_messages(prev)
+        _set_half_messages(*prev)
 
 
 def message_rows(tensor: torch.Tensor, edge_form: bool) -> torch.dtype:
@@ -318,3 +351,12 @@ def message_rows(tensor: torch.Tensor, edge_form: bool) -> torch.dtype:
     if not _half_messages:
         return torch.float32
     return edge_gemm_inputs(tensor) if edge_form else resolve(tensor)
+
+
+def mlp_message_rows(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the MLP-MP layer's message rows for an inference call on the states `tensor`: `mlp_inputs(tensor)`
+    when `set_half_messages` is on with `mlp=True`, that is a 16-bit type and the states are fp32 on a GPU; else
+    float32."""
+    if not (_half_messages and _half_messages_mlp) or not tensor.is_cuda or tensor.dtype != torch.float32:
+        return torch.float32
+    return mlp_inputs(tensor)
