@@ -264,6 +264,14 @@ enum {
   PTGNN_AMD_KERNEL_EDGE16_DST_ROWS16,                      /* ptgnn_amd_edge_rows16_dst_linear16 */
   PTGNN_AMD_KERNEL_ROWS16_END_
 };
+/* ... and one for the score-free loss with 16-bit matrix-core inputs (csrc/projection_loss16.hip), so the sixteenth
+ * range ends where it did */
+enum {
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_ = 1088,
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS16 = PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_, /* ptgnn_amd_scorefree_loss16 */
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS16_BACKWARD,                                    /* ptgnn_amd_scorefree_loss16_backward */
+  PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1325,6 +1333,31 @@ int ptgnn_amd_projection_loss_backward_f32(const float *projected, int64_t ld_p,
                                            float *grad_table, int64_t ld_gt, float *grad_bias /* nullable */,
                                            float *grad_extra /* nullable */, void *workspace, size_t workspace_bytes,
                                            void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The score-free loss above with 16-bit matrix-core inputs (csrc/projection_loss16.hip): what autocast gives an
+ * `enable_amp` user of the reference for the vocabulary einsum of grucopydecoder.py:111-118.  Arguments, outputs, edge
+ * rules, workspaces (the two *_workspace_bytes functions above) and fold orders are those of the fp32 pair, plus `dtype`
+ * (PTGNN_AMD_HALF_BF16 / _F16).  projected and table stay fp32 in memory, any leading dimension, 4-byte aligned; their rows
+ * are rounded to nearest even on the way into LDS and multiplied on v_mfma_f32_32x32x16_{bf16,f16}.  The fp32 accumulator
+ * is the score: bias, (max, sum), the target pick, G, grad_bias and grad_extra are unrounded fp32; G is rounded once for
+ * grad_projected = rnd(G) rnd(table) and grad_table = rnd(G)^T rnd(projected), accumulated in fp32.  No atomics; two
+ * calls give the same bits, whatever the leading dimensions and alignments.  1 <= dim <= 256.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_scorefree_loss16_supported(int32_t dim, int32_t dtype);
+int ptgnn_amd_scorefree_loss16(const float *projected, int64_t ld_p, const float *table, int64_t ld_t, int64_t rows,
+                               int32_t vocab, int32_t dim, const float *bias /* nullable */,
+                               const float *extra /* nullable */, const int64_t *targets /* nullable */, float *norm,
+                               float *picked /* with targets */, float *stats, void *workspace, size_t workspace_bytes,
+                               int32_t dtype, void *stream);
+int ptgnn_amd_scorefree_loss16_backward(const float *projected, int64_t ld_p, const float *table, int64_t ld_t,
+                                        int64_t rows, int32_t vocab, int32_t dim, const float *bias /* nullable */,
+                                        const float *extra /* nullable */, const int64_t *targets /* nullable */,
+                                        const float *stats, const float *g_norm /* nullable */,
+                                        const float *g_picked /* nullable */, float *grad_projected, int64_t ld_gp,
+                                        float *grad_table, int64_t ld_gt, float *grad_bias /* nullable */,
+                                        float *grad_extra /* nullable */, void *workspace, size_t workspace_bytes,
+                                        int32_t dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * One step of the copying decoder's greedy decoding (csrc/decode_step.hip), replacing the per-step host work of

@@ -190,6 +190,13 @@ SIGNATURES = {
     "ptgnn_amd_projection_loss_backward_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
     "ptgnn_amd_projection_loss_backward_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                                           _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _c.c_size_t, _vp]),
+    # the same loss with 16-bit matrix-core inputs (csrc/projection_loss16.hip); workspaces as above
+    "ptgnn_amd_scorefree_loss16_supported": (_c.c_int, [_i32, _c.c_int]),
+    "ptgnn_amd_scorefree_loss16": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _c.c_size_t, _c.c_int, _vp]),
+    "ptgnn_amd_scorefree_loss16_backward": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _c.c_size_t, _c.c_int,
+                                                       _vp]),
     "ptgnn_amd_decode_step_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
     "ptgnn_amd_decode_step_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i64,
                                              _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),

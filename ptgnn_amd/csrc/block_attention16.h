@@ -49,4 +49,30 @@ __device__ __forceinline__ typename half16::Half16<DT>::vec ba16_round8(const f3
   return __builtin_convertvector(f, typename half16::Half16<DT>::vec);
 }
 
+// acc = sum_d A[lane row][d] B[lane row][d] over `steps` k-steps of two row images (addresses of this lane's 8 values of
+// step 0)
+template <int DT>
+__device__ __forceinline__ f32x16 ba16_nt(const uint16_t *a, const uint16_t *b, int steps) {
+  f32x16 x;
+  half16::zero(x);
+  for (int s = 0; s < steps; ++s)
+    x = half16::Half16<DT>::mfma(half16::load8<DT>(a + 16 * s), half16::load8<DT>(b + 16 * s), x);
+  return x;
+}
+
+// z[t] += sum_i rnd(x[8 s + i]) tile[ba_row(8 s + i, h)][32 t + lane column], s = 0, 1: `tile` is this lane's address in
+// the transposed image (ba16_tr_off already added), row stride LDT
+template <int DT, int T, int LDT>
+__device__ __forceinline__ void ba16_tn(f32x16 (&z)[T], const f32x16 &x, const uint16_t *tile) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const typename half16::Half16<DT>::vec a = ba16_round8<DT>(x, s);
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const uint16_t *at = tile + 16 * s * LDT + 32 * t;
+      z[t] = half16::Half16<DT>::mfma(a, half16::tr8<DT>(at, at + 8 * LDT), z[t]);
+    }
+  }
+}
+
 }  // namespace ptgnn_amd

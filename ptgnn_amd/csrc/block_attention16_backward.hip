@@ -68,31 +68,6 @@ __device__ __forceinline__ void ba16_stage_own(uint16_t *img, int ldi, int width
   }
 }
 
-// acc = sum_d A[lane row][d] B[lane row][d] over `steps` k-steps of two row images (addresses of this lane's 8 values of
-// step 0)
-template <int DT>
-__device__ __forceinline__ f32x16 ba16_nt(const uint16_t *a, const uint16_t *b, int steps) {
-  f32x16 x;
-  zero(x);
-  for (int s = 0; s < steps; ++s) x = Half16<DT>::mfma(load8<DT>(a + 16 * s), load8<DT>(b + 16 * s), x);
-  return x;
-}
-
-// z[t] += sum_i rnd(x[8 s + i]) tile[ba_row(8 s + i, h)][32 t + lane column], s = 0, 1: `tile` is this lane's address in
-// the transposed image (ba16_tr_off already added), row stride LDT
-template <int DT, int T, int LDT>
-__device__ __forceinline__ void ba16_tn(f32x16 (&z)[T], const f32x16 &x, const uint16_t *tile) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const typename Half16<DT>::vec a = ba16_round8<DT>(x, s);
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const uint16_t *at = tile + 16 * s * LDT + 32 * t;
-      z[t] = Half16<DT>::mfma(a, tr8<DT>(at, at + 8 * LDT), z[t]);
-    }
-  }
-}
-
 // grad_kqv[k, head: keys] of the rows of one (window, head) row block
 template <int DT, int DKT>
 __global__ __launch_bounds__(kBa16Threads) void k_attention16_dkey(

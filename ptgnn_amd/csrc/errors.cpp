@@ -37,6 +37,7 @@ static std::atomic<int64_t> g_edge16_train_launches[PTGNN_AMD_KERNEL_EDGE16_TRAI
 static std::atomic<int64_t> g_attention_train16_launches[PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_END_ - PTGNN_AMD_KERNEL_ATTENTION_TRAIN16_FIRST_];
 static std::atomic<int64_t> g_projection_loss_launches[PTGNN_AMD_KERNEL_PROJECTION_LOSS_END_ - PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_];
 static std::atomic<int64_t> g_rows16_launches[PTGNN_AMD_KERNEL_ROWS16_END_ - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
+static std::atomic<int64_t> g_projection_loss16_launches[PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_ - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -71,6 +72,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_projection_loss_launches[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_ROWS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ROWS16_END_)
     return &g_rows16_launches[kernel_id - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_)
+    return &g_projection_loss16_launches[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -174,6 +177,11 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "agg16", "edge16_rows16", "edge16_shared_rows16", "linear_rows16", "agg16_epi", "edge16_dst_rows16"};
   if (kernel_id >= PTGNN_AMD_KERNEL_ROWS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ROWS16_END_)
     return rows16_names[kernel_id - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
+  static const char *const projection_loss16_names[PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_ -
+                                                   PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_] = {
+      "projection_loss16", "projection_loss16_backward"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_)
+    return projection_loss16_names[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

@@ -37,44 +37,12 @@
 //            backward 4 ceil(V / 1024) R E bytes (the partials of d_p).  Nothing of R V elements exists anywhere.
 //
 // Traffic: DESIGN.md, "Projection loss".
-#include <math.h>
-
 #include "block_attention.h"
-#include "segment_chunks.h"
-#include "softmax_state.h"
+#include "projection_loss.h"
 #include "vocab_loss.h"
 
 namespace ptgnn_amd {
 namespace {
-
-constexpr int kPlThreads = 256;
-constexpr int kPlRows = 64;          // rows of p of a workgroup (forward, dproj) / of a step (dtable)
-constexpr int kPlStep = 64;          // rows of T of a step (forward, dproj) / of a workgroup (dtable)
-constexpr int kPlFwdCols = 256;      // columns of a forward workgroup = of one (max, sum) partial
-constexpr int kPlBwdCols = 1024;     // columns of a dproj workgroup = of one partial of d_p
-constexpr int kPlMaxDim = 256;
-static_assert(kPlFwdCols % kPlStep == 0 && kPlBwdCols % kPlStep == 0, "a chunk is whole steps");
-
-// exp((s - M) - log_sum): the softmax term of G.  An empty state (M = -inf) has none; rows past the end carry M = +inf.
-__device__ __forceinline__ float pl_prob(float s, float m, float log_sum) {
-  return m == -INFINITY ? 0.0f : expf((s - m) - log_sum);
-}
-
-// the 16 scores of a lane into its running state: one rescale for their maximum, their terms added in register order
-__device__ __forceinline__ void push_tile(MaxSum &a, const f32x16 &x) {
-  float gm = x[0];
-#pragma unroll
-  for (int j = 1; j < 16; ++j) gm = fmaxf(gm, x[j]);
-  if (gm > a.m) {
-    a.s = a.m == -INFINITY ? 0.0f : a.s * expf(a.m - gm);
-    a.m = gm;
-  }
-  if (a.m == -INFINITY) return;
-  float t = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t += expf(x[j] - a.m);
-  a.s += t;
-}
 
 // one step's 64 rows of T and their bias (0 without one and past the vocabulary) into LDS
 __device__ __forceinline__ void pl_stage_table(float *__restrict__ Ts, float *__restrict__ bias_s, int ld,
@@ -289,65 +257,20 @@ __global__ __launch_bounds__(kPlThreads) void k_projection_loss_fold(const float
   d_p[i / dim * ld_dp + i % dim] = chunk_fold(part + i, rows * dim, 0, chunks);
 }
 
-int64_t pl_row_blocks(int64_t rows) { return (rows + kPlRows - 1) / kPlRows; }
-int64_t pl_fwd_chunks(int32_t vocab) { return ((int64_t)vocab + kPlFwdCols - 1) / kPlFwdCols; }
-int64_t pl_bwd_chunks(int32_t vocab) { return ((int64_t)vocab + kPlBwdCols - 1) / kPlBwdCols; }
-
-struct PlFwdWs {
-  size_t partial, target_score, bytes;
-};
-
-PlFwdWs pl_fwd_workspace(int64_t rows, int32_t vocab) {
-  Carve c;
-  PlFwdWs w;
-  w.partial = c.take((size_t)rows * pl_fwd_chunks(vocab) * sizeof(float2));
-  w.target_score = c.take((size_t)rows * sizeof(float));
-  w.bytes = c.off;
-  return w;
-}
-
-size_t pl_bwd_workspace(int64_t rows, int32_t vocab, int32_t dim) {
-  Carve c;
-  c.take((size_t)pl_bwd_chunks(vocab) * rows * dim * sizeof(float));
-  return c.off;
-}
-
 // two 64-row images and `extra` floats
 size_t pl_lds_bytes(int32_t dim, int extra) {
   const int ld = (dim + 31) / 32 * 32 + 1;
   return sizeof(float) * ((size_t)(kPlRows + kPlStep) * ld + extra);
 }
 
-// what the two entries share: sizes, leading dimensions, and everything a kernel indexes with an int fits one
-int pl_check(const char *what, const void *p, int64_t ld_p, const void *T, int64_t ld_t, int64_t rows, int32_t vocab,
-             int32_t dim) {
-  PTGNN_REQUIRE(rows >= 0 && vocab >= 1 && dim >= 1, PTGNN_AMD_EINVAL, "%s: bad sizes (rows %lld, vocab %d, dim %d)", what,
-                (long long)rows, vocab, dim);
-  PTGNN_REQUIRE(dim <= kPlMaxDim, PTGNN_AMD_EUNSUPPORTED, "%s: dimension %d exceeds %d", what, dim, kPlMaxDim);
-  PTGNN_REQUIRE(ld_p >= dim && ld_t >= dim, PTGNN_AMD_EINVAL, "%s: leading dimension (%lld, %lld) < dim %d", what,
-                (long long)ld_p, (long long)ld_t, dim);
-  const int64_t lim = (int64_t)1 << 31;
-  PTGNN_REQUIRE(vocab <= lim - 2 * kPlBwdCols && rows <= lim - 2 * kPlRows &&
-                    pl_row_blocks(rows) <= (lim - 1) / pl_fwd_chunks(vocab),
-                PTGNN_AMD_EUNSUPPORTED, "%s: too many rows / columns", what);
-  if (rows == 0) return PTGNN_AMD_OK;
-  PTGNN_REQUIRE(p && T, PTGNN_AMD_EINVAL, "%s: null pointer", what);
-  return PTGNN_AMD_OK;
+}  // namespace
+
+void launch_projection_loss_fold(const float *part, int64_t rows, int dim, int chunks, float *d_p, int64_t ld_dp,
+                                 hipStream_t st) {
+  k_projection_loss_fold<<<(unsigned)((rows * dim + kPlThreads - 1) / kPlThreads), kPlThreads, 0, st>>>(part, rows, dim,
+                                                                                                       chunks, d_p, ld_dp);
 }
 
-#define PL_TILES(n, ...)                                   \
-  switch (n) {                                             \
-    case 1: { constexpr int TT = 1; __VA_ARGS__; } break;  \
-    case 2: { constexpr int TT = 2; __VA_ARGS__; } break;  \
-    case 3: { constexpr int TT = 3; __VA_ARGS__; } break;  \
-    case 4: { constexpr int TT = 4; __VA_ARGS__; } break;  \
-    case 5: { constexpr int TT = 5; __VA_ARGS__; } break;  \
-    case 6: { constexpr int TT = 6; __VA_ARGS__; } break;  \
-    case 7: { constexpr int TT = 7; __VA_ARGS__; } break;  \
-    default: { constexpr int TT = 8; __VA_ARGS__; } break; \
-  }
-
-}  // namespace
 }  // namespace ptgnn_amd
 
 using namespace ptgnn_amd;
@@ -428,8 +351,7 @@ extern "C" int ptgnn_amd_projection_loss_backward_f32(const float *projected, in
                                                         extra, targets, row_stats, g_norm, g_picked, part, grad_extra);
     PTGNN_LAUNCH_CHECK();
   })
-  k_projection_loss_fold<<<(unsigned)((rows * dim + kPlThreads - 1) / kPlThreads), kPlThreads, 0, st>>>(
-      part, rows, dim, chunks, grad_projected, ld_gp);
+  launch_projection_loss_fold(part, rows, dim, chunks, grad_projected, ld_gp, st);
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_PROJECTION_LOSS_BACKWARD);
   return PTGNN_AMD_OK;

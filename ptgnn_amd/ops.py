@@ -86,11 +86,14 @@ _PROJECTION_LOSS_FAMILY_FIRST = 960  # PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_: 
 _ROWS16_FAMILY_FIRST = 1024  # PTGNN_AMD_KERNEL_ROWS16_FIRST_: the opt-in 16-bit message rows (producers + aggregation)
 
 
+_PROJECTION_LOSS16_FAMILY_FIRST = 1088  # PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_: the score-free loss on 16-bit inputs
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
                   beam_finish: bool = False, attention16: bool = False, projection_loss: bool = False,
-                  rows16: bool = False, attention16_training: bool = False, edge16_training: bool = False) -> dict:
+                  projection_loss16: bool = False, rows16: bool = False, attention16_training: bool = False, edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -109,7 +112,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     `edge16_training=True`
     the 16-bit-input edge-form training launches (edge16_masked: the masked per-edge GEMM in its forward and
     input-gradient modes; edge_wgrad16: the per-type weight gradient); `projection_loss=True` the copying decoder's
-    score-free loss (projection_loss, projection_loss_backward); `rows16=True` the opt-in 16-bit message rows (agg16: the
+    score-free loss (projection_loss, projection_loss_backward); `projection_loss16=True` the same loss with 16-bit
+    matrix-core inputs (projection_loss16, projection_loss16_backward); `rows16=True` the opt-in 16-bit message rows (agg16: the
     aggregation over them; edge16_rows16, edge16_shared_rows16, linear_rows16: the producers that store them; agg16_epi:
     the MLP-MP aggregation with a destination term and / or an epilogue; edge16_dst_rows16: the per-edge GEMM with a
     target-state half storing them)."""
@@ -126,6 +130,7 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_ATTENTION_TRAIN16_FAMILY_FIRST,) if attention16_training else ()) \
             + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()) \
             + ((_PROJECTION_LOSS_FAMILY_FIRST,) if projection_loss else ()) \
+            + ((_PROJECTION_LOSS16_FAMILY_FIRST,) if projection_loss16 else ()) \
             + ((_ROWS16_FAMILY_FIRST,) if rows16 else ()):
         i = first
         while True:
@@ -141,7 +146,8 @@ def launches_since(before: dict) -> dict:
     """Kernel families of `before = launch_counts(...)` launched since -> {name: count}, zero entries dropped."""
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
                         edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
-                        attention16_training=True, edge16_training=True, projection_loss=True, rows16=True)
+                        attention16_training=True, edge16_training=True, projection_loss=True, projection_loss16=True,
+                        rows16=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -3347,12 +3353,22 @@ def _projection_args(projected: torch.Tensor, table: torch.Tensor, bias, extra, 
     return projected, table, *(t.contiguous() if t is not None else None for t in (bias, extra, targets)), R, V, E
 
 
+def projection_loss16_supported(dim: int, dtype) -> bool:
+    """Whether the 16-bit-input projection-loss kernels take an embedding width and type
+    (ptgnn_amd_scorefree_loss16_supported; needs no device)."""
+    return dtype in HALF_IDS and bool(_lib.load().ptgnn_amd_scorefree_loss16_supported(int(dim), HALF_IDS[dtype]))
+
+
 def projection_loss(projected: torch.Tensor, table: torch.Tensor, bias: Optional[torch.Tensor] = None,
-                    extra: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None):
+                    extra: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None, inputs=None):
     """(norm [R], picked [R] or None, stats [R, 2]) of `vocab_loss` over the scores projected [R, E] @ table [V, E]^T, which
     are formed tile by tile in registers and never written (ptgnn_amd_projection_loss_f32; grucopydecoder.py:111-135,
-    178-181).  Rows of `projected` and `table` may be padded (unit inner stride)."""
+    178-181).  Rows of `projected` and `table` may be padded (unit inner stride).  `inputs=torch.bfloat16 / float16`
+    rounds the rows of both operands to that type on their way into LDS and multiplies them on the 16-bit matrix cores
+    (ptgnn_amd_scorefree_loss16, csrc/projection_loss16.hip); the scores and everything after them stay fp32.  None and
+    float32 mean the fp32 kernels."""
     lib = _lib.load()
+    half = _half_inputs(inputs)
     projected, table, bias, extra, targets, R, V, E = _projection_args(projected, table, bias, extra, targets,
                                                                         "projection_loss")
     dev = projected.device
@@ -3363,6 +3379,15 @@ def projection_loss(projected: torch.Tensor, table: torch.Tensor, bias: Optional
         return norm, picked, stats
     ws_bytes = int(lib.ptgnn_amd_projection_loss_workspace_bytes(R, V))
     ws = _workspace(ws_bytes, dev)
+    if half is not None:
+        with _timed("projection_loss16", flops=2.0 * R * V * E,
+                    bytes=4.0 * ((R + 63) // 64) * V * E + 4.0 * R * E * ((V + 255) // 256)):
+            rc = lib.ptgnn_amd_scorefree_loss16(projected.data_ptr(), _ld(projected), table.data_ptr(), _ld(table), R, V, E,
+                                                _opt_ptr(bias), _opt_ptr(extra), _opt_ptr(targets), norm.data_ptr(),
+                                                _opt_ptr(picked), stats.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                HALF_IDS[half], _stream(norm))
+        _lib.check(rc, "ptgnn_amd_scorefree_loss16")
+        return norm, picked, stats
     with _timed("projection_loss", flops=2.0 * R * V * E, bytes=4.0 * ((R + 63) // 64) * V * E + 4.0 * R * E * ((V + 255) // 256)):
         rc = lib.ptgnn_amd_projection_loss_f32(projected.data_ptr(), _ld(projected), table.data_ptr(), _ld(table), R, V, E,
                                                _opt_ptr(bias), _opt_ptr(extra), _opt_ptr(targets), norm.data_ptr(),
@@ -3373,12 +3398,16 @@ def projection_loss(projected: torch.Tensor, table: torch.Tensor, bias: Optional
 
 def projection_loss_backward(projected: torch.Tensor, table: torch.Tensor, bias: Optional[torch.Tensor],
                              extra: Optional[torch.Tensor], targets: Optional[torch.Tensor], stats: torch.Tensor,
-                             g_norm: Optional[torch.Tensor], g_picked: Optional[torch.Tensor], want_bias: bool = True):
+                             g_norm: Optional[torch.Tensor], g_picked: Optional[torch.Tensor], want_bias: bool = True,
+                             inputs=None):
     """(d_projected [R, E], d_table [V, E], d_bias [V] or None, d_extra [R] or None) of `projection_loss` from its `stats`
     and the gradients of its norm and picked outputs (device tensors, None = 0): the scores are recomputed twice, once by
     workgroups that own vocabulary entries (d_table, d_bias) and once by workgroups that own rows (d_projected, d_extra);
-    no [R, V] gradient exists (ptgnn_amd_projection_loss_backward_f32)."""
+    no [R, V] gradient exists (ptgnn_amd_projection_loss_backward_f32).  `inputs=` as in `projection_loss` (pass what the
+    forward got): the scores are recomputed from the rounded rows, the score gradient G is rounded once for the two
+    gradient products, and d_bias / d_extra come from the unrounded G (ptgnn_amd_scorefree_loss16_backward)."""
     lib = _lib.load()
+    half = _half_inputs(inputs)
     projected, table, bias, extra, targets, R, V, E = _projection_args(projected, table, bias, extra, targets,
                                                                         "projection_loss_backward")
     dev = projected.device
@@ -3395,6 +3424,16 @@ def projection_loss_backward(projected: torch.Tensor, table: torch.Tensor, bias:
     d_bias = torch.empty(V, dtype=torch.float32, device=dev) if want_bias else None
     ws_bytes = int(lib.ptgnn_amd_projection_loss_backward_workspace_bytes(R, V, E))
     ws = _workspace(ws_bytes, dev)
+    if half is not None:
+        with _timed("projection_loss16_backward", flops=8.0 * R * V * E,
+                    bytes=4.0 * V * E * (2 + (R + 63) // 64) + 4.0 * R * E * ((V + 63) // 64 + 3 * ((V + 1023) // 1024))):
+            rc = lib.ptgnn_amd_scorefree_loss16_backward(
+                projected.data_ptr(), _ld(projected), table.data_ptr(), _ld(table), R, V, E, _opt_ptr(bias),
+                _opt_ptr(extra), _opt_ptr(targets), stats.data_ptr(), _opt_ptr(g_norm), _opt_ptr(g_picked),
+                d_projected.data_ptr(), E, d_table.data_ptr(), E, _opt_ptr(d_bias), _opt_ptr(d_extra), ws.data_ptr(),
+                ws_bytes, HALF_IDS[half], _stream(d_table))
+        _lib.check(rc, "ptgnn_amd_scorefree_loss16_backward")
+        return d_projected, d_table, d_bias, d_extra
     with _timed("projection_loss_backward", flops=8.0 * R * V * E,
                 bytes=4.0 * V * E * (2 + (R + 63) // 64) + 4.0 * R * E * ((V + 63) // 64 + 3 * ((V + 1023) // 1024))):
         rc = lib.ptgnn_amd_projection_loss_backward_f32(

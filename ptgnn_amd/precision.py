@@ -185,6 +185,23 @@ applies), `_forward_pna`, deep or biased edge MLPs, edge features, `_forward_gen
 route.  CPU tensors (torch_route.mlp_layer) round each message once with torch under the same conditions (string
 aggregations only) -- the edge form's values; the GPU table form rounds the two halves separately.
 
+The SCORE-FREE GRAPH2SEQ LOSS (`GruCopyingDecoder.score_free_loss`) has a setting of its own as well -- the decoder
+stayed fp32 under everything above, and existing users keep their bits.  Under `enable_amp` the reference runs the
+vocabulary einsum (grucopydecoder.py:111-118) in the autocast dtype:
+
+    ptgnn_amd.set_matrix_inputs("autocast"); ptgnn_amd.set_vocabulary_loss(True)       # next to enable_amp
+    with ptgnn_amd.matrix_inputs(torch.bfloat16), ptgnn_amd.vocabulary_loss():
+        loss = decoder.score_free_loss(**batch); loss.backward()
+
+With the switch the loss node of that route (`sequence._ProjectionLoss`) runs csrc/projection_loss16.hip: the rows of the
+projected states and of the (dropped-out -- the dropout is applied in fp32 before the rounding, as autocast does) embedding
+table are rounded on their way into LDS, the score tiles and the two gradient products run on the 16-bit matrix cores, and
+the scores themselves, the bias, the normaliser, the target pick, the score gradient, d_bias and d_extra stay unrounded
+fp32; the score gradient is rounded once for d_projected and d_table.  `vocabulary_loss_inputs(tensor)` is what the decoder
+reads.  Off by default, untouched by `set_matrix_inputs` / `matrix_inputs`, and with a float32 dtype setting it means
+fp32.  What stays fp32 under the switch: `fused_loss`, `forward`, decoding, CPU tensors, and the first Linear (hidden ->
+projected, `dense.linear`) -- the next step.
+
 The setting is process-wide (like `ops.set_gemm_mode`); the layers read it, `ptgnn_amd.ops` never does -- its
 `inputs=` keyword is explicit, because inside an autograd `Function.forward` grad mode is off and an op could not tell
 inference from training.
@@ -207,6 +224,7 @@ _edge_training = False
 _attention_training = False
 _half_messages = False
 _half_messages_mlp = False
+_vocabulary_loss = False
 
 
 def _checked(v):
@@ -308,6 +326,30 @@ def attention_training_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the attention layer's training branch for a layer call on `tensor`: `resolve(tensor)` when
     `set_attention_training` is on and the tensor is on a GPU, else float32."""
     return resolve(tensor) if _attention_training and tensor.is_cuda else torch.float32
+
+
+def set_vocabulary_loss(on) -> bool:
+    """Whether `GruCopyingDecoder.score_free_loss` (the Graph2Seq loss with the second vocabulary Linear inside it) takes
+    the 16-bit type of the dtype setting for that Linear's operands; returns the previous value.  A setting of its own:
+    `set_matrix_inputs` / `matrix_inputs` neither read nor reset it."""
+    global _vocabulary_loss
+    prev, _vocabulary_loss = _vocabulary_loss, bool(on)
+    return prev
+
+
+@contextlib.contextmanager
+def vocabulary_loss(on=True):
+    prev = set_vocabulary_loss(on)
+    try:
+        yield
+    finally:
+        set_vocabulary_loss(prev)
+
+
+def vocabulary_loss_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the score-free loss's vocabulary product for a decoder call on `tensor`: `resolve(tensor)` when
+    `set_vocabulary_loss` is on and the tensor is on a GPU, else float32."""
+    return resolve(tensor) if _vocabulary_loss and tensor.is_cuda else torch.float32
 
 
 def set_half_messages(on, mlp=False) -> bool:

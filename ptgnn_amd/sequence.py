@@ -49,7 +49,7 @@ import math
 import torch
 from torch import nn
 
-from ptgnn_amd import _lib, _readback, dense, ops, scatter as scatter_facade
+from ptgnn_amd import _lib, _readback, dense, ops, precision, scatter as scatter_facade
 from ptgnn_amd.layers import _index_plan, _no_grad_needed
 from ptgnn_amd.reduceops import _AttentionPool
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_scores
@@ -130,11 +130,13 @@ class _ProjectionLoss(torch.autograd.Function):
     """(norm [R], picked [R]) = ops.projection_loss(projected [R, E], table [V, E], bias, total_copy [R], targets [R]) as one
     node: `_VocabLoss` with the second vocabulary Linear (grucopydecoder.py:111-118) inside it.  Neither the raw scores
     [R, V] nor their gradient exists; the backward recomputes the score tiles and returns the gradients of the projected
-    states and of the (dropped-out) table."""
+    states and of the (dropped-out) table.  `inputs`: the operand type of the vocabulary product (float32, or the 16-bit
+    type of csrc/projection_loss16.hip), used by the forward and the backward alike."""
 
     @staticmethod
-    def forward(ctx, projected, table, bias, total_copy, targets):
-        norm, picked, stats = ops.projection_loss(projected, table, bias, total_copy, targets)
+    def forward(ctx, projected, table, bias, total_copy, targets, inputs=torch.float32):
+        norm, picked, stats = ops.projection_loss(projected, table, bias, total_copy, targets, inputs=inputs)
+        ctx.inputs = inputs
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(projected, table, bias, total_copy, targets, stats)
         return norm, picked
@@ -144,8 +146,8 @@ class _ProjectionLoss(torch.autograd.Function):
         projected, table, bias, total_copy, targets, stats = ctx.saved_tensors
         d_projected, d_table, d_bias, d_extra = ops.projection_loss_backward(
             projected, table, bias, total_copy, targets, stats, g_norm, g_picked,
-            want_bias=bias is not None and ctx.needs_input_grad[2])
-        return d_projected, d_table, d_bias, d_extra if ctx.needs_input_grad[3] else None, None
+            want_bias=bias is not None and ctx.needs_input_grad[2], inputs=ctx.inputs)
+        return d_projected, d_table, d_bias, d_extra if ctx.needs_input_grad[3] else None, None, None
 
 
 class _CopyLossFinish(torch.autograd.Function):
@@ -429,8 +431,10 @@ class GruCopyingDecoder(nn.Module):
         targets = target_token_ids[:, 1:].contiguous()                                     # [B, L]
         if score_free:
             projected = self.__projected_states(attention_out, states)                     # [B * L, E]
+            # the one place the decoder reads a precision setting: the dropout stays fp32, the node rounds after it
             norm, picked = _ProjectionLoss.apply(projected, self.__dropout(self.__embedding_layer.weight),
-                                                 self.__vocab_bias, total_copy.reshape(B * L), targets.reshape(B * L))
+                                                 self.__vocab_bias, total_copy.reshape(B * L), targets.reshape(B * L),
+                                                 precision.vocabulary_loss_inputs(projected))
         else:
             raw_scores = self.__raw_vocabulary_scores(attention_out, states)               # [B * L, V]: the only one
             norm, picked = _VocabLoss.apply(raw_scores, self.__vocab_bias, total_copy.reshape(B * L),
