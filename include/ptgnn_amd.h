@@ -272,6 +272,15 @@ enum {
   PTGNN_AMD_KERNEL_PROJECTION_LOSS16_BACKWARD,                                    /* ptgnn_amd_scorefree_loss16_backward */
   PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_
 };
+/* ... and one for the panel-form 16-bit Linear of the attention layer's training step (csrc/panel_linear16.hip, and the
+ * masked form of csrc/wgrad16.hip), so the eighth and tenth ranges end where they did */
+enum {
+  PTGNN_AMD_KERNEL_PANEL16_FIRST_ = 1152,
+  PTGNN_AMD_KERNEL_PANEL_LINEAR16 = PTGNN_AMD_KERNEL_PANEL16_FIRST_, /* ptgnn_amd_panel_linear16 */
+  PTGNN_AMD_KERNEL_PANEL_LINEAR16_GRAD_INPUT,                        /* ptgnn_amd_panel_linear16_grad_input */
+  PTGNN_AMD_KERNEL_HALF_WGRAD_MASKED,                                /* ptgnn_amd_linear_weight_grad16_masked */
+  PTGNN_AMD_KERNEL_PANEL16_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -1883,6 +1892,50 @@ int ptgnn_amd_edge_rows16_dst_linear16(const float *x, int64_t ld_x, int64_t num
                                        const int64_t *const *src_per_type, const int64_t *const *dst_per_type,
                                        const int64_t *edges_per_type, const void *w, int32_t num_types, int32_t msg_dim,
                                        int act, int dtype, void *msg16, int64_t ld_msg, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in panel-form 16-bit Linear with a fused Dropout(act(.)) + residual epilogue and masked backward forms
+ * (csrc/panel_linear16.hip, csrc/wgrad16.hip's masked form).
+ *
+ * Replaces: the summarisation, intermediate and output Linears of selfattmessagepassing.py:104-122 in training under the
+ *   reference trainer's `enable_amp` (autocast runs them in the 16-bit type, dropout and residual around them).  OFF by
+ *   default: the host asks for it with ptgnn_amd.set_attention_training(True, linears=True).
+ *
+ * ptgnn_amd_panel_linear16:  y = dropout_p(act(rnd(x) rnd(W)^T + b)) + addend.  x fp32 [rows, k] (ld_x) rounded to
+ *   nearest even on its way into LDS, `w` the host-rounded 16-bit weights [n_out, k] (contiguous), one fp32 accumulator
+ *   per output, k ascending in steps of 16: with p = 0 and no addend the bits of ptgnn_amd_half_linear.  Then, all fp32
+ *   and individually rounded: v = act(acc + bias[col]); `y_act` (nullable, ld_y_act) receives v; with p > 0
+ *   v = keep ? v * (1 / (1 - p)) : +0, keep from the hash of dense_common.h at (seed, row, column pair) with
+ *   half_width = n_out / 2 (tests/helpers.py `dropout_keep_scale(seed, rows, n_out, p)`); `addend` (nullable fp32
+ *   [rows, n_out], ld_add) is added last.  No mask tensor exists.  Row r's bits do not depend on the row count.
+ * ptgnn_amd_panel_linear16_grad_input:  d_x [rows, k] (ld_dx) = rnd(g') rnd(W), g' = grad_y * (keep ? scale : 0) *
+ *   act'(y) formed in registers with the expressions (and so the bits) of ptgnn_amd_act_dropout_backward_f32 before its
+ *   one rounding; grad_y fp32 [rows, n_out] (ld_grad_y); `y` (ld_y) the activation's output rows, read only with an
+ *   activation; `wt` the host-rounded 16-bit TRANSPOSED weights [k, n_out] (contiguous).  With act none and p = 0 the
+ *   bits of ptgnn_amd_half_linear(grad_y, wt).
+ * ptgnn_amd_linear_weight_grad16_masked:  ptgnn_amd_linear_weight_grad16 on that same g' in place of grad_y -- formed on
+ *   the staged panel before both the fp32 bias sums and the rounding: grad_w = rnd(g')^T rnd(x), grad_b = column sums of
+ *   the unrounded g'.  Same workspace, chunking and reduction order: the bits of ptgnn_amd_linear_weight_grad16(x, g').
+ * ptgnn_amd_panel_linear16_supported(k, n_out, dtype): k % 32 == 0, n_out % 32 == 0, both in 32 .. 4096 (the masked
+ *   weight gradient: ptgnn_amd_half_supported(PTGNN_AMD_HALF_KIND_WGRAD, ...)); needs no device.
+ * x, grad_y, y, addend, w and wt must be 16-byte aligned with ld % 4 == 0 (PTGNN_AMD_EUNSUPPORTED otherwise); outputs and
+ * bias aligned to a float; 0 <= p < 1; rows == 0 returns without a launch.  Bad sizes / enums / null pointers answer
+ * PTGNN_AMD_EINVAL; messages start "panel_linear16:", "panel_linear16_grad_input:", "linear_weight_grad16:", before
+ * anything touches the device.  No atomics: two calls give the same bits.  Additive: the ABI version stays.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_panel_linear16_supported(int32_t k, int32_t n_out, int dtype);
+int ptgnn_amd_panel_linear16(const float *x, int64_t rows, int32_t k, int64_t ld_x, const void *w, int32_t n_out,
+                             const float *bias /* nullable */, int act, float p, uint64_t seed, int dtype,
+                             const float *addend /* nullable */, int64_t ld_add, float *y_act /* nullable */,
+                             int64_t ld_y_act, float *y, int64_t ld_y, void *stream);
+int ptgnn_amd_panel_linear16_grad_input(const float *grad_y, int64_t ld_grad_y, const float *y /* nullable */,
+                                        int64_t ld_y, int64_t rows, int32_t n_out, const void *wt, int32_t k, int act,
+                                        float p, uint64_t seed, int dtype, float *d_x, int64_t ld_dx, void *stream);
+int ptgnn_amd_linear_weight_grad16_masked(const float *x, int64_t ld_x, int32_t k, const float *grad_y, int64_t ld_grad_y,
+                                          const float *y /* nullable */, int64_t ld_y, int act, float p, uint64_t seed,
+                                          int64_t rows, int32_t n_out, int dtype, float *grad_w,
+                                          float *grad_b /* nullable */, void *workspace, size_t workspace_bytes,
+                                          void *stream);
 
 #pragma GCC visibility pop
 

@@ -217,6 +217,14 @@ SIGNATURES = {
                                            _i64, _vp]),
     "ptgnn_amd_linear_weight_grad16": (_c.c_int, [_vp, _i64, _i32, _vp, _i64, _i64, _i32, _c.c_int, _vp, _vp, _vp,
                                                   _c.c_size_t, _vp]),
+    "ptgnn_amd_linear_weight_grad16_masked": (_c.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _c.c_int, _c.c_float,
+                                                         _c.c_uint64, _i64, _i32, _c.c_int, _vp, _vp, _vp, _c.c_size_t,
+                                                         _vp]),
+    "ptgnn_amd_panel_linear16_supported": (_c.c_int, [_i32, _i32, _c.c_int]),
+    "ptgnn_amd_panel_linear16": (_c.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _c.c_int, _c.c_float, _c.c_uint64,
+                                            _c.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "ptgnn_amd_panel_linear16_grad_input": (_c.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i32, _c.c_int, _c.c_float,
+                                                       _c.c_uint64, _c.c_int, _vp, _i64, _vp]),
     "ptgnn_amd_wgrad16_workspace_bytes": (_c.c_size_t, [_i64, _i32, _i32]),
     "ptgnn_amd_wgrad16_chunk_rows": (_i64, [_i64, _i32, _i32]),
     "ptgnn_amd_gru_cell_train16": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _c.c_int, _vp,

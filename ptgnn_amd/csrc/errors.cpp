@@ -38,6 +38,7 @@ static std::atomic<int64_t> g_attention_train16_launches[PTGNN_AMD_KERNEL_ATTENT
 static std::atomic<int64_t> g_projection_loss_launches[PTGNN_AMD_KERNEL_PROJECTION_LOSS_END_ - PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_];
 static std::atomic<int64_t> g_rows16_launches[PTGNN_AMD_KERNEL_ROWS16_END_ - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
 static std::atomic<int64_t> g_projection_loss16_launches[PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_ - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
+static std::atomic<int64_t> g_panel16_launches[PTGNN_AMD_KERNEL_PANEL16_END_ - PTGNN_AMD_KERNEL_PANEL16_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -74,6 +75,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_rows16_launches[kernel_id - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_)
     return &g_projection_loss16_launches[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_PANEL16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PANEL16_END_)
+    return &g_panel16_launches[kernel_id - PTGNN_AMD_KERNEL_PANEL16_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -182,6 +185,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "projection_loss16", "projection_loss16_backward"};
   if (kernel_id >= PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_)
     return projection_loss16_names[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
+  static const char *const panel16_names[PTGNN_AMD_KERNEL_PANEL16_END_ - PTGNN_AMD_KERNEL_PANEL16_FIRST_] = {
+      "panel_linear16", "panel_linear16_grad_input", "half_wgrad_masked"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_PANEL16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PANEL16_END_)
+    return panel16_names[kernel_id - PTGNN_AMD_KERNEL_PANEL16_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

@@ -1,5 +1,5 @@
 // What the 16-bit-input kernels share (half_gemm.hip, edge_gemm16.hip, wgrad16.hip, edge_wgrad16.hip,
-// block_attention16.hip): the MFMA of
+// block_attention16.hip, panel_linear16.hip): the MFMA of
 // each 16-bit type and its fragment maps, the per-wave tile, the rounded LDS panel (row and transposed fragments), the
 // rounding store and the transposed read of an LDS image, the fragment epilogue, and the host's dispatch and alignment
 // checks.
@@ -167,6 +167,31 @@ __device__ __forceinline__ float act_runtime(float v, int act) {
   if (act == PTGNN_AMD_ACT_TANH) return fast_tanh(v);
   if (act == PTGNN_AMD_ACT_RELU) return v > 0.f ? v : 0.f;
   return v;
+}
+
+// The masked gradient of Dropout(act(.)) on 4 consecutive values (panel_linear16.hip, wgrad16.hip's masked form):
+// g * (keep ? scale : 0) * act'(y) with the expressions of ptgnn_amd_act_dropout_backward_f32 (row_epilogue.hip), so the
+// result has that kernel's bits; the keep bits are the hash of dense_common.h at (row, column pair) of the FORWARD
+// output (`col` a multiple of 4; d.thr == 0: no dropout).  ACT: `y` holds the activation's outputs, else it is not read.
+__device__ __forceinline__ float act_grad_runtime(float y, int act) {
+  if (act == PTGNN_AMD_ACT_TANH) return 1.0f - y * y;
+  if (act == PTGNN_AMD_ACT_RELU) return y > 0.f ? 1.0f : 0.f;
+  return 1.0f;
+}
+template <bool ACT>
+__device__ __forceinline__ float4 masked_grad4(float4 g, float4 y, int act, const DropoutParams &d, int64_t row, int col) {
+  float m[4] = {1.f, 1.f, 1.f, 1.f};
+  if (d.thr != 0) {
+    const uint32_t b0 = dropout_bits(d, row, col >> 1), b1 = dropout_bits(d, row, (col >> 1) + 1);
+    m[0] = (b0 & 0xffffu) >= d.thr ? d.scale : 0.f;
+    m[1] = (b0 >> 16) >= d.thr ? d.scale : 0.f;
+    m[2] = (b1 & 0xffffu) >= d.thr ? d.scale : 0.f;
+    m[3] = (b1 >> 16) >= d.thr ? d.scale : 0.f;
+  }
+  if constexpr (ACT)
+    return make_float4(g.x * m[0] * act_grad_runtime(y.x, act), g.y * m[1] * act_grad_runtime(y.y, act),
+                       g.z * m[2] * act_grad_runtime(y.z, act), g.w * m[3] * act_grad_runtime(y.w, act));
+  return make_float4(g.x * m[0] * 1.0f, g.y * m[1] * 1.0f, g.z * m[2] * 1.0f, g.w * m[3] * 1.0f);
 }
 
 // The per-wave tile: acc[t] = rnd(arow) . rnd(W)[col0 + 32 t + li, :]^T over all of K (K % 32 == 0: two MFMA k-steps

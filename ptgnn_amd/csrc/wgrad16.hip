@@ -60,11 +60,24 @@ inline int64_t chunks_for(int64_t rows, int n_out, int k) {
 // floats of one chunk's partial: the tile rows of grad_w, then the bias partial
 inline int64_t partial_floats(int n_out, int k) { return (int64_t)n_out * k + n_out; }
 
-template <int DT, int TN>
-__global__ __launch_bounds__(256) void k_wgrad16(const float *__restrict__ x, int64_t ld_x, int K,
-                                                 const float *__restrict__ g, int64_t ld_g, int64_t rows, int n_out,
-                                                 int64_t chunk_rows, int jtiles, int tiles, float *__restrict__ out_w,
-                                                 float *__restrict__ out_b, int64_t out_stride) {
+// The masked form (ptgnn_amd_linear_weight_grad16_masked: the backward of Dropout(act(Linear))): the grad_y half of every
+// staged panel becomes g' = g * (keep ? scale : 0) * act'(y) -- the expressions of ptgnn_amd_act_dropout_backward_f32,
+// the keep bit from the hash of (row, forward column) -- BEFORE both the fp32 bias sums and the one rounding of the
+// park.  MASK_DROP: the hash alone (no activation: nothing else is loaded); MASK_ACT: also the y rows, staged beside
+// grad_y (dropout then a uniform run-time branch).  Neither g' nor a mask tensor exists in memory.
+enum { MASK_NONE = 0, MASK_DROP = 1, MASK_ACT = 2 };
+struct MaskArgs {
+  const float *y;      // [rows, n_out] act output (MASK_ACT)
+  int64_t ld_y;
+  int act;
+  DropoutParams drop;  // half_width = n_out / 2; thr == 0: no dropout
+};
+
+template <int DT, int TN, int MASK>
+__device__ __forceinline__ void wgrad16_body(const float *__restrict__ x, int64_t ld_x, int K,
+                                             const float *__restrict__ g, int64_t ld_g, int64_t rows, int n_out,
+                                             int64_t chunk_rows, int jtiles, int tiles, float *__restrict__ out_w,
+                                             float *__restrict__ out_b, int64_t out_stride, const MaskArgs &mk) {
   using H = Half16<DT>;
   using vec = typename H::vec;
   constexpr int KT = kTM + TN;
@@ -114,10 +127,40 @@ __global__ __launch_bounds__(256) void k_wgrad16(const float *__restrict__ x, in
     }
   };
 
-  panel.prime(rows_of(0), live_of(0));
+  // masked forms: the y values beside the staged grad_y float4s (slots of the x half stay unused), and the edit of the
+  // panel last fetched (rows past the chunk are zeros and stay zeros)
+  float4 ys[MASK == MASK_ACT ? Panel::NV : 1];
+  auto fetch_y = [&](int64_t p) {
+    if constexpr (MASK == MASK_ACT) {
+      const int live = live_of(p);
+#pragma unroll
+      for (int i = 0; i < Panel::NV; ++i) {
+        const int v = threadIdx.x + i * 256, r = v / Panel::RV, c = (v % Panel::RV) * 4;
+        const int gc = m0 + c < n_out ? m0 + c : m0 + c % 32;
+        ys[i] = r < live && c < kTM ? *reinterpret_cast<const float4 *>(mk.y + (e0 + p * kPE + r) * mk.ld_y + gc)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+  };
+  auto edit = [&](int64_t p) {
+    if constexpr (MASK != MASK_NONE) {
+      panel.edit([&](int i, int r, int c, float4 &v) {
+        if (c < kTM) {
+          const int gc = m0 + c < n_out ? m0 + c : m0 + c % 32;
+          v = masked_grad4<MASK == MASK_ACT>(v, MASK == MASK_ACT ? ys[i] : v, mk.act, mk.drop, e0 + p * kPE + r, gc);
+        }
+      });
+    }
+  };
+
+  panel.fetch(rows_of(0), live_of(0));
+  fetch_y(0);
+  edit(0);
+  panel.start();
   add_bias();
   for (int64_t p = 0; p < num_panels; ++p) {
     panel.fetch(rows_of(p + 1), live_of(p + 1));        // past the last panel: live = 0, zeros, no load
+    fetch_y(p + 1);
 #pragma unroll
     for (int ks = 0; ks < kPE / 16; ++ks) {
       vec av[SM], bv[SJ];
@@ -130,6 +173,7 @@ __global__ __launch_bounds__(256) void k_wgrad16(const float *__restrict__ x, in
 #pragma unroll
         for (int b = 0; b < SJ; ++b) acc[a][b] = H::mfma(av[a], bv[b], acc[a][b]);
     }
+    edit(p + 1);
     panel.flip();
     add_bias();
   }
@@ -163,6 +207,24 @@ __global__ __launch_bounds__(256) void k_wgrad16(const float *__restrict__ x, in
       (out_b + chunk * out_stride)[m0 + c] = s;
     }
   }
+}
+
+template <int DT, int TN>
+__global__ __launch_bounds__(256) void k_wgrad16(const float *__restrict__ x, int64_t ld_x, int K,
+                                                 const float *__restrict__ g, int64_t ld_g, int64_t rows, int n_out,
+                                                 int64_t chunk_rows, int jtiles, int tiles, float *__restrict__ out_w,
+                                                 float *__restrict__ out_b, int64_t out_stride) {
+  wgrad16_body<DT, TN, MASK_NONE>(x, ld_x, K, g, ld_g, rows, n_out, chunk_rows, jtiles, tiles, out_w, out_b, out_stride,
+                                  MaskArgs{});
+}
+
+template <int DT, int TN, int MASK>
+__global__ __launch_bounds__(256) void k_wgrad16_masked(const float *__restrict__ x, int64_t ld_x, int K,
+                                                        const float *__restrict__ g, int64_t ld_g, int64_t rows,
+                                                        int n_out, int64_t chunk_rows, int jtiles, int tiles,
+                                                        float *__restrict__ out_w, float *__restrict__ out_b,
+                                                        int64_t out_stride, MaskArgs mk) {
+  wgrad16_body<DT, TN, MASK>(x, ld_x, K, g, ld_g, rows, n_out, chunk_rows, jtiles, tiles, out_w, out_b, out_stride, mk);
 }
 
 // out[f] = sum over chunks of partial[chunk][f], f a float4 of [grad_w | grad_b]: fixed order (file header)
@@ -206,10 +268,10 @@ extern "C" size_t ptgnn_amd_wgrad16_workspace_bytes(int64_t rows, int32_t n_out,
   return chunks <= 1 ? 0 : (size_t)chunks * (size_t)partial_floats(n_out, k) * sizeof(float);
 }
 
-extern "C" int ptgnn_amd_linear_weight_grad16(const float *x, int64_t ld_x, int32_t k, const float *grad_y,
-                                              int64_t ld_grad_y, int64_t rows, int32_t n_out, int dtype,
-                                              float *grad_w, float *grad_b, void *workspace, size_t workspace_bytes,
-                                              void *stream_) {
+// the two entries: `mask` = MASK_NONE is ptgnn_amd_linear_weight_grad16 itself (its kernel, its messages)
+static int wgrad16_entry(const float *x, int64_t ld_x, int32_t k, const float *grad_y, int64_t ld_grad_y, int64_t rows,
+                         int32_t n_out, int dtype, float *grad_w, float *grad_b, void *workspace,
+                         size_t workspace_bytes, void *stream_, int mask, const MaskArgs &mk) {
   PTGNN_REQUIRE(rows >= 0 && k > 0 && n_out > 0, PTGNN_AMD_EINVAL, "linear_weight_grad16: bad sizes");
   PTGNN_REQUIRE(dtype_ok(dtype), PTGNN_AMD_EINVAL,
                 "linear_weight_grad16: dtype %d is neither PTGNN_AMD_HALF_BF16 nor _F16", dtype);
@@ -241,8 +303,16 @@ extern "C" int ptgnn_amd_linear_weight_grad16(const float *x, int64_t ld_x, int3
   float *out_b = !grad_b ? nullptr : (direct ? grad_b : out_w + (int64_t)n_out * k);
   with_dtype(dtype, [&](auto dt) {
     with_case<128, 64, 32>(tn, [&](auto t) {
-      k_wgrad16<decltype(dt)::value, decltype(t)::value><<<(unsigned)blocks, 256, 0, st>>>(
-          x, ld_x, k, grad_y, ld_grad_y, rows, n_out, chunk, jtiles, (int)tiles, out_w, out_b, stride);
+      constexpr int DT = decltype(dt)::value, TN = decltype(t)::value;
+      if (mask == MASK_NONE)
+        k_wgrad16<DT, TN><<<(unsigned)blocks, 256, 0, st>>>(x, ld_x, k, grad_y, ld_grad_y, rows, n_out, chunk, jtiles,
+                                                            (int)tiles, out_w, out_b, stride);
+      else if (mask == MASK_DROP)
+        k_wgrad16_masked<DT, TN, MASK_DROP><<<(unsigned)blocks, 256, 0, st>>>(
+            x, ld_x, k, grad_y, ld_grad_y, rows, n_out, chunk, jtiles, (int)tiles, out_w, out_b, stride, mk);
+      else
+        k_wgrad16_masked<DT, TN, MASK_ACT><<<(unsigned)blocks, 256, 0, st>>>(
+            x, ld_x, k, grad_y, ld_grad_y, rows, n_out, chunk, jtiles, (int)tiles, out_w, out_b, stride, mk);
     });
   });
   PTGNN_LAUNCH_CHECK();
@@ -252,6 +322,37 @@ extern "C" int ptgnn_amd_linear_weight_grad16(const float *x, int64_t ld_x, int3
                                                                                grad_w, grad_b);
     PTGNN_LAUNCH_CHECK();
   }
-  count_launch(PTGNN_AMD_KERNEL_HALF_WGRAD);
+  count_launch(mask == MASK_NONE ? PTGNN_AMD_KERNEL_HALF_WGRAD : PTGNN_AMD_KERNEL_HALF_WGRAD_MASKED);
   return PTGNN_AMD_OK;
+}
+
+extern "C" int ptgnn_amd_linear_weight_grad16(const float *x, int64_t ld_x, int32_t k, const float *grad_y,
+                                              int64_t ld_grad_y, int64_t rows, int32_t n_out, int dtype,
+                                              float *grad_w, float *grad_b, void *workspace, size_t workspace_bytes,
+                                              void *stream_) {
+  return wgrad16_entry(x, ld_x, k, grad_y, ld_grad_y, rows, n_out, dtype, grad_w, grad_b, workspace, workspace_bytes,
+                       stream_, MASK_NONE, MaskArgs{});
+}
+
+extern "C" int ptgnn_amd_linear_weight_grad16_masked(const float *x, int64_t ld_x, int32_t k, const float *grad_y,
+                                                     int64_t ld_grad_y, const float *y, int64_t ld_y, int act, float p,
+                                                     uint64_t seed, int64_t rows, int32_t n_out, int dtype,
+                                                     float *grad_w, float *grad_b, void *workspace,
+                                                     size_t workspace_bytes, void *stream_) {
+  PTGNN_REQUIRE(act >= PTGNN_AMD_ACT_NONE && act <= PTGNN_AMD_ACT_RELU && p >= 0.f && p < 1.f, PTGNN_AMD_EINVAL,
+                "linear_weight_grad16: masked: bad act or p");
+  const bool with_y = act != PTGNN_AMD_ACT_NONE;
+  PTGNN_REQUIRE(!with_y || rows == 0 || (y && ld_y >= n_out), PTGNN_AMD_EINVAL,
+                "linear_weight_grad16: masked: an activation needs its output rows y");
+  PTGNN_REQUIRE(!with_y || rows == 0 || rows16(y, ld_y), PTGNN_AMD_EUNSUPPORTED,
+                "linear_weight_grad16: masked: y must be 16-byte aligned with ld_y %% 4 == 0 (ld_y=%lld)", (long long)ld_y);
+  MaskArgs mk;
+  mk.y = y;
+  mk.ld_y = ld_y;
+  mk.act = act;
+  mk.drop = make_dropout(p, seed, n_out);
+  const int mask = with_y ? MASK_ACT : (p > 0.f ? MASK_DROP : MASK_NONE);   // nothing to mask: the plain kernel
+  const int rc = wgrad16_entry(x, ld_x, k, grad_y, ld_grad_y, rows, n_out, dtype, grad_w, grad_b, workspace,
+                               workspace_bytes, stream_, mask, mk);
+  return rc;
 }

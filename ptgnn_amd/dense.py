@@ -155,14 +155,68 @@ class _LinearActDropout(torch.autograd.Function):
         return d_x, d_w, d_b, None, None, None
 
 
+class _LinearActDropout16(torch.autograd.Function):
+    """Dropout(act(rnd(x) rnd(W)^T + b)) + addend as ONE autograd node on the panel-form 16-bit Linear
+    (csrc/panel_linear16.hip): the forward is one launch -- bias, activation, the hash dropout of `seed` and the residual
+    add ride its store epilogue, fp32 --, and the backward two: d x = rnd(g') rnd(W) and d W = rnd(g')^T rnd(x), both
+    forming g' = g * (keep ? scale : 0) * act'(y) in registers before its one rounding (the mask regenerated from the
+    seed: no mask tensor, no masked gradient in memory); d b = column sums of the unrounded g' from the weight-gradient
+    pass; d addend = g.  Saves x, the weight, and the activation's output only where act' needs it (the output itself
+    where nothing followed the activation)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, p, seed, addend, dt):
+        want_act = act is not None and (p > 0.0 or addend is not None)
+        res = ops.panel_linear16(x, weight, bias, act, dt, p=p, seed=seed, addend=addend, want_act=want_act,
+                                 rounded=_transposed(weight, dt, False))
+        out, y = res if want_act else (res, None)
+        ctx.save_for_backward(x, weight, y if want_act else (out if act is not None else None))
+        ctx.has_bias, ctx.has_addend, ctx.act, ctx.p, ctx.seed, ctx.dt = bias is not None, addend is not None, act, p, seed, dt
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, y = ctx.saved_tensors
+        g = g.contiguous()
+        d_x = d_w = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_x = ops.panel_linear16_grad_input(g, y, _transposed(weight), ctx.act, ctx.dt, p=ctx.p, seed=ctx.seed,
+                                                rounded=_transposed(weight, ctx.dt, True))
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            res = ops.half_linear_weight_grad_masked(x, g, y, ctx.act, ctx.dt, p=ctx.p, seed=ctx.seed, want_bias=want_b)
+            d_w, d_b = res if want_b else (res, None)
+        d_add = g if ctx.has_addend and ctx.needs_input_grad[6] else None
+        return d_x, d_w, d_b, None, None, None, d_add, None
+
+
+def _panel16_ok(x: torch.Tensor, weight: torch.Tensor, addend: Optional[torch.Tensor], dt) -> bool:
+    """Whether `_LinearActDropout16` takes the call: widths of all three launches, 16-byte aligned rows."""
+    n_out, k = weight.shape
+    return (dt is not None and ops.panel_linear16_supported(k, n_out, dt)
+            and ops.half_supported(ops.HALF_KIND_WGRAD, k, n_out, dt) and ops._half_rows_ok(ops._rowmajor(x))
+            and (addend is None or (addend.is_cuda and addend.dtype == torch.float32
+                                    and tuple(addend.shape) == (x.shape[0], n_out)
+                                    and ops._half_rows_ok(ops._rowmajor(addend)))))
+
+
 def linear_act_dropout(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: Optional[str],
-                       p: float, training: bool) -> Optional[torch.Tensor]:
-    """Dropout(act(Linear(x))) as one autograd node, or None when the shape is not the fused node's (widths that are not
-    multiples of 4, non-fp32): the caller then composes `linear` with torch's activation / dropout modules."""
+                       p: float, training: bool, inputs=None, seed: int = 0,
+                       addend: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Dropout(act(Linear(x))) (+ addend) as one autograd node, or None when the shape is not the fused node's (widths that
+    are not multiples of 4, non-fp32): the caller then composes `linear` with torch's activation / dropout modules (and
+    adds the addend itself).
+    `inputs` = a 16-bit dtype: `_LinearActDropout16` where the panel-form 16-bit Linear takes the shape -- the dropout
+    mask is then the hash of `seed` (the caller's, one per launch), and `addend` rides the store epilogue; otherwise the
+    fp32 node, silently, with torch's add for the addend."""
     n_out, k = weight.shape
     if not _kernel_dims_ok(x, weight) or k % 4 != 0 or n_out % 4 != 0 or x.stride(0) % 4 != 0 or p >= 1.0:
         return None
-    return _LinearActDropout.apply(x, weight, bias, act, float(p), bool(training))
+    dt = _half(inputs)
+    if _panel16_ok(x, weight, addend, dt):
+        return _LinearActDropout16.apply(x, weight, bias, act, float(p) if training else 0.0, int(seed), addend, dt)
+    y = _LinearActDropout.apply(x, weight, bias, act, float(p), bool(training))
+    return y if addend is None else y + addend
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, inputs=None) -> torch.Tensor:

@@ -891,7 +891,9 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
     Under `ptgnn_amd.set_attention_training(True)` (off by default) the TRAINING branch runs the head-transform Linear as
     the 16-bit Linear node and the attention as the 16-bit attention node (csrc/block_attention16.hip with dropout,
     csrc/block_attention16_backward.hip); the summarisation, intermediate and output Linears stay on the fused fp32
-    Linear + activation + dropout node (the next step), as do LayerNorms and residuals."""
+    Linear + activation + dropout node unless the switch was set with `linears=True`: then each is one node on the
+    panel-form 16-bit Linear (csrc/panel_linear16.hip: dropout and the residual in its epilogue, masked 16-bit backward).
+    LayerNorms stay fp32."""
 
     def __init__(self, input_state_dimension: int, key_query_dimension: int, value_dimension: int,
                  output_dimension: int, intermediate_dimension: int, num_heads: int, dropout_rate: float = 0.0,
@@ -987,18 +989,24 @@ class MultiHeadSelfAttentionMessagePassing(AbstractMessagePassingLayer):
         dt = precision.attention_training_inputs(x)
         kqv = dense.linear(x, w_h.weight, inputs=dt)
         values = block_attention_autograd(kqv, windows, self.__max_num_nodes, heads, dk, dv, drop, seed, inputs=dt)
-        a = dense.row_epilogue(self.__linear_dropout(values, w_s, None, drop) + residual, False, ln1)
-        hidden = self.__linear_dropout(a, w_i, "relu", 0.0)
-        return dense.row_epilogue(self.__linear_dropout(hidden, w_o, None, drop) + a, False, ln2)
+        # float32 unless the switch is on with linears=True: then each of the three Linears below is one 16-bit node with
+        # the hash dropout of its own seed and the residual in its store epilogue (dense._LinearActDropout16)
+        ldt = precision.attention_linear_inputs(x)
+        a = dense.row_epilogue(self.__linear_dropout(values, w_s, None, drop, ldt, seed + 1, residual), False, ln1)
+        hidden = self.__linear_dropout(a, w_i, "relu", 0.0, ldt, seed + 2)
+        return dense.row_epilogue(self.__linear_dropout(hidden, w_o, None, drop, ldt, seed + 3, a), False, ln2)
 
     @staticmethod
-    def __linear_dropout(x: torch.Tensor, lin: nn.Linear, act: Optional[str], p: float) -> torch.Tensor:
-        """dropout(act(Linear(x))) as one autograd node where the widths allow, else composed from the HIP Linear."""
-        y = dense.linear_act_dropout(x, lin.weight, lin.bias, act, p, p > 0)
+    def __linear_dropout(x: torch.Tensor, lin: nn.Linear, act: Optional[str], p: float, inputs=None, seed: int = 0,
+                         addend: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dropout(act(Linear(x))) (+ addend) as one autograd node where the widths allow, else composed from the HIP
+        Linear."""
+        y = dense.linear_act_dropout(x, lin.weight, lin.bias, act, p, p > 0, inputs=inputs, seed=seed, addend=addend)
         if y is None:
             y = dense.linear(x, lin.weight, lin.bias)
             y = torch.relu(y) if act == "relu" else y
             y = nn.functional.dropout(y, p, True) if p > 0 else y
+            y = y if addend is None else y + addend
         return y
 
     def forward_sharded(self, node_states: torch.Tensor, shard) -> torch.Tensor:

@@ -89,11 +89,15 @@ _ROWS16_FAMILY_FIRST = 1024  # PTGNN_AMD_KERNEL_ROWS16_FIRST_: the opt-in 16-bit
 _PROJECTION_LOSS16_FAMILY_FIRST = 1088  # PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_: the score-free loss on 16-bit inputs
 
 
+_PANEL16_FAMILY_FIRST = 1152  # PTGNN_AMD_KERNEL_PANEL16_FIRST_: the panel-form 16-bit Linear and its masked backward
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
                   beam_finish: bool = False, attention16: bool = False, projection_loss: bool = False,
-                  projection_loss16: bool = False, rows16: bool = False, attention16_training: bool = False, edge16_training: bool = False) -> dict:
+                  projection_loss16: bool = False, rows16: bool = False, panel16: bool = False,
+                  attention16_training: bool = False, edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -116,7 +120,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     matrix-core inputs (projection_loss16, projection_loss16_backward); `rows16=True` the opt-in 16-bit message rows (agg16: the
     aggregation over them; edge16_rows16, edge16_shared_rows16, linear_rows16: the producers that store them; agg16_epi:
     the MLP-MP aggregation with a destination term and / or an epilogue; edge16_dst_rows16: the per-edge GEMM with a
-    target-state half storing them)."""
+    target-state half storing them); `panel16=True` the panel-form 16-bit Linear of the attention layer's training step
+    (panel_linear16, panel_linear16_grad_input, half_wgrad_masked)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -131,7 +136,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_EDGE16_TRAIN_FAMILY_FIRST,) if edge16_training else ()) \
             + ((_PROJECTION_LOSS_FAMILY_FIRST,) if projection_loss else ()) \
             + ((_PROJECTION_LOSS16_FAMILY_FIRST,) if projection_loss16 else ()) \
-            + ((_ROWS16_FAMILY_FIRST,) if rows16 else ()):
+            + ((_ROWS16_FAMILY_FIRST,) if rows16 else ()) \
+            + ((_PANEL16_FAMILY_FIRST,) if panel16 else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -147,7 +153,7 @@ def launches_since(before: dict) -> dict:
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
                         edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
                         attention16_training=True, edge16_training=True, projection_loss=True, projection_loss16=True,
-                        rows16=True)
+                        rows16=True, panel16=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -1972,6 +1978,129 @@ def half_linear_weight_grad(x: torch.Tensor, grad_y: torch.Tensor, dtype, want_b
                                                 grad_b.data_ptr() if want_bias else None, ws.data_ptr(), ws_bytes,
                                                 _stream(grad_w))
     _lib.check(rc, "ptgnn_amd_linear_weight_grad16")
+    return (grad_w, grad_b) if want_bias else grad_w
+
+
+def panel_linear16_supported(k: int, n_out: int, dtype) -> bool:
+    """Whether the panel-form 16-bit Linear takes the widths (ptgnn_amd_panel_linear16_supported; needs no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_panel_linear16_supported(int(k), int(n_out), HALF_IDS[dtype]))
+
+
+def _panel_rows(name: str, t: torch.Tensor, rows: int, width: int) -> torch.Tensor:
+    """An fp32 [rows, width] operand of the panel launches: row-major with 16-byte aligned rows, or this raises (the
+    callers decide beforehand with `panel_linear16_supported` and `_half_rows_ok`; there is no fall-back here)."""
+    _require_cuda_f32(name, t)
+    t = _rowmajor(t)
+    if tuple(t.shape) != (rows, width) or not _half_rows_ok(t):
+        raise _lib.PtgnnAmdError(f"panel_linear16: {name} must be [{rows}, {width}] with 16-byte aligned rows "
+                                 f"(got {tuple(t.shape)}, ld {_ld(t)})")
+    return t
+
+
+def panel_linear16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: Optional[str], dtype,
+                   p: float = 0.0, seed: int = 0, addend: Optional[torch.Tensor] = None, want_act: bool = False,
+                   rounded: Optional[torch.Tensor] = None):
+    """dropout_p(act(rnd(x) rnd(W)^T + b)) + addend in ONE launch of the panel-form 16-bit Linear
+    (csrc/panel_linear16.hip: both operands staged through LDS; bias, activation, the hash dropout of `seed` and the
+    residual add in the store epilogue, all fp32).  With p = 0 and no addend the bits of `linear(..., inputs=dtype)`.
+    `want_act`: also return the activation's output before the dropout -> (y, y_act).  `rounded`: the caller's
+    `weight.to(dtype)`.  Raises where `panel_linear16_supported` refuses the widths or a row is not 16-byte aligned."""
+    lib = _lib.load()
+    _require_cuda_f32("weight", weight)
+    n_out, k = weight.shape
+    half = _half_inputs(dtype)
+    if half is None or not panel_linear16_supported(k, n_out, half):
+        raise _lib.PtgnnAmdError(f"panel_linear16: k={k}, n_out={n_out}, dtype={dtype!r} is not a shape of the kernel")
+    rows = x.shape[0]
+    x = _panel_rows("x", x, rows, k)
+    if addend is not None:
+        addend = _panel_rows("addend", addend, rows, n_out)
+    w16 = _rounded_weight(weight, half, rounded)
+    if bias is not None:
+        bias = bias.contiguous()
+    y = torch.empty(rows, n_out, dtype=torch.float32, device=x.device)
+    y_act = torch.empty_like(y) if want_act else None
+    n_io = 1 + (addend is not None) + bool(want_act)
+    with _timed("panel_linear16", flops=2.0 * rows * k * n_out, bytes=4.0 * rows * (k + n_io * n_out) + 2.0 * n_out * k):
+        rc = lib.ptgnn_amd_panel_linear16(x.data_ptr() if rows else None, rows, k, _ld(x), w16.data_ptr(), n_out,
+                                          bias.data_ptr() if bias is not None else None, ACT_IDS[act], float(p),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, HALF_IDS[half],
+                                          addend.data_ptr() if addend is not None and rows else None,
+                                          _ld(addend) if addend is not None else 0,
+                                          y_act.data_ptr() if want_act and rows else None, n_out,
+                                          y.data_ptr() if rows else None, n_out, _stream(y))
+    _lib.check(rc, "ptgnn_amd_panel_linear16")
+    return (y, y_act) if want_act else y
+
+
+def panel_linear16_grad_input(grad_y: torch.Tensor, y: Optional[torch.Tensor], weight_t: torch.Tensor,
+                              act: Optional[str], dtype, p: float = 0.0, seed: int = 0,
+                              rounded: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_x [rows, k] = rnd(g') rnd(W) with g' = grad_y * (keep ? 1 / (1 - p) : 0) * act'(y) formed in registers (the bits
+    of `act_dropout_backward`, never in memory) from the hash mask of `seed`; `weight_t` = W^T [k, n_out], `rounded` its
+    16-bit copy; `y`: the activation's output rows (needed with an activation only)."""
+    lib = _lib.load()
+    _require_cuda_f32("weight_t", weight_t)
+    k, n_out = weight_t.shape
+    half = _half_inputs(dtype)
+    if half is None or not panel_linear16_supported(k, n_out, half):
+        raise _lib.PtgnnAmdError(f"panel_linear16_grad_input: k={k}, n_out={n_out}, dtype={dtype!r} is not a shape of "
+                                 "the kernel")
+    rows = grad_y.shape[0]
+    grad_y = _panel_rows("grad_y", grad_y, rows, n_out)
+    with_y = ACT_IDS[act] != 0
+    if with_y:
+        y = _panel_rows("y", y, rows, n_out)
+    wt16 = _rounded_weight(weight_t, half, rounded)
+    d_x = torch.empty(rows, k, dtype=torch.float32, device=grad_y.device)
+    with _timed("panel_linear16_grad_input", flops=2.0 * rows * k * n_out,
+                bytes=4.0 * rows * (k + (2 if with_y else 1) * n_out) + 2.0 * n_out * k):
+        rc = lib.ptgnn_amd_panel_linear16_grad_input(grad_y.data_ptr() if rows else None, _ld(grad_y),
+                                                     y.data_ptr() if with_y and rows else None,
+                                                     _ld(y) if with_y else 0, rows, n_out, wt16.data_ptr(), k,
+                                                     ACT_IDS[act], float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                     HALF_IDS[half], d_x.data_ptr() if rows else None, k, _stream(d_x))
+    _lib.check(rc, "ptgnn_amd_panel_linear16_grad_input")
+    return d_x
+
+
+def half_linear_weight_grad_masked(x: torch.Tensor, grad_y: torch.Tensor, y: Optional[torch.Tensor], act: Optional[str],
+                                   dtype, p: float = 0.0, seed: int = 0, want_bias: bool = False):
+    """`half_linear_weight_grad(x, g', dtype, want_bias)` with g' = grad_y * (keep ? 1 / (1 - p) : 0) * act'(y) formed on
+    the staged panels inside the kernel (ptgnn_amd_linear_weight_grad16_masked: same kernel, chunking and reduction
+    order, so the same bits); the bias gradient is the column sums of the unrounded g'.  Raises where
+    `half_supported(HALF_KIND_WGRAD, ...)` refuses the widths or a row is not 16-byte aligned."""
+    lib = _lib.load()
+    _require_cuda_f32("x", x)
+    rows, k = x.shape
+    n_out = grad_y.shape[1]
+    half = _half_inputs(dtype)
+    if half is None or not half_supported(HALF_KIND_WGRAD, k, n_out, half):
+        raise _lib.PtgnnAmdError(f"half_linear_weight_grad_masked: k={k}, n_out={n_out}, dtype={dtype!r} is not a shape "
+                                 "of the kernel")
+    x = _panel_rows("x", x, rows, k)
+    grad_y = _panel_rows("grad_y", grad_y, rows, n_out)
+    with_y = ACT_IDS[act] != 0
+    if with_y:
+        y = _panel_rows("y", y, rows, n_out)
+    if rows == 0:
+        gw = torch.zeros(n_out, k, dtype=torch.float32, device=x.device)
+        return (gw, torch.zeros(n_out, dtype=torch.float32, device=x.device)) if want_bias else gw
+    grad_w = torch.empty(n_out, k, dtype=torch.float32, device=x.device)
+    grad_b = torch.empty(n_out, dtype=torch.float32, device=x.device) if want_bias else None
+    ws_bytes = lib.ptgnn_amd_wgrad16_workspace_bytes(rows, n_out, k)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    with _timed("half_linear_weight_grad_masked", flops=2.0 * rows * k * n_out,
+                bytes=4.0 * (rows * k + (2 if with_y else 1) * rows * n_out + n_out * k) + 2.0 * ws_bytes):
+        rc = lib.ptgnn_amd_linear_weight_grad16_masked(x.data_ptr(), _ld(x), k, grad_y.data_ptr(), _ld(grad_y),
+                                                       y.data_ptr() if with_y else None, _ld(y) if with_y else 0,
+                                                       ACT_IDS[act], float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, rows,
+                                                       n_out, HALF_IDS[half], grad_w.data_ptr(),
+                                                       grad_b.data_ptr() if want_bias else None, ws.data_ptr(), ws_bytes,
+                                                       _stream(grad_w))
+    _lib.check(rc, "ptgnn_amd_linear_weight_grad16_masked")
     return (grad_w, grad_b) if want_bias else grad_w
 
 

@@ -101,9 +101,27 @@ Linear in front of it becomes the 16-bit Linear node of `training=True` (ptgnn_a
 tensors, D = sum dOut o out, every gradient in memory and every accumulation stay fp32; fp16 overflow of a rounded
 gradient becomes inf, as `tensor.half()` gives and `GradScaler` expects.  The dtype comes from `set_matrix_inputs`
 ("autocast" included); the switch is off by default, independent of the five flags, untouched by `set_matrix_inputs`
-and `matrix_inputs`, and with a float32 dtype setting it means fp32.  What stays fp32 under the switch: the
-summarisation, intermediate and output Linears (the fused fp32 Linear + activation + dropout node) -- the next step --,
-both LayerNorms, the residuals, CPU tensors and the inference branch (which follows `attention=True` alone).
+and `matrix_inputs`, and with a float32 dtype setting it means fp32.  What stays fp32 under the plain switch: the
+summarisation, intermediate and output Linears (the fused fp32 Linear + activation + dropout node), both LayerNorms, the
+residuals, CPU tensors and the inference branch (which follows `attention=True` alone).
+
+Those three Linears are a second part of that switch -- `set_attention_training(True)` keeps meaning "attention and head
+transforms only", and its users keep their bits:
+
+    ptgnn_amd.set_attention_training(True, linears=True)
+    with ptgnn_amd.matrix_inputs(torch.bfloat16), ptgnn_amd.attention_training(linears=True):
+        loss = model(batch); loss.backward()
+
+With `linears=True` each of the three becomes one `dense._LinearActDropout16` node on the panel-form 16-bit Linear
+(csrc/panel_linear16.hip), as autocast runs them in the reference (selfattmessagepassing.py:104-122): the forward rounds
+x in the kernel and the weight by torch -- one rounding of each operand --, accumulates in fp32 and applies bias, ReLU,
+the hash dropout (seeds `seed + 1 / 2 / 3` beside the attention's `seed`: no two launches share a mask) and the residual
+add in fp32 in its store epilogue; the input gradient and the weight gradient (csrc/wgrad16.hip's masked form) form
+g * (keep ? 1 / (1 - p) : 0) * act'(y) in fp32 in registers and round it once; the bias gradient sums the unrounded
+values; no mask tensor and no masked gradient reach memory.  `attention_linear_inputs(tensor)` is what the layer reads.
+Widths the kernels do not take (not multiples of 32, beyond 1024) keep the fp32 node, silently.  Still fp32 under
+`linears=True`: both LayerNorms, saved tensors, every gradient in memory, CPU tensors, the inference branch and every
+other user of `dense.linear_act_dropout` (the MLP-MP dense update).
 
 The edge form of the GGNN TRAINING step -- what a Graph2Class batch takes, and every batch once the layer has per-edge
 dropout (`dropout_rate > 0` in train(): the reference's Typilus configuration) -- has a switch of its own as well; it
@@ -222,6 +240,7 @@ _mlp = False
 _attention = False
 _edge_training = False
 _attention_training = False
+_attention_linears = False
 _half_messages = False
 _half_messages_mlp = False
 _vocabulary_loss = False
@@ -304,28 +323,42 @@ def attention_inputs(tensor: torch.Tensor) -> torch.dtype:
     return resolve(tensor) if _attention else torch.float32
 
 
-def set_attention_training(on) -> bool:
+def set_attention_training(on, linears=False) -> bool:
     """Whether the attention layer's TRAINING branch (block attention forward with dropout, its backward, the
-    head-transform Linear) takes the 16-bit type of the dtype setting; returns the previous value.  A setting of its own:
-    `set_matrix_inputs` / `matrix_inputs` neither read nor reset it."""
-    global _attention_training
-    prev, _attention_training = _attention_training, bool(on)
+    head-transform Linear) takes the 16-bit type of the dtype setting -- and, with `linears=True`, whether its
+    summarisation, intermediate and output Linears do too (the panel-form 16-bit Linear + activation + dropout + residual
+    node); returns the previous value of the first.  A setting of its own: `set_matrix_inputs` / `matrix_inputs` neither
+    read nor reset it.  Every call without the keyword means `linears=False`."""
+    return _set_attention_training(on, linears)[0]
+
+
+def _set_attention_training(on, linears):
+    global _attention_training, _attention_linears
+    prev = (_attention_training, _attention_linears)
+    _attention_training, _attention_linears = bool(on), bool(on) and bool(linears)
     return prev
 
 
 @contextlib.contextmanager
-def attention_training(on=True):
-    prev = set_attention_training(on)
+def attention_training(on=True, linears=False):
+    prev = _set_attention_training(on, linears)
     try:
         yield
     finally:
-        set_attention_training(prev)
+        _set_attention_training(*prev)
 
 
 def attention_training_inputs(tensor: torch.Tensor) -> torch.dtype:
     """The dtype of the attention layer's training branch for a layer call on `tensor`: `resolve(tensor)` when
     `set_attention_training` is on and the tensor is on a GPU, else float32."""
     return resolve(tensor) if _attention_training and tensor.is_cuda else torch.float32
+
+
+def attention_linear_inputs(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the summarisation, intermediate and output Linears of the attention layer's training branch for a
+    layer call on `tensor`: `resolve(tensor)` when `set_attention_training` is on with `linears=True` and the tensor is
+    on a GPU, else float32."""
+    return resolve(tensor) if _attention_training and _attention_linears and tensor.is_cuda else torch.float32
 
 
 def set_vocabulary_loss(on) -> bool:
