@@ -878,6 +878,48 @@ int ptgnn_amd_segment_scores_backward_f32(const float *y, int64_t ld_y, const fl
                                           float *grad_v, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Segment softmax / log-softmax / logsumexp of a general source x [num_elements, dim] over an arbitrary (unsorted)
+ * index, and their backwards (csrc/segment_softmax.hip), fp32:
+ *   m[s,c] = max_{i : index[i] == s} x[i,c]      lognorm[s,c] = log(sum_{i : index[i] == s} exp(x[i,c] - m[s,c]) + eps)
+ *   log-softmax y = x - m[index] - lognorm[index]      softmax y = exp(that)      logsumexp L = lognorm + m
+ * Replaces: torch_scatter.composite's scatter_log_softmax / scatter_softmax / scatter_logsumexp as the reference calls
+ *   them (varsizedsummary.py:57,106,158, varmisuse.py:79, grucopydecoder.py:100,122,190): a segment max, a gather, sub / exp, a segment sum, a
+ *   second gather and log / sub / div, each over [num_elements, dim].
+ * ptgnn_amd_segment_softmax_state_f32: ONE walk over the plan of the index (rowptr [num_segments + 1], perm
+ *   [num_elements] = the element of every slot), folding per (segment, column)
+ *     PTGNN_AMD_SSM_FOLD_MAXSUM  the running (max, sum exp) of a:  p0 = m, p1 = lognorm, and, where `lse` is not NULL,
+ *                                lse = lognorm + m (-inf for a segment without elements, or whose elements are all -inf)
+ *     PTGNN_AMD_SSM_FOLD_SUM     p0 = sum a                 (the log-softmax backward's sum of g)
+ *     PTGNN_AMD_SSM_FOLD_DOT     p0 = sum a * b             (the softmax backward's sum of g y)
+ *   a (ld_a), b (ld_b; read by FOLD_DOT only) [num_elements, dim]; p0, p1, lse [num_segments, dim] contiguous, every
+ *   entry OVERWRITTEN.  Segments of up to 128 slots are folded by one lane group each; longer ones in 128-slot chunks
+ *   counted from the segment's own start, merged in chunk order.  No float atomics: a segment's value is a fixed function
+ *   of its elements and their slot order.  workspace: ptgnn_amd_segment_softmax_workspace_bytes(..., fold).
+ * ptgnn_amd_segment_softmax_write_f32: the element-parallel pass, out [num_elements, dim] (ld_out), with u = p0[index[i]]
+ *   and w = p1[index[i]] (`index` int64 [num_elements]; an entry outside [0, num_segments) writes NaN):
+ *     PTGNN_AMD_SSM_LOG_SOFTMAX           out = a - u - w                       a = x, (p0, p1) = (m, lognorm)
+ *     PTGNN_AMD_SSM_SOFTMAX               out = exp(a - u - w)
+ *     PTGNN_AMD_SSM_LOG_SOFTMAX_BACKWARD  out = a - exp(b) u                    a = g, b = y, p0 = sum g
+ *     PTGNN_AMD_SSM_SOFTMAX_BACKWARD      out = b (a - u)                       a = g, b = y, p0 = sum g y
+ *     PTGNN_AMD_SSM_LOGSUMEXP_BACKWARD    out = a == -inf ? 0 : u exp(a - w)    a = x, p0 = g [num_segments, dim], p1 = L
+ * A segment whose elements are all -inf: NaN from the two softmaxes, -inf from logsumexp (as the chain they replace).
+ * num_elements, num_segments and num_segments * dim must each stay below 2^31 (ptgnn_amd_segment_softmax_supported),
+ *   else EUNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+enum { PTGNN_AMD_SSM_FOLD_MAXSUM = 0, PTGNN_AMD_SSM_FOLD_SUM = 1, PTGNN_AMD_SSM_FOLD_DOT = 2 };
+enum { PTGNN_AMD_SSM_LOG_SOFTMAX = 0, PTGNN_AMD_SSM_SOFTMAX = 1, PTGNN_AMD_SSM_LOG_SOFTMAX_BACKWARD = 2,
+       PTGNN_AMD_SSM_SOFTMAX_BACKWARD = 3, PTGNN_AMD_SSM_LOGSUMEXP_BACKWARD = 4 };
+int ptgnn_amd_segment_softmax_supported(int64_t num_segments, int64_t num_elements, int64_t dim);
+size_t ptgnn_amd_segment_softmax_workspace_bytes(int64_t num_segments, int64_t num_elements, int32_t dim, int32_t fold);
+int ptgnn_amd_segment_softmax_state_f32(const float *a, int64_t ld_a, const float *b, int64_t ld_b,
+                                        const int32_t *rowptr, const int32_t *perm, int64_t num_segments,
+                                        int64_t num_elements, int32_t dim, int32_t fold, float eps, float *p0, float *p1,
+                                        float *lse, void *workspace, size_t workspace_bytes, void *stream);
+int ptgnn_amd_segment_softmax_write_f32(const float *a, int64_t ld_a, const float *b, int64_t ld_b, const int64_t *index,
+                                        const float *p0, const float *p1, int64_t num_segments, int64_t num_elements,
+                                        int32_t dim, int32_t mode, float *out, int64_t ld_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * GraphNorm: per-graph normalisation of node states, per graph g with n_g nodes, per column, fp32:
  *   mu[g] = (1/n_g) sum_{i in g} x_i      s_i = x_i - alpha * mu[g]      sig2[g] = (1/n_g) sum_{i in g} s_i^2 + eps
  *   y_i = gamma * s_i / sqrt(sig2[g]) + bias

@@ -28,4 +28,7 @@ def __getattr__(name):
                 "vocabulary_loss", "vocabulary_loss_inputs"):
         from ptgnn_amd import precision
         return getattr(precision, name)
+    if name in ("set_fused_softmax", "fused_softmax"):   # the facade's fused segment-softmax switch (scatter.py)
+        from ptgnn_amd import scatter
+        return getattr(scatter, name)
     raise AttributeError(f"module 'ptgnn_amd' has no attribute {name!r}")

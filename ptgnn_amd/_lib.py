@@ -126,6 +126,12 @@ SIGNATURES = {
     "ptgnn_amd_segment_scores_backward_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32, _i32]),
     "ptgnn_amd_segment_scores_backward_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp,
                                                          _vp, _vp, _vp, _i64, _vp, _vp, _c.c_size_t, _vp]),
+    "ptgnn_amd_segment_softmax_supported": (_c.c_int, [_i64, _i64, _i64]),
+    "ptgnn_amd_segment_softmax_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32, _i32]),
+    "ptgnn_amd_segment_softmax_state_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp,
+                                                       _vp, _vp, _vp, _c.c_size_t, _vp]),
+    "ptgnn_amd_segment_softmax_write_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp,
+                                                       _i64, _vp]),
     "ptgnn_amd_graph_norm_supported": (_c.c_int, [_i32]),
     "ptgnn_amd_graph_norm_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i32]),
     "ptgnn_amd_graph_norm_f32": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp,

@@ -2539,6 +2539,109 @@ def segment_scores_backward(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, s
     return gy, gv
 
 
+SOFTMAX_KINDS = ("softmax", "log_softmax", "logsumexp")
+_SSM_FOLD = {"maxsum": 0, "sum": 1, "dot": 2}             # PTGNN_AMD_SSM_FOLD_*
+_SSM_WRITE = {"log_softmax": 0, "softmax": 1, "log_softmax_backward": 2, "softmax_backward": 3,
+              "logsumexp_backward": 4}                    # PTGNN_AMD_SSM_*
+
+
+def segment_softmax_supported(num_segments: int, num_elements: int, dim: int) -> bool:
+    """Whether the fused segment softmax takes the sizes (ptgnn_amd_segment_softmax_supported: elements, segments and
+    segments * dim each below 2^31)."""
+    return bool(_lib.load().ptgnn_amd_segment_softmax_supported(int(num_segments), int(num_elements), int(dim)))
+
+
+def _segment_softmax_args(what: str, x: torch.Tensor, index: torch.Tensor, plan: GraphPlan, kind: str):
+    if kind not in SOFTMAX_KINDS:
+        raise _lib.PtgnnAmdError(f"{what}: kind must be one of {SOFTMAX_KINDS} (got {kind!r})")
+    _require_cuda_f32("x", x)
+    x = _rowmajor(x)
+    E, D = x.shape
+    if index.dtype != torch.int64 or index.dim() != 1 or index.shape[0] != E or not index.is_cuda \
+            or E != plan.num_edges or plan.perm is None or D < 1:
+        raise _lib.PtgnnAmdError(f"{what}: x {tuple(x.shape)} and an int64 index {tuple(index.shape)} on its device must "
+                                 f"fit a plan of {plan.num_edges} elements")
+    if not segment_softmax_supported(plan.num_nodes, E, D):
+        raise _lib.PtgnnAmdError(f"{what}: {E} elements / {plan.num_nodes} segments / dim {D} are outside the kernels' "
+                                 "range (each of elements, segments and segments * dim below 2^31)")
+    return x, index.contiguous(), E, D, plan.num_nodes
+
+
+def _segment_softmax_state(a, b, plan: GraphPlan, fold: str, eps: float, p0, p1=None, lse=None):
+    """One walk of csrc/segment_softmax.hip over `plan`: p0 (and p1, lse) [n, D] from the element rows a (and b)."""
+    lib = _lib.load()
+    E, D = a.shape
+    n = plan.num_nodes
+    ws_bytes = int(lib.ptgnn_amd_segment_softmax_workspace_bytes(n, E, D, _SSM_FOLD[fold]))
+    ws = _workspace(ws_bytes, a.device)
+    rc = lib.ptgnn_amd_segment_softmax_state_f32(
+        *_rows_arg(a, D), *(_rows_arg(b, D) if b is not None else (None, D)), plan.rowptr.data_ptr(),
+        plan.perm.data_ptr() if E else None, n, E, D, _SSM_FOLD[fold], float(eps), p0.data_ptr(),
+        p1.data_ptr() if p1 is not None else None, lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws_bytes,
+        _stream(p0))
+    _lib.check(rc, "ptgnn_amd_segment_softmax_state_f32")
+
+
+def _segment_softmax_write(a, b, index, p0, p1, n: int, mode: str) -> torch.Tensor:
+    E, D = a.shape
+    out = torch.empty(E, D, dtype=torch.float32, device=a.device)
+    rc = _lib.load().ptgnn_amd_segment_softmax_write_f32(
+        *_rows_arg(a, D), *(_rows_arg(b, D) if b is not None else (None, D)), index.data_ptr() if E else None,
+        p0.data_ptr(), p1.data_ptr() if p1 is not None else None, n, E, D, _SSM_WRITE[mode],
+        out.data_ptr() if E else None, D, _stream(out))
+    _lib.check(rc, "ptgnn_amd_segment_softmax_write_f32")
+    return out
+
+
+def segment_softmax(x: torch.Tensor, index: torch.Tensor, plan: GraphPlan, kind: str, eps: float = 1e-12):
+    """torch_scatter.composite's scatter_softmax / scatter_log_softmax / scatter_logsumexp of fp32 x [E, D] over the
+    int64 `index` [E] whose plan is `plan`, on csrc/segment_softmax.hip: one walk over the plan leaves the state
+    (m, log(sum exp(x - m) + eps)) per (segment, column), one element-parallel pass writes the result -- x is read twice
+    and the result written once, nothing else of size [E, D] exists.  Returns (out, state): out [E, D] for "softmax" /
+    "log_softmax", [n, D] (-inf for a segment without elements) for "logsumexp"; state [2, n, D] = (m, lognorm)."""
+    x, index, E, D, n = _segment_softmax_args("segment_softmax", x, index, plan, kind)
+    state = torch.empty(2, n, D, dtype=torch.float32, device=x.device)
+    lse = torch.empty(n, D, dtype=torch.float32, device=x.device) if kind == "logsumexp" else None
+    if n == 0:
+        return (lse if lse is not None else torch.empty(E, D, dtype=torch.float32, device=x.device)), state
+    plan.wait()
+    moved = (2 * E * D + 2 * n * D + E) if lse is not None else (3 * E * D + 4 * n * D + 3 * E)
+    with _timed("segment_softmax", bytes=4.0 * moved):
+        _segment_softmax_state(x, None, plan, "maxsum", eps, state[0], state[1], lse)
+        out = lse if lse is not None else _segment_softmax_write(x, None, index, state[0], state[1], n, kind)
+    return out, state
+
+
+def segment_softmax_backward(grad: torch.Tensor, index: torch.Tensor, plan: GraphPlan, kind: str,
+                             y: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None,
+                             lse: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d x [E, D] of `segment_softmax` from grad = dL/d out:
+        "log_softmax"  g - exp(y) sum_seg g        "softmax"  y (g - sum_seg g y)        (y: the forward's output)
+        "logsumexp"    x == -inf ? 0 : g[index] exp(x - lse[index])                      (x, lse: its input and output)
+    The per-segment sum is the forward's walk with another fold; the rest is one element-parallel pass."""
+    rows = x if kind == "logsumexp" else y
+    if rows is None or (kind == "logsumexp" and lse is None):
+        raise _lib.PtgnnAmdError("segment_softmax_backward: needs y (softmax, log_softmax) or x and lse (logsumexp)")
+    rows, index, E, D, n = _segment_softmax_args("segment_softmax_backward", rows, index, plan, kind)
+    _require_cuda_f32("grad", grad)
+    grad = _rowmajor(grad)
+    want = (n, D) if kind == "logsumexp" else (E, D)
+    if tuple(grad.shape) != want:
+        raise _lib.PtgnnAmdError(f"segment_softmax_backward: grad {tuple(grad.shape)} must be {want}")
+    if n == 0 or E == 0:
+        return torch.zeros(E, D, dtype=torch.float32, device=rows.device)
+    plan.wait()
+    if kind == "logsumexp":
+        with _timed("segment_softmax_backward", bytes=4.0 * (2 * E * D + 2 * n * D) + 8.0 * E):
+            return _segment_softmax_write(rows, None, index, grad.contiguous(), lse.contiguous(), n,
+                                          "logsumexp_backward")
+    total = torch.empty(n, D, dtype=torch.float32, device=rows.device)
+    with _timed("segment_softmax_backward", bytes=4.0 * ((5 if kind == "softmax" else 4) * E * D + 2 * n * D) + 12.0 * E):
+        _segment_softmax_state(grad, rows if kind == "softmax" else None, plan, "dot" if kind == "softmax" else "sum",
+                               0.0, total)
+        return _segment_softmax_write(grad, rows, index, total, None, n, kind + "_backward")
+
+
 BAG_MODES = {"sum": 0, "mean": 1, "max": 2}
 
 

@@ -321,6 +321,73 @@ def gather_rows(x: torch.Tensor, index: torch.Tensor, plan: "ops.GraphPlan") -> 
     return _GatherRows.apply(x, index, plan)
 
 
+class _SegmentSoftmax(torch.autograd.Function):
+    """scatter_softmax / scatter_log_softmax / scatter_logsumexp of fp32 x [E, D] over the plan of `index` as ONE node on
+    csrc/segment_softmax.hip: the forward is a walk over the plan (the running (max, sum) state) plus one element-parallel
+    write, the backward the same walk with another fold plus one write (logsumexp: the write alone).  Saves the output
+    (softmax, log_softmax) or the input and the output (logsumexp): nothing else of size [E, D]."""
+
+    @staticmethod
+    def forward(ctx, x, index, plan, kind, eps):
+        out, _ = ops.segment_softmax(x, index, plan, kind, eps)
+        ctx.plan, ctx.kind = plan, kind
+        if kind == "logsumexp":
+            ctx.save_for_backward(index, x, out)
+        else:
+            ctx.save_for_backward(index, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        index, *rest = ctx.saved_tensors
+        if ctx.kind == "logsumexp":
+            g = ops.segment_softmax_backward(grad_out.contiguous(), index, ctx.plan, ctx.kind, x=rest[0], lse=rest[1])
+        else:
+            g = ops.segment_softmax_backward(grad_out.contiguous(), index, ctx.plan, ctx.kind, y=rest[0])
+        return g, None, None, None, None
+
+
+def segment_softmax(src: torch.Tensor, index: torch.Tensor, plan: "ops.GraphPlan", kind: str,
+                    eps: float = 1e-12) -> torch.Tensor:
+    """Differentiable fused "softmax" / "log_softmax" ([E, D]) or "logsumexp" ([n, D], -inf for a segment without
+    elements) of fp32 src [E, D] over the int64 `index` [E]; `plan` must be the segment plan of `index` (a caller that
+    already holds it builds no second one).  The facade's formulas: eps is added to the sum taken relative to the
+    segment's maximum.  A segment whose elements are all -inf answers NaN (the softmaxes) / -inf (logsumexp)."""
+    return _SegmentSoftmax.apply(src, index.to(torch.int64), plan, kind, float(eps))
+
+
+_FUSED_SOFTMAX = False
+
+
+def set_fused_softmax(on: bool) -> bool:
+    """Route the GPU branch of `scatter_softmax`, `scatter_log_softmax` and `scatter_logsumexp` through the fused node
+    (`segment_softmax`) instead of the composed chain of segment reduces, gathers and torch operators.  Off by default:
+    the results differ from the chain's by fp32 rounding.  Process-wide; returns the previous setting."""
+    global _FUSED_SOFTMAX
+    previous, _FUSED_SOFTMAX = _FUSED_SOFTMAX, bool(on)
+    return previous
+
+
+class fused_softmax:
+    """`with scatter.fused_softmax():` -- `set_fused_softmax(on)` for the block, the previous setting after it."""
+
+    def __init__(self, on: bool = True):
+        self.on = on
+
+    def __enter__(self):
+        self.previous = set_fused_softmax(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_fused_softmax(self.previous)
+        return False
+
+
+def _fused_softmax_takes(x: torch.Tensor, plan: "ops.GraphPlan") -> bool:
+    # sizes the kernels do not index (2^31 elements / segments / segments * D) stay on the composed route
+    return _FUSED_SOFTMAX and ops.segment_softmax_supported(plan.num_nodes, x.shape[0], x.shape[1])
+
+
 @_any_rank
 def scatter_log_softmax(src, index, dim: int = -1, eps: float = 1e-12,
                         dim_size: Optional[int] = None) -> torch.Tensor:
@@ -332,6 +399,9 @@ def scatter_log_softmax(src, index, dim: int = -1, eps: float = 1e-12,
     x = src2.to(torch.float32)
     if x.shape[0] == 0:
         return src.clone()
+    if _fused_softmax_takes(x, plan):
+        res = segment_softmax(x, index, plan, "log_softmax", eps).to(src.dtype)
+        return res.squeeze(1) if squeeze else res
     with torch.no_grad():   # the shift is a constant of the (shift-invariant) function
         shift = ops.gather_rows(ops.segment_reduce(x.detach(), plan, "max"), index)
     rec = x - shift
@@ -350,6 +420,9 @@ def scatter_softmax(src, index, dim: int = -1, eps: float = 1e-12,
     x = src2.to(torch.float32)
     if x.shape[0] == 0:
         return src.clone()
+    if _fused_softmax_takes(x, plan):
+        res = segment_softmax(x, index, plan, "softmax", eps).to(src.dtype)
+        return res.squeeze(1) if squeeze else res
     with torch.no_grad():
         shift = ops.gather_rows(ops.segment_reduce(x.detach(), plan, "max"), index)
     e = (x - shift).exp()
@@ -370,6 +443,9 @@ def scatter_logsumexp(src, index, dim: int = -1, out=None, dim_size: Optional[in
     n, D = plan.num_nodes, x.shape[1]
     if x.shape[0] == 0:
         res = torch.full((n, D), float("-inf"), dtype=src.dtype, device=src.device)
+        return res.squeeze(1) if squeeze else res
+    if _fused_softmax_takes(x, plan):
+        res = segment_softmax(x, index, plan, "logsumexp", eps).to(src.dtype)
         return res.squeeze(1) if squeeze else res
     with torch.no_grad():
         vals, slot = ops.gather_reduce(x.detach(), plan, D, "max", return_arg=True, type_bits=0, col=plan.perm)
