@@ -262,6 +262,10 @@ enum {
   PTGNN_AMD_KERNEL_LINEAR_ROWS16,                          /* ptgnn_amd_linear_rows16 */
   PTGNN_AMD_KERNEL_AGG16_EPI,                              /* ptgnn_amd_gather_reduce16_epi */
   PTGNN_AMD_KERNEL_EDGE16_DST_ROWS16,                      /* ptgnn_amd_edge_rows16_dst_linear16 */
+  PTGNN_AMD_KERNEL_SEGMENT_REDUCE16,                       /* ptgnn_amd_segment_reduce16 */
+  PTGNN_AMD_KERNEL_SEGMENT_SPREAD16,                       /* ptgnn_amd_segment_spread16 */
+  PTGNN_AMD_KERNEL_EDGE16_TRAIN_ROWS16,                    /* ptgnn_amd_edge_train_rows16_linear16 */
+  PTGNN_AMD_KERNEL_EDGE_WGRAD16_ROWS16,                    /* ptgnn_amd_edge_rows16_weight_grad16 */
   PTGNN_AMD_KERNEL_ROWS16_END_
 };
 /* ... and one for the score-free loss with 16-bit matrix-core inputs (csrc/projection_loss16.hip), so the sixteenth
@@ -1978,6 +1982,88 @@ int ptgnn_amd_linear_weight_grad16_masked(const float *x, int64_t ld_x, int32_t 
                                           int64_t rows, int32_t n_out, int dtype, float *grad_w,
                                           float *grad_b /* nullable */, void *workspace, size_t workspace_bytes,
                                           void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in 16-bit MESSAGE AND GRADIENT ROWS for the GGNN layer's edge-form TRAINING step: the aggregation with an arg over
+ * 16-bit rows and its 16-bit spread (csrc/segment_reduce16.hip), the masked per-edge GEMM reading and / or storing 16-bit
+ * rows (csrc/edge_gemm16.hip, template flags SRC16 / ROWS16 beside MASK) and the weight gradient over 16-bit gradient
+ * rows (csrc/edge_wgrad16.hip, template flag G16).
+ *
+ * Replaces: the [E, .] tensors of gatedmessagepassing.py:57-61 in training as an `enable_amp` user of the reference
+ *   gets them (trainer.py:205,221): the autocast Linear returns 16-bit messages, its output gradient and its input
+ *   gradient are 16-bit too, and the up-cast happens only at the scatter of abstractmessagepassing.py:43-50
+ *   (torch_scatter.scatter on messages.to(torch.float32), whose backward hands a gradient back that autograd casts to the
+ *   messages' 16-bit type).  OFF by default: the host asks with ptgnn_amd.precision.set_half_messages(True,
+ *   training=True) on top of `edge_training=True`; every entry above is what it was.
+ *
+ * ptgnn_amd_segment_reduce16:  out[v, :] = reduce over the CSR slots i of row v of float(rows16[col[i], :]) -- the edge
+ *   form of ptgnn_amd_gather_reduce16 (type_bits 0, `col` the slot -> message row map) over all rows, PLUS, for max / min
+ *   with a non-null `argout` (int32 [num_nodes, msg_dim], contiguous), the winning CSR slot of every (row, column) in the
+ *   format and with the tie rule of ptgnn_amd_gather_reduce_f32 -- what ptgnn_amd_segment_spread_f32 /
+ *   ptgnn_amd_segment_spread16 consume (abstractmessagepassing.py:44-50: torch_scatter's arg_out): the EARLIEST slot
+ *   that holds the extreme value, -1 for an empty row (and for a column no value of which beats the -FLT_MAX / +FLT_MAX
+ *   start).  Rows of up to `hub_threshold` in-edges fold serially in CSR order (sums: the bits of the serial fp32 fold of
+ *   the up-cast values); rows beyond it (0 = none) are folded by a whole workgroup in contiguous runs combined in run
+ *   order inside the same launch: max / min and their arg are exact everywhere, such a row's sum differs from the serial
+ *   order by fp32 rounding only.  No atomics, deterministic.
+ *   ptgnn_amd_segment_reduce16_supported(msg_dim, dtype): msg_dim % 32 == 0, msg_dim <= 256, a known dtype; no device.
+ *   rows16, out and argout 16-byte aligned, ld_rows % 8 == 0, ld_out % 4 == 0 (PTGNN_AMD_EUNSUPPORTED otherwise); argout
+ *   with sum / mean, bad sizes / enums / null pointers answer PTGNN_AMD_EINVAL; messages start "segment_reduce16:" and
+ *   answer before anything touches the device.
+ *
+ * ptgnn_amd_segment_spread16:  the backward of that reduce w.r.t. the messages, as 16-bit rows in MESSAGE order:
+ *       out16[perm[s], c] = rnd(g[slot_row[s], c])                                      sum
+ *                           rnd(g[slot_row[s], c] * (1.0f / deg(slot_row[s])))          mean: one IEEE fp32 division per
+ *                                                                                       row, one fp32 multiply per value
+ *                           arg[slot_row[s], c] == s ? rnd(g[slot_row[s], c]) : +0      max / min
+ *   for every CSR slot s < num_slots; g fp32 [N, dim] (ld_grad), slot_row / perm as ptgnn_amd_segment_spread_f32 takes
+ *   them, rowptr (mean only) the plan's, arg (max / min only) the reduce's argout; one rounding to nearest even, as
+ *   tensor.to(dtype); every message row is written exactly once.  No [N, dim] temporary is needed for the mean.
+ *   ptgnn_amd_segment_spread16_supported(dim, dtype): dim % 32 == 0, dim <= 256, a known dtype; no device.
+ *   grad, arg and out16 16-byte aligned, ld_grad % 4 == 0, ld_out % 8 == 0 (elements); messages start
+ *   "segment_spread16:"; error codes as above.
+ *
+ * ptgnn_amd_edge_train_rows16_linear16:  ptgnn_amd_edge_masked_linear16 with a 16-bit source and / or a 16-bit store.
+ *   x_rows16 != 0: `x` is 16-bit rows of `dtype` (ld_x in elements, 16-byte aligned rows) and the fragments / the LDS
+ *   panel are filled straight from them -- the bits of the fp32-source launch on the up-cast rows, whose rounding is the
+ *   identity there.  msg_rows16 != 0: `msg` is 16-bit rows of `dtype` (4-byte aligned, even ld_msg) holding
+ *   rnd(final fp32 value) -- in mode 2 after mask and scale -- i.e. `fp32-output launch(...).to(dtype)`.  The forms of the
+ *   training step: mode 1 with fp32 x and 16-bit msg (the forward with dropout; without dropout the forward is
+ *   ptgnn_amd_edge_rows16_linear16), modes 0 and 2 with 16-bit x and either store (the input gradient over an identity
+ *   index); a dropout mode needs dropout_p > 0 and mask_bits.
+ *   ptgnn_amd_edge_train_rows16_linear16_supported(state_dim, msg_dim, num_types, dtype, mode, x_rows16, msg_rows16):
+ *   one of those forms within the limits of ptgnn_amd_edge_linear16_supported; no device.  Messages start
+ *   "edge_linear16: train rows16:"; error codes as ptgnn_amd_edge_masked_linear16.
+ *
+ * ptgnn_amd_edge_rows16_weight_grad16:  ptgnn_amd_edge_weight_grad16 over grad_msg rows that are 16-bit values of `dtype`
+ *   (ld_grad_msg in elements, 16-byte aligned rows): the g half of the panel is filled straight from them; x is gathered,
+ *   masked, scaled and rounded as there; same workspace, chunks and reduction order: the bits of the fp32 entry on the
+ *   up-cast rows.  ptgnn_amd_edge_rows16_weight_grad16_supported = ptgnn_amd_edge_weight_grad16_supported.  Messages start
+ *   "edge_weight_grad16:".
+ * Additive: the ABI version stays.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_segment_reduce16_supported(int32_t msg_dim, int dtype);
+int ptgnn_amd_segment_reduce16(const void *rows16, int64_t ld_rows, int dtype, const int32_t *rowptr, const int32_t *col,
+                               int64_t num_nodes, int32_t msg_dim, int reduce, float *out, int64_t ld_out,
+                               int32_t *argout /* nullable */, int64_t num_edges, int32_t hub_threshold, void *stream);
+int ptgnn_amd_segment_spread16_supported(int32_t dim, int dtype);
+int ptgnn_amd_segment_spread16(const float *grad, int64_t ld_grad, const int32_t *arg /* nullable */,
+                               const int32_t *rowptr /* nullable */, const int32_t *slot_row, const int32_t *perm,
+                               int64_t num_slots, int32_t dim, int reduce, int dtype, void *out16, int64_t ld_out,
+                               void *stream);
+int ptgnn_amd_edge_train_rows16_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype,
+                                                   int dropout_mode, int x_rows16, int msg_rows16);
+int ptgnn_amd_edge_train_rows16_linear16(const void *x, int x_rows16, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                         const int64_t *const *src_per_type, const int64_t *edges_per_type, const void *w,
+                                         int32_t num_types, int32_t msg_dim, int dtype, void *msg, int msg_rows16,
+                                         int64_t ld_msg, int dropout_mode, float dropout_p,
+                                         const uint32_t *mask_bits /* nullable */, void *stream);
+int ptgnn_amd_edge_rows16_weight_grad16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types, int dtype);
+int ptgnn_amd_edge_rows16_weight_grad16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                        const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                        const void *grad_msg16, int64_t ld_grad_msg, int32_t num_types, int32_t msg_dim,
+                                        int dtype, float dropout_p, const uint32_t *mask_bits /* nullable */,
+                                        float *grad_w, void *workspace, size_t workspace_bytes, void *stream);
 
 #pragma GCC visibility pop
 

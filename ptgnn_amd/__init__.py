@@ -24,7 +24,8 @@ def __getattr__(name):
     if name in ("set_matrix_inputs", "get_matrix_inputs", "matrix_inputs", "edge_gemm_inputs", "training_inputs",
                 "edge_training_inputs", "mlp_inputs", "attention_inputs", "set_attention_training",
                 "attention_training", "attention_training_inputs", "attention_linear_inputs", "set_half_messages", "get_half_messages",
-                "half_messages", "message_rows", "get_half_messages_mlp", "mlp_message_rows", "set_vocabulary_loss",
+                "half_messages", "message_rows", "get_half_messages_mlp", "mlp_message_rows", "training_message_rows",
+                "set_vocabulary_loss",
                 "vocabulary_loss", "vocabulary_loss_inputs"):
         from ptgnn_amd import precision
         return getattr(precision, name)

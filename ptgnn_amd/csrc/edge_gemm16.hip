@@ -14,6 +14,10 @@
 //   ptgnn_amd_edge_masked_linear16 : the per-edge form with the dropout mask from its keep bits (template flag MASK) --
 //                                    1: on the gathered input before it is rounded (the forward); 2: on the fp32
 //                                    accumulator before the store (the input gradient, over an identity index)
+//   ptgnn_amd_edge_train_rows16_linear16 : the masked forms for the 16-bit rows of the training step (template flags
+//                                    SRC16 / ROWS16 beside MASK): the A rows read as 16-bit values already in memory (the
+//                                    incoming 16-bit grad_msg of the input gradient) and / or the result stored as 16-bit
+//                                    rows -- rnd(final fp32 value), after mask and scale
 // The DST form runs
 // over the same two kernels (template flag DST): the unit carries a second id list, W_t is [M, 2 H], and the chain runs
 // over the source half and then over the target half into the same accumulators.  k_edge16_ws takes it at 2 H in
@@ -68,6 +72,9 @@ struct Edge16Args {
   // the row-storing forms (template flag ROWS16): the messages leave as 16-bit rows of the operand type, rounded in the
   // fragment epilogue (half16.h store_frag_rows16); ld_msg is then in 16-bit elements and `msg` is unused
   uint16_t *msg16;
+  // the 16-bit-source forms (template flag SRC16): the A rows are 16-bit values of the operand type already (ld_x in
+  // 16-bit elements; `x` is unused): fragments and the LDS panel are filled straight from them, no conversion
+  const uint16_t *x16;
 };
 
 // The id lists are global memory; read out of a table in device memory the pointers would be generic and their loads
@@ -92,6 +99,11 @@ struct Unit {
   }
   __device__ __forceinline__ const float *dst_row(const float *x, int64_t ld_x, int64_t num_rows, int r) const {
     return row_of(dst_ids, x, ld_x, num_rows, r);
+  }
+  // ... of a 16-bit source (SRC16)
+  __device__ __forceinline__ const uint16_t *row16(const uint16_t *x, int64_t ld_x, int64_t num_rows, int r) const {
+    const int64_t id = ids[r < left ? r : left - 1];
+    return x + (id < 0 ? 0 : (id < num_rows ? id : num_rows - 1)) * ld_x;
   }
 };
 template <bool DST = false>
@@ -140,6 +152,31 @@ __device__ __forceinline__ void wave_tile_masked(const float *__restrict__ arow,
   }
 }
 
+// wave_tile (half16.h) over a row that is 16-bit values of type DT already (SRC16): the fragment is the memory order, one
+// 16-byte load per k-step, no conversion.  The same chain: one accumulator per tile, zeroed, k ascending in steps of 16.
+template <int DT, int TILES>
+__device__ __forceinline__ void wave_tile_src16(const uint16_t *__restrict__ arow, const uint16_t *__restrict__ w, int K,
+                                                int col0, int tiles, f32x16 (&acc)[TILES]) {
+  using H = Half16<DT>;
+  const int li = frag_li(), hi = frag_hi();
+  const uint16_t *ap = arow + 8 * hi;
+  const uint16_t *bp[TILES];
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) {
+    const int tc = t < tiles ? t : tiles - 1;
+    bp[t] = w + (int64_t)(col0 + tc * 32 + li) * K + 8 * hi;
+    zero(acc[t]);
+  }
+  for (int kk = 0; kk < K; kk += 32) {
+#pragma unroll
+    for (int k0 = kk; k0 < kk + 32; k0 += 16) {
+      const typename H::vec a = load8<DT>(ap + k0);
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) acc[t] = H::mfma(a, load8<DT>(bp[t] + k0), acc[t]);
+    }
+  }
+}
+
 // DST (both kernels): the message input is [x[src] | x[dst]] and W_t is [M, 2 H] -- one chain over the source half, then
 // over the target half, into the same accumulators.
 // MASK (both kernels; per-edge form without a target half, no activation): the per-edge dropout of the training step from
@@ -147,8 +184,11 @@ __device__ __forceinline__ void wave_tile_masked(const float *__restrict__ arow,
 // store (the input gradient).  0: no mask -- the code of the unmasked instantiations is what it was.
 // ROWS16 (both kernels; unmasked, with or without a target half): the accumulators are those of the fp32-output launch and
 // leave rounded to the operand type as 16-bit message rows -- the bits of `msg.to(dtype)`, whichever kernel and launch
-// form ran.
-template <int DT, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
+// form ran.  With MASK 2 the stored value is rnd(keep ? accumulator * scale : 0): one rounding, after mask and scale.
+// SRC16 (both kernels; per-edge form, MASK 0 or 2): the A rows are 16-bit values of the operand type in memory (the
+// training step's 16-bit grad_msg) -- the chain of the fp32-source launch on the up-cast rows without its rounding, which
+// is the identity on such values: the same bits.
+template <int DT, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false, bool SRC16 = false>
 __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
@@ -170,6 +210,8 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
       for (int n = 0; n < kTiles; ++n) zero(acc[n]);
       wave_tile_more<DT>(q.row(p.x, p.ld_x, p.num_rows, li), w, 2 * p.H, p.H, col0, tiles, acc);
       wave_tile_more<DT>(q.dst_row(p.x, p.ld_x, p.num_rows, li), w + p.H, 2 * p.H, p.H, col0, tiles, acc);
+    } else if constexpr (SRC16) {
+      wave_tile_src16<DT>(q.row16(p.x16, p.ld_x, p.num_rows, li), p.w + (int64_t)q.t * p.M * p.H, p.H, col0, tiles, acc);
     } else if constexpr (MASK == 1) {   // the mask row of a row past the type's end: the last row's, like the gather
       const uint32_t *mrow = p.mask + (q.out0 + (li < q.left ? li : q.left - 1)) * p.mask_ld;
       wave_tile_masked<DT>(q.row(p.x, p.ld_x, p.num_rows, li), mrow, p.scale, p.w + (int64_t)q.t * p.M * p.H, p.H, col0,
@@ -181,7 +223,14 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
     for (int n = 0; n < kTiles; ++n) {
       if (n < tiles) {
         const int col = col0 + n * 32 + li;
-        if constexpr (ROWS16) {
+        if constexpr (ROWS16 && MASK == 2) {   // a row past the type's end reads the last row's keep word; never stored
+          const int hi = frag_hi();
+          store_frag_rows16<DT>(p.msg16, p.ld_msg, q.out0, q.out0 + q.left, col, [&](int r) {
+            const int fr = frag_row(r, hi);
+            const int64_t row = q.out0 + (fr < q.left ? fr : q.left - 1);
+            return keep_scaled(acc[n][r], p.mask[row * p.mask_ld + (col >> 5)], li, p.scale);
+          });
+        } else if constexpr (ROWS16) {
           store_frag_rows16<DT>(p.msg16, p.ld_msg, q.out0, q.out0 + q.left, col,
                                 [&](int r) { return act_runtime(acc[n][r], p.act); });
         } else
@@ -196,12 +245,13 @@ __global__ __launch_bounds__(256) void k_edge16(Edge16Args p) {
   }
 }
 
-template <int DT, int KS, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
+template <int DT, int KS, bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false, bool SRC16 = false>
 __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   using Hf = Half16<DT>;
   using vec = typename Hf::vec;
   constexpr int H = 16 * KS;             // the K of the chain = the panel's width; DST: 2 x state_dim
-  RoundedPanel<DT, 32, H> panel;
+  using Panel = std::conditional_t<SRC16, RawPanel<DT, 32, H>, RoundedPanel<DT, 32, H>>;
+  Panel panel;
 
   const StreamEdgeTable *tabp;
   if constexpr (INDIRECT) tabp = p.tab_dev; else tabp = &p.tab;
@@ -219,9 +269,12 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
   // first gather compiles to a branch per id and the four id -> row chains of the prologue run one after the other.
   const float *const x = p.x;
   const int64_t ld_x = p.ld_x, num_rows = p.num_rows;
+  const uint16_t *const x16 = p.x16;
   auto rows_of = [=](const Unit &q) {
     return [=](int r, int c) {
-      if constexpr (DST)                 // a panel row is [x[src] | x[dst]]; a float4 never straddles (H / 2 % 4 == 0)
+      if constexpr (SRC16)               // a 16-byte vector of the 16-bit row: 8 values
+        return q.row16(x16, ld_x, num_rows, r) + c;
+      else if constexpr (DST)                 // a panel row is [x[src] | x[dst]]; a float4 never straddles (H / 2 % 4 == 0)
         return c < H / 2 ? q.row(x, ld_x, num_rows, r) + c : q.dst_row(x, ld_x, num_rows, r) + (c - H / 2);
       else
         return q.row(x, ld_x, num_rows, r) + c;
@@ -230,7 +283,6 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
 
   // MASK 1: one keep word per staged float4 (8 threads share a word: one request) rides with the unit's rows and is
   // consumed while they are rounded into the panel -- the kept values scaled in fp32 before the one rounding.
-  using Panel = RoundedPanel<DT, 32, H>;
   const uint32_t *const mask = p.mask;
   const int mask_ld = p.mask_ld;
   const float scale = p.scale;
@@ -274,7 +326,12 @@ __global__ __launch_bounds__(256) void k_edge16_ws(Edge16Args p) {
       zero(acc);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) acc = Hf::mfma(panel.frag(li, ks), bw[ks], acc);
-      if constexpr (ROWS16) {
+      if constexpr (ROWS16 && MASK == 2) {
+        store_frag_rows16<DT>(p.msg16, p.ld_msg, cur.out0, cur.out0 + cur.left, j, [&](int r) {
+          const uint32_t lo = __builtin_amdgcn_readlane(mrow, frag_row(r, 0)), up = __builtin_amdgcn_readlane(mrow, frag_row(r, 1));
+          return keep_scaled(acc[r], hi ? up : lo, li, scale);
+        });
+      } else if constexpr (ROWS16) {
         store_frag_rows16<DT>(p.msg16, p.ld_msg, cur.out0, cur.out0 + cur.left, j,
                               [&](int r) { return act_runtime(acc[r], p.act); });
       } else
@@ -361,11 +418,11 @@ int host_table(const char *who, const int64_t *const *src_per_type, const int64_
 // Workgroups of a weight-stationary instance that one CU holds at once (registers and LDS decide; asked once).  The
 // launch is ONE such round: measured at the cfg3 layer shapes, any grid that needs a partly filled second round loses
 // 15 - 20 % to it (profiles/edge_inputs_notes.md).
-template <int DT, int KS, bool INDIRECT, bool DST, int MASK, bool ROWS16>
+template <int DT, int KS, bool INDIRECT, bool DST, int MASK, bool ROWS16, bool SRC16>
 int ws_resident_per_cu() {
   static const int per_cu = [] {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST, MASK, ROWS16>, 256, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_edge16_ws<DT, KS, INDIRECT, DST, MASK, ROWS16, SRC16>, 256, 0) != hipSuccess ||
         n < 1) {
       (void)hipGetLastError();
       n = 2;
@@ -377,9 +434,10 @@ int ws_resident_per_cu() {
 
 // `units` < 0: unknown on the host (shared form) -- the launch is sized for the device, workgroups without units leave
 // DST: the chain is 2 H long, so the weight-stationary register budgets (KS = 8, 16) hold H in {64, 128}
-template <bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false>
+template <bool INDIRECT, bool DST = false, int MASK = 0, bool ROWS16 = false, bool SRC16 = false>
 int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
-  static_assert(!ROWS16 || MASK == 0, "16-bit message rows: the unmasked forms");
+  static_assert(!(MASK != 0 || SRC16) || (!INDIRECT && !DST), "masks and 16-bit sources: the per-edge form, no target half");
+  static_assert(!(SRC16 && MASK == 1), "the forward gathers fp32 states");
   const int64_t cus = num_compute_units();
   const int k = DST ? 2 * p.H : p.H;
   const bool ws = (k == 128 || k == 256 || (!DST && k == 64)) && p.M <= 128 &&
@@ -389,9 +447,9 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
     with_dtype(dtype, [&](auto dt) {
       auto run = [&](auto ks) {
         constexpr int DT = decltype(dt)::value, KS = decltype(ks)::value;
-        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST, MASK, ROWS16>());
+        int64_t grid = cus * (knob ? knob : ws_resident_per_cu<DT, KS, INDIRECT, DST, MASK, ROWS16, SRC16>());
         if (units >= 0 && units < grid) grid = units;
-        k_edge16_ws<DT, KS, INDIRECT, DST, MASK, ROWS16><<<(unsigned)grid, 256, 0, st>>>(p);
+        k_edge16_ws<DT, KS, INDIRECT, DST, MASK, ROWS16, SRC16><<<(unsigned)grid, 256, 0, st>>>(p);
       };
       if constexpr (DST) with_case<8, 16>(k / 16, run); else with_case<4, 8, 16>(k / 16, run);
     });
@@ -400,9 +458,13 @@ int launch(const Edge16Args &p, int dtype, int64_t units, hipStream_t st) {
     int64_t grid = cus * 8;
     if (units >= 0 && (units * col_groups + 3) / 4 < grid) grid = (units * col_groups + 3) / 4;
     with_dtype(dtype,
-               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST, MASK, ROWS16><<<(unsigned)grid, 256, 0, st>>>(p); });
+               [&](auto dt) { k_edge16<decltype(dt)::value, INDIRECT, DST, MASK, ROWS16, SRC16><<<(unsigned)grid, 256, 0, st>>>(p); });
   }
   PTGNN_LAUNCH_CHECK();
+  if ((ROWS16 && MASK != 0) || SRC16) {
+    count_launch(PTGNN_AMD_KERNEL_EDGE16_TRAIN_ROWS16);
+    return PTGNN_AMD_OK;
+  }
   if (ROWS16) {
     count_launch(DST ? PTGNN_AMD_KERNEL_EDGE16_DST_ROWS16
                      : (INDIRECT ? PTGNN_AMD_KERNEL_EDGE16_SHARED_ROWS16 : PTGNN_AMD_KERNEL_EDGE16_ROWS16));
@@ -574,4 +636,64 @@ extern "C" int ptgnn_amd_edge_shared_rows16_linear16(const float *x, int64_t ld_
   p.x = x; p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
   p.H = state_dim; p.M = msg_dim; p.act = act; p.msg16 = static_cast<uint16_t *>(msg16); p.ld_msg = ld_msg;
   return launch<true, false, 0, true>(p, dtype, -1, (hipStream_t)stream_);
+}
+
+// The training step's forms over 16-bit rows (contract: include/ptgnn_amd.h).
+static bool train_rows16_ok(int dropout_mode, int x_rows16, int msg_rows16) {
+  if (x_rows16) return dropout_mode == 0 || dropout_mode == 2;   // the input gradient: 16-bit grad_msg in, either store
+  return dropout_mode == 1 && msg_rows16;                          // the forward with dropout: fp32 states in, 16-bit out
+}
+
+extern "C" int ptgnn_amd_edge_train_rows16_linear16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types,
+                                                              int dtype, int dropout_mode, int x_rows16,
+                                                              int msg_rows16) {
+  return train_rows16_ok(dropout_mode, x_rows16, msg_rows16) && dtype_ok(dtype) &&
+                 shape_ok(state_dim, msg_dim, num_types) ? 1 : 0;
+}
+
+extern "C" int ptgnn_amd_edge_train_rows16_linear16(const void *x, int x_rows16, int64_t ld_x, int64_t num_rows,
+                                                    int32_t state_dim, const int64_t *const *src_per_type,
+                                                    const int64_t *edges_per_type, const void *w, int32_t num_types,
+                                                    int32_t msg_dim, int dtype, void *msg, int msg_rows16, int64_t ld_msg,
+                                                    int dropout_mode, float dropout_p, const uint32_t *mask_bits,
+                                                    void *stream_) {
+  PTGNN_REQUIRE(dropout_mode >= 0 && dropout_mode <= 2 && dropout_p >= 0.f && dropout_p < 1.f, PTGNN_AMD_EINVAL,
+                "edge_linear16: train rows16: bad dropout mode / probability");
+  PTGNN_REQUIRE(dropout_mode == 0 || (dropout_p > 0.f && mask_bits != nullptr), PTGNN_AMD_EINVAL,
+                "edge_linear16: train rows16: a dropout mode needs dropout_p > 0 and mask_bits");
+  if (const int rc = check_shape(" train rows16:", state_dim, num_types, msg_dim, PTGNN_AMD_ACT_NONE, dtype)) return rc;
+  PTGNN_REQUIRE(train_rows16_ok(dropout_mode, x_rows16, msg_rows16), PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: train rows16: mode %d with x_rows16=%d msg_rows16=%d is not a form of the training step "
+                "(16-bit x: modes 0 and 2; fp32 x: mode 1 storing 16-bit rows)", dropout_mode, x_rows16, msg_rows16);
+  Edge16Args p{};
+  int64_t units = 0;
+  if (const int rc = host_table(" train rows16:", src_per_type, nullptr, edges_per_type, num_types, false, p.tab, units))
+    return rc;
+  if (units == 0) return PTGNN_AMD_OK;                       // no rows: no launch
+  PTGNN_REQUIRE(x && w && msg, PTGNN_AMD_EINVAL, "edge_linear16: train rows16: null pointer");
+  PTGNN_REQUIRE(num_rows > 0 && ld_x >= state_dim && ld_msg >= msg_dim, PTGNN_AMD_EINVAL,
+                "edge_linear16: train rows16: num_rows must be positive, ld_x >= state_dim and ld_msg >= msg_dim");
+  PTGNN_REQUIRE((x_rows16 ? rows16_half(x, ld_x) : rows16(x, ld_x)) && aligned16(w) && aligned4(msg) &&
+                    (!msg_rows16 || ld_msg % 2 == 0),
+                PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: train rows16: x and w must be 16-byte aligned with 16-byte rows of x (ld_x=%lld), msg "
+                "4-byte aligned (16-bit rows: an even ld_msg=%lld)", (long long)ld_x, (long long)ld_msg);
+  PTGNN_REQUIRE(dropout_mode == 0 || aligned4(mask_bits), PTGNN_AMD_EUNSUPPORTED,
+                "edge_linear16: train rows16: mask_bits must be 4-byte aligned");
+  p.ld_x = ld_x; p.num_rows = num_rows; p.w = static_cast<const uint16_t *>(w);
+  p.H = state_dim; p.M = msg_dim; p.act = PTGNN_AMD_ACT_NONE; p.ld_msg = ld_msg;
+  if (x_rows16) p.x16 = static_cast<const uint16_t *>(x); else p.x = static_cast<const float *>(x);
+  if (msg_rows16) p.msg16 = static_cast<uint16_t *>(msg); else p.msg = static_cast<float *>(msg);
+  if (dropout_mode != 0) {
+    p.mask = mask_bits;
+    p.mask_ld = (dropout_mode == 2 ? msg_dim : state_dim) / 32;
+    p.scale = 1.0f / (1.0f - dropout_p);
+  }
+  hipStream_t st = (hipStream_t)stream_;
+  if (dropout_mode == 1) return launch<false, false, 1, true, false>(p, dtype, units, st);
+  if (dropout_mode == 2)
+    return msg_rows16 ? launch<false, false, 2, true, true>(p, dtype, units, st)
+                      : launch<false, false, 2, false, true>(p, dtype, units, st);
+  return msg_rows16 ? launch<false, false, 0, true, true>(p, dtype, units, st)
+                    : launch<false, false, 0, false, true>(p, dtype, units, st);
 }

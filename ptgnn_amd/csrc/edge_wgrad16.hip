@@ -5,6 +5,11 @@
 //
 // on v_mfma_f32_32x32x16_{bf16,f16}, fp32 accumulation; g_t = the type's rows of grad_msg.  Entry points
 //   ptgnn_amd_edge_weight_grad16          : the product
+//   ptgnn_amd_edge_rows16_weight_grad16   : the product over grad_msg rows that are 16-bit values already (template flag
+//                                           G16: the g half of the panel is filled straight from them -- one 8-byte vector
+//                                           per slot, parked as it is; the x half is gathered, masked, scaled and rounded
+//                                           as before).  The bits of the fp32 entry on the up-cast rows: its rounding of g
+//                                           is the identity on 16-bit values.
 //   ptgnn_amd_edge_wgrad16_workspace_bytes: bytes of partials the call needs
 //   ptgnn_amd_edge_wgrad16_chunk_edges    : edges one workgroup partial covers; no device needed
 //   ptgnn_amd_edge_weight_grad16_supported: the shapes
@@ -71,9 +76,9 @@ inline int64_t chunk_edges_for(int64_t edges, int m, int h) {
   return c > kMinChunk ? c : kMinChunk;
 }
 
-template <int DT, int TN, bool MASK>
+template <int DT, int TN, bool MASK, bool G16 = false>
 __global__ __launch_bounds__(256) void k_edge_wgrad16(EdgeWgrad16Table tab, const float *__restrict__ x, int64_t ld_x,
-                                                      int64_t num_rows, int H, const float *__restrict__ g,
+                                                      int64_t num_rows, int H, const void *__restrict__ g_,
                                                       int64_t ld_g, int M, int64_t chunk_edges, int jtiles, int tiles,
                                                       const uint32_t *__restrict__ mask, float scale,
                                                       float *__restrict__ grad_w, float *__restrict__ partial) {
@@ -84,6 +89,8 @@ __global__ __launch_bounds__(256) void k_edge_wgrad16(EdgeWgrad16Table tab, cons
   using Panel = RoundedPanel<DT, kPE, KT, LD>;
   constexpr int NJ = TN / 32, WJ = NJ >= 2 ? 2 : 1, WM = 4 / WJ, SM = 4 / WM, SJ = NJ / WJ;
   Panel panel;
+  using GElem = std::conditional_t<G16, uint16_t, float>;   // ld_g counts these
+  const GElem *const g = static_cast<const GElem *>(g_);
 
   const int wave = threadIdx.x >> 6, li = frag_li();
   const int wm = wave / WJ, wn = wave % WJ;
@@ -133,10 +140,10 @@ __global__ __launch_bounds__(256) void k_edge_wgrad16(EdgeWgrad16Table tab, cons
     if (c >= kTM) v = keep_scaled4(v, mw[i], (c - kTM) & 31, scale);   // j0 % 32 == 0
   };
   auto rows_of = [&](int64_t p) {        // panel p: [grad_msg columns m0 .. | x columns j0 ..] of edges e0 + 32 p ..
-    return [&, p](int i, int r, int c) {
+    return [&, p](int i, int r, int c) -> const void * {
       const int gc = m0 + c < M ? m0 + c : m0 + c % 32;                   // a sub-tile past M: a live one, not stored
-      return c < kTM ? g + (row0 + e0 + p * kPE + r) * ld_g + gc          // row < e1 wherever fetch dereferences
-                     : x + (int64_t)nid[i] * ld_x + j0 + (c - kTM);
+      if (c < kTM) return g + (row0 + e0 + p * kPE + r) * ld_g + gc;      // row < e1 wherever fetch dereferences
+      return x + (int64_t)nid[i] * ld_x + j0 + (c - kTM);
     };
   };
   auto live_of = [&](int64_t p) {
@@ -150,14 +157,17 @@ __global__ __launch_bounds__(256) void k_edge_wgrad16(EdgeWgrad16Table tab, cons
 #pragma unroll
     for (int b = 0; b < SJ; ++b) zero(acc[a][b]);
 
+  constexpr int RAWC = G16 ? kTM : 0;    // the panel columns that are 16-bit in memory
   fetch_ids(0);
-  panel.fetch_slots(rows_of(0), live_of(0));
+  if constexpr (G16) panel.template fetch_slots_raw<RAWC>(rows_of(0), live_of(0));
+  else panel.fetch_slots(rows_of(0), live_of(0));
   if constexpr (MASK) fetch_mask(0);
   fetch_ids(1);
   if constexpr (MASK) panel.edit(drop);
-  panel.start();
+  if constexpr (G16) panel.template start_raw<RAWC>(); else panel.start();
   for (int64_t p = 0; p < num_panels; ++p) {
-    panel.fetch_slots(rows_of(p + 1), live_of(p + 1));  // past the last panel: live = 0, zeros, no load
+    if constexpr (G16) panel.template fetch_slots_raw<RAWC>(rows_of(p + 1), live_of(p + 1));
+    else panel.fetch_slots(rows_of(p + 1), live_of(p + 1));  // past the last panel: live = 0, zeros, no load
     if constexpr (MASK) fetch_mask(p + 1);
     fetch_ids(p + 2);
 #pragma unroll
@@ -173,7 +183,7 @@ __global__ __launch_bounds__(256) void k_edge_wgrad16(EdgeWgrad16Table tab, cons
         for (int b = 0; b < SJ; ++b) acc[a][b] = Hf::mfma(av[a], bv[b], acc[a][b]);
     }
     if constexpr (MASK) panel.edit(drop);
-    panel.flip();
+    if constexpr (G16) panel.template flip_raw<RAWC>(); else panel.flip();
   }
 
   // the tile: register r of sub-tile (a, b) is grad_w[t][m0 + 32 (wm SM + a) + frag_row(r)][j0 + 32 (wn SJ + b) + li];
@@ -245,11 +255,13 @@ extern "C" size_t ptgnn_amd_edge_wgrad16_workspace_bytes(int64_t num_edges, int3
   return (size_t)chunks * (size_t)msg_dim * (size_t)state_dim * sizeof(float);
 }
 
-extern "C" int ptgnn_amd_edge_weight_grad16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
-                                            const int64_t *const *src_per_type, const int64_t *edges_per_type,
-                                            const float *grad_msg, int64_t ld_grad_msg, int32_t num_types,
-                                            int32_t msg_dim, int dtype, float dropout_p, const uint32_t *mask_bits,
-                                            float *grad_w, void *workspace, size_t workspace_bytes, void *stream_) {
+// both entries; G16: grad_msg is 16-bit rows of `dtype` (ld_grad_msg in 16-bit elements)
+template <bool G16>
+static int edge_weight_grad16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                              const int64_t *const *src_per_type, const int64_t *edges_per_type, const void *grad_msg,
+                              int64_t ld_grad_msg, int32_t num_types, int32_t msg_dim, int dtype, float dropout_p,
+                              const uint32_t *mask_bits, float *grad_w, void *workspace, size_t workspace_bytes,
+                              void *stream_) {
   PTGNN_REQUIRE(num_types > 0 && state_dim > 0 && msg_dim > 0, PTGNN_AMD_EINVAL, "edge_weight_grad16: bad sizes");
   PTGNN_REQUIRE(dtype_ok(dtype), PTGNN_AMD_EINVAL, "edge_weight_grad16: dtype %d is neither PTGNN_AMD_HALF_BF16 nor _F16",
                 dtype);
@@ -274,9 +286,10 @@ extern "C" int ptgnn_amd_edge_weight_grad16(const float *x, int64_t ld_x, int64_
   PTGNN_REQUIRE(num_rows > 0 && ld_x >= state_dim && ld_grad_msg >= msg_dim, PTGNN_AMD_EINVAL,
                 "edge_weight_grad16: num_rows must be positive, ld_x >= state_dim and ld_grad_msg >= msg_dim");
   PTGNN_REQUIRE(num_rows < ((int64_t)1 << 31), PTGNN_AMD_EUNSUPPORTED, "edge_weight_grad16: too many rows of x");
-  PTGNN_REQUIRE(rows16(x, ld_x) && rows16(grad_msg, ld_grad_msg), PTGNN_AMD_EUNSUPPORTED,
-                "edge_weight_grad16: x and grad_msg must be 16-byte aligned with ld %% 4 == 0 (ld_x=%lld, "
-                "ld_grad_msg=%lld)", (long long)ld_x, (long long)ld_grad_msg);
+  PTGNN_REQUIRE(rows16(x, ld_x) && (G16 ? rows16_half(grad_msg, ld_grad_msg) : rows16(grad_msg, ld_grad_msg)),
+                PTGNN_AMD_EUNSUPPORTED,
+                "edge_weight_grad16: x and grad_msg must be 16-byte aligned with rows a multiple of 16 bytes apart "
+                "(ld_x=%lld, ld_grad_msg=%lld)", (long long)ld_x, (long long)ld_grad_msg);
   const bool masked = mask_bits != nullptr && dropout_p > 0.f;
   PTGNN_REQUIRE(!masked || aligned4(mask_bits), PTGNN_AMD_EUNSUPPORTED,
                 "edge_weight_grad16: mask_bits must be 4-byte aligned");
@@ -312,11 +325,11 @@ extern "C" int ptgnn_amd_edge_weight_grad16(const float *x, int64_t ld_x, int64_
     with_case<128, 64, 32>(tn, [&](auto tnc) {
       constexpr int DT = decltype(dt)::value, TN = decltype(tnc)::value;
       if (masked)
-        k_edge_wgrad16<DT, TN, true><<<(unsigned)blocks, 256, 0, st>>>(tab, x, ld_x, num_rows, state_dim, grad_msg,
+        k_edge_wgrad16<DT, TN, true, G16><<<(unsigned)blocks, 256, 0, st>>>(tab, x, ld_x, num_rows, state_dim, grad_msg,
                                                                       ld_grad_msg, msg_dim, ch, jtiles, (int)tiles,
                                                                       mask_bits, scale, grad_w, partial);
       else
-        k_edge_wgrad16<DT, TN, false><<<(unsigned)blocks, 256, 0, st>>>(tab, x, ld_x, num_rows, state_dim, grad_msg,
+        k_edge_wgrad16<DT, TN, false, G16><<<(unsigned)blocks, 256, 0, st>>>(tab, x, ld_x, num_rows, state_dim, grad_msg,
                                                                        ld_grad_msg, msg_dim, ch, jtiles, (int)tiles,
                                                                        nullptr, scale, grad_w, partial);
     });
@@ -326,6 +339,31 @@ extern "C" int ptgnn_amd_edge_weight_grad16(const float *x, int64_t ld_x, int64_
   k_edge_wgrad16_reduce<<<(unsigned)((per_type4 * num_types * kSplit + 255) / 256), 256, 0, st>>>(tab.chunks, partial,
                                                                                                  per_type4, grad_w);
   PTGNN_LAUNCH_CHECK();
-  count_launch(PTGNN_AMD_KERNEL_EDGE_WGRAD16);
+  count_launch(G16 ? PTGNN_AMD_KERNEL_EDGE_WGRAD16_ROWS16 : PTGNN_AMD_KERNEL_EDGE_WGRAD16);
   return PTGNN_AMD_OK;
+}
+
+extern "C" int ptgnn_amd_edge_weight_grad16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                            const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                            const float *grad_msg, int64_t ld_grad_msg, int32_t num_types,
+                                            int32_t msg_dim, int dtype, float dropout_p, const uint32_t *mask_bits,
+                                            float *grad_w, void *workspace, size_t workspace_bytes, void *stream_) {
+  return edge_weight_grad16<false>(x, ld_x, num_rows, state_dim, src_per_type, edges_per_type, grad_msg, ld_grad_msg,
+                                   num_types, msg_dim, dtype, dropout_p, mask_bits, grad_w, workspace, workspace_bytes,
+                                   stream_);
+}
+
+extern "C" int ptgnn_amd_edge_rows16_weight_grad16_supported(int32_t state_dim, int32_t msg_dim, int32_t num_types,
+                                                             int dtype) {
+  return ptgnn_amd_edge_weight_grad16_supported(state_dim, msg_dim, num_types, dtype);
+}
+
+extern "C" int ptgnn_amd_edge_rows16_weight_grad16(const float *x, int64_t ld_x, int64_t num_rows, int32_t state_dim,
+                                                   const int64_t *const *src_per_type, const int64_t *edges_per_type,
+                                                   const void *grad_msg16, int64_t ld_grad_msg, int32_t num_types,
+                                                   int32_t msg_dim, int dtype, float dropout_p, const uint32_t *mask_bits,
+                                                   float *grad_w, void *workspace, size_t workspace_bytes, void *stream_) {
+  return edge_weight_grad16<true>(x, ld_x, num_rows, state_dim, src_per_type, edges_per_type, grad_msg16, ld_grad_msg,
+                                  num_types, msg_dim, dtype, dropout_p, mask_bits, grad_w, workspace, workspace_bytes,
+                                  stream_);
 }

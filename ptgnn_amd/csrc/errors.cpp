@@ -177,7 +177,8 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
   if (kernel_id >= PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PROJECTION_LOSS_END_)
     return projection_loss_names[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS_FIRST_];
   static const char *const rows16_names[PTGNN_AMD_KERNEL_ROWS16_END_ - PTGNN_AMD_KERNEL_ROWS16_FIRST_] = {
-      "agg16", "edge16_rows16", "edge16_shared_rows16", "linear_rows16", "agg16_epi", "edge16_dst_rows16"};
+      "agg16", "edge16_rows16", "edge16_shared_rows16", "linear_rows16", "agg16_epi", "edge16_dst_rows16",
+      "segment_reduce16", "segment_spread16", "edge16_train_rows16", "edge_wgrad16_rows16"};
   if (kernel_id >= PTGNN_AMD_KERNEL_ROWS16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_ROWS16_END_)
     return rows16_names[kernel_id - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
   static const char *const projection_loss16_names[PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_ -

@@ -342,6 +342,104 @@ struct RoundedPanel {
     __syncthreads();                     // the other buffer is complete; everyone is done reading this one
     cur ^= 1;
   }
+  // The walk of a panel whose columns below RAWC come from rows that are ALREADY 16-bit values of type DT in memory
+  // (edge_wgrad16.hip over 16-bit gradient rows): src(i, r, c) of such a slot points at its 4 16-bit values, which are
+  // loaded as one 8-byte vector into the slot's first two words and parked as they are -- no conversion, no rounding;
+  // the other slots are fp32 and rounded as everywhere.  fetch_slots_raw; edit(fn); start_raw(); and per panel
+  // fetch_slots_raw(next); MFMAs; edit(fn); flip_raw();
+  template <int RAWC, class Src>
+  __device__ __forceinline__ void fetch_slots_raw(Src &&src, int live) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256, c = (v % RV) * 4;
+      stage[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (v / RV < live) {
+        if (c < RAWC) {
+          const float2 t = *reinterpret_cast<const float2 *>(src(i, v / RV, c));
+          stage[i].x = t.x;
+          stage[i].y = t.y;
+        } else {
+          stage[i] = *reinterpret_cast<const float4 *>(src(i, v / RV, c));
+        }
+      }
+    }
+  }
+  template <int RAWC>
+  __device__ __forceinline__ void park_raw(int buf) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256, c = (v % RV) * 4;
+      uint16_t *at = buffer(buf) + (v / RV) * LD + c;
+      if (c < RAWC) {
+        *reinterpret_cast<float2 *>(at) = make_float2(stage[i].x, stage[i].y);
+      } else {
+        const f32x4 f = {stage[i].x, stage[i].y, stage[i].z, stage[i].w};
+        *reinterpret_cast<half4 *>(at) = __builtin_convertvector(f, half4);
+      }
+    }
+  }
+  template <int RAWC>
+  __device__ __forceinline__ void start_raw() {
+    park_raw<RAWC>(0);
+    __syncthreads();
+    cur = 0;
+  }
+  template <int RAWC>
+  __device__ __forceinline__ void flip_raw() {
+    park_raw<RAWC>(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+};
+
+// The row panel of a source that is ALREADY 16-bit values of type DT in memory (edge_gemm16.hip over 16-bit gradient
+// rows): the LDS image, the fragments and the two-buffer walk of RoundedPanel, filled with 16-byte vectors of 8 values
+// straight from the 16-bit rows -- no conversion.  src(r, c) is the address of the 8 values at row r, columns c .. c + 7.
+template <int DT, int ROWS, int KT, int LD_ = KT + 8>
+struct RawPanel {
+  using vec = typename Half16<DT>::vec;
+  static constexpr int LD = LD_;                // LDS row stride in 16-bit elements
+  static constexpr int RV = KT / 8;             // 16-byte vectors per panel row
+  static constexpr int NV = ROWS * RV / 256;    // vectors per thread and panel
+  static_assert(ROWS * RV % 256 == 0 && LD >= KT && (LD / 8) % 2 == 1, "panel shape");
+
+  vec stage[NV];
+  int cur;
+
+  static __device__ __forceinline__ uint16_t *buffer(int buf) {
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2][ROWS * LD];
+    return lds[buf];
+  }
+  template <class Src>
+  __device__ __forceinline__ void fetch(Src &&src) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      stage[i] = *reinterpret_cast<const vec *>(src(v / RV, (v % RV) * 8));
+    }
+  }
+  __device__ __forceinline__ void park(int buf) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = threadIdx.x + i * 256;
+      *reinterpret_cast<vec *>(buffer(buf) + (v / RV) * LD + (v % RV) * 8) = stage[i];
+    }
+  }
+  template <class Src>
+  __device__ __forceinline__ void prime(Src &&src) {
+    fetch(src);
+    park(0);
+    __syncthreads();
+    cur = 0;
+  }
+  __device__ __forceinline__ vec frag(int row, int ks) const {
+    return *reinterpret_cast<const vec *>(buffer(cur) + row * LD + ks * 16 + 8 * frag_hi());
+  }
+  __device__ __forceinline__ void flip() {
+    park(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
 };
 
 inline bool dtype_ok(int dtype) { return dtype == PTGNN_AMD_HALF_BF16 || dtype == PTGNN_AMD_HALF_F16; }
@@ -349,6 +447,8 @@ inline bool dtype_ok(int dtype) { return dtype == PTGNN_AMD_HALF_BF16 || dtype =
 // a float matrix the fragment loads can read: 16-byte aligned base, rows a multiple of 16 bytes apart
 inline bool rows16(const void *p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
 inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+// a 16-bit matrix whose rows the 16-byte vector loads can read: 16-byte aligned base, rows a multiple of 8 elements apart
+inline bool rows16_half(const void *p, int64_t ld) { return aligned16(p) && ld % 8 == 0; }
 
 // Host dispatch of a runtime value onto template arguments: calls fn(std::integral_constant<int, V>) for the V among
 // Vs that equals v.  False: none does.

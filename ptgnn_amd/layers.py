@@ -68,7 +68,8 @@ from ptgnn_amd import _lib, dense, ops, precision, torch_route
 from ptgnn_amd.scatter import (block_attention as block_attention_autograd, edge_linear as edge_linear_autograd,
                                edge_linear_feat as edge_linear_feat_autograd,
                                gather_reduce as gather_reduce_autograd, graph_norm as graph_norm_autograd,
-                               pna_aggregate as pna_aggregate_autograd, scatter_mean, segment_reduce)
+                               pna_aggregate as pna_aggregate_autograd, scatter_mean, segment_reduce,
+                               training_rows16_supported)
 
 try:  # inside a ptgnn install the layers ARE ptgnn layers
     from ptgnn.neuralmodels.gnn.messagepassing.abstractmessagepassing import (  # type: ignore
@@ -236,14 +237,20 @@ def _dropout_seed() -> int:
 
 
 def _train_edge_messages(owner, x, plan, weights, use_dst: bool, p: float = 0.0, seed_xor: int = 0, key: str = "edge_w",
-                         inputs=None):
+                         inputs=None, rows=None, reduce: str = "sum"):
     """Training, edge form: the grouped per-edge GEMM as one autograd node (forward + both gradients on HIP) over the
     per-type weights stacked once per forward scope, with the reference's per-edge input dropout folded in as a hash
     mask (one seed draw per call with p > 0; `seed_xor` tells the ranks of a sharded graph apart).  `inputs`: the 16-bit
-    operand type of the node's three GEMMs (precision.edge_training_inputs; None / float32: the fp32 node)."""
+    operand type of the node's three GEMMs (precision.edge_training_inputs; None / float32: the fp32 node).  `rows`:
+    the 16-bit type of the step's [E, .] rows (precision.training_message_rows) ahead of the aggregation `reduce`; it is
+    honoured where every launch of the step takes the call (scatter.training_rows16_supported), else the rows stay fp32,
+    silently."""
     w_stack = _scoped(owner, key, lambda: torch.stack(weights))
+    if rows not in (None, torch.float32) and not (rows == inputs and not use_dst and training_rows16_supported(
+            x, plan, w_stack, reduce, p, rows)):
+        rows = None
     return edge_linear_autograd(x, plan, w_stack, use_dst, p, (_dropout_seed() ^ seed_xor) if p > 0 else 0,
-                                inputs=inputs)
+                                inputs=inputs, rows=rows)
 
 
 _AMP_DTYPES = (torch.float16, torch.bfloat16)
@@ -535,8 +542,11 @@ class GatedMessagePassingLayer(AbstractMessagePassingLayer):
             # training, edge form: grouped per-edge GEMM with the reference's per-edge input dropout
             # folded in (forward + both gradients on HIP), HIP segment reduce, torch GRU cell.  The node's three GEMMs
             # take 16-bit operands when the matrix-input setting was made with edge_training=True.
+            # Under `precision.half_messages(training=True)` the step's [E, .] tensors (messages, grad_msg, the input
+            # gradient) are 16-bit rows wherever every launch takes the shape.
             agg = segment_reduce(_train_edge_messages(self, node_states, plan, ws, False, p,
-                                                      inputs=precision.edge_training_inputs(node_states)),
+                                                      inputs=precision.edge_training_inputs(node_states),
+                                                      rows=precision.training_message_rows(node_states), reduce=agg_fn),
                                  plan, agg_fn)
         elif self._table_ok(node_states, edge_features):
             # training without per-edge dropout, few edge types: differentiable HIP GEMM nodes (ptgnn_amd/dense.py)

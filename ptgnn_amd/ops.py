@@ -120,7 +120,9 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     matrix-core inputs (projection_loss16, projection_loss16_backward); `rows16=True` the opt-in 16-bit message rows (agg16: the
     aggregation over them; edge16_rows16, edge16_shared_rows16, linear_rows16: the producers that store them; agg16_epi:
     the MLP-MP aggregation with a destination term and / or an epilogue; edge16_dst_rows16: the per-edge GEMM with a
-    target-state half storing them); `panel16=True` the panel-form 16-bit Linear of the attention layer's training step
+    target-state half storing them; segment_reduce16, segment_spread16, edge16_train_rows16, edge_wgrad16_rows16: the
+    edge-form training step's aggregation with an arg, its 16-bit spread, the masked per-edge GEMM reading / storing 16-bit
+    rows and the weight gradient over 16-bit gradient rows); `panel16=True` the panel-form 16-bit Linear of the attention layer's training step
     (panel_linear16, panel_linear16_grad_input, half_wgrad_masked)."""
     lib = _lib.load()
     out = {}
@@ -1651,13 +1653,25 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     `mask_bits`, or with dropout and a target half, a 16-bit `inputs` raises, and with `use_dst` it wants GPU states.
     `rows` = the same 16-bit type (no dropout, no edge features): the messages are stored as 16-bit rows of that type,
     `msg.to(rows)` bit for bit (ptgnn_amd_edge_rows16_linear16, with `use_dst` ptgnn_amd_edge_rows16_dst_linear16;
-    `gather_reduce` reads them); raises where the 16-bit launch does not take the call."""
+    `gather_reduce` reads them); raises where the 16-bit launch does not take the call.
+    The edge-form training step's 16-bit rows (ptgnn_amd_edge_train_rows16_linear16; no target half, no activation):
+    `rows` together with `dropout` mode 1 and `mask_bits` stores the masked forward's messages as 16-bit rows, and an `x`
+    that is already 16-bit rows of the `inputs` type (the incoming 16-bit grad_msg of the input gradient, dropout mode 2
+    or none) is read as it is -- the bits of the call on `x.float()` -- with fp32 or, under `rows`, 16-bit output rows
+    (rounded once, after mask and scale)."""
     half = _half_inputs(inputs)
     dropping = dropout is not None and dropout[0] != 0 and dropout[1] > 0.0
     rows16 = _half_rows(rows, half, "edge_linear")
-    if rows16 is not None and (dropping or
-                               (edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats))):
-        raise _lib.PtgnnAmdError("edge_linear: 16-bit message rows take no dropout or edge features")
+    has_feats = edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats)
+    if rows16 is not None and (has_feats or (dropping and (mask_bits is None or use_dst))):
+        raise _lib.PtgnnAmdError("edge_linear: 16-bit message rows take no edge features, and dropout only as mask_bits "
+                                 "without a target-state half")
+    if x.dtype in HALF_IDS or (rows16 is not None and dropping):
+        if half is None or x.dtype not in (half, torch.float32) or use_dst or act is not None or has_feats:
+            raise _lib.PtgnnAmdError(f"edge_linear: 16-bit rows of x need `inputs` of their type ({x.dtype}), no target "
+                                     "half, no activation and no edge features")
+        return _edge_linear_train_rows16(x, adjacency_lists, weights, dropout if dropping else None, mask_bits, half,
+                                         rounded, rows16 is not None)
     if half is not None and edge_feats is not None and any(f is not None and f.shape[-1] > 0 for f in edge_feats):
         raise _lib.PtgnnAmdError("edge_linear: 16-bit inputs take neither dropout nor edge features")
     if half is not None and dropping and (use_dst or mask_bits is None):
@@ -1790,6 +1804,61 @@ def edge_linear(x: torch.Tensor, adjacency_lists, weights: Sequence[torch.Tensor
     return msg[:E] if E > 0 else msg[:0]
 
 
+def edge_linear16_train_rows16_supported(state_dim: int, msg_dim: int, num_types: int, dtype, mode: int, x_rows16: bool,
+                                         msg_rows16: bool) -> bool:
+    """Whether the masked per-edge GEMM takes the form and shape with a 16-bit source and / or a 16-bit store
+    (ptgnn_amd_edge_train_rows16_linear16_supported; needs no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_edge_train_rows16_linear16_supported(
+        int(state_dim), int(msg_dim), int(num_types), HALF_IDS[dtype], int(mode), int(bool(x_rows16)),
+        int(bool(msg_rows16))))
+
+
+def _edge_linear_train_rows16(x, adjacency_lists, weights, dropout, mask_bits, half, rounded, msg_rows16: bool):
+    """`edge_linear` over / into the 16-bit rows of the edge-form training step: one launch of
+    ptgnn_amd_edge_train_rows16_linear16, or an error -- never another kernel."""
+    lib = _lib.load()
+    x16 = x.dtype in HALF_IDS
+    if not x.is_cuda or x.dim() != 2:
+        raise _lib.PtgnnAmdError(f"edge_linear: x must be a 2-D GPU tensor (got {tuple(x.shape)} on {x.device})")
+    x = _rowmajor(x)
+    T, H, M = len(adjacency_lists), x.shape[1], weights[0].shape[0]
+    mode = int(dropout[0]) if dropout is not None else 0
+    counts = [int(a[0].shape[0]) for a in adjacency_lists]
+    E = sum(counts)
+    aligned = x.data_ptr() % 16 == 0 and _ld(x) % (8 if x16 else 4) == 0
+    if not (edge_linear16_train_rows16_supported(H, M, T, half, mode, x16, msg_rows16) and aligned):
+        raise _lib.PtgnnAmdError(f"edge_linear: the 16-bit training rows take dropout mode 1 on float32 x storing 16-bit "
+                                 f"rows, or mode 2 / no dropout on 16-bit x, at a shape the 16-bit GEMM takes with 16-byte "
+                                 f"aligned rows (mode {mode}, x {x.dtype}, state_dim={H}, msg_dim={M}, {T} edge types)")
+    ws = [w.detach().contiguous() for w in weights]
+    for w in ws:
+        if tuple(w.shape) != (M, H) or not w.is_cuda or w.dtype != torch.float32:
+            raise _lib.PtgnnAmdError(f"edge_linear: weight shape {tuple(w.shape)} does not match [{M}, {H}]")
+    if mode != 0:
+        words = (M if mode == 2 else H) // 32
+        if (mask_bits is None or tuple(mask_bits.shape) != (E, words) or mask_bits.dtype != torch.int32
+                or not mask_bits.is_cuda):
+            raise _lib.PtgnnAmdError(f"edge_linear: mask_bits must be int32 [{E}, {words}] on the device")
+        mask_bits = mask_bits.contiguous()
+    srcs = [a[0].contiguous() for a in adjacency_lists]
+    PtrArr, CntArr = ctypes.c_void_p * T, ctypes.c_int64 * T
+    sp = PtrArr(*[s_.data_ptr() if s_.numel() else None for s_ in srcs])
+    cn = CntArr(*counts)
+    w16 = _edge16_stack(ws, half, rounded)
+    msg = torch.empty(max(E, 1), M, dtype=half if msg_rows16 else torch.float32, device=x.device)
+    with _timed("edge_linear16_train_rows16", flops=2.0 * E * H * M,
+                bytes=E * ((2.0 if x16 else 4.0) * H + (2.0 if msg_rows16 else 4.0) * M) + 2.0 * T * M * H + 8.0 * E
+                + (4.0 * E * ((M if mode == 2 else H) // 32) if mode else 0.0)):
+        rc = lib.ptgnn_amd_edge_train_rows16_linear16(
+            x.data_ptr(), int(x16), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p),
+            ctypes.cast(cn, ctypes.c_void_p), w16.data_ptr(), T, M, HALF_IDS[half], msg.data_ptr(), int(msg_rows16), M,
+            mode, float(dropout[1]) if mode else 0.0, mask_bits.data_ptr() if mode else None, _stream(msg))
+    _lib.check(rc, "ptgnn_amd_edge_train_rows16_linear16")
+    return msg[:E] if E > 0 else msg[:0]
+
+
 def _edge_linear_feat(x, adjacency_lists, weights, use_dst: bool, act, edge_feats) -> torch.Tensor:
     """The grouped per-edge GEMM with feature rows as a third K range of its A operand: nothing of the reference's
     [E, H (+H) + F] message input is materialised.  Feature widths that are not a multiple of 4 are zero-padded (the
@@ -1847,10 +1916,15 @@ def edge_weight_grad(x: torch.Tensor, adjacency_lists, grad_msg: torch.Tensor, u
     `inputs` = torch.bfloat16 / torch.float16: both operands -- grad_msg and the gathered, masked, scaled x -- are rounded
     to that type in the kernel and multiplied on the 16-bit matrix cores (ptgnn_amd_edge_weight_grad16: fp32 accumulation
     and output, deterministic) where `edge_weight_grad16_supported` takes the shape, there is no target half, the rows are
-    16-byte aligned and dropout (if any) comes with `mask_bits`; otherwise the fp32 kernels run, silently."""
+    16-byte aligned and dropout (if any) comes with `mask_bits`; otherwise the fp32 kernels run, silently.
+    A `grad_msg` that is already 16-bit rows of the `inputs` type (the edge-form training step's 16-bit grad_msg) is read
+    as it is by ptgnn_amd_edge_rows16_weight_grad16 -- the bits of the call on `grad_msg.float()` -- and raises where that
+    launch does not take the call."""
     lib = _lib.load()
     _require_cuda_f32("x", x)
-    _require_cuda_f32("grad_msg", grad_msg)
+    g16 = grad_msg.dtype in HALF_IDS
+    if not g16:
+        _require_cuda_f32("grad_msg", grad_msg)
     x, grad_msg = _rowmajor(x), _rowmajor(grad_msg)
     T, H, M = len(adjacency_lists), x.shape[1], grad_msg.shape[1]
     K = H * (2 if use_dst else 1)
@@ -1866,8 +1940,17 @@ def edge_weight_grad(x: torch.Tensor, adjacency_lists, grad_msg: torch.Tensor, u
     cn = CntArr(*counts)
     grad_w = torch.empty(T, M, K, dtype=torch.float32, device=x.device)
     half = _half_inputs(inputs)
-    if (half is not None and not use_dst and E > 0 and (dropout_p <= 0.0 or mask_bits is not None)
-            and edge_weight_grad16_supported(H, M, T, half) and _half_rows_ok(x) and _half_rows_ok(grad_msg)):
+    if g16:
+        if (half != grad_msg.dtype or use_dst or not grad_msg.is_cuda or (dropout_p > 0.0 and mask_bits is None)
+                or not edge_weight_grad16_supported(H, M, T, half) or not _half_rows_ok(x)
+                or grad_msg.data_ptr() % 16 != 0 or _ld(grad_msg) % 8 != 0):
+            raise _lib.PtgnnAmdError(f"edge_weight_grad: 16-bit grad_msg rows need `inputs` of their type "
+                                     f"({grad_msg.dtype}), no target half, dropout as mask_bits, a shape the 16-bit "
+                                     f"kernel takes (state_dim={H}, msg_dim={M}, {T} edge types) and 16-byte aligned rows")
+        if E == 0:
+            return grad_w.zero_()
+    if g16 or (half is not None and not use_dst and E > 0 and (dropout_p <= 0.0 or mask_bits is not None)
+               and edge_weight_grad16_supported(H, M, T, half) and _half_rows_ok(x) and _half_rows_ok(grad_msg)):
         if dropout_p > 0.0:
             if tuple(mask_bits.shape) != (E, H // 32) or mask_bits.dtype != torch.int32 or not mask_bits.is_cuda:
                 raise _lib.PtgnnAmdError(f"edge_weight_grad: mask_bits must be int32 [{E}, {H // 32}] on the device")
@@ -1875,15 +1958,16 @@ def edge_weight_grad(x: torch.Tensor, adjacency_lists, grad_msg: torch.Tensor, u
         ws_bytes = lib.ptgnn_amd_edge_wgrad16_workspace_bytes(E, T, M, H)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
         # roofline bytes: the fp32 operand rows once, the ids, the mask, the result, and the partials written and read once
-        with _timed("edge_weight_grad16", flops=2.0 * E * H * M,
-                    bytes=4.0 * (E * H + E * M + T * M * H) + 8.0 * E + (E * H / 8.0 if dropout_p > 0.0 else 0.0)
-                    + 2.0 * ws_bytes):
-            rc = lib.ptgnn_amd_edge_weight_grad16(
+        entry = lib.ptgnn_amd_edge_rows16_weight_grad16 if g16 else lib.ptgnn_amd_edge_weight_grad16
+        with _timed("edge_weight_grad16_rows16" if g16 else "edge_weight_grad16", flops=2.0 * E * H * M,
+                    bytes=4.0 * (E * H + T * M * H) + (2.0 if g16 else 4.0) * E * M + 8.0 * E
+                    + (E * H / 8.0 if dropout_p > 0.0 else 0.0) + 2.0 * ws_bytes):
+            rc = entry(
                 x.data_ptr(), _ld(x), x.shape[0], H, ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(cn, ctypes.c_void_p),
                 grad_msg.data_ptr(), _ld(grad_msg), T, M, HALF_IDS[half], float(dropout_p),
                 mask_bits.data_ptr() if dropout_p > 0.0 else None, grad_w.data_ptr(), ws.data_ptr(), ws_bytes,
                 _stream(grad_w))
-        _lib.check(rc, "ptgnn_amd_edge_weight_grad16")
+        _lib.check(rc, "ptgnn_amd_edge_rows16_weight_grad16" if g16 else "ptgnn_amd_edge_weight_grad16")
         return grad_w
     ws_bytes = lib.ptgnn_amd_edge_wgrad_workspace_bytes(E, T, M, K)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
@@ -2123,6 +2207,87 @@ def segment_spread(grad: torch.Tensor, arg: Optional[torch.Tensor], plan: GraphP
                                               plan.slot_rows().data_ptr(), plan.perm.data_ptr(), E, D,
                                               out.data_ptr(), D, _stream(out))
     _lib.check(rc, "ptgnn_amd_segment_spread_f32")
+    return out
+
+
+def segment_reduce16_supported(msg_dim: int, dtype) -> bool:
+    """Whether the training step's aggregation over 16-bit message rows (with an arg for max / min) takes the width
+    (ptgnn_amd_segment_reduce16_supported; needs no device): msg_dim % 32 == 0, msg_dim <= 256, bfloat16 / float16."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_segment_reduce16_supported(int(msg_dim), HALF_IDS[dtype]))
+
+
+def segment_spread16_supported(dim: int, dtype) -> bool:
+    """Whether the 16-bit spread takes the width (ptgnn_amd_segment_spread16_supported; needs no device)."""
+    if dtype not in HALF_IDS:
+        return False
+    return bool(_lib.load().ptgnn_amd_segment_spread16_supported(int(dim), HALF_IDS[dtype]))
+
+
+def segment_reduce16(rows: torch.Tensor, plan: GraphPlan, reduce: str, return_arg: bool = False):
+    """out[v] = reduce over the plan's slots of v of float(rows[perm[slot]]): the aggregation of the edge-form training
+    step over 16-bit message rows [E, M] in message order (ptgnn_amd_segment_reduce16), fp32 accumulation and output.
+    `return_arg` (max / min): also the int32 [N, M] winning slot of every (row, column), -1 for an empty row -- the
+    format and tie rule of `gather_reduce(..., return_arg=True)`: the earliest slot that holds the extreme value."""
+    lib = _lib.load()
+    if reduce not in REDUCE_IDS:
+        raise ValueError(f"unknown aggregation function {reduce!r}")
+    if rows.dtype not in HALF_IDS or not rows.is_cuda or rows.dim() != 2:
+        raise _lib.PtgnnAmdError(f"segment_reduce16: rows must be a 2-D bfloat16 / float16 GPU tensor (got {rows.dtype} "
+                                 f"{tuple(rows.shape)} on {rows.device})")
+    if return_arg and reduce not in ("max", "min"):
+        raise _lib.PtgnnAmdError("segment_reduce16: an arg output exists for max / min only")
+    if rows.shape[0] != plan.num_edges:
+        raise _lib.PtgnnAmdError(f"segment_reduce16: {rows.shape[0]} message rows for a plan of {plan.num_edges} edges")
+    rows = _rowmajor(rows)
+    M, N = rows.shape[1], plan.num_nodes
+    if not segment_reduce16_supported(M, rows.dtype) or rows.data_ptr() % 16 != 0 or _ld(rows) % 8 != 0:
+        raise _lib.PtgnnAmdError(f"segment_reduce16: needs msg_dim % 32 == 0, msg_dim <= 256 and 16-byte aligned rows "
+                                 f"(msg_dim={M}, row stride {_ld(rows)})")
+    out = torch.empty(N, M, dtype=torch.float32, device=rows.device)
+    arg = torch.empty(N, M, dtype=torch.int32, device=rows.device) if return_arg else None
+    plan.wait()
+    nbytes = plan.num_edges * (2.0 * M + 4) + N * (4.0 * M + 4) + (N * 4.0 * M if return_arg else 0.0)
+    with _timed("segment_reduce16", bytes=nbytes):
+        rc = lib.ptgnn_amd_segment_reduce16(_ptr_or(rows, plan.rowptr), _ld(rows), HALF_IDS[rows.dtype],
+                                            plan.rowptr.data_ptr(), plan.perm.data_ptr(), N, M, REDUCE_IDS[reduce],
+                                            out.data_ptr(), M, arg.data_ptr() if return_arg else None, plan.num_edges,
+                                            HUB_THRESHOLD, _stream(out))
+    _lib.check(rc, "ptgnn_amd_segment_reduce16")
+    return (out, arg) if return_arg else out
+
+
+def segment_spread16(grad: torch.Tensor, arg: Optional[torch.Tensor], plan: GraphPlan, reduce: str, dtype) -> torch.Tensor:
+    """Backward of `segment_reduce16` w.r.t. the messages as 16-bit rows: fp32 [N, D] row gradients -> `dtype` [E, D]
+    in message order, rounded once to nearest even.  sum: rnd(g[dst]); mean: rnd(g[dst] * (1.0f / deg)) -- the reciprocal
+    formed by one fp32 division, then one fp32 multiply per value, inside the kernel; max / min: rnd(g[dst]) at the slot
+    `arg` names, +0 elsewhere."""
+    lib = _lib.load()
+    if reduce not in REDUCE_IDS:
+        raise ValueError(f"unknown aggregation function {reduce!r}")
+    _require_cuda_f32("grad", grad)
+    grad = _rowmajor(grad)
+    E, D = plan.num_edges, grad.shape[1]
+    minmax = reduce in ("max", "min")
+    if minmax != (arg is not None):
+        raise _lib.PtgnnAmdError("segment_spread16: max / min take the forward's arg, sum / mean take none")
+    if not segment_spread16_supported(D, dtype) or grad.data_ptr() % 16 != 0 or _ld(grad) % 4 != 0:
+        raise _lib.PtgnnAmdError(f"segment_spread16: needs dim % 32 == 0, dim <= 256, a 16-bit dtype and 16-byte aligned "
+                                 f"rows (dim={D}, dtype={dtype})")
+    out = torch.empty(E, D, dtype=dtype, device=grad.device)
+    if E == 0:
+        return out
+    if arg is not None:
+        if tuple(arg.shape) != (plan.num_nodes, D) or arg.dtype != torch.int32 or not arg.is_cuda:
+            raise _lib.PtgnnAmdError(f"segment_spread16: arg must be int32 [{plan.num_nodes}, {D}] on the device")
+        arg = arg.contiguous()
+    plan.wait()
+    with _timed("segment_spread16", bytes=E * (2.0 * D + 8) + plan.num_nodes * 4.0 * D * (2 if arg is not None else 1)):
+        rc = lib.ptgnn_amd_segment_spread16(grad.data_ptr(), _ld(grad), arg.data_ptr() if arg is not None else None,
+                                            plan.rowptr.data_ptr(), plan.slot_rows().data_ptr(), plan.perm.data_ptr(), E,
+                                            D, REDUCE_IDS[reduce], HALF_IDS[dtype], out.data_ptr(), D, _stream(out))
+    _lib.check(rc, "ptgnn_amd_segment_spread16")
     return out
 
 

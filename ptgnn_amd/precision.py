@@ -243,6 +243,7 @@ _attention_training = False
 _attention_linears = False
 _half_messages = False
 _half_messages_mlp = False
+_half_messages_training = False
 _vocabulary_loss = False
 
 
@@ -385,18 +386,20 @@ def vocabulary_loss_inputs(tensor: torch.Tensor) -> torch.dtype:
     return resolve(tensor) if _vocabulary_loss and tensor.is_cuda else torch.float32
 
 
-def set_half_messages(on, mlp=False) -> bool:
+def set_half_messages(on, mlp=False, training=False) -> bool:
     """Whether the GGNN inference route stores its messages as 16-bit rows of the dtype setting and aggregates them with
-    the 16-bit-row kernel -- and, with `mlp=True`, whether the MLP-MP layer's inference routes do too; returns the
-    previous value of the first.  A setting of its own: `set_matrix_inputs` / `matrix_inputs` neither read nor reset it.
-    Every call without the keyword means `mlp=False`."""
-    return _set_half_messages(on, mlp)[0]
+    the 16-bit-row kernel -- with `mlp=True`, whether the MLP-MP layer's inference routes do too, and with
+    `training=True`, whether the GGNN edge-form training step keeps its messages, their gradient and the per-edge input
+    gradient as 16-bit rows; returns the previous value of the first.  A setting of its own: `set_matrix_inputs` /
+    `matrix_inputs` neither read nor reset it.  Every call without a keyword means `mlp=False, training=False`."""
+    return _set_half_messages(on, mlp, training)[0]
 
 
-def _set_half_messages(on, mlp):
-    global _half_messages, _half_messages_mlp
-    prev = (_half_messages, _half_messages_mlp)
-    _half_messages, _half_messages_mlp = bool(on), bool(on) and bool(mlp)
+def _set_half_messages(on, mlp, training=False):
+    global _half_messages, _half_messages_mlp, _half_messages_training
+    prev = (_half_messages, _half_messages_mlp, _half_messages_training)
+    _half_messages, _half_messages_mlp, _half_messages_training = \
+        bool(on), bool(on) and bool(mlp), bool(on) and bool(training)
     return prev
 
 
@@ -411,8 +414,8 @@ def get_half_messages_mlp() -> bool:
 
 
 @contextlib.contextmanager
-def half_messages(on=True, mlp=False):
-    prev = _set_half_messages(on, mlp)
+def half_messages(on=True, mlp=False, training=False):
+    prev = _set_half_messages(on, mlp, training)
     try:
         yield
     finally:
@@ -435,3 +438,12 @@ def mlp_message_rows(tensor: torch.Tensor) -> torch.dtype:
     if not (_half_messages and _half_messages_mlp) or not tensor.is_cuda or tensor.dtype != torch.float32:
         return torch.float32
     return mlp_inputs(tensor)
+
+
+def training_message_rows(tensor: torch.Tensor) -> torch.dtype:
+    """The dtype of the [E, .] rows of the GGNN edge-form training step (messages, their gradient, the per-edge input
+    gradient) for a layer call on the states `tensor`: `edge_training_inputs(tensor)` when `set_half_messages` is on with
+    `training=True`, that is a 16-bit type and the states are fp32 on a GPU; else float32."""
+    if not (_half_messages and _half_messages_training) or not tensor.is_cuda or tensor.dtype != torch.float32:
+        return torch.float32
+    return edge_training_inputs(tensor)

@@ -50,6 +50,32 @@ class _SegmentReduce(torch.autograd.Function):
         return ops.segment_spread(grad_out, arg, plan), None, None
 
 
+class _SegmentReduce16(torch.autograd.Function):
+    """16-bit messages [E, D] (type-major edge order) --plan--> fp32 [N, D]; the backward hands a 16-bit grad_msg back
+    (the edge-form training step under `precision.half_messages(training=True)`): the reference's scatter on
+    messages.to(float32) (abstractmessagepassing.py:43-50), whose gradient autograd casts to the messages' type.
+    forward : ops.segment_reduce16 (fp32 accumulation; max / min keep the winning slot);
+    backward: ops.segment_spread16 -- rnd(g[dst]), the mean's 1 / deg folded in before the one rounding, max / min only
+              at the winning slot."""
+
+    @staticmethod
+    def forward(ctx, messages, plan, reduce):
+        need_arg = reduce in ("max", "min") and messages.requires_grad
+        res = ops.segment_reduce16(messages, plan, reduce, return_arg=need_arg)
+        ctx.plan, ctx.reduce, ctx.dtype = plan, reduce, messages.dtype
+        if need_arg:
+            out, arg = res
+            ctx.save_for_backward(arg)
+            ctx.mark_non_differentiable(arg)
+            return out
+        return res
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        arg = ctx.saved_tensors[0] if ctx.reduce in ("max", "min") else None
+        return ops.segment_spread16(grad_out.contiguous(), arg, ctx.plan, ctx.reduce, ctx.dtype), None, None
+
+
 class _SegmentMul(torch.autograd.Function):
     """reduce="mul" (torch_scatter.scatter_mul): out = product per destination in edge order, empty rows 1;
     backward as torch_scatter's ScatterMul: grad_src = (grad_out * out)[index] / src, NaN (0 / 0) -> 0."""
@@ -83,6 +109,8 @@ def segment_reduce(messages: torch.Tensor, plan: "ops.GraphPlan", reduce: str) -
         return _SegmentMul.apply(messages, plan)
     if reduce not in ops.REDUCE_IDS:
         raise ValueError(f"unknown aggregation function {reduce!r}")
+    if messages.dtype in ops.HALF_IDS:   # the 16-bit rows of `_EdgeLinear(rows=)`: a node of their own
+        return _SegmentReduce16.apply(messages, plan, reduce)
     return _SegmentReduce.apply(messages, plan, reduce)
 
 
@@ -546,10 +574,16 @@ class _EdgeLinear(torch.autograd.Function):
     the kernels, the [T, M, H] weight stack and its transpose by torch, once per call -- and run on the 16-bit matrix
     cores (csrc/edge_gemm16.hip's masked forms, csrc/edge_wgrad16.hip) where the ops take the shape; saved tensors,
     grad_msg, the [E, K] input gradient, the segment sums, d x and d W stay fp32.  None / float32: the fp32 kernels.
+
+    `rows` = the same 16-bit type (`training_rows16_supported` decides, before anything is launched): every [E, .] tensor
+    of the step is 16-bit rows -- the messages this node returns (rounded once in the GEMM's epilogue), the grad_msg it
+    receives (from `_SegmentReduce16`; both gradient GEMMs read it as it is, no rounding), and the [E, K] input gradient
+    (rounded once, after mask and scale), which ptgnn_amd_gather_reduce16 sums over the transposed plan.  x, w_stack, the
+    mask bits, d x, d W and all accumulation stay fp32.
     """
 
     @staticmethod
-    def forward(ctx, x, plan, use_dst, dropout_p, dropout_seed, w_stack, inputs=None):
+    def forward(ctx, x, plan, use_dst, dropout_p, dropout_seed, w_stack, inputs=None, rows=None):
         adj = plan._adj
         if use_dst or inputs == torch.float32:
             inputs = None
@@ -561,12 +595,15 @@ class _EdgeLinear(torch.autograd.Function):
             bits = ops.dropout_bitmask(plan.num_edges, x.shape[1], dropout_p, dropout_seed, x.device)
         if drop is not None and bits is None:
             inputs = None                  # the hash form of the mask (a width off the 32-bit words): fp32 kernels only
+        if inputs is None or rows == torch.float32:
+            rows = None
         if inputs is None:
             msg = ops.edge_linear(x, adj, list(w_stack.unbind(0)), use_dst, dropout=drop, mask_bits=bits)
         else:
             msg = ops.edge_linear(x, adj, list(w_stack.unbind(0)), False, dropout=drop, mask_bits=bits, inputs=inputs,
-                                  rounded=_rounded_stack(w_stack, inputs))
+                                  rounded=_rounded_stack(w_stack, inputs), rows=rows)
         ctx.plan, ctx.use_dst, ctx.drop, ctx.bits, ctx.inputs = plan, use_dst, (dropout_p, dropout_seed), bits, inputs
+        ctx.rows = rows
         ctx.save_for_backward(x, w_stack)
         return msg
 
@@ -591,7 +628,7 @@ class _EdgeLinear(torch.autograd.Function):
                 drop = (2, p, seed) if p > 0.0 else None
                 g_in = ops.edge_linear(gm, [(i, i) for i in plan.identity_index()], list(wt.unbind(0)),
                                        False, dropout=drop, mask_bits=ctx.bits, inputs=inputs,
-                                       rounded=_rounded_stack(wt, inputs))  # [E, K]
+                                       rounded=_rounded_stack(wt, inputs), rows=ctx.rows)  # [E, K]; 16-bit under rows
                 tp = plan.transposed_plan()
                 d_x = ops.gather_reduce(g_in[:, :H] if use_dst else g_in, tp, H, "sum", type_bits=0,
                                         col=tp.perm)
@@ -603,7 +640,29 @@ class _EdgeLinear(torch.autograd.Function):
                         d_x = d_x + d_dst
                     else:
                         d_x[: d_dst.shape[0]] += d_dst
-        return d_x, None, None, None, None, d_w, None
+        return d_x, None, None, None, None, d_w, None, None
+
+
+def training_rows16_supported(x: torch.Tensor, plan: "ops.GraphPlan", w_stack: torch.Tensor, reduce: str,
+                              dropout_p: float, dtype) -> bool:
+    """Whether `_EdgeLinear(rows=dtype)` and the aggregation after it take the call -- every launch of the step, decided
+    from the `*_supported` predicates before the forward producer runs: the producer (the row-storing per-edge GEMM, or
+    its masked form from mask bits), the aggregation with an arg, the 16-bit spread, both gradient GEMMs over 16-bit
+    gradient rows and the 16-bit segment sum of the input gradient.  `reduce` "mul" and the hash form of the mask (a
+    state width off the 32-bit mask words) stay on fp32 rows."""
+    if dtype not in ops.HALF_IDS or reduce not in ops.REDUCE_IDS:
+        return False
+    T, M, H = w_stack.shape
+    if not ops.message_rows16_supported(x, M, dtype):                       # 16-byte state rows, the aggregation's widths
+        return False
+    if dropout_p > 0.0 and H % 32 != 0:
+        return False
+    mode = 2 if dropout_p > 0.0 else 0
+    return (ops.segment_reduce16_supported(M, dtype) and ops.segment_spread16_supported(M, dtype)
+            and (ops.edge_linear16_train_rows16_supported(H, M, T, dtype, 1, False, True) if dropout_p > 0.0
+                 else ops.edge_linear16_supported(H, M, T, dtype))
+            and ops.edge_linear16_train_rows16_supported(M, H, T, dtype, mode, True, True)
+            and ops.edge_weight_grad16_supported(H, M, T, dtype) and ops.gather_reduce16_supported(H, dtype))
 
 
 def _rounded_stack(stack: torch.Tensor, inputs):
@@ -700,12 +759,15 @@ def edge_linear_feat(x: torch.Tensor, plan: "ops.GraphPlan", weights, use_dst: b
 
 
 def edge_linear(x: torch.Tensor, plan: "ops.GraphPlan", weights, use_dst: bool, dropout_p: float = 0.0,
-                dropout_seed: int = 0, inputs=None) -> torch.Tensor:
+                dropout_seed: int = 0, inputs=None, rows=None) -> torch.Tensor:
     """Differentiable grouped per-edge Linear over the plan's adjacency lists (see `_EdgeLinear`).
     `weights`: the per-type nn.Linear weights as a list, or already stacked [T, M, K] (a stack shared by
     the tied layers of a forward makes autograd accumulate ONE [T, M, K] gradient per use instead of T).
     `inputs`: torch.bfloat16 / torch.float16 run the node's three GEMMs on the 16-bit matrix cores (no target half; see
-    `_EdgeLinear`); None or float32 is the fp32 node, and so is `use_dst=True` under any `inputs`."""
+    `_EdgeLinear`); None or float32 is the fp32 node, and so is `use_dst=True` under any `inputs`.
+    `rows`: the same 16-bit type keeps the step's [E, .] tensors as 16-bit rows (see `_EdgeLinear`; the messages come back
+    in that type and `segment_reduce` aggregates them on the node of their own); None or float32 is what it was.  The
+    caller decides with `training_rows16_supported`; a call the launches do not take raises."""
     if plan._adj is None:
         raise _lib.PtgnnAmdError("edge_linear: the plan must keep its adjacency lists")
     w_stack = weights if isinstance(weights, torch.Tensor) else torch.stack(list(weights))
@@ -719,7 +781,10 @@ def edge_linear(x: torch.Tensor, plan: "ops.GraphPlan", weights, use_dst: bool, 
     if inputs not in ops.HALF_IDS:
         raise _lib.PtgnnAmdError(f"edge_linear: inputs must be None, torch.float32, torch.bfloat16 or torch.float16 "
                                  f"(got {inputs!r})")
-    return _EdgeLinear.apply(x, plan, False, float(dropout_p), int(dropout_seed), w_stack, inputs)
+    if rows is not None and rows != torch.float32 and rows != inputs:
+        raise _lib.PtgnnAmdError(f"edge_linear: rows must be None, torch.float32 or the 16-bit type of `inputs` "
+                                 f"(got rows={rows!r}, inputs={inputs!r})")
+    return _EdgeLinear.apply(x, plan, False, float(dropout_p), int(dropout_seed), w_stack, inputs, rows)
 
 
 class _GatherReduce(torch.autograd.Function):
