@@ -285,6 +285,16 @@ enum {
   PTGNN_AMD_KERNEL_HALF_WGRAD_MASKED,                                /* ptgnn_amd_linear_weight_grad16_masked */
   PTGNN_AMD_KERNEL_PANEL16_END_
 };
+/* ... and one for the opt-in matrix-core attention pool and copy scores past 8 heads (csrc/wide_heads.hip), so the
+ * aggregation range ends where it did */
+enum {
+  PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_ = 1216,
+  PTGNN_AMD_KERNEL_WIDE_HEADS_POOL = PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_, /* ptgnn_amd_wide_heads_pool_f32 */
+  PTGNN_AMD_KERNEL_WIDE_HEADS_POOL_BACKWARD,                             /* ptgnn_amd_wide_heads_pool_backward_f32 */
+  PTGNN_AMD_KERNEL_WIDE_HEADS_SCORES,                                    /* ptgnn_amd_wide_heads_scores_f32 */
+  PTGNN_AMD_KERNEL_WIDE_HEADS_SCORES_BACKWARD,                           /* ptgnn_amd_wide_heads_scores_backward_f32 */
+  PTGNN_AMD_KERNEL_WIDE_HEADS_END_
+};
 int64_t ptgnn_amd_launch_count(int kernel_id);
 const char *ptgnn_amd_launch_name(int kernel_id);
 
@@ -880,6 +890,42 @@ int ptgnn_amd_segment_scores_backward_f32(const float *y, int64_t ld_y, const fl
                                           int32_t num_vectors, const float *scores, const float *lse,
                                           const float *grad_scores, const float *grad_lse, float *grad_y, int64_t ld_gy,
                                           float *grad_v, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The attention pool and the segment scores above for 9 .. 64 heads / vectors per sample, on exact-fp32 matrix-core
+ * tiles (csrc/wide_heads.hip): the same arguments, outputs, stats and overwrite rules as ptgnn_amd_attention_pool_f32 /
+ * ptgnn_amd_attention_pool_backward_f32 and ptgnn_amd_segment_scores_f32 / ptgnn_amd_segment_scores_backward_f32, the
+ * same 128-row chunks merged in chunk order (no float atomics; a sample has the same bits alone and inside a batch).
+ * Replaces: for a target of more than 8 decoding steps, the whole attention of GruCopyingDecoder._compute_logprobs,
+ *   ptgnn/neuralmodels/sequence/grucopydecoder.py:79-124 (both memory Linears over all memories, the [num_inputs, L, H]
+ *   gather, both einsums, scatter_log_softmax, the [num_inputs, L, H] weighted rows, scatter_add and scatter_logsumexp);
+ *   for more than 8 heads, MultiheadSelfAttentionVarSizedElementReduce.forward, reduceops/varsizedsummary.py:140-178.
+ * ptgnn_amd_wide_heads_supported: 9 <= heads <= 64 and dim <= 512, dim <= 256 past 32 heads; other shapes answer
+ *   EUNSUPPORTED (1 .. 8 heads are the shapes of the entry points above).
+ * ptgnn_amd_wide_heads_workspace_bytes: mode 0 = pool, 1 = scores; backward 0 / 1.
+ * ---------------------------------------------------------------------------------------- */
+int ptgnn_amd_wide_heads_supported(int32_t dim, int32_t num_heads);
+size_t ptgnn_amd_wide_heads_workspace_bytes(int32_t mode, int32_t backward, int64_t num_segments, int64_t num_elements,
+                                            int32_t dim, int32_t num_heads);
+int ptgnn_amd_wide_heads_pool_f32(const float *x, int64_t ld_x, const float *u, const int32_t *rowptr,
+                                  const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                  int32_t num_heads, float *out, float *stats, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+int ptgnn_amd_wide_heads_pool_backward_f32(const float *x, int64_t ld_x, const float *u, const int32_t *rowptr,
+                                           const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                           int32_t num_heads, const float *out, const float *stats,
+                                           const float *grad_out, float *grad_x, int64_t ld_gx, float *grad_u,
+                                           void *workspace, size_t workspace_bytes, void *stream);
+int ptgnn_amd_wide_heads_scores_f32(const float *y, int64_t ld_y, const float *v, const int32_t *rowptr,
+                                    const int32_t *perm, int64_t num_segments, int64_t num_elements, int32_t dim,
+                                    int32_t num_vectors, float *scores, float *lse, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+int ptgnn_amd_wide_heads_scores_backward_f32(const float *y, int64_t ld_y, const float *v, const int32_t *rowptr,
+                                             const int32_t *perm, int64_t num_segments, int64_t num_elements,
+                                             int32_t dim, int32_t num_vectors, const float *scores, const float *lse,
+                                             const float *grad_scores, const float *grad_lse, float *grad_y,
+                                             int64_t ld_gy, float *grad_v, void *workspace, size_t workspace_bytes,
+                                             void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Segment softmax / log-softmax / logsumexp of a general source x [num_elements, dim] over an arbitrary (unsorted)

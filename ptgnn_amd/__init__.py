@@ -26,7 +26,7 @@ def __getattr__(name):
                 "attention_training", "attention_training_inputs", "attention_linear_inputs", "set_half_messages", "get_half_messages",
                 "half_messages", "message_rows", "get_half_messages_mlp", "mlp_message_rows", "training_message_rows",
                 "set_vocabulary_loss",
-                "vocabulary_loss", "vocabulary_loss_inputs"):
+                "vocabulary_loss", "vocabulary_loss_inputs", "set_wide_heads", "get_wide_heads", "wide_heads"):
         from ptgnn_amd import precision
         return getattr(precision, name)
     if name in ("set_fused_softmax", "fused_softmax"):   # the facade's fused segment-softmax switch (scatter.py)

@@ -443,6 +443,14 @@ int attn_check(const char *what, int64_t num_segments, int64_t num_elements, int
 }
 
 }  // namespace
+
+void launch_attn_merge(const float *partial, const float *stat_partial, const int32_t *chunk_start, int dim, int heads,
+                       int64_t segments, float *out, float *stats, hipStream_t st) {
+  const int64_t total = segments * heads * dim;
+  k_attn_merge<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(partial, stat_partial, chunk_start, dim, heads, segments,
+                                                                 out, stats);
+}
+
 }  // namespace ptgnn_amd
 
 using namespace ptgnn_amd;
@@ -483,9 +491,7 @@ extern "C" int ptgnn_amd_attention_pool_f32(const float *x, int64_t ld_x, const 
                   L.R, L.S, (int)num_segments, (const int32_t *)chunk_start, vec4, partial, stat_partial);
     if (rc != PTGNN_AMD_OK) return rc;
   }
-  const int64_t total = num_segments * num_heads * dim;
-  k_attn_merge<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(partial, stat_partial, chunk_start, dim, num_heads,
-                                                                 num_segments, out, stats);
+  launch_attn_merge(partial, stat_partial, chunk_start, dim, num_heads, num_segments, out, stats, st);
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_ATTENTION_POOL);
   return PTGNN_AMD_OK;

@@ -21,6 +21,13 @@ constexpr int kAttnMaxDim = 1024;
 constexpr size_t kAttnMaxLds = 160 * 1024;     // LDS of one CU (gfx950)
 
 #ifdef __HIPCC__
+// the chunk merges of the two kernels, shared with wide_heads.hip so a segment's chunks meet in one order (defined in
+// attention_pool.hip and segment_scores.hip; the launch check is the caller's)
+void launch_attn_merge(const float *partial, const float *stat_partial, const int32_t *chunk_start, int dim, int heads,
+                       int64_t segments, float *out, float *stats, hipStream_t st);
+void launch_scores_merge(const float *stat_partial, const int32_t *chunk_start, int vectors, int64_t segments,
+                         float *lse, hipStream_t st);
+
 // [dim][HP] image of the segment's [heads][dim] rows (padded heads 0)
 template <int HP>
 __device__ __forceinline__ void attn_stage_heads(float *__restrict__ dst, const float *__restrict__ src, int dim,

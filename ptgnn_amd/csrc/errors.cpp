@@ -39,6 +39,7 @@ static std::atomic<int64_t> g_projection_loss_launches[PTGNN_AMD_KERNEL_PROJECTI
 static std::atomic<int64_t> g_rows16_launches[PTGNN_AMD_KERNEL_ROWS16_END_ - PTGNN_AMD_KERNEL_ROWS16_FIRST_];
 static std::atomic<int64_t> g_projection_loss16_launches[PTGNN_AMD_KERNEL_PROJECTION_LOSS16_END_ - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
 static std::atomic<int64_t> g_panel16_launches[PTGNN_AMD_KERNEL_PANEL16_END_ - PTGNN_AMD_KERNEL_PANEL16_FIRST_];
+static std::atomic<int64_t> g_wide_heads_launches[PTGNN_AMD_KERNEL_WIDE_HEADS_END_ - PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_];
 static std::atomic<int64_t> *counter(int kernel_id) {
   if (kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_) return &g_launches[kernel_id];
   if (kernel_id >= PTGNN_AMD_KERNEL_AGG_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_AGG_END_)
@@ -77,6 +78,8 @@ static std::atomic<int64_t> *counter(int kernel_id) {
     return &g_projection_loss16_launches[kernel_id - PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIRST_];
   if (kernel_id >= PTGNN_AMD_KERNEL_PANEL16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PANEL16_END_)
     return &g_panel16_launches[kernel_id - PTGNN_AMD_KERNEL_PANEL16_FIRST_];
+  if (kernel_id >= PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_WIDE_HEADS_END_)
+    return &g_wide_heads_launches[kernel_id - PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_];
   return nullptr;
 }
 void count_launch(int kernel_id) {
@@ -190,6 +193,10 @@ extern "C" const char *ptgnn_amd_launch_name(int kernel_id) {
       "panel_linear16", "panel_linear16_grad_input", "half_wgrad_masked"};
   if (kernel_id >= PTGNN_AMD_KERNEL_PANEL16_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_PANEL16_END_)
     return panel16_names[kernel_id - PTGNN_AMD_KERNEL_PANEL16_FIRST_];
+  static const char *const wide_heads_names[PTGNN_AMD_KERNEL_WIDE_HEADS_END_ - PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_] = {
+      "wide_heads_pool", "wide_heads_pool_backward", "wide_heads_scores", "wide_heads_scores_backward"};
+  if (kernel_id >= PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_ && kernel_id < PTGNN_AMD_KERNEL_WIDE_HEADS_END_)
+    return wide_heads_names[kernel_id - PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_];
   return kernel_id >= 0 && kernel_id < PTGNN_AMD_KERNEL_COUNT_ ? names[kernel_id] : nullptr;
 }
 

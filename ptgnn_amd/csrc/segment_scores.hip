@@ -245,6 +245,13 @@ int scores_check(const char *what, int64_t num_segments, int64_t num_elements, i
 }
 
 }  // namespace
+
+void launch_scores_merge(const float *stat_partial, const int32_t *chunk_start, int vectors, int64_t segments,
+                         float *lse, hipStream_t st) {
+  const int64_t total = segments * vectors;
+  k_scores_merge<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(stat_partial, chunk_start, vectors, segments, lse);
+}
+
 }  // namespace ptgnn_amd
 
 using namespace ptgnn_amd;
@@ -288,9 +295,7 @@ extern "C" int ptgnn_amd_segment_scores_f32(const float *y, int64_t ld_y, const 
                                 (const int32_t *)chunk_start, vec4, scores, stat_partial);
     if (rc != PTGNN_AMD_OK) return rc;
   }
-  const int64_t total = num_segments * num_vectors;
-  k_scores_merge<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(stat_partial, chunk_start, num_vectors, num_segments,
-                                                                   lse);
+  launch_scores_merge(stat_partial, chunk_start, num_vectors, num_segments, lse, st);
   PTGNN_LAUNCH_CHECK();
   count_launch(PTGNN_AMD_KERNEL_SEGMENT_SCORES);
   return PTGNN_AMD_OK;

@@ -52,6 +52,16 @@ __device__ __forceinline__ void push4(MaxSum &a, const float (&v)[4]) {
   if (a.m != -INFINITY) a.s += (expf(v[0] - a.m) + expf(v[1] - a.m)) + (expf(v[2] - a.m) + expf(v[3] - a.m));
 }
 
+// the state moves to the maximum m >= a.m; returns the factor its sum was scaled by, for a caller that keeps further sums
+// relative to the same maximum (the accumulator tiles of wide_heads.hip).  The caller then adds the block's
+// sum exp(. - m) to a.s.
+__device__ __forceinline__ float raise_max(MaxSum &a, float m) {
+  const float alpha = a.m == -INFINITY ? 0.0f : expf(a.m - m);
+  a.s *= alpha;
+  a.m = m;
+  return alpha;
+}
+
 __device__ __forceinline__ MaxSum lane_xor(const MaxSum &a, int o) { return MaxSum{lane_xor(a.m, o), lane_xor(a.s, o)}; }
 
 constexpr int kSoftNone = INT_MAX;

@@ -92,12 +92,16 @@ _PROJECTION_LOSS16_FAMILY_FIRST = 1088  # PTGNN_AMD_KERNEL_PROJECTION_LOSS16_FIR
 _PANEL16_FAMILY_FIRST = 1152  # PTGNN_AMD_KERNEL_PANEL16_FIRST_: the panel-form 16-bit Linear and its masked backward
 
 
+_WIDE_HEADS_FAMILY_FIRST = 1216  # PTGNN_AMD_KERNEL_WIDE_HEADS_FIRST_: the matrix-core pool and copy scores past 8 heads
+
+
 def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool = False,
                   sequence: bool = False, decode: bool = False, beam: bool = False, half: bool = False,
                   edge16: bool = False, half_training: bool = False, edge16_dst: bool = False,
                   beam_finish: bool = False, attention16: bool = False, projection_loss: bool = False,
                   projection_loss16: bool = False, rows16: bool = False, panel16: bool = False,
-                  attention16_training: bool = False, edge16_training: bool = False) -> dict:
+                  wide_heads: bool = False, attention16_training: bool = False,
+                  edge16_training: bool = False) -> dict:
     """{kernel family: launches made by this process} (ptgnn_amd_launch_count): tests take differences around a call
     to assert which kernel a shape / size / mode was dispatched to.  `aggregation=True` adds the aggregation families
     (k_gather_reduce, egc_gather_combine, egc_combine, egc_combine_backward, pna_aggregate, pna_aggregate_backward,
@@ -123,7 +127,9 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
     target-state half storing them; segment_reduce16, segment_spread16, edge16_train_rows16, edge_wgrad16_rows16: the
     edge-form training step's aggregation with an arg, its 16-bit spread, the masked per-edge GEMM reading / storing 16-bit
     rows and the weight gradient over 16-bit gradient rows); `panel16=True` the panel-form 16-bit Linear of the attention layer's training step
-    (panel_linear16, panel_linear16_grad_input, half_wgrad_masked)."""
+    (panel_linear16, panel_linear16_grad_input, half_wgrad_masked); `wide_heads=True` the opt-in matrix-core attention
+    pool and copy scores past 8 heads (wide_heads_pool, wide_heads_pool_backward, wide_heads_scores,
+    wide_heads_scores_backward)."""
     lib = _lib.load()
     out = {}
     for first in (0,) + ((_AGG_FAMILY_FIRST,) if aggregation else ()) + ((_CHAR_FAMILY_FIRST,) if char_cnn else ()) \
@@ -139,7 +145,8 @@ def launch_counts(aggregation: bool = False, char_cnn: bool = False, heads: bool
             + ((_PROJECTION_LOSS_FAMILY_FIRST,) if projection_loss else ()) \
             + ((_PROJECTION_LOSS16_FAMILY_FIRST,) if projection_loss16 else ()) \
             + ((_ROWS16_FAMILY_FIRST,) if rows16 else ()) \
-            + ((_PANEL16_FAMILY_FIRST,) if panel16 else ()):
+            + ((_PANEL16_FAMILY_FIRST,) if panel16 else ()) \
+            + ((_WIDE_HEADS_FAMILY_FIRST,) if wide_heads else ()):
         i = first
         while True:
             name = lib.ptgnn_amd_launch_name(i)
@@ -155,7 +162,7 @@ def launches_since(before: dict) -> dict:
     now = launch_counts(aggregation=True, char_cnn=True, heads=True, sequence=True, decode=True, beam=True, half=True,
                         edge16=True, half_training=True, edge16_dst=True, beam_finish=True, attention16=True,
                         attention16_training=True, edge16_training=True, projection_loss=True, projection_loss16=True,
-                        rows16=True, panel16=True)
+                        rows16=True, panel16=True, wide_heads=True)
     return {k: now[k] - v for k, v in before.items() if now[k] != v}
 
 
@@ -2587,33 +2594,43 @@ def _attention_pool_args(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, what
     return x, u.contiguous(), n, d, G, H
 
 
-def attention_pool(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan):
-    """Multi-head segment-softmax pool over the plan of an element -> sample map (ptgnn_amd_attention_pool_f32):
+def _wide_workspace_bytes(lib, mode: int, backward: bool, G: int, n: int, d: int, H: int) -> int:
+    return int(lib.ptgnn_amd_wide_heads_workspace_bytes(mode, int(backward), G, n, d, H))
+
+
+def attention_pool(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, wide: bool = False):
+    """Multi-head segment-softmax pool over the plan of an element -> sample map (ptgnn_amd_attention_pool_f32; with
+    `wide`, ptgnn_amd_wide_heads_pool_f32: 9 .. 64 heads on the matrix cores):
         s[i,h] = u[g(i),h] . x_i,   p = softmax of s[., h] within each sample,   P[g,h] = sum_{i in g} p[i,h] x_i
     in one pass over x.  Returns (P [G, heads, D], stats [G, 2 * heads] = per-(g, h) max score | log-sum-exp)."""
     lib = _lib.load()
-    x, u, n, d, G, H = _attention_pool_args(x, u, plan, "attention_pool")
+    name = "wide_heads_pool" if wide else "attention_pool"
+    x, u, n, d, G, H = _attention_pool_args(x, u, plan, name)
     out = torch.empty(G, H, d, dtype=torch.float32, device=x.device)
     stats = torch.empty(G, 2 * H, dtype=torch.float32, device=x.device)
     if G == 0:
         return out, stats
-    ws_bytes = int(lib.ptgnn_amd_attention_pool_workspace_bytes(G, n, d, H))
+    ws_bytes = _wide_workspace_bytes(lib, 0, False, G, n, d, H) if wide \
+        else int(lib.ptgnn_amd_attention_pool_workspace_bytes(G, n, d, H))
     ws = _workspace(ws_bytes, x.device)
     plan.wait()
-    with _timed("attention_pool", bytes=4.0 * (n * d + 2 * G * H * d) + 4.0 * n):
-        rc = lib.ptgnn_amd_attention_pool_f32(*_rows_arg(x, d), u.data_ptr(),
-                                              plan.rowptr.data_ptr(), plan.perm.data_ptr() if n else None, G, n, d, H,
-                                              out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws_bytes, _stream(out))
-    _lib.check(rc, "ptgnn_amd_attention_pool_f32")
+    with _timed(name, flops=4.0 * n * H * d if wide else 0.0, bytes=4.0 * (n * d + 2 * G * H * d) + 4.0 * n):
+        rc = getattr(lib, f"ptgnn_amd_{name}_f32")(*_rows_arg(x, d), u.data_ptr(),
+                                                   plan.rowptr.data_ptr(), plan.perm.data_ptr() if n else None, G, n, d,
+                                                   H, out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                   _stream(out))
+    _lib.check(rc, f"ptgnn_amd_{name}_f32")
     return out, stats
 
 
 def attention_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, pooled: torch.Tensor,
-                            stats: torch.Tensor, grad_out: torch.Tensor):
+                            stats: torch.Tensor, grad_out: torch.Tensor, wide: bool = False):
     """(grad_x [n, D], grad_u [G, heads, D]) of `attention_pool` from grad_out = dL/dP [G, heads, D] and the forward's P
-    and stats (ptgnn_amd_attention_pool_backward_f32: one pass over x, grad_u folded in a fixed order)."""
+    and stats (ptgnn_amd_attention_pool_backward_f32, with `wide` ptgnn_amd_wide_heads_pool_backward_f32: one pass over
+    x, grad_u folded in a fixed order)."""
     lib = _lib.load()
-    x, u, n, d, G, H = _attention_pool_args(x, u, plan, "attention_pool_backward")
+    name = "wide_heads_pool_backward" if wide else "attention_pool_backward"
+    x, u, n, d, G, H = _attention_pool_args(x, u, plan, name)
     _require_cuda_f32("grad_out", grad_out, dims=3)
     pooled, stats, grad_out = pooled.contiguous(), stats.contiguous(), grad_out.contiguous()
     if tuple(grad_out.shape) != (G, H, d) or tuple(pooled.shape) != (G, H, d) or tuple(stats.shape) != (G, 2 * H):
@@ -2623,16 +2640,45 @@ def attention_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, p
     gu = torch.empty(G, H, d, dtype=torch.float32, device=x.device)
     if G == 0:
         return gx, gu
-    ws_bytes = int(lib.ptgnn_amd_attention_pool_backward_workspace_bytes(G, n, d, H))
+    ws_bytes = _wide_workspace_bytes(lib, 0, True, G, n, d, H) if wide \
+        else int(lib.ptgnn_amd_attention_pool_backward_workspace_bytes(G, n, d, H))
     ws = _workspace(ws_bytes, x.device)
     plan.wait()
-    with _timed("attention_pool_backward", bytes=4.0 * (2 * n * d + 4 * G * H * d) + 4.0 * n):
-        rc = lib.ptgnn_amd_attention_pool_backward_f32(
+    with _timed(name, flops=12.0 * n * H * d if wide else 0.0, bytes=4.0 * (2 * n * d + 4 * G * H * d) + 4.0 * n):
+        rc = getattr(lib, f"ptgnn_amd_{name}_f32")(
             *_rows_arg(x, d), u.data_ptr(), plan.rowptr.data_ptr(),
             plan.perm.data_ptr() if n else None, G, n, d, H, pooled.data_ptr(), stats.data_ptr(), grad_out.data_ptr(),
             gx.data_ptr() if n else None, d, gu.data_ptr(), ws.data_ptr(), ws_bytes, _stream(gu))
-    _lib.check(rc, "ptgnn_amd_attention_pool_backward_f32")
+    _lib.check(rc, f"ptgnn_amd_{name}_f32")
     return gx, gu
+
+
+def wide_heads_supported(dim: int, num_heads: int) -> bool:
+    """Whether the matrix-core pool and scores take (dim, heads / vectors) (ptgnn_amd_wide_heads_supported: 9 .. 64
+    heads, dim <= 512, dim <= 256 past 32 heads)."""
+    return bool(_lib.load().ptgnn_amd_wide_heads_supported(int(dim), int(num_heads)))
+
+
+def wide_heads_pool(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan):
+    """`attention_pool` for 9 .. 64 heads on exact-fp32 matrix-core tiles (ptgnn_amd_wide_heads_pool_f32)."""
+    return attention_pool(x, u, plan, wide=True)
+
+
+def wide_heads_pool_backward(x: torch.Tensor, u: torch.Tensor, plan: GraphPlan, pooled: torch.Tensor,
+                             stats: torch.Tensor, grad_out: torch.Tensor):
+    """`attention_pool_backward` for 9 .. 64 heads (ptgnn_amd_wide_heads_pool_backward_f32)."""
+    return attention_pool_backward(x, u, plan, pooled, stats, grad_out, wide=True)
+
+
+def wide_heads_scores(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan):
+    """`segment_scores` for 9 .. 64 vectors per sample (ptgnn_amd_wide_heads_scores_f32)."""
+    return segment_scores(y, v, plan, wide=True)
+
+
+def wide_heads_scores_backward(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, scores: torch.Tensor,
+                               lse: torch.Tensor, grad_scores: torch.Tensor, grad_lse: torch.Tensor):
+    """`segment_scores_backward` for 9 .. 64 vectors per sample (ptgnn_amd_wide_heads_scores_backward_f32)."""
+    return segment_scores_backward(y, v, plan, scores, lse, grad_scores, grad_lse, wide=True)
 
 
 def segment_scores_supported(dim: int, num_vectors: int) -> bool:
@@ -2653,33 +2699,36 @@ def _segment_scores_args(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, what
     return y, v.contiguous(), n, k, G, L
 
 
-def segment_scores(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan):
+def segment_scores(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, wide: bool = False):
     """Scores of every element against the vectors of its sample over the plan of an element -> sample map, and their
     per-sample log-sum-exp (ptgnn_amd_segment_scores_f32):
         scores[i,l] = v[g(i),l] . y_i,   lse[g,l] = log sum_{i in g} exp(scores[i,l])   (-inf for an empty sample)
     in one pass over y.  Returns (scores [n, L] in element order, lse [G, L])."""
     lib = _lib.load()
-    y, v, n, k, G, L = _segment_scores_args(y, v, plan, "segment_scores")
+    name = "wide_heads_scores" if wide else "segment_scores"      # wide: ptgnn_amd_wide_heads_scores_f32, 9 .. 64 vectors
+    y, v, n, k, G, L = _segment_scores_args(y, v, plan, name)
     scores = torch.empty(n, L, dtype=torch.float32, device=y.device)
     lse = torch.empty(G, L, dtype=torch.float32, device=y.device)
-    ws_bytes = int(lib.ptgnn_amd_segment_scores_workspace_bytes(G, n, k, L))
+    ws_bytes = _wide_workspace_bytes(lib, 1, False, G, n, k, L) if wide \
+        else int(lib.ptgnn_amd_segment_scores_workspace_bytes(G, n, k, L))
     ws = _workspace(ws_bytes, y.device)
     plan.wait()
-    with _timed("segment_scores", bytes=4.0 * (n * k + n * L + G * L * (k + 1)) + 4.0 * n):
-        rc = lib.ptgnn_amd_segment_scores_f32(*_rows_arg(y, k), v.data_ptr() if G else None, plan.rowptr.data_ptr(),
-                                              plan.perm.data_ptr() if n else None, G, n, k, L,
-                                              scores.data_ptr() if n else None, lse.data_ptr() if G else None,
-                                              ws.data_ptr(), ws_bytes, _stream(lse))
-    _lib.check(rc, "ptgnn_amd_segment_scores_f32")
+    with _timed(name, flops=2.0 * n * L * k if wide else 0.0, bytes=4.0 * (n * k + n * L + G * L * (k + 1)) + 4.0 * n):
+        rc = getattr(lib, f"ptgnn_amd_{name}_f32")(*_rows_arg(y, k), v.data_ptr() if G else None,
+                                                   plan.rowptr.data_ptr(), plan.perm.data_ptr() if n else None, G, n, k,
+                                                   L, scores.data_ptr() if n else None, lse.data_ptr() if G else None,
+                                                   ws.data_ptr(), ws_bytes, _stream(lse))
+    _lib.check(rc, f"ptgnn_amd_{name}_f32")
     return scores, lse
 
 
 def segment_scores_backward(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, scores: torch.Tensor, lse: torch.Tensor,
-                            grad_scores: torch.Tensor, grad_lse: torch.Tensor):
+                            grad_scores: torch.Tensor, grad_lse: torch.Tensor, wide: bool = False):
     """(grad_y [n, K], grad_v [G, L, K]) of `segment_scores` from grad_scores [n, L], grad_lse [G, L] and the forward's
     scores and lse (ptgnn_amd_segment_scores_backward_f32: one pass over y, grad_v folded in a fixed order)."""
     lib = _lib.load()
-    y, v, n, k, G, L = _segment_scores_args(y, v, plan, "segment_scores_backward")
+    name = "wide_heads_scores_backward" if wide else "segment_scores_backward"
+    y, v, n, k, G, L = _segment_scores_args(y, v, plan, name)
     _require_cuda_f32("grad_scores", grad_scores)
     _require_cuda_f32("grad_lse", grad_lse)
     scores, lse, grad_scores, grad_lse = (t.contiguous() for t in (scores, lse, grad_scores, grad_lse))
@@ -2690,17 +2739,19 @@ def segment_scores_backward(y: torch.Tensor, v: torch.Tensor, plan: GraphPlan, s
                                  f"{tuple(grad_lse.shape)} do not match ({n}, {L}) and ({G}, {L})")
     gy = torch.empty(n, k, dtype=torch.float32, device=y.device)
     gv = torch.empty(G, L, k, dtype=torch.float32, device=y.device)
-    ws_bytes = int(lib.ptgnn_amd_segment_scores_backward_workspace_bytes(G, n, k, L))
+    ws_bytes = _wide_workspace_bytes(lib, 1, True, G, n, k, L) if wide \
+        else int(lib.ptgnn_amd_segment_scores_backward_workspace_bytes(G, n, k, L))
     ws = _workspace(ws_bytes, y.device)
     plan.wait()
-    with _timed("segment_scores_backward", bytes=4.0 * (2 * n * k + 2 * n * L + 2 * G * L * (k + 1)) + 4.0 * n):
-        rc = lib.ptgnn_amd_segment_scores_backward_f32(
+    with _timed(name, flops=4.0 * n * L * k if wide else 0.0,
+                bytes=4.0 * (2 * n * k + 2 * n * L + 2 * G * L * (k + 1)) + 4.0 * n):
+        rc = getattr(lib, f"ptgnn_amd_{name}_f32")(
             *_rows_arg(y, k), v.data_ptr() if G else None, plan.rowptr.data_ptr(),
             plan.perm.data_ptr() if n else None, G, n, k, L, scores.data_ptr() if n else None,
             lse.data_ptr() if G else None, grad_scores.data_ptr() if n else None,
             grad_lse.data_ptr() if G else None, gy.data_ptr() if n else None, k, gv.data_ptr() if G else None,
             ws.data_ptr(), ws_bytes, _stream(gv))
-    _lib.check(rc, "ptgnn_amd_segment_scores_backward_f32")
+    _lib.check(rc, f"ptgnn_amd_{name}_f32")
     return gy, gv
 
 

@@ -386,6 +386,34 @@ def vocabulary_loss_inputs(tensor: torch.Tensor) -> torch.dtype:
     return resolve(tensor) if _vocabulary_loss and tensor.is_cuda else torch.float32
 
 
+_wide_heads = False
+
+
+def set_wide_heads(on) -> bool:
+    """Whether the attention pool and the copy scores past 8 heads / decoding steps run on the matrix-core kernels of
+    csrc/wide_heads.hip instead of the composed operator sequence (the multi-head attention reducer with 9 .. 64 heads;
+    `GruCopyingDecoder`'s training attention for targets of 9 .. 64 steps); returns the previous value.  Off by default:
+    the results differ from the composed chain by fp32 rounding.  A setting of its own: `set_matrix_inputs` /
+    `matrix_inputs` neither read nor reset it.  CPU tensors, up to 8 heads and shapes outside
+    `ops.wide_heads_supported` ignore it."""
+    global _wide_heads
+    prev, _wide_heads = _wide_heads, bool(on)
+    return prev
+
+
+def get_wide_heads() -> bool:
+    return _wide_heads
+
+
+@contextlib.contextmanager
+def wide_heads(on=True):
+    prev = set_wide_heads(on)
+    try:
+        yield
+    finally:
+        set_wide_heads(prev)
+
+
 def set_half_messages(on, mlp=False, training=False) -> bool:
     """Whether the GGNN inference route stores its messages as 16-bit rows of the dtype setting and aggregates them with
     the 16-bit-row kernel -- with `mlp=True`, whether the MLP-MP layer's inference routes do too, and with

@@ -13,7 +13,7 @@ from typing import NamedTuple, Optional, Union
 import torch
 from torch import nn
 
-from ptgnn_amd import _lib, dense, ops, scatter as scatter_facade, torch_route
+from ptgnn_amd import _lib, dense, ops, precision, scatter as scatter_facade, torch_route
 from ptgnn_amd.layers import (AbstractMessagePassingLayer, _check_device, _index_plan, _no_grad_needed,  # noqa: F401
                               _num_samples)
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_reduce
@@ -98,20 +98,28 @@ class WeightedSumVarSizedElementReduce(AbstractVarSizedElementReduce):
 
 class _AttentionPool(torch.autograd.Function):
     """P[g,h] = sum_{i in g} softmax_g(u[g,h] . x_i) x_i over the plan of the element -> sample map as ONE node: forward
-    and backward are the two passes of csrc/attention_pool.hip (no [N, heads * D] tensor, deterministic grad_u)."""
+    and backward are the two passes of csrc/attention_pool.hip (no [N, heads * D] tensor, deterministic grad_u) -- with
+    `wide`, of csrc/wide_heads.hip (9 .. 64 heads; the callers decide with `_wide_heads_take`)."""
 
     @staticmethod
-    def forward(ctx, x, u, plan):
-        pooled, stats = ops.attention_pool(x, u, plan)
-        ctx.plan = plan
+    def forward(ctx, x, u, plan, wide=False):
+        pooled, stats = (ops.wide_heads_pool if wide else ops.attention_pool)(x, u, plan)
+        ctx.plan, ctx.wide = plan, wide
         ctx.save_for_backward(x, u, pooled, stats)
         return pooled
 
     @staticmethod
     def backward(ctx, grad):
         x, u, pooled, stats = ctx.saved_tensors
-        gx, gu = ops.attention_pool_backward(x, u, ctx.plan, pooled, stats, grad.contiguous())
-        return gx, gu, None
+        backward = ops.wide_heads_pool_backward if ctx.wide else ops.attention_pool_backward
+        gx, gu = backward(x, u, ctx.plan, pooled, stats, grad.contiguous())
+        return gx, gu, None, None
+
+
+def _wide_heads_take(dim: int, num_heads: int) -> bool:
+    """Whether a GPU call with `num_heads` heads / vectors of width `dim` goes to csrc/wide_heads.hip: the opt-in
+    `precision.set_wide_heads` is on and the shape is one of that kernel's."""
+    return precision.get_wide_heads() and ops.wide_heads_supported(dim, num_heads)
 
 
 class _HeadExpand(torch.autograd.Function):
@@ -192,11 +200,12 @@ def _attention_summary(inputs, queries: torch.Tensor, key_weight: torch.Tensor, 
     wv = value_weight.to(torch.float32) if value_weight is not None else None
     plan = _index_plan(index, G)
     hidden, D = wk.shape
-    if not ops.attention_pool_supported(D, num_heads):
+    wide = _wide_heads_take(D, num_heads)
+    if not (wide or ops.attention_pool_supported(D, num_heads)):
         return _composed_attention_summary(xf, index, plan, G, q, wk, wv, wo, num_heads, single_head).to(dt)
     scale = 1.0 if single_head else 1.0 / math.sqrt(hidden // num_heads)
     u = _HeadExpand.apply(q.contiguous(), wk, num_heads, scale)                 # [G, heads, D]
-    pooled = _AttentionPool.apply(xf, u, plan)                                  # [G, heads, D]
+    pooled = _AttentionPool.apply(xf, u, plan, wide)                               # [G, heads, D]
     if wv is not None:
         pooled = _HeadContract.apply(pooled, wv, num_heads)                     # [G, hidden]
     return dense.linear(pooled.reshape(G, -1), wo).to(dt)

@@ -207,9 +207,9 @@ class _SegmentScores(torch.autograd.Function):
     passes of csrc/segment_scores.hip (no [n, L, K] gather of the vectors, deterministic grad_v)."""
 
     @staticmethod
-    def forward(ctx, y, v, plan):
-        scores, lse = ops.segment_scores(y, v, plan)
-        ctx.plan = plan
+    def forward(ctx, y, v, plan, wide=False):
+        scores, lse = (ops.wide_heads_scores if wide else ops.segment_scores)(y, v, plan)    # wide: 9 .. 64 vectors
+        ctx.plan, ctx.wide = plan, wide
         ctx.save_for_backward(y, v, scores, lse)
         return scores, lse
 
@@ -218,13 +218,17 @@ class _SegmentScores(torch.autograd.Function):
         y, v, scores, lse = ctx.saved_tensors
         grad_scores = torch.zeros_like(scores) if grad_scores is None else grad_scores.contiguous()
         grad_lse = torch.zeros_like(lse) if grad_lse is None else grad_lse.contiguous()
-        gy, gv = ops.segment_scores_backward(y, v, ctx.plan, scores, lse, grad_scores, grad_lse)
-        return gy, gv, None
+        backward = ops.wide_heads_scores_backward if ctx.wide else ops.segment_scores_backward
+        gy, gv = backward(y, v, ctx.plan, scores, lse, grad_scores, grad_lse)
+        return gy, gv, None, None
 
 
 def segment_scores(y: torch.Tensor, v: torch.Tensor, plan: "ops.GraphPlan"):
-    """Differentiable (scores [n, L], lse [G, L]) of fp32 rows y [n, K] against the vectors v [G, L, K] of their sample."""
-    return _SegmentScores.apply(y, v, plan)
+    """Differentiable (scores [n, L], lse [G, L]) of fp32 rows y [n, K] against the vectors v [G, L, K] of their sample.
+    Up to 8 vectors: csrc/segment_scores.hip.  9 .. 64 vectors with `precision.set_wide_heads` on: csrc/wide_heads.hip."""
+    from ptgnn_amd import precision
+    wide = precision.get_wide_heads() and y.is_cuda and ops.wide_heads_supported(y.shape[1], v.shape[1])
+    return _SegmentScores.apply(y, v, plan, wide)
 
 
 def _prepare(src: torch.Tensor, index: torch.Tensor, dim: int, out, dim_size):

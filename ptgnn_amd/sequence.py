@@ -51,7 +51,7 @@ from torch import nn
 
 from ptgnn_amd import _lib, _readback, dense, ops, precision, scatter as scatter_facade
 from ptgnn_amd.layers import _index_plan, _no_grad_needed
-from ptgnn_amd.reduceops import _AttentionPool
+from ptgnn_amd.reduceops import _AttentionPool, _wide_heads_take
 from ptgnn_amd.scatter import gather_rows as gather_rows_autograd, segment_scores
 
 _HALF = (torch.float16, torch.bfloat16)
@@ -283,10 +283,12 @@ class GruCopyingDecoder(nn.Module):
         B, L = output_states.shape[:2]
         states = output_states.reshape(B * L, H)
         drop = self.training and self.__dropout.p > 0.0
-        if not (ops.attention_pool_supported(Dm, L) and ops.segment_scores_supported(H if drop else Dm, L)):
+        # past 8 vectors: csrc/wide_heads.hip under the opt-in precision.set_wide_heads, else the composed sequence
+        wide = _wide_heads_take(Dm, L) and _wide_heads_take(H if drop else Dm, L)
+        if not (wide or (ops.attention_pool_supported(Dm, L) and ops.segment_scores_supported(H if drop else Dm, L))):
             return self.__composed_attention(x, index, plan, output_states)
         queries = dense.linear(states, w_s.t()).reshape(B, L, Dm)                          # u_s = W_s^T o
-        pooled = _AttentionPool.apply(x, queries, plan)                                    # [B, L, Dm]
+        pooled = _AttentionPool.apply(x, queries, plan, wide)                              # [B, L, Dm]
         attention_out = dense.linear(pooled.reshape(B * L, Dm), w_s)                       # A = W_s P
         if drop:
             rows = dense.linear_act_dropout(x, w_c, None, None, self.__dropout.p, True)
